@@ -12,20 +12,22 @@ of that size (weak scaling) and scores B pairs whose users fall in
 collective for pair scoring.
 
 Rank 0 prints ONE JSON line (and writes it to --out) with `roofline` (HBM, from HIP events around every launch on the
-stream the kernel runs on) and `cpu_baseline` (the CPU restatement of the reference graph timed on this box's host
-cores; TF itself is unavailable).  Legs outside the timed region (benchlib/) add, as nested objects AND as top-level
-scalars: `survey_8d_*` (SURVEY.md 8d's byte count on a run that fetches every row), `hbm_only_*`, `stream_probe_GBps`,
-`cfg2_mlp_*` (BASELINE configs[2], the MFMA head at E = 128), `cfg4_topk_*` (configs[4], one round of the E = 128
-retrieval), `topk_path_*` / `scaling_path` (configs[3], the user-sharded top-k path north_star's ">= 6x at 8 GPUs"
-speaks of), `cfg1_ingredients_*`, `catalogue_topk`, `evaluator`.  `--config 3|4` makes the sharded top-k path the
-timed step itself.  An N > 1 line carries `world`: ranks_seen, distinct_devices, backend, RCCL version.
+stream the kernel runs on).  A plain run does no more: set-up, warm-up, the K timed steps, --dump-outputs DIR (what the
+last timed step computed, benchlib/dump.py), the line.  With --full, `cpu_baseline` (the CPU restatement of the
+reference graph timed on the host cores, TF itself is unavailable) and the legs outside the timed region (benchlib/)
+add, as nested objects AND as top-level scalars: `survey_8d_*` (SURVEY.md 8d's byte count on a run that fetches every
+row), `hbm_only_*`, `stream_probe_GBps`, `cfg2_mlp_*` (BASELINE configs[2], the MFMA head at E = 128), `cfg4_topk_*`
+(configs[4], one round of the E = 128 retrieval), `topk_path_*` / `scaling_path` (configs[3], the user-sharded top-k
+path north_star's ">= 6x at 8 GPUs" speaks of), `cfg1_ingredients_*`, `catalogue_topk`, `evaluator`.  `--config 3|4`
+makes the sharded top-k path the timed step itself.  An N > 1 line carries `world`: ranks_seen, distinct_devices,
+backend, RCCL version.
 
 `--gpus N` with N > 1 and no launcher environment: this process starts the N ranks itself (the command above, as a
 child, BEFORE importing torch or touching a GPU) and exits with the child's status.
 
-Exit status: 3 when an in-run parity check of a timed kernel against the CPU restatement fails; 4 when a leg after
-the timed region did not return within --side-timeout (the headline line is still printed; `side_legs` names the leg
-and rank in flight).
+Exit status, --full only: 3 when an in-run parity check of a timed kernel against the CPU restatement fails; 4 when a
+leg after the timed region did not return within --side-timeout (the headline line is still printed; `side_legs` names
+the leg and rank in flight).
 """
 from __future__ import annotations
 
@@ -113,7 +115,7 @@ def main():
     import torch
     import torch.distributed as dist
 
-    from benchlib import baselines, configs, evaluator, mlp as mlplib, pairs as pairlib, topk as topklib, train
+    from benchlib import baselines, configs, dump, evaluator, mlp as mlplib, pairs as pairlib, topk as topklib, train
     from benchlib.common import random_masks
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -192,6 +194,7 @@ def main():
         gen = torch.Generator(device=dev).manual_seed(11 + rank)
         tk_users = (torch.randperm(U, generator=gen, device=dev)[:n_tk].to(torch.int32) + int(user_base)).contiguous()
         sharded = UserShardedScorer(eng, world * U, device=dev)
+    last = {}                                                            # the top-k step's result, for --dump-outputs
 
     def step():
         if wl == "pairs":
@@ -201,9 +204,9 @@ def main():
         elif wl == "mlp":
             eng.score_pairs_mlp(users, items, out=out)
         elif a.config is not None:                                       # every user of the shard, ONE all-gather
-            sharded.topk_all_users(10, round_users=round_cfg)
+            last["topk"] = sharded.topk_all_users(10, round_users=round_cfg)
         else:                                                            # retrieval: per-shard top-k, then the exchange
-            sharded.topk_users_gathered(tk_users, a.topk_k)
+            last["topk"] = sharded.topk_users_gathered(tk_users, a.topk_k)
 
     def barrier():
         torch.cuda.synchronize()
@@ -235,17 +238,20 @@ def main():
     if use_dist:
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
     wall_max = float(t.item())
+    if a.dump_outputs and rank == 0:                                     # before any leg writes `out` again
+        res = dict(zip(("topk_scores", "topk_dish_ids"), last["topk"])) if wl == "topk" else {"scores": out}
+        dump.write_outputs(a.dump_outputs, res)
 
     # what the timed region ran and produced -- read BEFORE any side leg launches another kernel or writes a buffer
     kernel_used = eng.last_kernel()
     opts_used = {k: eng.get_option(k) for k in ("prefetch", "nt_loads", "blocks_per_cu", "skip_masked")}
     Bc = min(1 << 18, B)
-    timed_sample = out[:Bc].clone() if wl == "pairs" else None           # parity sample of the TIMED kernel's scores
-    mlp_sample = out[:4096].clone() if wl == "mlp" else None             # same, for the head (checked in mlp_baseline)
+    timed_sample = out[:Bc].clone() if a.full and wl == "pairs" else None  # parity sample of the TIMED kernel's scores
+    mlp_sample = out[:4096].clone() if a.full and wl == "mlp" else None    # same, for the head (mlp_baseline)
     ident = world_identity(torch, dist_or_none, dev, world, rank)        # who took part (collective: every rank)
 
     survey = None
-    if rank == 0 and wl == "pairs" and opts_used["skip_masked"] != 0 and not a.no_side:
+    if rank == 0 and a.full and wl == "pairs" and opts_used["skip_masked"] != 0 and not a.no_side:
         survey = pairlib.survey_8d_leg(torch, eng, users, items, cats, C, E, a.steps)
 
     rc = 0
@@ -257,7 +263,7 @@ def main():
         bpp = algorithmic_bytes_per_pair(C, E, mean_active) if skip else bpp_survey
         avg_ms = sum(per_launch_ms) / len(per_launch_ms)
         achieved = bpp * B / (avg_ms * 1e-3) / 1e9
-        traffic, traffic_probe = committed_traffic(E, B, U, I, skip)
+        traffic, traffic_probe = committed_traffic(E, B, U, I, skip) if a.full else (None, None)
         table_bytes = 4 * (PM.numel() + RE.numel())
         cache_resident = table_bytes <= INFINITY_CACHE_BYTES
         units = (tk_users.numel() * I) if wl == "topk" else B           # (user, dish) pairs scored per step per GPU
@@ -324,7 +330,7 @@ def main():
 
     # legs every rank takes part in: the user-sharded retrieval step, the owner-routed pair step, scaling_path
     topk_ag = routed = scaling = None
-    side = not a.no_side and wl == "pairs"
+    side = a.full and not a.no_side and wl == "pairs"
     if side:
         if a.topk_users > 0:
             topk_ag = guarded("sharded_topk_allgather", sharded_topk_leg, torch, dist_or_none, eng, U, I, C, E, dev,
@@ -366,7 +372,7 @@ def main():
                                        "dish table")
             line["roofline"], line["dtype"] = mlplib.mlp_roofline(torch, eng, kernel_used, mlp_cats, items, C, E, B,
                                                                   avg_ms)
-            if not a.no_cpu_baseline and world == 1:
+            if a.full and not a.no_cpu_baseline and world == 1:
                 in_flight["leg"] = "mlp cpu_baseline"
                 cb, ok = baselines.mlp_baseline(torch, PM, RE, CE, mlp_cats, mlp_head, users, items, user_base,
                                                 mlp_sample, a.cpu_seconds)
@@ -448,7 +454,7 @@ def main():
             line["routed_pairs_alltoall"] = routed
         if a.unique_users:
             line["config"]["workload"] += " [--unique-users: every user at most once per step]"
-        if world == 1 and not a.no_cpu_baseline and wl == "pairs":
+        if a.full and world == 1 and not a.no_cpu_baseline and wl == "pairs":
             in_flight["leg"] = "cpu_baseline"
             cb, ref, _ = baselines.cpu_baseline(torch, PM, RE, CE, users, items, cats, a.cpu_seconds)
             if not baselines.check_timed_sample(torch, cb, timed_sample, ref):

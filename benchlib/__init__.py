@@ -10,4 +10,5 @@
     evaluator   evaluate.py's loop beside the one-launch device evaluator
     train       --workload train
     line        flattening of nested legs into the top-level scalars a key-only record keeps
+    dump        --dump-outputs: the last timed step's outputs as .npy files
 """

@@ -57,6 +57,13 @@ def parse(argv=None):
     p.add_argument("--sweep", action="store_true", help="also time the kernel knobs (stderr only)")
     p.add_argument("--opt", action="append", default=[], help="engine option name=value")
     p.add_argument("--out", default=None, help="also write the JSON line to this file (rank 0)")
+    p.add_argument("--full", action="store_true",
+                   help="also run everything beyond the headline: the legs after the timed region (CPU baseline and "
+                        "its parity check, SURVEY 8d run, stream probe, other configs, scaling path, ...) and the "
+                        "committed counter reading; off: set up, warm up, time --steps, print the line")
+    p.add_argument("--dump-outputs", default=None, metavar="DIR",
+                   help="after the timed steps, write what the last timed step computed as DIR/<name>.npy (float32, "
+                        "or float64 for ids; rank 0; a fixed seeded sample of rows beyond 64 MB in all)")
     p.add_argument("--settle-ms", type=float, default=150.0,
                    help="before the W warmup steps: run the step untimed for this long so that the part's clocks have "
                         "ramped (the first ~25 launches after an idle period run 5-7 %% slow); not counted as steps, "

@@ -4,6 +4,7 @@ from __future__ import annotations
 import sys
 
 from .common import HBM_PEAK_GBS, make_inputs, time_steps
+from .dump import write_outputs
 
 
 def train_workload(a, torch, foodrec_amd, dev):
@@ -21,13 +22,18 @@ def train_workload(a, torch, foodrec_amd, dev):
     eng = foodrec_amd.ScoringEngine(PM, RE, CE, coef=0.99, device=dev)
     eng.train_begin(a.learner, 0.001)
 
+    last = {}
+
     def step():
-        eng.train_step(users, items, cats, labels)
+        last["out"] = eng.train_step(users, items, cats, labels)
     for _ in range(a.warmup):
         step()
     eng.check()
     wall, per = time_steps(torch, eng, users, items, cats, None, a.steps, step)
     eng.check()
+    if a.dump_outputs:        # what a caller has after the last step: loss, grad norm, clip scale, lr; the tables
+        write_outputs(a.dump_outputs, {"step_out": last["out"], "personal_memory": PM, "recipe_embedding": RE,
+                                       "category_embedding": CE})
     avg_ms = sum(per) / len(per)
     table_bytes = 4 * (PM.numel() + RE.numel() + CE.numel())
     dense = a.learner.lower() == "adam"

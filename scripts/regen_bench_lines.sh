@@ -2,7 +2,7 @@
 # Every line is written by bench.py itself (--out): a file holds the line alone, never a banner a library printed first.
 set -o pipefail
 D=gpurun_out/${ROUND:-r06}/lines; mkdir -p $D
-run() { name=$1; shift; python bench.py "$@" --out $D/bench_$name.json > /dev/null 2> $D/bench_$name.err; echo $name rc=$?; }
+run() { name=$1; shift; python bench.py --full "$@" --out $D/bench_$name.json > /dev/null 2> $D/bench_$name.err; echo $name rc=$?; }
 run default
 run e128 --embed 128 --no-cpu-baseline --scaling-users 0 --no-config-legs
 run 10Musers_1Mdishes --users 10000000 --dishes 1000000 --no-cpu-baseline --scaling-users 0 --no-config-legs
@@ -20,7 +20,7 @@ run topk_1Mdishes_e128 --workload topk --dishes 1000000 --embed 128 --no-cpu-bas
 run train_sgd_refdefault --workload train --learner sgd --steps 300
 run train_adam_refdefault --workload train --learner adam --steps 300
 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29533 bench.py --gpus 1 \
-       --no-cpu-baseline --out $D/bench_dist1.json > /dev/null 2> $D/bench_dist1.err; echo dist1 rc=$?
+       --full --no-cpu-baseline --out $D/bench_dist1.json > /dev/null 2> $D/bench_dist1.err; echo dist1 rc=$?
 for f in $D/*.json; do python -c "
 import json,sys; d=json.load(open('$f')); r=d['roofline']
 print('$f'.split('/')[-1], round(d['value']/1e9,3), 'G/s', round(d['ms_per_step'],4), 'ms', r.get('bound'), r.get('frac'))"; done

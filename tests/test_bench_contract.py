@@ -134,6 +134,46 @@ def test_flags_and_defaults(monkeypatch):
     assert (a.gpus, a.steps, a.warmup) == (8, 7, 3)
 
 
+def test_plain_run_is_the_default_and_full_is_opt_in(monkeypatch):
+    """`bench.py --gpus 1 --steps K --warmup W` runs the headline only; the legs beyond it and the output dump are opt-in."""
+    b = _bench()
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "3"])
+    a = b.parse()
+    assert a.full is False and a.dump_outputs is None
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--dump-outputs", "outs"])
+    a = b.parse()
+    assert a.full is True and a.dump_outputs == "outs"
+
+
+def test_dumped_outputs_keep_their_values_and_the_size_budget(tmp_path):
+    """benchlib.dump.write_outputs: scores as float32, ids as float64 (exact); over the budget, a fixed seeded sample of rows,
+    the same rows for arrays of the same length, named in <name>_rows.npy -- and a small array beside them stays whole."""
+    import numpy as np
+    import torch
+    from benchlib import dump
+    s = torch.randn(1000, 10)
+    ids = torch.arange(10000, dtype=torch.int32).view(1000, 10)
+    assert dump.write_outputs(str(tmp_path / "all"), {"s": s, "ids": ids}) == {"s": 1000, "ids": 1000}
+    assert np.load(str(tmp_path / "all" / "s.npy")).dtype == np.float32
+    assert np.array_equal(np.load(str(tmp_path / "all" / "s.npy")), s.numpy())
+    got_ids = np.load(str(tmp_path / "all" / "ids.npy"))
+    assert got_ids.dtype == np.float64 and np.array_equal(got_ids, ids.numpy())
+    assert not os.path.exists(str(tmp_path / "all" / "s_rows.npy"))
+    budget = 40 * 1000 // 4
+    small = torch.tensor([0.5, 1.0, 2.0, 4.0])
+    for tag in ("x", "y"):
+        n = dump.write_outputs(str(tmp_path / tag), {"s": s, "ids": ids, "small": small}, budget=budget)
+        assert 0 < n["s"] == n["ids"] < 1000 and n["small"] == 4
+        assert np.array_equal(np.load(str(tmp_path / tag / "small.npy")), small.numpy())
+        assert not os.path.exists(str(tmp_path / tag / "small_rows.npy"))
+        files = [np.load(str(tmp_path / tag / f)) for f in ("s.npy", "ids.npy", "s_rows.npy", "ids_rows.npy", "small.npy")]
+        assert sum(f.nbytes for f in files) <= budget
+        rows = files[2].astype(np.int64)
+        assert np.array_equal(files[0], s.numpy()[rows]) and np.array_equal(files[1], ids.numpy()[rows])
+        assert np.array_equal(files[2], files[3])
+    assert np.array_equal(np.load(str(tmp_path / "x" / "s_rows.npy")), np.load(str(tmp_path / "y" / "s_rows.npy")))
+
+
 def test_round_size_of_the_sharded_topk_path():
     """--round-users 0 (the default): a shard is ranked in the fewest EVEN rounds of at most 524 288 users -- BASELINE configs[3]'s
     10 M users: 20 rounds of 500 000 at N = 1, 3 of 416 667 at N = 8 (1.25 M per GPU) -- and an explicit value is taken as is."""

@@ -26,7 +26,7 @@ def test_two_rank_bench_line_over_gloo_on_one_gpu(tmp_path):
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "5", "--warmup", "2",
            "--users", "100000", "--dishes", "20000", "--pairs", "262144", "--topk-users", "4096", "--scaling-users", "200000",
-           "--settle-ms", "20", "--no-cpu-baseline", "--side-timeout", "240", "--out", out]
+           "--settle-ms", "20", "--no-cpu-baseline", "--side-timeout", "240", "--full", "--out", out]
     res = subprocess.run(cmd, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=420)
     assert res.returncode == 0, res.stderr[-3000:]
     line = json.load(open(out))
@@ -59,7 +59,8 @@ def test_one_rank_bench_line_over_rccl(tmp_path):
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr", "127.0.0.1",
            "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "5", "--warmup", "2",
            "--users", "100000", "--dishes", "20000", "--pairs", "262144", "--topk-users", "4096", "--scaling-users", "200000",
-           "--settle-ms", "20", "--no-cpu-baseline", "--no-config-legs", "--no-projection", "--side-timeout", "240", "--out", out]
+           "--settle-ms", "20", "--no-cpu-baseline", "--no-config-legs", "--no-projection", "--side-timeout", "240", "--full",
+           "--out", out]
     res = subprocess.run(cmd, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=420)
     assert res.returncode == 0, res.stderr[-3000:]
     line = json.load(open(out))
