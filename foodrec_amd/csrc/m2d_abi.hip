@@ -137,6 +137,8 @@ void release(m2d_engine *h)
     if (h->topk_flags) (void)hipFree(h->topk_flags);
     if (h->topk_plan) (void)hipFree(h->topk_plan);
     if (h->topk_ex) (void)hipFree(h->topk_ex);
+    if (h->rank_buf) (void)hipFree(h->rank_buf);
+    if (h->rank_tnorm) (void)hipFree(h->rank_tnorm);
     if (h->err_dev) (void)hipFree(h->err_dev);
     if (h->err_host) (void)hipHostFree(h->err_host);
 }
@@ -503,6 +505,19 @@ int m2d_topk_users(m2d_engine *h, const int32_t *users, int64_t nU, int32_t k, f
     return m2d_launch_topk_users(h, users, nU, k, out_scores, out_ids, (hipStream_t)stream);
 }
 
+int m2d_catalogue_rank(m2d_engine *h, const int32_t *users, const int32_t *items, int64_t n, const int64_t *excl_off,
+                       const int32_t *excl_ids, int32_t *out_rank, float *out_scores, void *stream)
+{
+    if (!h) return M2D_ERR_INVALID_ARG;
+    if (n < 0) return fail(h, M2D_ERR_INVALID_ARG, "m2d_catalogue_rank: need n >= 0");
+    if (n == 0) return M2D_OK;
+    if (!users || !items || !out_rank || (excl_off && !excl_ids))
+        return fail(h, M2D_ERR_INVALID_ARG, "m2d_catalogue_rank: null buffer");
+    if (!h->dish_cats) return fail(h, M2D_ERR_NOT_CONFIGURED, "call m2d_set_dish_categories first");
+    M2D_HIP_TRY(h, hipSetDevice(h->device));
+    return m2d_launch_catalogue_rank(h, users, items, n, excl_off, excl_ids, out_rank, out_scores, (hipStream_t)stream);
+}
+
 int m2d_clear_ingredients(m2d_engine *h)
 {
     if (!h) return M2D_ERR_INVALID_ARG;
@@ -746,6 +761,11 @@ int m2d_check(m2d_engine *h, void *stream, int64_t *bad_value, int64_t *bad_inde
                         "words (stage " + std::to_string(value) + "): that call's lists are invalid";
         return code;
     }
+    if (code == M2D_ERR_INVALID_ARG) {              // m2d_catalogue_rank's exclusion lists
+        h->last_error = "m2d_catalogue_rank: exclusion list not ascending: value " + std::to_string(value) + " at position " +
+                        std::to_string(index) + " (an id below its predecessor in excl_ids, or an offset below its predecessor in excl_off)";
+        return code;
+    }
     const char *what = code == M2D_ERR_BAD_USER_ID ? "user" : code == M2D_ERR_BAD_ITEM_ID ? "item" : "ingredient";
     h->last_error = std::string(what) + " id " + std::to_string(value) + " at position " +
                     std::to_string(code == M2D_ERR_BAD_INGREDIENT ? (int64_t)h->err_host[2] : index) + " is out of range";
@@ -821,6 +841,18 @@ int m2d_get_option(const m2d_engine *h, const char *name, int64_t *value)
             *value = !strcmp(name, "topk_tiles_completed") ? (h->topk_apx_last ? (int64_t)v[1] : -1) : (int64_t)v[0];
         }
         else if (!strcmp(name, "topk_tiles_completed")) *value = -1;
+    }
+    else if (!strcmp(name, "rank_tiles_scanned") || !strcmp(name, "rank_resolved")) {
+        // diagnostic (synchronises the device): the last m2d_catalogue_rank call's 32-dish tiles multiplied by the count kernel,
+        // and the (query, dish) pairs it decided in the exact arithmetic
+        *value = 0;
+        if (h->rank_counters) {
+            unsigned long long v[2] = {0, 0};
+            if (hipSetDevice(h->device) != hipSuccess || hipDeviceSynchronize() != hipSuccess ||
+                hipMemcpy(v, h->rank_counters, sizeof v, hipMemcpyDeviceToHost) != hipSuccess)
+                return M2D_ERR_HIP;
+            *value = (int64_t)v[!strcmp(name, "rank_resolved") ? 1 : 0];
+        }
     }
     else if (!strcmp(name, "topk_grouped")) *value = h->opt_topk_grouped;
     else if (!strcmp(name, "mlp_bf16x3")) *value = h->opt_mlp_bf16x3;

@@ -8,6 +8,7 @@
 //   m2d_catalogue_scan_bf16.hip   m2d_topk_grouped_bf16 / _bf16_pipe2: the same scan on split-bf16 MFMA (the default, E = 64 / 128)
 //   m2d_catalogue_merge.hip       dish ranges' partial lists -> a user's list; near-tied lists finished in plain f32 (m2d_topk_refine)
 //   m2d_catalogue_repair.hip      users whose k-th score is tied three ways or more: re-ranked over their patterns in id order
+//   m2d_catalogue_rank.hip        m2d_catalogue_rank: a held-out dish's rank over the catalogue, in the repair's arithmetic
 //
 // Reference behaviour all of it reproduces: score = Model_Recommender.py:67-96 per (user, dish), ranking = heapq.nlargest
 // (evaluate.py:63: score descending, ties to the lower dish id, NaN last).
@@ -139,6 +140,11 @@ M2D_INTERNAL void m2d_topk_launch_tie_compact(const float *tie_final, int64_t nU
                                               int64_t I, int refined, hipStream_t st);
 M2D_INTERNAL void m2d_topk_launch_refine(const RefineArgs &f, bool flag_pass, hipStream_t st);
 M2D_INTERNAL int m2d_topk_launch_repair(m2d_engine *h, const RepairArgs &r, bool hv, hipStream_t st);
+// m2d_catalogue_plan.hip, for m2d_catalogue_rank: the sorted dish table (ensure_grouped, refresh_grouped_nonfinite), and the
+// sort of 8-float plan records by their word-5 pattern mask (m2d_plan_hist / _scan / _scatter; `hist`: PLAN_SORT_KEYS words)
+constexpr int PLAN_SORT_KEYS = 1 << 15;
+M2D_INTERNAL int m2d_grouped_tables(m2d_engine *h, hipStream_t st);
+M2D_INTERNAL int m2d_plan_sort_launch(m2d_engine *h, const float *plan, int64_t nU, int32_t *hist, int32_t *order, hipStream_t st);
 
 namespace {
 

@@ -683,6 +683,7 @@ int ensure_grouped(m2d_engine *h, hipStream_t st)
     h->grp_nonfinite = host[3] != 0;
     h->grp_nonfinite_known = true;
     h->grp_valid = true;
+    ++h->grp_gen;
     return M2D_OK;
 }
 
@@ -979,6 +980,31 @@ int launch_grouped(m2d_engine *h, const int E8, const int KR, const bool BF16X3,
 }
 
 }  // namespace
+
+// for m2d_catalogue_rank (m2d_catalogue_rank.hip): the sorted dish table and its "a table value is not finite" word, as a retrieval
+// call would have them
+int m2d_grouped_tables(m2d_engine *h, hipStream_t st)
+{
+    int rc;
+    if ((rc = ensure_grouped(h, st)) != M2D_OK) return rc;
+    return refresh_grouped_nonfinite(h, st);
+}
+
+// the counting sort of plan records (stride 8) by word 5, as a retrieval call sorts its users: `hist` holds PLAN_SORT_KEYS words
+int m2d_plan_sort_launch(m2d_engine *h, const float *plan, int64_t nU, int32_t *hist, int32_t *order, hipStream_t st)
+{
+    static_assert(PLAN_SORT_KEYS == PLAN_KEYS, "m2d_catalogue.h: PLAN_SORT_KEYS");
+    const size_t tab = (size_t)PLAN_KEYS * sizeof(int32_t);
+    const unsigned sblocks = (unsigned)((nU + 1023) / 1024 < 4 * h->num_cu ? (nU + 1023) / 1024 : 4 * h->num_cu);
+    M2D_HIP_TRY(h, hipMemsetAsync(hist, 0, tab, st));
+    M2D_HIP_TRY(h, m2d_lds_limit((const void *)m2d_plan_hist, (int)tab));
+    M2D_HIP_TRY(h, m2d_lds_limit((const void *)m2d_plan_scatter, (int)tab));
+    hipLaunchKernelGGL(m2d_plan_hist, dim3(sblocks), dim3(1024), tab, st, plan, nU, hist);
+    hipLaunchKernelGGL(m2d_plan_scan, dim3(1), dim3(1024), 0, st, hist);
+    hipLaunchKernelGGL(m2d_plan_scatter, dim3(sblocks), dim3(1024), tab, st, plan, nU, hist, order);
+    M2D_HIP_TRY(h, hipGetLastError());
+    return M2D_OK;
+}
 
 int m2d_launch_topk_users(m2d_engine *h, const int32_t *users, int64_t nU, int32_t k, float *out_scores,
                           int32_t *out_ids, hipStream_t stream)

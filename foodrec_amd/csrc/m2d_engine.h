@@ -87,6 +87,15 @@ struct m2d_engine {
     bool grp_valid = false, grp_binary = false;
     bool grp_nonfinite = false;         // *nonfinite_dev as last read by the retrieval launcher (with the table build, or again
     bool grp_nonfinite_known = false;   //  after a writer that leaves the sorted dish rows alone: m2d_write_memory on Personal_Memory)
+    uint64_t grp_gen = 0;               // counts the sorted table's builds (what is derived from it rebuilds with it)
+
+    // m2d_catalogue_rank (m2d_catalogue_rank.hip): per-query records | sort | counters, and the per-tile row-norm table
+    float *rank_buf = nullptr;
+    size_t rank_cap = 0;                // floats
+    unsigned long long *rank_counters = nullptr;   // [0] tiles multiplied, [1] (query, dish) pairs decided exactly, of the last call
+    float *rank_tnorm = nullptr;        // [tiles] largest row norm of each 32-row tile of the sorted table
+    int64_t rank_tnorm_cap = 0;
+    uint64_t rank_tnorm_gen = ~0ull;    // the grp_gen it was built for
 
     // training step: optimizer slots and gradient scratch, created by m2d_train_begin
     m2d_train_state *train = nullptr;
@@ -236,3 +245,5 @@ int m2d_launch_rank_candidates(m2d_engine *h, const int32_t *users, const int32_
                                int32_t *out_items, int32_t *out_flags, hipStream_t stream);
 int m2d_launch_topk_users(m2d_engine *h, const int32_t *users, int64_t nU, int32_t k, float *out_scores,
                           int32_t *out_ids, hipStream_t stream);
+int m2d_launch_catalogue_rank(m2d_engine *h, const int32_t *users, const int32_t *items, int64_t n, const int64_t *excl_off,
+                              const int32_t *excl_ids, int32_t *out_rank, float *out_scores, hipStream_t stream);

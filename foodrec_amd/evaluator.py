@@ -227,3 +227,38 @@ def evaluate_model(sess, model: Model, testRatings: Dict[str, List[int]], testNe
     for r in np.flatnonzero(flags & 1).tolist():            # NaN among the scores: the reference's host sequence
         hits[r], ndcgs[r] = eval_one_rating(model, plan.users[r], testRatings, testNegatives, K, dish_to_category)
     return hits, ndcgs
+
+
+def evaluate_model_full(sess, model: Model, testRatings: Dict[str, List[int]], trainRatings, K: int,
+                        dish_to_category: Dict[str, list]) -> Tuple[List[int], List[float]]:
+    """HR@K / NDCG@K under the full-ranking protocol: each user's held-out dish ``testRatings[u][0]`` ranked against the whole
+    catalogue, leaving out the dishes of ``trainRatings[u]`` (the split's training dict, ``Dataset.trainMatrix``; None = no
+    exclusion).  ``evaluate_model``'s argument order with ``trainRatings`` in the place of ``testNegatives``.
+
+    Per user, in ``testRatings`` order: ``hit = rank < K`` and ``ndcg = log 2 / log(rank + 2)`` if hit, else 0 -- getHitRatio /
+    getNDCG (evaluate.py:69-81) applied to the first K dishes of the filtered full ranking.  The rank is
+    ``ScoringEngine.catalogue_rank`` (one launch for all users, no limit on K).  ``dish_to_category`` becomes the engine's
+    resident mask table, as in ``evaluate_model``."""
+    if isinstance(K, bool) or not isinstance(K, (int, np.integer)) or K < 1:
+        raise ValueError("evaluate_model_full: K must be a positive int, got %r" % (K,))
+    if not testRatings:
+        return [], []
+    users = list(testRatings.keys())
+    for u in users:
+        if len(testRatings[u]) == 0:
+            raise TypeError("cannot unpack non-iterable NoneType object (user %s has no test rating)" % u)
+    held = [testRatings[u][0] for u in users]
+    eng = model.engine
+    model.set_dish_categories(dish_to_category)
+    exclude = None
+    if trainRatings is not None:
+        exclude = [trainRatings.get(u, ()) for u in users]
+    ranks, _ = eng.catalogue_rank(users, held, exclude)
+    eng.check()
+    ranks = ranks.cpu().numpy()
+    hit = ranks < K
+    hits: List[int] = hit.astype(np.int64).tolist()
+    ndcgs: List[float] = [0.0] * len(users)
+    for i in np.flatnonzero(hit).tolist():
+        ndcgs[i] = math.log(2) / math.log(int(ranks[i]) + 2)
+    return hits, ndcgs

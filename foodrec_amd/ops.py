@@ -33,6 +33,47 @@ def _dev_f32(x, device) -> torch.Tensor:
     return t.to(device=device, dtype=torch.float32).contiguous()
 
 
+def _int32_ids(x, what: str) -> np.ndarray:
+    """ids -> int32 array; an id outside the int32 range raises IndexError (as recommender._ids does)."""
+    a = np.asarray(x.cpu().numpy() if isinstance(x, torch.Tensor) else x)
+    if a.size == 0:
+        return np.zeros(0, dtype=np.int32)
+    if a.dtype.kind not in "iu":
+        a = np.array(a, dtype=np.int64)
+    a = a.astype(np.int64, copy=False).reshape(-1)
+    if a.min() < -(2 ** 31) or a.max() >= 2 ** 31:
+        raise IndexError("%s id does not fit int32" % what)
+    return a.astype(np.int32)
+
+
+def exclusion_csr(exclude, n: int):
+    """Per-query exclusion lists -> (offsets int64[n + 1], ids int32[nnz]), ids ascending and distinct within each query.
+
+    ``exclude``: a tuple ``(offsets, ids)``, or a list (any non-tuple sequence) of n id lists; ids in any order, repeats allowed.
+    Vectorised: one lexsort."""
+    if isinstance(exclude, tuple):
+        off = np.asarray(exclude[0].cpu().numpy() if isinstance(exclude[0], torch.Tensor) else exclude[0], dtype=np.int64).reshape(-1)
+        ids = _int32_ids(exclude[1], "excluded item")
+        if off.size != n + 1 or off[0] != 0 or np.any(np.diff(off) < 0) or off[-1] != ids.size:
+            raise ValueError("exclude: offsets must be non-decreasing from 0 to len(ids), n + 1 of them")
+        lens = np.diff(off)
+    else:
+        lists = list(exclude)
+        if len(lists) != n:
+            raise ValueError("exclude: %d lists for %d queries" % (len(lists), n))
+        lens = np.fromiter(map(len, lists), dtype=np.int64, count=n)
+        ids = _int32_ids(np.fromiter(itertools.chain.from_iterable(lists), dtype=np.int64, count=int(lens.sum())), "excluded item")
+    seg = np.repeat(np.arange(n, dtype=np.int64), lens)
+    o = np.lexsort((ids, seg))
+    seg, ids = seg[o], ids[o]
+    keep = np.ones(ids.size, dtype=bool)
+    keep[1:] = (seg[1:] != seg[:-1]) | (ids[1:] != ids[:-1])
+    seg, ids = seg[keep], ids[keep]
+    off = np.zeros(n + 1, dtype=np.int64)
+    np.cumsum(np.bincount(seg, minlength=n), out=off[1:])
+    return off, np.ascontiguousarray(ids, dtype=np.int32)
+
+
 class ScoringEngine:
     """Owns one ``m2d_engine`` and the HBM tables it borrows.
 
@@ -380,6 +421,45 @@ class ScoringEngine:
         _native.raise_for(rc, self._h)
         return out_s, out_i
 
+    def catalogue_rank(self, users, items, exclude=None):
+        """Full-catalogue rank of held-out dishes (``m2d_catalogue_rank``, include/m2d.h): for each query (users[i], items[i]) the
+        number of dishes ranked before items[i] in ``topk_users``' order, leaving out the query's excluded ids.
+
+        ``exclude``: None, a tuple ``(offsets, ids)`` (CSR, offsets of length n + 1), or a list of n per-query id lists; either form
+        is sorted and de-duplicated per query here.  Returns device tensors (ranks i32[n], held-out scores f32[n]) without
+        synchronising; out-of-range ids surface as IndexError from ``check()``."""
+        users = self._as_ids(users, "user")
+        items = self._as_ids(items, "item")
+        n = users.numel()
+        if items.numel() != n:
+            raise ValueError("catalogue_rank: users[%d] and items[%d] disagree" % (n, items.numel()))
+        off = ids = None
+        if exclude is not None:
+            off_np, ids_np = exclusion_csr(exclude, n)
+            off = torch.from_numpy(off_np).to(self.device)
+            ids = torch.from_numpy(ids_np).to(self.device) if ids_np.size else torch.zeros(1, dtype=torch.int32, device=self.device)
+        ranks = torch.empty(n, dtype=torch.int32, device=self.device)
+        scores = torch.empty(n, dtype=torch.float32, device=self.device)
+        if n == 0:
+            return ranks, scores
+        with torch.cuda.device(self.device):
+            rc = _native.lib().m2d_catalogue_rank(self._h, users.data_ptr(), items.data_ptr(), n,
+                                                  off.data_ptr() if off is not None else None,
+                                                  ids.data_ptr() if ids is not None else None,
+                                                  ranks.data_ptr(), scores.data_ptr(), _stream_ptr())
+        _native.raise_for(rc, self._h)
+        self._rank_keep = (users, items, off, ids)       # inputs stay alive until the queued kernels have read them
+        return ranks, scores
+
+    def _as_ids(self, x, what: str) -> torch.Tensor:
+        if isinstance(x, torch.Tensor):
+            if x.dtype != torch.int32:
+                raise TypeError("%s ids must be int32 tensors" % what)
+            if x.device != self.device:
+                raise NotImplementedError("m2d ops run on %s only; got %s" % (self.device, x.device))
+            return x.contiguous().reshape(-1)
+        return torch.from_numpy(_int32_ids(x, what)).to(self.device)
+
     def stream_read_probe(self, buf: torch.Tensor, sink: torch.Tensor):
         """Calibration only: plain streaming read of `buf` (achievable HBM read rate of this box)."""
         nbytes = buf.numel() * buf.element_size()
@@ -446,3 +526,17 @@ def topk_users_op(engine: int, users: torch.Tensor, k: int) -> tuple[torch.Tenso
 def _(engine, users, k):
     return (users.new_empty((users.numel(), k), dtype=torch.float32),
             users.new_empty((users.numel(), k), dtype=torch.int32))
+
+
+@torch.library.custom_op("m2d::catalogue_rank", mutates_args=(), device_types="cuda")
+def catalogue_rank_op(engine: int, users: torch.Tensor, items: torch.Tensor, excl_off: Optional[torch.Tensor] = None,
+                      excl_ids: Optional[torch.Tensor] = None) -> tuple[torch.Tensor, torch.Tensor]:
+    exclude = None if excl_off is None else (excl_off, excl_ids)
+    r, s = _engine(engine).catalogue_rank(users, items, exclude)
+    return r, s
+
+
+@catalogue_rank_op.register_fake
+def _(engine, users, items, excl_off=None, excl_ids=None):
+    return (users.new_empty((users.numel(),), dtype=torch.int32),
+            users.new_empty((users.numel(),), dtype=torch.float32))

@@ -127,6 +127,26 @@ int m2d_rank_candidates(m2d_engine *h, const int32_t *users, const int32_t *item
 int m2d_topk_users(m2d_engine *h, const int32_t *users, int64_t nU, int32_t k, float *out_scores,
                    int32_t *out_ids, void *stream);
 
+/* Full-catalogue rank (build-defined; the full-ranking protocol of leave-one-out evaluation).  A query is (user u, held-out dish p),
+ * X its optional set of excluded dish ids:
+ *     rank = #{ d in [0, I), d not in X, d != p : d precedes p }
+ * in m2d_topk_users' order (score descending, NaN scores last, equal scores -- NaN included -- to the lower dish id).  The score is the
+ * plain-f32 arithmetic m2d_topk_users finishes near-tied lists in (alpha_P from the retrieval plan's <U_high, CE_c>, a float4 column per
+ * lane of 16 in fmaf chains, the 16-lane rotation sum, alpha_P + b low / n_P; an empty mask scores NaN), so wherever retrieval lists are
+ * index-exact (default options: E = 32 / 64 with k <= 16, E = 128 with k <= 10) rank(u, ids[u][j]) == j for every listed dish.
+ * An id of X equal to p is ignored; repeated ids count once.
+ * For n queries (users[i], items[i]): out_rank i32[n] as defined above; out_scores f32[n] (may be NULL) receives the
+ * held-out dish's score in the ranking arithmetic.  excl_off i64[n + 1] (NULL = no exclusions) and excl_ids i32[excl_off[n]]
+ * are device memory; ids ascending within each segment.
+ * Needs the dish masks (M2D_ERR_NOT_CONFIGURED); C = 4, 0/1 masks, finite tables, E a multiple of 4 up to 256, no ingredient table
+ * and no MLP head -- anything else is M2D_ERR_UNSUPPORTED, the message naming the condition.  Bad user / held-out / excluded ids are
+ * latched as M2D_ERR_BAD_USER_ID / M2D_ERR_BAD_ITEM_ID and a segment that is not ascending as M2D_ERR_INVALID_ARG, reported by
+ * m2d_check with their positions (query index; for excluded ids the index into excl_ids).  Diagnostics: "rank_tiles_scanned",
+ * "rank_resolved" (m2d_get_option).  The m2d_topk_users diagnostics are left as they were. */
+int m2d_catalogue_rank(m2d_engine *h, const int32_t *users, const int32_t *items, int64_t n,
+                       const int64_t *excl_off, const int32_t *excl_ids,
+                       int32_t *out_rank, float *out_scores, void *stream);
+
 /* Memory write (training side).  Replaces Model.Write_Memory
  * (Model_Recommender.py:106-220) -- the `personal` / `general` fetches of Train_recommender.py:180-199 --
  * with an O(B (C+1) E) atomic scatter-add in place of the reference's dense one-hot matmuls:
@@ -226,6 +246,8 @@ int m2d_score_pairs_mlp(m2d_engine *h, const int32_t *users, const int32_t *item
 /* Synchronise `stream` and report (then clear) the first id error latched by kernels since the
  * previous check: M2D_OK, M2D_ERR_BAD_USER_ID or M2D_ERR_BAD_ITEM_ID.  TF-CPU GatherV2 raises
  * InvalidArgument for such ids; the kernels never read out of bounds and write NaN for the pair.
+ * M2D_ERR_INVALID_ARG: an exclusion list of m2d_catalogue_rank is not ascending (bad_value: the id or offset, bad_index: its
+ * position in excl_ids / excl_off).
  * bad_value / bad_index (host pointers, may be NULL) receive the offending id and its position. */
 int m2d_check(m2d_engine *h, void *stream, int64_t *bad_value, int64_t *bad_index);
 
@@ -293,6 +315,10 @@ int m2d_check(m2d_engine *h, void *stream, int64_t *bad_value, int64_t *bad_inde
  * topk_tiles_scanned     32-dish tiles the blocks stepped through;  topk_tiles_full: what they would have without pruning
  * topk_tiles_completed   the hi x hi first form (see topk_form): (wave, tile) pairs whose cross products were multiplied; -1 if another form ran
  * topk_block_users       users per block of that launch (128 or 256);  num_cu: compute units of the device
+ *
+ * ---- read-only diagnostics of the last m2d_catalogue_rank call (they synchronise the device) ------------------------------------------------
+ * rank_tiles_scanned     32-dish tiles the count kernel multiplied (tiles whose bound settled every query of a wave are counted unmultiplied)
+ * rank_resolved          (query, dish) pairs decided in the exact arithmetic
  */
 int m2d_set_option(m2d_engine *h, const char *name, int64_t value);
 int m2d_get_option(const m2d_engine *h, const char *name, int64_t *value);
