@@ -50,6 +50,7 @@ SIGNATURES = {
     "m2d_rank_candidates": (_c.c_int, [_vp, _vp, _vp, _vp, _i64, _i32, _i32, _vp, _vp, _vp, _vp]),
     "m2d_topk_users": (_c.c_int, [_vp, _vp, _i64, _i32, _vp, _vp, _vp]),
     "m2d_catalogue_rank": (_c.c_int, [_vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp]),
+    "m2d_topk_users_excluding": (_c.c_int, [_vp, _vp, _i64, _i32, _vp, _vp, _vp, _vp, _vp]),
     "m2d_set_ingredients": (_c.c_int, [_vp, _vp, _i64, _vp, _vp, _vp, _i64, _c.c_int]),
     "m2d_clear_ingredients": (_c.c_int, [_vp]),
     "m2d_score_pairs_ingredients": (_c.c_int, [_vp, _vp, _vp, _vp, _i64, _vp, _vp]),

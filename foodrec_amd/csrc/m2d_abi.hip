@@ -139,6 +139,7 @@ void release(m2d_engine *h)
     if (h->topk_ex) (void)hipFree(h->topk_ex);
     if (h->rank_buf) (void)hipFree(h->rank_buf);
     if (h->rank_tnorm) (void)hipFree(h->rank_tnorm);
+    if (h->excl_buf) (void)hipFree(h->excl_buf);
     if (h->err_dev) (void)hipFree(h->err_dev);
     if (h->err_host) (void)hipHostFree(h->err_host);
 }
@@ -518,6 +519,20 @@ int m2d_catalogue_rank(m2d_engine *h, const int32_t *users, const int32_t *items
     return m2d_launch_catalogue_rank(h, users, items, n, excl_off, excl_ids, out_rank, out_scores, (hipStream_t)stream);
 }
 
+int m2d_topk_users_excluding(m2d_engine *h, const int32_t *users, int64_t nU, int32_t k, const int64_t *excl_off,
+                             const int32_t *excl_ids, float *out_scores, int32_t *out_ids, void *stream)
+{
+    if (!h) return M2D_ERR_INVALID_ARG;
+    if (nU < 0 || k < 1 || k > 16 || (int64_t)k > h->I)
+        return fail(h, M2D_ERR_INVALID_ARG, "m2d_topk_users_excluding: need nU >= 0 and 1 <= k <= min(16, I)");
+    if (nU == 0) return M2D_OK;
+    if (!users || !out_scores || !out_ids || (excl_off && !excl_ids))
+        return fail(h, M2D_ERR_INVALID_ARG, "m2d_topk_users_excluding: null buffer");
+    if (!h->dish_cats) return fail(h, M2D_ERR_NOT_CONFIGURED, "call m2d_set_dish_categories first");
+    M2D_HIP_TRY(h, hipSetDevice(h->device));
+    return m2d_launch_topk_users_excluding(h, users, nU, k, excl_off, excl_ids, out_scores, out_ids, (hipStream_t)stream);
+}
+
 int m2d_clear_ingredients(m2d_engine *h)
 {
     if (!h) return M2D_ERR_INVALID_ARG;
@@ -761,8 +776,8 @@ int m2d_check(m2d_engine *h, void *stream, int64_t *bad_value, int64_t *bad_inde
                         "words (stage " + std::to_string(value) + "): that call's lists are invalid";
         return code;
     }
-    if (code == M2D_ERR_INVALID_ARG) {              // m2d_catalogue_rank's exclusion lists
-        h->last_error = "m2d_catalogue_rank: exclusion list not ascending: value " + std::to_string(value) + " at position " +
+    if (code == M2D_ERR_INVALID_ARG) {              // the exclusion lists of m2d_catalogue_rank / m2d_topk_users_excluding
+        h->last_error = "m2d_catalogue_rank / m2d_topk_users_excluding: exclusion list not ascending: value " + std::to_string(value) + " at position " +
                         std::to_string(index) + " (an id below its predecessor in excl_ids, or an offset below its predecessor in excl_off)";
         return code;
     }
@@ -796,6 +811,7 @@ int m2d_set_option(m2d_engine *h, const char *name, int64_t value)
     else if (!strcmp(name, "topk_block")) h->opt_topk_block = (int)value;
     else if (!strcmp(name, "topk_refine")) h->opt_topk_refine = (int)value;
     else if (!strcmp(name, "topk_grouped")) h->opt_topk_grouped = (int)value;
+    else if (!strcmp(name, "topk_excl_tier")) h->opt_topk_excl_tier = (int)value;
     else if (!strcmp(name, "mlp_bf16x3")) h->opt_mlp_bf16x3 = (int)value;
     else if (!strcmp(name, "mlp_form")) h->opt_mlp_form = (int)value;
     else if (!strcmp(name, "skip_masked")) h->opt_skip_masked = (int)value;
@@ -852,6 +868,22 @@ int m2d_get_option(const m2d_engine *h, const char *name, int64_t *value)
                 hipMemcpy(v, h->rank_counters, sizeof v, hipMemcpyDeviceToHost) != hipSuccess)
                 return M2D_ERR_HIP;
             *value = (int64_t)v[!strcmp(name, "rank_resolved") ? 1 : 0];
+        }
+    }
+    else if (!strcmp(name, "topk_excl_tier")) *value = h->opt_topk_excl_tier;
+    else if (!strcmp(name, "topk_excl_short") || !strcmp(name, "topk_excl_tiles_scanned")) {
+        // diagnostic (synchronises the device): users the last m2d_topk_users_excluding call sent to the exact scan, and the
+        // 32-dish tiles that scan multiplied
+        *value = 0;
+        const bool tiles = !strcmp(name, "topk_excl_tiles_scanned");
+        if (!tiles && h->excl_all_short >= 0) *value = h->excl_all_short;
+        else if (tiles ? h->excl_counters != nullptr : h->excl_short != nullptr) {
+            unsigned long long v = 0;
+            int32_t c = 0;
+            if (hipSetDevice(h->device) != hipSuccess || hipDeviceSynchronize() != hipSuccess ||
+                (tiles ? hipMemcpy(&v, h->excl_counters, sizeof v, hipMemcpyDeviceToHost) : hipMemcpy(&c, h->excl_short, sizeof c, hipMemcpyDeviceToHost)) != hipSuccess)
+                return M2D_ERR_HIP;
+            *value = tiles ? (int64_t)v : (int64_t)c;
         }
     }
     else if (!strcmp(name, "topk_grouped")) *value = h->opt_topk_grouped;

@@ -9,6 +9,7 @@
 //   m2d_catalogue_merge.hip       dish ranges' partial lists -> a user's list; near-tied lists finished in plain f32 (m2d_topk_refine)
 //   m2d_catalogue_repair.hip      users whose k-th score is tied three ways or more: re-ranked over their patterns in id order
 //   m2d_catalogue_rank.hip        m2d_catalogue_rank: a held-out dish's rank over the catalogue, in the repair's arithmetic
+//   m2d_catalogue_excl.hip        m2d_topk_users_excluding: the top k without each user's excluded dishes, in the same arithmetic
 //
 // Reference behaviour all of it reproduces: score = Model_Recommender.py:67-96 per (user, dish), ranking = heapq.nlargest
 // (evaluate.py:63: score descending, ties to the lower dish id, NaN last).
@@ -145,6 +146,8 @@ M2D_INTERNAL int m2d_topk_launch_repair(m2d_engine *h, const RepairArgs &r, bool
 constexpr int PLAN_SORT_KEYS = 1 << 15;
 M2D_INTERNAL int m2d_grouped_tables(m2d_engine *h, hipStream_t st);
 M2D_INTERNAL int m2d_plan_sort_launch(m2d_engine *h, const float *plan, int64_t nU, int32_t *hist, int32_t *order, hipStream_t st);
+// m2d_catalogue_rank.hip, for m2d_topk_users_excluding: the per-tile largest row norms of the sorted table (h->rank_tnorm), built once per table
+M2D_INTERNAL int m2d_rank_tile_norms_ensure(m2d_engine *h, hipStream_t st);
 
 namespace {
 
@@ -583,6 +586,167 @@ __device__ __forceinline__ void grouped_publish(float *ls, int32_t *li, const fl
             ex[0] = o.s1; ex[1] = __int_as_float(o.i1); ex[2] = o.s2; ex[3] = __int_as_float(o.i2); ex[4] = o.s3;
         }
     }
+}
+
+// =====================================================================================================
+// The ranking arithmetic and its bounds: what m2d_catalogue_rank (m2d_catalogue_rank.hip) and m2d_topk_users_excluding
+// (m2d_catalogue_excl.hip) share, so that a rank and a list position are the same integer.
+// =====================================================================================================
+__device__ __forceinline__ void rank_latch(int32_t *err, const int32_t code, const int32_t value, const int64_t pos)
+{
+    if (atomicCAS(&err[0], 0, code) == 0) {
+        err[1] = value;
+        err[2] = (int32_t)(pos & 0xffffffff);
+        err[3] = (int32_t)(pos >> 32);
+    }
+}
+
+// does dish (s, d) precede the held-out (t, p)?  score descending, NaN last, equal scores (NaN included) to the lower id
+__device__ __forceinline__ bool rank_precedes(const float s, const int32_t d, const float t, const int32_t p)
+{
+    if (d == p) return false;
+    if (t != t) return s == s || d < p;
+    return s > t || (s == t && d < p);
+}
+
+__device__ __forceinline__ int dish_pattern(const float *cats, const int64_t d)
+{
+    const v4f m = *reinterpret_cast<const v4f *>(cats + (size_t)d * 4);
+    return (m.x != 0.f ? 1 : 0) | (m.y != 0.f ? 2 : 0) | (m.z != 0.f ? 4 : 0) | (m.w != 0.f ? 8 : 0);
+}
+
+// A user's sums from 16 lanes (j = lane & 15), every lane returning the same bits: <U_high, CE_c> (hc) bit for bit as
+// m2d_topk_user_plan sums it; ha and G: the bound sums (any order: the bounds allow for it)
+__device__ __forceinline__ void rank_user_sums16(const v4f *pmu, const float *ce, const int E4, const int j, float (&hc)[4], float (&ha)[4],
+                                                 float (&G)[10])
+{
+    const v4f *ce4 = reinterpret_cast<const v4f *>(ce);
+#pragma unroll
+    for (int c = 0; c < 4; ++c) hc[c] = ha[c] = 0.f;
+#pragma unroll
+    for (int i = 0; i < 10; ++i) G[i] = 0.f;
+    for (int c4 = j; c4 < E4; c4 += 16) {
+        const v4f uh = pmu[c4];
+        v4f r[4];
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+            const v4f w = ce4[c * E4 + c4];
+            hc[c] += fmaf(uh.x, w.x, uh.y * w.y) + fmaf(uh.z, w.z, uh.w * w.w);
+            ha[c] += (fabsf(uh.x * w.x) + fabsf(uh.y * w.y)) + (fabsf(uh.z * w.z) + fabsf(uh.w * w.w));
+            r[c] = pmu[(c + 1) * E4 + c4];
+        }
+        int i = 0;
+#pragma unroll
+        for (int c = 0; c < 4; ++c)
+#pragma unroll
+            for (int d = c; d < 4; ++d, ++i) G[i] += fmaf(r[c].x, r[d].x, r[c].y * r[d].y) + fmaf(r[c].z, r[d].z, r[c].w * r[d].w);
+    }
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+        hc[c] = row16_sum(hc[c]);
+        ha[c] = row16_sum(ha[c]);
+    }
+#pragma unroll
+    for (int i = 0; i < 10; ++i) G[i] = row16_sum(G[i]);
+}
+
+// The same score as rank_exact_score16 below from ONE lane that holds w_P's float4 columns in registers (E <= 128), the dish row
+// wave-uniform: lane j's chain of the 16-lane form is the chain of part[j] here (float4 columns j, j + 16, ... in order),
+// row16_sum's rotations are the pairs (i, i + 8), (i, i + 4), (i, i + 2), (i, i + 1) -- float addition commutes, so every order
+// of a pair gives the same bits.
+template <int E4MAX>
+__device__ __forceinline__ float rank_exact_score_lane(const v4f (&w)[E4MAX], const v4f *row, const int E4, const float alpha, const float b,
+                                                       const float npat)
+{
+    float part[16];
+#pragma unroll
+    for (int i = 0; i < 16; ++i) part[i] = 0.f;
+#pragma unroll
+    for (int c4 = 0; c4 < E4MAX; ++c4) {
+        if (c4 < E4) {
+            const v4f it = row[c4];
+            part[c4 & 15] = fmaf(it.x, w[c4].x, fmaf(it.y, w[c4].y, fmaf(it.z, w[c4].z, fmaf(it.w, w[c4].w, part[c4 & 15]))));
+        }
+    }
+    float a8[8], a4[4];
+#pragma unroll
+    for (int i = 0; i < 8; ++i) a8[i] = part[i] + part[i + 8];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) a4[i] = a8[i] + a8[i + 4];
+    const float lo = (a4[0] + a4[2]) + (a4[1] + a4[3]);
+    return repair_score_planned(alpha, b, lo / npat);
+}
+
+// w_P's float4 columns for that form: the sum over the pattern's categories of U_low,c, in category order
+template <int E4MAX>
+__device__ __forceinline__ void rank_pattern_weights(v4f (&w)[E4MAX], const v4f *pmu, const int E4, const int pt)
+{
+#pragma unroll
+    for (int c4 = 0; c4 < E4MAX; ++c4) {
+        w[c4] = v4f{0.f, 0.f, 0.f, 0.f};
+        if (c4 < E4) {
+#pragma unroll
+            for (int c = 0; c < 4; ++c) w[c4] += ((pt >> c) & 1) ? pmu[(c + 1) * E4 + c4] : v4f{0.f, 0.f, 0.f, 0.f};
+        }
+    }
+}
+
+// The exact score of dish d for the user whose Personal_Memory block is pmu, 16 lanes (j = lane & 15): the repair's arithmetic step for
+// step -- w_P = sum over the pattern's categories of U_low,c (w += m ? row : 0), lane j's fmaf chain over the float4 columns j, j + 16, ...,
+// row16_sum, repair_score_planned(alpha_P, b, low / n_P).  Every lane returns the same bits.
+__device__ __forceinline__ float rank_exact_score16(const v4f *pmu, const float *re, const int E4, const int j, const int64_t d, const int pt,
+                                                    const float a, const float b, const float (&hc)[4])
+{
+    const v4f *r4 = reinterpret_cast<const v4f *>(re) + (size_t)d * E4;
+    float lo = 0.f;
+    for (int q = j; q < E4; q += 16) {
+        v4f w = v4f{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int c = 0; c < 4; ++c) w += ((pt >> c) & 1) ? pmu[(c + 1) * E4 + q] : v4f{0.f, 0.f, 0.f, 0.f};
+        const v4f it = r4[q];
+        lo = fmaf(it.x, w.x, fmaf(it.y, w.y, fmaf(it.z, w.z, fmaf(it.w, w.w, lo))));
+    }
+    lo = row16_sum(lo);
+    return repair_score_planned(repair_alpha(a, hc, pt), b, lo / (float)__builtin_popcount(pt));
+}
+
+// A pattern's bound with the row-norm bound a parameter: grouped_pattern_terms' expressions, operation for operation, with rmax
+// left out of the products it multiplies (reach = (c1 rmax) (1 + gam), W = cw rmax) -- so that a tile's largest row norm can take
+// the pattern's place.  What the bound holds for is any f32 / split-bf16 arithmetic of a score, the repair's included.
+struct RankBound {
+    float alpha, c1, cw, A, gam;
+};
+
+__device__ __forceinline__ RankBound rank_bound_terms(const float (&hc)[4], const float (&ha)[4], const float (&G)[10], const int pt, const float a,
+                                                      const float b, const int E)
+{
+    const float inv_n = 1.0f / (float)__builtin_popcount(pt);
+    const float gam = (float)(E + 32) * 1.1920929e-7f;
+    float hs = 0.f, as = 0.f, w2 = 0.f, S = 0.f;
+    int i = 0;
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+        hs += ((pt >> c) & 1) ? hc[c] : 0.f;
+        as += ((pt >> c) & 1) ? ha[c] : 0.f;
+        S += ((pt >> c) & 1) ? sqrtf(G[i]) : 0.f;
+#pragma unroll
+        for (int d = c; d < 4; ++d, ++i) w2 += (((pt >> c) & 1) && ((pt >> d) & 1)) ? (c == d ? G[i] : 2.f * G[i]) : 0.f;
+    }
+    RankBound r;
+    r.alpha = a * (hs * inv_n);
+    r.A = fabsf(a) * inv_n * as;
+    r.cw = fabsf(b) * inv_n * S;
+    r.c1 = (fabsf(b) * inv_n) * sqrtf(fmaxf(w2, 0.f) + gam * (S * S));
+    r.gam = gam;
+    return r;
+}
+
+__device__ __forceinline__ void rank_bound(const RankBound &r, const float rmax, float &lo, float &hi)
+{
+    const float reach = r.c1 * rmax * (1.0f + r.gam);
+    const float slack = 1e-4f * reach + r.gam * (r.A + r.cw * rmax) + 1e-30f;
+    lo = r.alpha - reach - slack;
+    hi = r.alpha + reach + slack;
 }
 
 #ifndef M2D_TOPK_HALF_BLOCKS

@@ -39,87 +39,6 @@ struct RankArgs {
     unsigned long long *counters;    // [0] tiles multiplied, [1] pairs decided in the exact arithmetic
 };
 
-__device__ __forceinline__ void rank_latch(int32_t *err, const int32_t code, const int32_t value, const int64_t pos)
-{
-    if (atomicCAS(&err[0], 0, code) == 0) {
-        err[1] = value;
-        err[2] = (int32_t)(pos & 0xffffffff);
-        err[3] = (int32_t)(pos >> 32);
-    }
-}
-
-// does dish (s, d) precede the held-out (t, p)?  score descending, NaN last, equal scores (NaN included) to the lower id
-__device__ __forceinline__ bool rank_precedes(const float s, const int32_t d, const float t, const int32_t p)
-{
-    if (d == p) return false;
-    if (t != t) return s == s || d < p;
-    return s > t || (s == t && d < p);
-}
-
-__device__ __forceinline__ int dish_pattern(const float *cats, const int64_t d)
-{
-    const v4f m = *reinterpret_cast<const v4f *>(cats + (size_t)d * 4);
-    return (m.x != 0.f ? 1 : 0) | (m.y != 0.f ? 2 : 0) | (m.z != 0.f ? 4 : 0) | (m.w != 0.f ? 8 : 0);
-}
-
-// The exact score of dish d for the user whose Personal_Memory block is pmu, 16 lanes (j = lane & 15): the repair's arithmetic step for
-// step -- w_P = sum over the pattern's categories of U_low,c (w += m ? row : 0), lane j's fmaf chain over the float4 columns j, j + 16, ...,
-// row16_sum, repair_score_planned(alpha_P, b, low / n_P).  Every lane returns the same bits.
-__device__ __forceinline__ float rank_exact_score16(const v4f *pmu, const float *re, const int E4, const int j, const int64_t d, const int pt,
-                                                    const float a, const float b, const float (&hc)[4])
-{
-    const v4f *r4 = reinterpret_cast<const v4f *>(re) + (size_t)d * E4;
-    float lo = 0.f;
-    for (int q = j; q < E4; q += 16) {
-        v4f w = v4f{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int c = 0; c < 4; ++c) w += ((pt >> c) & 1) ? pmu[(c + 1) * E4 + q] : v4f{0.f, 0.f, 0.f, 0.f};
-        const v4f it = r4[q];
-        lo = fmaf(it.x, w.x, fmaf(it.y, w.y, fmaf(it.z, w.z, fmaf(it.w, w.w, lo))));
-    }
-    lo = row16_sum(lo);
-    return repair_score_planned(repair_alpha(a, hc, pt), b, lo / (float)__builtin_popcount(pt));
-}
-
-// A pattern's bound with the row-norm bound a parameter: grouped_pattern_terms' expressions, operation for operation, with rmax
-// left out of the products it multiplies (reach = (c1 rmax) (1 + gam), W = cw rmax) -- so that a tile's largest row norm can take
-// the pattern's place.  What the bound holds for is any f32 / split-bf16 arithmetic of a score, the repair's included.
-struct RankBound {
-    float alpha, c1, cw, A, gam;
-};
-
-__device__ __forceinline__ RankBound rank_bound_terms(const float (&hc)[4], const float (&ha)[4], const float (&G)[10], const int pt, const float a,
-                                                      const float b, const int E)
-{
-    const float inv_n = 1.0f / (float)__builtin_popcount(pt);
-    const float gam = (float)(E + 32) * 1.1920929e-7f;
-    float hs = 0.f, as = 0.f, w2 = 0.f, S = 0.f;
-    int i = 0;
-#pragma unroll
-    for (int c = 0; c < 4; ++c) {
-        hs += ((pt >> c) & 1) ? hc[c] : 0.f;
-        as += ((pt >> c) & 1) ? ha[c] : 0.f;
-        S += ((pt >> c) & 1) ? sqrtf(G[i]) : 0.f;
-#pragma unroll
-        for (int d = c; d < 4; ++d, ++i) w2 += (((pt >> c) & 1) && ((pt >> d) & 1)) ? (c == d ? G[i] : 2.f * G[i]) : 0.f;
-    }
-    RankBound r;
-    r.alpha = a * (hs * inv_n);
-    r.A = fabsf(a) * inv_n * as;
-    r.cw = fabsf(b) * inv_n * S;
-    r.c1 = (fabsf(b) * inv_n) * sqrtf(fmaxf(w2, 0.f) + gam * (S * S));
-    r.gam = gam;
-    return r;
-}
-
-__device__ __forceinline__ void rank_bound(const RankBound &r, const float rmax, float &lo, float &hi)
-{
-    const float reach = r.c1 * rmax * (1.0f + r.gam);
-    const float slack = 1e-4f * reach + r.gam * (r.A + r.cw * rmax) + 1e-30f;
-    lo = r.alpha - reach - slack;
-    hi = r.alpha + reach + slack;
-}
-
 // ---- per query: checks, sums, s*, the patterns' classes ----------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void m2d_rank_plan(RankArgs p)
 {
@@ -142,35 +61,9 @@ __global__ __launch_bounds__(256) void m2d_rank_plan(RankArgs p)
         it = 0;
         bad = true;
     }
-    // <U_high, CE_c> (hc) bit for bit as m2d_topk_user_plan sums it; ha and G: the bound sums (any order: the bounds allow for it)
     const v4f *pmu = reinterpret_cast<const v4f *>(p.pm) + (size_t)ul * (5 * E4);
-    const v4f *ce4 = reinterpret_cast<const v4f *>(p.ce);
-    float hc[4] = {0.f, 0.f, 0.f, 0.f}, ha[4] = {0.f, 0.f, 0.f, 0.f}, G[10];
-#pragma unroll
-    for (int i = 0; i < 10; ++i) G[i] = 0.f;
-    for (int c4 = j; c4 < E4; c4 += 16) {
-        const v4f uh = pmu[c4];
-        v4f r[4];
-#pragma unroll
-        for (int c = 0; c < 4; ++c) {
-            const v4f w = ce4[c * E4 + c4];
-            hc[c] += fmaf(uh.x, w.x, uh.y * w.y) + fmaf(uh.z, w.z, uh.w * w.w);
-            ha[c] += (fabsf(uh.x * w.x) + fabsf(uh.y * w.y)) + (fabsf(uh.z * w.z) + fabsf(uh.w * w.w));
-            r[c] = pmu[(c + 1) * E4 + c4];
-        }
-        int i = 0;
-#pragma unroll
-        for (int c = 0; c < 4; ++c)
-#pragma unroll
-            for (int d = c; d < 4; ++d, ++i) G[i] += fmaf(r[c].x, r[d].x, r[c].y * r[d].y) + fmaf(r[c].z, r[d].z, r[c].w * r[d].w);
-    }
-#pragma unroll
-    for (int c = 0; c < 4; ++c) {
-        hc[c] = row16_sum(hc[c]);
-        ha[c] = row16_sum(ha[c]);
-    }
-#pragma unroll
-    for (int i = 0; i < 10; ++i) G[i] = row16_sum(G[i]);
+    float hc[4], ha[4], G[10];
+    rank_user_sums16(pmu, p.ce, E4, j, hc, ha, G);
     const int ppt = dish_pattern(p.cats, it);
     const float s = rank_exact_score16(pmu, p.re, E4, j, it, ppt, p.a, p.b, hc);
     // lane j >= 1 classifies pattern j
@@ -269,14 +162,7 @@ __global__ __launch_bounds__(256) void m2d_rank_count(RankArgs p)
         const float alpha = repair_alpha(p.a, hc, q);
         const float npat = (float)__builtin_popcount(q);
         v4f w[E4MAX];
-#pragma unroll
-        for (int c4 = 0; c4 < E4MAX; ++c4) {
-            w[c4] = v4f{0.f, 0.f, 0.f, 0.f};
-            if (c4 < E4) {
-#pragma unroll
-                for (int c = 0; c < 4; ++c) w[c4] += ((q >> c) & 1) ? pmu[(c + 1) * E4 + c4] : v4f{0.f, 0.f, 0.f, 0.f};
-            }
-        }
+        rank_pattern_weights<E4MAX>(w, pmu, E4, q);
         for (int64_t t = lo_t; t < hi_t; ++t) {
             const int64_t tile = tfirst + (t - c0);
             const int nrows = p.tile_info[tile] >> 8;
@@ -293,23 +179,7 @@ __global__ __launch_bounds__(256) void m2d_rank_count(RankArgs p)
                 const int64_t slot = tile * 32 + r;
                 const int32_t id = __builtin_amdgcn_readfirstlane(p.perm[slot]);
                 const v4f *row = rows4 + (size_t)slot * EW4;
-                float part[16];
-#pragma unroll
-                for (int i = 0; i < 16; ++i) part[i] = 0.f;
-#pragma unroll
-                for (int c4 = 0; c4 < E4MAX; ++c4) {
-                    if (c4 < E4) {
-                        const v4f it = row[c4];
-                        part[c4 & 15] = fmaf(it.x, w[c4].x, fmaf(it.y, w[c4].y, fmaf(it.z, w[c4].z, fmaf(it.w, w[c4].w, part[c4 & 15]))));
-                    }
-                }
-                float a8[8], a4[4];
-#pragma unroll
-                for (int i = 0; i < 8; ++i) a8[i] = part[i] + part[i + 8];
-#pragma unroll
-                for (int i = 0; i < 4; ++i) a4[i] = a8[i] + a8[i + 4];
-                const float lo = (a4[0] + a4[2]) + (a4[1] + a4[3]);
-                const float sc = repair_score_planned(alpha, p.b, lo / npat);
+                const float sc = rank_exact_score_lane<E4MAX>(w, row, E4, alpha, p.b, npat);
                 count += (need && rank_precedes(sc, id, s, pd)) ? 1 : 0;
             }
         }
@@ -432,6 +302,25 @@ __global__ __launch_bounds__(256) void m2d_rank_tile_norms(const float *rs, int6
 
 }  // namespace
 
+// h->rank_tnorm for the sorted table as it stands: rebuilt when the table was (grp_gen); also m2d_topk_users_excluding's tile bounds
+int m2d_rank_tile_norms_ensure(m2d_engine *h, hipStream_t st)
+{
+    const int64_t tiles = h->grp_tiles;
+    if (h->rank_tnorm_gen != h->grp_gen) {
+        if (h->rank_tnorm_cap < tiles + 1) {
+            if (h->rank_tnorm) M2D_HIP_TRY(h, hipFree(h->rank_tnorm));
+            h->rank_tnorm = nullptr; h->rank_tnorm_cap = 0;
+            M2D_HIP_TRY(h, hipMalloc((void **)&h->rank_tnorm, (size_t)(tiles + 1) * sizeof(float)));
+            h->rank_tnorm_cap = tiles + 1;
+        }
+        if (tiles > 0)
+            hipLaunchKernelGGL(m2d_rank_tile_norms, dim3((unsigned)((tiles + 3) / 4)), dim3(256), 0, st, h->grp_rs, tiles, h->E, h->grp_ew, h->rank_tnorm);
+        M2D_HIP_TRY(h, hipGetLastError());
+        h->rank_tnorm_gen = h->grp_gen;
+    }
+    return M2D_OK;
+}
+
 int m2d_launch_catalogue_rank(m2d_engine *h, const int32_t *users, const int32_t *items, int64_t n, const int64_t *excl_off,
                               const int32_t *excl_ids, int32_t *out_rank, float *out_scores, hipStream_t st)
 {
@@ -448,19 +337,7 @@ int m2d_launch_catalogue_rank(m2d_engine *h, const int32_t *users, const int32_t
     if ((rc = m2d_grouped_tables(h, st)) != M2D_OK) return rc;
     if (!h->grp_binary) return refuse("needs 0/1 dish masks (a mask weight is neither 0 nor 1)");
     if (h->grp_nonfinite) return refuse("needs finite tables (a table value is inf or NaN)");
-    const int64_t tiles = h->grp_tiles;
-    if (h->rank_tnorm_gen != h->grp_gen) {
-        if (h->rank_tnorm_cap < tiles + 1) {
-            if (h->rank_tnorm) M2D_HIP_TRY(h, hipFree(h->rank_tnorm));
-            h->rank_tnorm = nullptr; h->rank_tnorm_cap = 0;
-            M2D_HIP_TRY(h, hipMalloc((void **)&h->rank_tnorm, (size_t)(tiles + 1) * sizeof(float)));
-            h->rank_tnorm_cap = tiles + 1;
-        }
-        if (tiles > 0)
-            hipLaunchKernelGGL(m2d_rank_tile_norms, dim3((unsigned)((tiles + 3) / 4)), dim3(256), 0, st, h->grp_rs, tiles, h->E, h->grp_ew, h->rank_tnorm);
-        M2D_HIP_TRY(h, hipGetLastError());
-        h->rank_tnorm_gen = h->grp_gen;
-    }
+    if ((rc = m2d_rank_tile_norms_ensure(h, st)) != M2D_OK) return rc;
     // records [n, 8] | bound sums [n, 16] | order [n] | sort histogram | counters
     const size_t n4 = ((size_t)n + 3) & ~(size_t)3;
     const size_t need = (size_t)n * 24 + n4 + PLAN_SORT_KEYS + 8;

@@ -97,6 +97,14 @@ struct m2d_engine {
     int64_t rank_tnorm_cap = 0;
     uint64_t rank_tnorm_gen = ~0ull;    // the grp_gen it was built for
 
+    // m2d_topk_users_excluding (m2d_catalogue_excl.hip): unfiltered lists | short users | records | sort | counters | partial lists
+    float *excl_buf = nullptr;
+    size_t excl_cap = 0;                // floats
+    unsigned long long *excl_counters = nullptr;   // [0] tiles the exact scan multiplied in the last call
+    int32_t *excl_short = nullptr;      // [0] users the last call's filter sent to the exact scan
+    int64_t excl_all_short = -1;        // >= 0: the last call sent every user there (this many), the device word is not used
+    int opt_topk_excl_tier = 0;         // 0 = filter m2d_topk_users' lists where they are index-exact, exact scan for the rest; 2 = exact scan for all (A/B)
+
     // training step: optimizer slots and gradient scratch, created by m2d_train_begin
     m2d_train_state *train = nullptr;
 
@@ -247,3 +255,5 @@ int m2d_launch_topk_users(m2d_engine *h, const int32_t *users, int64_t nU, int32
                           int32_t *out_ids, hipStream_t stream);
 int m2d_launch_catalogue_rank(m2d_engine *h, const int32_t *users, const int32_t *items, int64_t n, const int64_t *excl_off,
                               const int32_t *excl_ids, int32_t *out_rank, float *out_scores, hipStream_t stream);
+int m2d_launch_topk_users_excluding(m2d_engine *h, const int32_t *users, int64_t nU, int32_t k, const int64_t *excl_off,
+                                    const int32_t *excl_ids, float *out_scores, int32_t *out_ids, hipStream_t stream);

@@ -74,6 +74,17 @@ def exclusion_csr(exclude, n: int):
     return off, np.ascontiguousarray(ids, dtype=np.int32)
 
 
+def topk_excluding_args(n_users: int, k, exclude):
+    """Host-side argument checks of ``topk_users_excluding``: k in 1..16; ``exclude`` None, or a list of ``n_users`` id lists /
+    an ``(offsets, ids)`` pair, which goes through ``exclusion_csr`` (sorted, de-duplicated, int32 range checked).
+    Returns (offsets int64[n + 1], ids int32[nnz]) or (None, None)."""
+    if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or not 1 <= int(k) <= 16:
+        raise ValueError("topk_users_excluding: k must be an int in 1..16, got %r" % (k,))
+    if exclude is None:
+        return None, None
+    return exclusion_csr(exclude, n_users)
+
+
 class ScoringEngine:
     """Owns one ``m2d_engine`` and the HBM tables it borrows.
 
@@ -451,6 +462,45 @@ class ScoringEngine:
         self._rank_keep = (users, items, off, ids)       # inputs stay alive until the queued kernels have read them
         return ranks, scores
 
+    def topk_users_excluding(self, users, k: int, exclude=None):
+        """``topk_users`` without each user's excluded dishes (``m2d_topk_users_excluding``, include/m2d.h): for users[i] the first k
+        dishes of the ranking over the catalogue less ``exclude[i]``, in ``catalogue_rank``'s order and arithmetic -- for the same
+        excluded set ``catalogue_rank(users[i], ids[i][j], exclude[i]) == j``.  Rows end in id -1 / NaN when fewer than k dishes remain.
+
+        ``exclude``: None, a list of n per-user id lists or an ``(offsets, ids)`` pair (sorted, de-duplicated and range-checked on the
+        host by ``exclusion_csr``) -- or, as is, a pair of device tensors (int64 offsets[n + 1], int32 ids, ascending within each
+        segment: the kernels check it).  Returns device tensors (scores f32[n, k], ids i32[n, k]) without synchronising; bad ids
+        and unsorted device segments surface from ``check()``."""
+        users = self._as_ids(users, "user")
+        n = users.numel()
+        raw = (isinstance(exclude, tuple) and len(exclude) == 2 and all(isinstance(t, torch.Tensor) and t.device == self.device for t in exclude))
+        if raw:
+            topk_excluding_args(n, k, None)
+            off, ids = exclude[0].contiguous(), exclude[1].contiguous()
+            if off.dtype != torch.int64 or ids.dtype != torch.int32 or off.numel() != n + 1:
+                raise ValueError("topk_users_excluding: device exclusions are (int64 offsets[%d], int32 ids)" % (n + 1))
+            if ids.numel() == 0:
+                ids = torch.zeros(1, dtype=torch.int32, device=self.device)
+        else:
+            off_np, ids_np = topk_excluding_args(n, k, exclude)
+            off = ids = None
+            if off_np is not None:
+                off = torch.from_numpy(off_np).to(self.device)
+                ids = torch.from_numpy(ids_np).to(self.device) if ids_np.size else torch.zeros(1, dtype=torch.int32, device=self.device)
+        k = int(k)
+        out_s = torch.empty((n, k), dtype=torch.float32, device=self.device)
+        out_i = torch.empty((n, k), dtype=torch.int32, device=self.device)
+        if n == 0:
+            return out_s, out_i
+        with torch.cuda.device(self.device):
+            rc = _native.lib().m2d_topk_users_excluding(self._h, users.data_ptr(), n, k,
+                                                        off.data_ptr() if off is not None else None,
+                                                        ids.data_ptr() if ids is not None else None,
+                                                        out_s.data_ptr(), out_i.data_ptr(), _stream_ptr())
+        _native.raise_for(rc, self._h)
+        self._excl_keep = (users, off, ids)              # inputs stay alive until the queued kernels have read them
+        return out_s, out_i
+
     def _as_ids(self, x, what: str) -> torch.Tensor:
         if isinstance(x, torch.Tensor):
             if x.dtype != torch.int32:
@@ -540,3 +590,17 @@ def catalogue_rank_op(engine: int, users: torch.Tensor, items: torch.Tensor, exc
 def _(engine, users, items, excl_off=None, excl_ids=None):
     return (users.new_empty((users.numel(),), dtype=torch.int32),
             users.new_empty((users.numel(),), dtype=torch.float32))
+
+
+@torch.library.custom_op("m2d::topk_users_excluding", mutates_args=(), device_types="cuda")
+def topk_users_excluding_op(engine: int, users: torch.Tensor, k: int, excl_off: Optional[torch.Tensor] = None,
+                            excl_ids: Optional[torch.Tensor] = None) -> tuple[torch.Tensor, torch.Tensor]:
+    exclude = None if excl_off is None else (excl_off, excl_ids)
+    s, i = _engine(engine).topk_users_excluding(users, k, exclude)
+    return s, i
+
+
+@topk_users_excluding_op.register_fake
+def _(engine, users, k, excl_off=None, excl_ids=None):
+    return (users.new_empty((users.numel(), k), dtype=torch.float32),
+            users.new_empty((users.numel(), k), dtype=torch.int32))

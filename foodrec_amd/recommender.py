@@ -333,13 +333,28 @@ class Model:
 
 
     # -- retrieval and build-defined extensions (no reference counterpart; DESIGN.md sections 4.3-4.4, 8) ---
-    def topk(self, users, k: int = 10):
+    def topk(self, users, k: int = 10, exclude=None):
         """The k best dishes of every user in `users` over the whole catalogue -- the ranking rule of
         evaluate.py:63 applied to all dishes instead of 51 candidates.  Needs `set_dish_categories`.
-        Returns (scores float32 [n, k], dish ids int32 [n, k])."""
+        Returns (scores float32 [n, k], dish ids int32 [n, k]).
+
+        `exclude` leaves out dishes per user (the ones already had): a dict such as ``Dataset.trainMatrix`` keyed by the user as
+        given in `users` (a missing key excludes nothing), or a list aligned with `users`.  The lists are then those
+        ``evaluate_model_full`` measures (``ScoringEngine.topk_users_excluding``: k <= 16; rows end in id -1 / NaN when fewer than k
+        dishes remain).  None: the unfiltered lists, as before."""
+        if exclude is not None:
+            from .ops import topk_excluding_args
+            if isinstance(exclude, dict):
+                exclude = [exclude.get(u, ()) for u in users]
+            elif len(exclude) != len(users):
+                raise ValueError("topk: %d exclusion lists for %d users" % (len(exclude), len(users)))
+            off, ids = topk_excluding_args(len(users), k, list(exclude))
         u = _ids(users, "user")
         ut = u.to(self.device, torch.int32) if isinstance(u, torch.Tensor) else torch.from_numpy(u).to(self.device)
-        s, i = torch.ops.m2d.topk_users(self.engine.id, ut, int(k))
+        if exclude is not None:
+            s, i = self.engine.topk_users_excluding(ut, int(k), (torch.from_numpy(off).to(self.device), torch.from_numpy(ids).to(self.device)))
+        else:
+            s, i = torch.ops.m2d.topk_users(self.engine.id, ut, int(k))
         self.engine.check()
         return s.cpu().numpy(), i.cpu().numpy()
 

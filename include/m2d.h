@@ -147,6 +147,31 @@ int m2d_catalogue_rank(m2d_engine *h, const int32_t *users, const int32_t *items
                        const int64_t *excl_off, const int32_t *excl_ids,
                        int32_t *out_rank, float *out_scores, void *stream);
 
+/* Full-catalogue retrieval without each user's excluded dishes (build-defined; the serving half of the full-ranking protocol).  For
+ * user i, X_i = excl_ids[excl_off[i] .. excl_off[i + 1]):  out_ids i32[nU, k] / out_scores f32[nU, k] receive the first k dishes of
+ * the ranking over { d in [0, I) : d not in X_i } in m2d_topk_users' order (score descending, NaN scores last, equal scores -- NaN
+ * included -- to the lower dish id).  Ids are decided and scores written in m2d_catalogue_rank's arithmetic, bit for bit that call's
+ * out_scores, so for the same user and X:  m2d_catalogue_rank(u, out_ids[u][j], X) == j  for every listed dish, whatever the options
+ * and the launch shape.  When fewer than k dishes remain the row ends in id -1 with a NaN score.
+ * excl_off i64[nU + 1] (NULL = no exclusions) and excl_ids are device memory, ids ascending within each segment, repeated ids count
+ * once (m2d_catalogue_rank's conventions).  1 <= k <= 16; k > I is M2D_ERR_INVALID_ARG as in m2d_topk_users.
+ * Two tiers, both exact.  Where m2d_topk_users' lists are index-exact (default retrieval options, E = 32 / 64 with K1 = 16, E = 128 with
+ * K1 = 10, k <= K1) the unfiltered top K1 is retrieved into engine scratch and filtered: it holds every dish that can precede its own
+ * last entry, so k survivors are the filtered top k.  Users with fewer survivors -- and every user for other E, larger k or
+ * non-default retrieval options -- take an exact scan with exclusions over the patterns that can reach their top k (m2d_catalogue_rank's
+ * tables, bounds and arithmetic; csrc/m2d_catalogue_excl.hip).  The call allocates nothing after its first launch of a size and
+ * never synchronises.
+ * Needs what m2d_catalogue_rank needs: dish masks (M2D_ERR_NOT_CONFIGURED); C = 4, 0/1 masks, finite tables, E a multiple of 4 up to
+ * 256, no ingredient table, no MLP head (M2D_ERR_UNSUPPORTED, the message naming the condition).  A bad user id or excluded id is
+ * latched as M2D_ERR_BAD_USER_ID / M2D_ERR_BAD_ITEM_ID, a segment (or offset) that is not ascending as M2D_ERR_INVALID_ARG; m2d_check
+ * reports them with the user index, or the index into excl_ids / excl_off.  The rows of a call with a latched error are unspecified.
+ * m2d_set_user_base is honoured (ids stay global).  Diagnostics: "topk_excl_short", "topk_excl_tiles_scanned"; A/B: "topk_excl_tier".
+ * The m2d_catalogue_rank diagnostics are left as they were; the m2d_topk_users diagnostics ("topk_*" below) afterwards describe
+ * the call's internal retrieval of K1 entries when the first tier ran, and are left as they were when it did not. */
+int m2d_topk_users_excluding(m2d_engine *h, const int32_t *users, int64_t nU, int32_t k,
+                             const int64_t *excl_off, const int32_t *excl_ids,
+                             float *out_scores, int32_t *out_ids, void *stream);
+
 /* Memory write (training side).  Replaces Model.Write_Memory
  * (Model_Recommender.py:106-220) -- the `personal` / `general` fetches of Train_recommender.py:180-199 --
  * with an O(B (C+1) E) atomic scatter-add in place of the reference's dense one-hot matmuls:
@@ -246,7 +271,7 @@ int m2d_score_pairs_mlp(m2d_engine *h, const int32_t *users, const int32_t *item
 /* Synchronise `stream` and report (then clear) the first id error latched by kernels since the
  * previous check: M2D_OK, M2D_ERR_BAD_USER_ID or M2D_ERR_BAD_ITEM_ID.  TF-CPU GatherV2 raises
  * InvalidArgument for such ids; the kernels never read out of bounds and write NaN for the pair.
- * M2D_ERR_INVALID_ARG: an exclusion list of m2d_catalogue_rank is not ascending (bad_value: the id or offset, bad_index: its
+ * M2D_ERR_INVALID_ARG: an exclusion list of m2d_catalogue_rank / m2d_topk_users_excluding is not ascending (bad_value: the id or offset, bad_index: its
  * position in excl_ids / excl_off).
  * bad_value / bad_index (host pointers, may be NULL) receive the offending id and its position. */
 int m2d_check(m2d_engine *h, void *stream, int64_t *bad_value, int64_t *bad_index);
@@ -300,6 +325,8 @@ int m2d_check(m2d_engine *h, void *stream, int64_t *bad_value, int64_t *bad_inde
  *                                        grid's launch order, 7 a user's dish ranges keep their thresholds apart (by default they meet in one atomic-max
  *                                        word per user, E = 64), 9 the tie repair reads every pattern's dishes.  Same lists, bit for bit.
  * topk_block       0        0 128 256    users per block of a pruned pipelined launch (0 = the launcher's choice)
+ * topk_excl_tier   0        0 / 2        m2d_topk_users_excluding: 0 = m2d_topk_users' lists filtered where they are index-exact, the exact scan
+ *                                        for the users left short and for every other case; 2 = the exact scan for every user.  Same ids, same score bits.
  * variant          0        7 9 11 12 13 14 15 16, 100 + n
  *                                        7 / 9: retrieval on the dense MFMA kernel / on the one-block-per-user kernel; 9 also forces the generic pair
  *                                        and head kernels; 11 / 12: the pair kernel's throughput / latency form whatever the batch size; 13: tie
@@ -319,6 +346,11 @@ int m2d_check(m2d_engine *h, void *stream, int64_t *bad_value, int64_t *bad_inde
  * ---- read-only diagnostics of the last m2d_catalogue_rank call (they synchronise the device) ------------------------------------------------
  * rank_tiles_scanned     32-dish tiles the count kernel multiplied (tiles whose bound settled every query of a wave are counted unmultiplied)
  * rank_resolved          (query, dish) pairs decided in the exact arithmetic
+ *
+ * ---- read-only diagnostics of the last m2d_topk_users_excluding call (they synchronise the device) ------------------------------------------
+ * topk_excl_short          users sent to the exact scan: those the filter left with fewer than k dishes, or all of them
+ * topk_excl_tiles_scanned  32-dish tiles the exact scan multiplied
+ * (the "topk_*" diagnostics above then describe the call's internal m2d_topk_users retrieval, if its first tier ran)
  */
 int m2d_set_option(m2d_engine *h, const char *name, int64_t value);
 int m2d_get_option(const m2d_engine *h, const char *name, int64_t *value);
