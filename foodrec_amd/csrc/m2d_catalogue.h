@@ -142,14 +142,26 @@ M2D_INTERNAL void m2d_topk_launch_tie_compact(const float *tie_final, int64_t nU
 M2D_INTERNAL void m2d_topk_launch_refine(const RefineArgs &f, bool flag_pass, hipStream_t st);
 M2D_INTERNAL int m2d_topk_launch_repair(m2d_engine *h, const RepairArgs &r, bool hv, hipStream_t st);
 // m2d_catalogue_plan.hip, for m2d_catalogue_rank: the sorted dish table (ensure_grouped, refresh_grouped_nonfinite), and the
-// sort of 8-float plan records by their word-5 pattern mask (m2d_plan_hist / _scan / _scatter; `hist`: PLAN_SORT_KEYS words)
-constexpr int PLAN_SORT_KEYS = 1 << 15;
+// sort of 8-float plan records by their word-5 pattern mask (m2d_plan_hist / _scan / _scatter; `hist`: PLAN_KEYS words)
+constexpr int PLAN_KEYS = 1 << 15;                         // a mask holds bits 1..15: key = mask >> 1
 M2D_INTERNAL int m2d_grouped_tables(m2d_engine *h, hipStream_t st);
-M2D_INTERNAL int m2d_plan_sort_launch(m2d_engine *h, const float *plan, int64_t nU, int32_t *hist, int32_t *order, hipStream_t st);
-// m2d_catalogue_rank.hip, for m2d_topk_users_excluding: the per-tile largest row norms of the sorted table (h->rank_tnorm), built once per table
-M2D_INTERNAL int m2d_rank_tile_norms_ensure(m2d_engine *h, hipStream_t st);
+M2D_INTERNAL int m2d_plan_sort_launch(m2d_engine *h, const float *plan, int64_t nU, int32_t *hist, int32_t *order, hipStream_t st,
+                                      bool hist_zeroed = false);
+// m2d_catalogue_rank.hip, also for m2d_topk_users_excluding (`entry`): the refusals of a model the ranking arithmetic does not cover, the
+// sorted dish table, the per-tile largest row norms of that table (h->rank_tnorm, built once per table)
+M2D_INTERNAL int m2d_rank_prepare(m2d_engine *h, const char *entry, hipStream_t st);
 
 namespace {
+
+// the engine's id-error latch (m2d_engine::err_dev): the first error of a call wins -- its code, the bad value, where it stood
+__device__ __forceinline__ void latch_error(int32_t *err, const int32_t code, const int32_t value, const int64_t pos)
+{
+    if (atomicCAS(&err[0], 0, code) == 0) {
+        err[1] = value;
+        err[2] = (int32_t)(pos & 0xffffffff);
+        err[3] = (int32_t)(pos >> 32);
+    }
+}
 
 __device__ __forceinline__ bool ahead(float v, float w)
 {
@@ -373,6 +385,7 @@ constexpr int GRP_KEYS = GRP_MAXPAT * GRP_NB;   // sort key = pattern * GRP_NB +
 //   [64..64+GRP_KEYS) first slot of each (pattern, bucket) key        [GRP_STAT..+4) row-norm statistics (floats)
 //   [GRP_RMAX..+16) largest row norm of each pattern (float bits; scan-start threshold, grouped_threshold_seed)
 constexpr int GRP_KEYOFF = 64, GRP_STAT = 64 + GRP_KEYS, GRP_RMAX = GRP_STAT + 8, GRP_WORDS = GRP_RMAX + 16;
+inline int32_t *grouped_grp(const m2d_engine *h) { return h->grp_work + (size_t)((h->I + 255) / 256) * GRP_KEYS; }   // (a histogram per 256 dishes)
 
 // float <-> int32 with the same order (an involution): thresholds of a user's dish ranges meet in one atomicMax word
 __device__ __forceinline__ int32_t thr_key(const float f)
@@ -413,12 +426,16 @@ struct PatternBound {
     float alpha, reach, slack;                              // lo = alpha - reach - slack, hi = alpha + reach + slack
 };
 
-__device__ __forceinline__ PatternBound grouped_pattern_terms(const float (&hc)[4], const float (&ha)[4], const float (&G)[10], const int32_t *grp,
-                                                              const int pt, const int k, const float a, const float b, const int E, float &lo,
-                                                              float &hi)
+// The bound's terms with the row-norm bound left a parameter (reach = (c1 rmax) (1 + gam), W = cw rmax), so that a tile's largest
+// row norm can take the pattern's place (m2d_catalogue_rank, m2d_topk_users_excluding).  This is the one statement of the formula:
+// the scan's plan, a rank and an exclusion list are the same integers because they all come through here.
+struct PatternBoundTerms {
+    float alpha, c1, cw, A, gam;
+};
+
+__device__ __forceinline__ PatternBoundTerms pattern_bound_terms(const float (&hc)[4], const float (&ha)[4], const float (&G)[10], const int pt,
+                                                                 const float a, const float b, const int E)
 {
-    const int rows = grp[40 + pt];                          // wave-uniform
-    const float rmax = __int_as_float(grp[GRP_RMAX + pt]);
     const float inv_n = 1.0f / (float)__builtin_popcount(pt);
     const float gam = (float)(E + 32) * 1.1920929e-7f;      // 2 (E + 32) 2^-24
     float hs = 0.f, as = 0.f, w2 = 0.f, S = 0.f;
@@ -431,13 +448,33 @@ __device__ __forceinline__ PatternBound grouped_pattern_terms(const float (&hc)[
 #pragma unroll
         for (int d = c; d < 4; ++d, ++i) w2 += (((pt >> c) & 1) && ((pt >> d) & 1)) ? (c == d ? G[i] : 2.f * G[i]) : 0.f;
     }
+    PatternBoundTerms r;
+    r.alpha = a * (hs * inv_n);                             // the scan kernels' own expression, bit for bit
+    r.A = fabsf(a) * inv_n * as;
+    r.cw = fabsf(b) * inv_n * S;
+    r.c1 = (fabsf(b) * inv_n) * sqrtf(fmaxf(w2, 0.f) + gam * (S * S));
+    r.gam = gam;
+    return r;
+}
+
+__device__ __forceinline__ PatternBound pattern_bound(const PatternBoundTerms &r, const float rmax, float &lo, float &hi)
+{
     PatternBound pb;
-    pb.alpha = a * (hs * inv_n);                            // the scan kernels' own expression, bit for bit
-    const float A = fabsf(a) * inv_n * as, W = fabsf(b) * inv_n * S * rmax;
-    pb.reach = (fabsf(b) * inv_n) * sqrtf(fmaxf(w2, 0.f) + gam * (S * S)) * rmax * (1.0f + gam);
-    pb.slack = 1e-4f * pb.reach + gam * (A + W) + 1e-30f;
-    lo = pb.alpha - pb.reach - pb.slack;                    // k dishes at or above this ...
-    hi = pb.alpha + pb.reach + pb.slack;                    // ... no dish of the pattern above this
+    pb.alpha = r.alpha;
+    pb.reach = r.c1 * rmax * (1.0f + r.gam);
+    pb.slack = 1e-4f * pb.reach + r.gam * (r.A + r.cw * rmax) + 1e-30f;
+    lo = pb.alpha - pb.reach - pb.slack;                    // the pattern's dishes at or above this ...
+    hi = pb.alpha + pb.reach + pb.slack;                    // ... none of them above this
+    return pb;
+}
+
+// the bound of pattern pt from the table's own largest row norm; lo only where the pattern holds k dishes, hi only where it holds any
+__device__ __forceinline__ PatternBound grouped_pattern_terms(const float (&hc)[4], const float (&ha)[4], const float (&G)[10], const int32_t *grp,
+                                                              const int pt, const int k, const float a, const float b, const int E, float &lo,
+                                                              float &hi)
+{
+    const int rows = grp[40 + pt];                          // wave-uniform
+    const PatternBound pb = pattern_bound(pattern_bound_terms(hc, ha, G, pt, a, b, E), __int_as_float(grp[GRP_RMAX + pt]), lo, hi);
     if (rows < k) lo = -INFINITY;                            // (branches, not selects: a wave-uniform select between a vector value and
     if (rows <= 0) hi = -INFINITY;                           //  a constant sent hipcc 7.2 into "Illegal instruction detected")
     return pb;
@@ -592,13 +629,44 @@ __device__ __forceinline__ void grouped_publish(float *ls, int32_t *li, const fl
 // The ranking arithmetic and its bounds: what m2d_catalogue_rank (m2d_catalogue_rank.hip) and m2d_topk_users_excluding
 // (m2d_catalogue_excl.hip) share, so that a rank and a list position are the same integer.
 // =====================================================================================================
-__device__ __forceinline__ void rank_latch(int32_t *err, const int32_t code, const int32_t value, const int64_t pos)
+// A CSR exclusion list -- offsets off[0 .. n], ascending dish ids per segment -- as both calls check it.  Offset q: non-decreasing from 0.
+__device__ __forceinline__ void csr_check_offset(const int64_t *off, const int64_t q, int32_t *err)
 {
-    if (atomicCAS(&err[0], 0, code) == 0) {
-        err[1] = value;
-        err[2] = (int32_t)(pos & 0xffffffff);
-        err[3] = (int32_t)(pos >> 32);
+    const int64_t o = off[q];
+    if ((q == 0 && o != 0) || (q > 0 && o < off[q - 1])) latch_error(err, M2D_ERR_INVALID_ARG, (int32_t)o, q);
+}
+
+// the segment position i lies in: the last q with off[q] <= i
+__device__ __forceinline__ int64_t csr_owner(const int64_t *off, const int64_t n, const int64_t i)
+{
+    int64_t lo = 0, hi = n;
+    while (hi - lo > 1) {
+        const int64_t mid = (lo + hi) >> 1;
+        if (off[mid] <= i) lo = mid; else hi = mid;
     }
+    return lo;
+}
+
+// The id x at position i: a dish of the catalogue, and not below the id before it in its segment q (set once x is in range).  Returns 0
+// for an id that is neither, 2 for one that repeats the id before it, else 1; `report`: whether this thread latches the violation -- the
+// callers' threads per id differ.
+__device__ __forceinline__ int csr_check_id(const int64_t *off, const int32_t *ids, const int64_t n, const int64_t I, const int64_t i,
+                                            const bool report, int32_t *err, int32_t &x, int64_t &q)
+{
+    x = ids[i];
+    int r = 1;
+    if (x < 0 || (int64_t)x >= I) {
+        if (report) latch_error(err, M2D_ERR_BAD_ITEM_ID, x, i);
+        r = 0;
+    } else {
+        q = csr_owner(off, n, i);
+        if (i > off[q]) {
+            const int32_t prev = ids[i - 1];
+            if (prev > x && report) latch_error(err, M2D_ERR_INVALID_ARG, x, i);
+            r = prev > x ? 0 : (prev == x ? 2 : 1);
+        }
+    }
+    return r;
 }
 
 // does dish (s, d) precede the held-out (t, p)?  score descending, NaN last, equal scores (NaN included) to the lower id
@@ -708,45 +776,6 @@ __device__ __forceinline__ float rank_exact_score16(const v4f *pmu, const float 
     }
     lo = row16_sum(lo);
     return repair_score_planned(repair_alpha(a, hc, pt), b, lo / (float)__builtin_popcount(pt));
-}
-
-// A pattern's bound with the row-norm bound a parameter: grouped_pattern_terms' expressions, operation for operation, with rmax
-// left out of the products it multiplies (reach = (c1 rmax) (1 + gam), W = cw rmax) -- so that a tile's largest row norm can take
-// the pattern's place.  What the bound holds for is any f32 / split-bf16 arithmetic of a score, the repair's included.
-struct RankBound {
-    float alpha, c1, cw, A, gam;
-};
-
-__device__ __forceinline__ RankBound rank_bound_terms(const float (&hc)[4], const float (&ha)[4], const float (&G)[10], const int pt, const float a,
-                                                      const float b, const int E)
-{
-    const float inv_n = 1.0f / (float)__builtin_popcount(pt);
-    const float gam = (float)(E + 32) * 1.1920929e-7f;
-    float hs = 0.f, as = 0.f, w2 = 0.f, S = 0.f;
-    int i = 0;
-#pragma unroll
-    for (int c = 0; c < 4; ++c) {
-        hs += ((pt >> c) & 1) ? hc[c] : 0.f;
-        as += ((pt >> c) & 1) ? ha[c] : 0.f;
-        S += ((pt >> c) & 1) ? sqrtf(G[i]) : 0.f;
-#pragma unroll
-        for (int d = c; d < 4; ++d, ++i) w2 += (((pt >> c) & 1) && ((pt >> d) & 1)) ? (c == d ? G[i] : 2.f * G[i]) : 0.f;
-    }
-    RankBound r;
-    r.alpha = a * (hs * inv_n);
-    r.A = fabsf(a) * inv_n * as;
-    r.cw = fabsf(b) * inv_n * S;
-    r.c1 = (fabsf(b) * inv_n) * sqrtf(fmaxf(w2, 0.f) + gam * (S * S));
-    r.gam = gam;
-    return r;
-}
-
-__device__ __forceinline__ void rank_bound(const RankBound &r, const float rmax, float &lo, float &hi)
-{
-    const float reach = r.c1 * rmax * (1.0f + r.gam);
-    const float slack = 1e-4f * reach + r.gam * (r.A + r.cw * rmax) + 1e-30f;
-    lo = r.alpha - reach - slack;
-    hi = r.alpha + reach + slack;
 }
 
 #ifndef M2D_TOPK_HALF_BLOCKS

@@ -408,12 +408,7 @@ int launch_mfma(m2d_engine *h, TopkArgs &a, float *final_s, int32_t *final_i, hi
     a.nsplit = nsplit;
     if (nsplit > 1) {
         const size_t need = (size_t)a.nU * nsplit * a.k * 8 + 256;
-        if (h->scratch_bytes < need) {
-            if (h->scratch) M2D_HIP_TRY(h, hipFree(h->scratch));
-            h->scratch = nullptr; h->scratch_bytes = 0;
-            M2D_HIP_TRY(h, hipMalloc((void **)&h->scratch, need));
-            h->scratch_bytes = need;
-        }
+        if (int rc = m2d_grow(h, h->scratch, h->scratch_bytes, need, 1)) return rc;
         a.out_scores = h->scratch;
         a.out_ids = reinterpret_cast<int32_t *>(h->scratch + (size_t)a.nU * nsplit * a.k);
     } else {

@@ -135,24 +135,11 @@ __device__ __forceinline__ void excl_list_store(const float (&ls)[EXCL_KR], cons
 __global__ __launch_bounds__(256) void m2d_topk_excl_check(ExclArgs p)
 {
     const int64_t t0 = (int64_t)blockIdx.x * 256 + threadIdx.x, nt = (int64_t)gridDim.x * 256;
-    for (int64_t q = t0; q <= p.nU; q += nt) {              // the offsets: non-decreasing from 0
-        const int64_t o = p.excl_off[q];
-        if ((q == 0 && o != 0) || (q > 0 && o < p.excl_off[q - 1])) rank_latch(p.err, M2D_ERR_INVALID_ARG, (int32_t)o, q);
-    }
+    for (int64_t q = t0; q <= p.nU; q += nt) csr_check_offset(p.excl_off, q, p.err);
     const int64_t nnz = p.excl_off[p.nU];
-    for (int64_t i = t0; i < nnz; i += nt) {
-        const int32_t x = p.excl_ids[i];
-        if (x < 0 || (int64_t)x >= p.I) {
-            rank_latch(p.err, M2D_ERR_BAD_ITEM_ID, x, i);
-            continue;
-        }
-        int64_t lo = 0, hi = p.nU;                          // the user: the last q with excl_off[q] <= i
-        while (hi - lo > 1) {
-            const int64_t mid = (lo + hi) >> 1;
-            if (p.excl_off[mid] <= i) lo = mid; else hi = mid;
-        }
-        if (i > p.excl_off[lo] && p.excl_ids[i - 1] > x) rank_latch(p.err, M2D_ERR_INVALID_ARG, x, i);
-    }
+    int32_t x;
+    int64_t user;
+    for (int64_t i = t0; i < nnz; i += nt) csr_check_id(p.excl_off, p.excl_ids, p.nU, p.I, i, true, p.err, x, user);      // (a thread per id)
 }
 
 // ---- tier 1: the unfiltered top K1 without the listed ids ----------------------------------------------------------------------------
@@ -165,7 +152,7 @@ __global__ __launch_bounds__(256) void m2d_topk_excl_filter(ExclArgs p)
     const int32_t uid = p.users[u];
     int64_t ul = (int64_t)uid - p.user_base;
     if (ul < 0 || ul >= p.U) {
-        if (j == 0) rank_latch(p.err, M2D_ERR_BAD_USER_ID, uid, u);
+        if (j == 0) latch_error(p.err, M2D_ERR_BAD_USER_ID, uid, u);
         return;                                             // (the rows of a call with a latched error are unspecified)
     }
     int64_t x0, x1;
@@ -208,7 +195,7 @@ __global__ __launch_bounds__(256) void m2d_topk_excl_plan(ExclArgs p)
         const int32_t uid = p.users[u];
         ul = (int64_t)uid - p.user_base;
         if (ul < 0 || ul >= p.U) {
-            if (j == 0) rank_latch(p.err, M2D_ERR_BAD_USER_ID, uid, u);
+            if (j == 0) latch_error(p.err, M2D_ERR_BAD_USER_ID, uid, u);
             u = -1;
         }
     }
@@ -282,7 +269,7 @@ __global__ __launch_bounds__(256) void m2d_topk_excl_scan(ExclArgs p)
 #pragma unroll
     for (int q = 1; q < GRP_MAXPAT; ++q) {
         float lo, hi;
-        rank_bound(rank_bound_terms(hc, ha, G, q, p.a, p.b, p.E), __int_as_float(p.grp[GRP_RMAX + q]), lo, hi);
+        pattern_bound(pattern_bound_terms(hc, ha, G, q, p.a, p.b, p.E), __int_as_float(p.grp[GRP_RMAX + q]), lo, hi);
         float v = ((mask >> q) & 1u) ? fmaxf(hi, -INFINITY) : -INFINITY;
 #pragma unroll
         for (int off = 32; off >= 1; off >>= 1) v = fmaxf(v, __shfl_xor(v, off, 64));
@@ -317,7 +304,7 @@ __global__ __launch_bounds__(256) void m2d_topk_excl_scan(ExclArgs p)
         const int64_t c0 = cum;
         cum += nt;
         if (lo_t >= hi_t) continue;
-        const RankBound rb = rank_bound_terms(hc, ha, G, q, p.a, p.b, p.E);
+        const PatternBoundTerms rb = pattern_bound_terms(hc, ha, G, q, p.a, p.b, p.E);
         const float alpha = repair_alpha(p.a, hc, q);
         const float npat = (float)__builtin_popcount(q);
         v4f w[E4MAX];
@@ -326,7 +313,7 @@ __global__ __launch_bounds__(256) void m2d_topk_excl_scan(ExclArgs p)
             const int64_t tile = tfirst + (t - c0);
             const int nrows = p.tile_info[tile] >> 8;
             float blo, bhi;
-            rank_bound(rb, p.tnorm[tile], blo, bhi);
+            pattern_bound(rb, p.tnorm[tile], blo, bhi);
             // the lane's k-th score, the seed while its list is not full; strict: a row equal to either must reach the insertion
             const float thr = li[EXCL_KR - 1] != EXCL_NONE ? ls[EXCL_KR - 1] : seed;
             if (__ballot(live && !(bhi < thr)) == 0ull) continue;
@@ -404,12 +391,12 @@ __global__ __launch_bounds__(256) void m2d_topk_excl_scan16(ExclArgs p)
         const int64_t c0 = cum;
         cum += nt;
         if (lo_t >= hi_t) continue;
-        const RankBound rb = rank_bound_terms(hc, ha, G, q, p.a, p.b, p.E);
+        const PatternBoundTerms rb = pattern_bound_terms(hc, ha, G, q, p.a, p.b, p.E);
         for (int64_t t = lo_t; t < hi_t; ++t) {
             const int64_t tile = tfirst + (t - c0);
             const int nrows = p.tile_info[tile] >> 8;
             float blo, bhi;
-            rank_bound(rb, p.tnorm[tile], blo, bhi);
+            pattern_bound(rb, p.tnorm[tile], blo, bhi);
             const float thr = li[EXCL_KR - 1] != EXCL_NONE ? ls[EXCL_KR - 1] : seed;
             if (bhi < thr) continue;                        // (the same in all 16 lanes)
             multiplied += 1ull;
@@ -484,20 +471,8 @@ __global__ __launch_bounds__(256) void m2d_topk_excl_merge(ExclArgs p)
 int m2d_launch_topk_users_excluding(m2d_engine *h, const int32_t *users, int64_t nU, int32_t k, const int64_t *excl_off,
                                     const int32_t *excl_ids, float *out_scores, int32_t *out_ids, hipStream_t st)
 {
-    auto refuse = [&](const char *why) {
-        h->last_error = std::string("m2d_topk_users_excluding: ") + why;
-        return M2D_ERR_UNSUPPORTED;
-    };
-    if (h->C != 4) return refuse("needs C = 4 categories");
-    if (h->E % 4 != 0 || h->E > 256) return refuse("needs E a multiple of 4 up to 256");
-    if (h->ing || h->dish_high) return refuse("the ingredient table is set (not supported)");
-    if (h->mlp_w1) return refuse("the MLP head is set (not supported)");
     int rc;
-    if ((rc = m2d_ensure_finite_scan(h, st)) != M2D_OK) return rc;
-    if ((rc = m2d_grouped_tables(h, st)) != M2D_OK) return rc;
-    if (!h->grp_binary) return refuse("needs 0/1 dish masks (a mask weight is neither 0 nor 1)");
-    if (h->grp_nonfinite) return refuse("needs finite tables (a table value is inf or NaN)");
-    if ((rc = m2d_rank_tile_norms_ensure(h, st)) != M2D_OK) return rc;
+    if ((rc = m2d_rank_prepare(h, "m2d_topk_users_excluding", st)) != M2D_OK) return rc;
 
     // tier 1 where m2d_topk_users' lists are index-exact against the ranking arithmetic (include/m2d.h), under the default options
     const int K1 = h->E == 128 ? 10 : 16;
@@ -513,18 +488,12 @@ int m2d_launch_topk_users_excluding(m2d_engine *h, const int32_t *users, int64_t
     // counters | partial lists: scores, ids [items, k]
     const size_t n4 = ((size_t)nU + 3) & ~(size_t)3;
     const size_t part = (size_t)items * (h->E <= 128 ? 64 : 1) * k;
-    const size_t need = (size_t)nU * 32 + (4 + n4) + (size_t)nU * 24 + n4 + PLAN_SORT_KEYS + 8 + 2 * part;
-    if (h->excl_cap < need) {
-        h->excl_counters = nullptr; h->excl_short = nullptr;
-        if (h->excl_buf) M2D_HIP_TRY(h, hipFree(h->excl_buf));
-        h->excl_buf = nullptr; h->excl_cap = 0;
-        M2D_HIP_TRY(h, hipMalloc((void **)&h->excl_buf, need * sizeof(float)));
-        h->excl_cap = need;
-    }
+    const size_t need = (size_t)nU * 32 + (4 + n4) + (size_t)nU * 24 + n4 + PLAN_KEYS + 8 + 2 * part;
+    if ((rc = m2d_grow(h, h->excl_buf, h->excl_cap, need, sizeof(float), h->excl_counters, h->excl_short)) != M2D_OK) return rc;
     ExclArgs a;
     a.pm = h->pm; a.re = h->re; a.ce = h->ce; a.cats = h->dish_cats; a.rs = h->grp_rs; a.tnorm = h->rank_tnorm;
     a.perm = h->grp_perm; a.tile_info = h->grp_tile_info;
-    a.grp = h->grp_work + (size_t)((h->I + 255) / 256) * GRP_KEYS;
+    a.grp = grouped_grp(h);
     a.users = users; a.excl_off = excl_off; a.excl_ids = excl_ids;
     a.nU = nU; a.U = h->U; a.I = h->I; a.user_base = h->user_base; a.E = h->E; a.ew = h->grp_ew; a.k = k; a.want = want; a.K1 = K1;
     a.all_short = tier1 ? 0 : 1; a.a = h->a; a.b = h->b;
@@ -536,8 +505,8 @@ int m2d_launch_topk_users_excluding(m2d_engine *h, const int32_t *users, int64_t
     a.bnd = a.plan + (size_t)nU * 8;
     int32_t *order = reinterpret_cast<int32_t *>(a.bnd + (size_t)nU * 16);
     int32_t *hist = order + n4;
-    a.counters = reinterpret_cast<unsigned long long *>(hist + PLAN_SORT_KEYS);
-    a.part_s = reinterpret_cast<float *>(hist + PLAN_SORT_KEYS + 8);
+    a.counters = reinterpret_cast<unsigned long long *>(hist + PLAN_KEYS);
+    a.part_s = reinterpret_cast<float *>(hist + PLAN_KEYS + 8);
     a.part_i = reinterpret_cast<int32_t *>(a.part_s + part);
     a.order = order;
     a.out_scores = out_scores; a.out_ids = out_ids; a.err = h->err_dev;

@@ -374,7 +374,6 @@ __global__ __launch_bounds__(256) void m2d_topk_user_plan(const float *pm, const
 // pass; one per wave and distinct mask, found with ballots: 50 us).  Now a workgroup counts its users in a 128-KiB LDS table
 // of all 32 768 keys and adds only the table's non-zero entries to the global counts; the scatter reserves a range per
 // non-zero entry the same way and places its users inside the ranges with LDS atomics.
-constexpr int PLAN_KEYS = 1 << 15;                         // a mask holds bits 1..15: key = mask >> 1
 __device__ __forceinline__ int plan_key(const float *plan, const int64_t u)
 {
     return (int)((__float_as_uint(plan[(size_t)u * 8 + 5]) >> 1) & (PLAN_KEYS - 1));
@@ -551,8 +550,7 @@ __global__ __launch_bounds__(256) void m2d_grp_first_ids(const float *cats, int6
 
 int32_t *grouped_first_ids(m2d_engine *h)                  // behind the row norms, in the table build's work area
 {
-    const size_t nblk = (size_t)((h->I + 255) / 256);
-    return h->grp_work + nblk * GRP_KEYS + GRP_WORDS + 4 + (size_t)h->I;
+    return grouped_grp(h) + GRP_WORDS + 4 + (size_t)h->I;
 }
 
 // 16 lanes per user: <U_high, CE_c> exactly as m2d_topk_user_plan sums it (a float4 column per lane, row rotations), alpha_P as
@@ -570,11 +568,7 @@ __global__ __launch_bounds__(256) void m2d_topk_high_level_only(const float *pm,
         const int32_t uid = users[u];
         ul = (int64_t)uid - user_base;
         if (ul < 0 || ul >= U) {
-            if (j == 0 && atomicCAS(&err[0], 0, M2D_ERR_BAD_USER_ID) == 0) {
-                err[1] = uid;
-                err[2] = (int32_t)(u & 0xffffffff);
-                err[3] = (int32_t)(u >> 32);
-            }
+            if (j == 0) latch_error(err, M2D_ERR_BAD_USER_ID, uid, u);
             ul = 0;
         }
     }
@@ -651,7 +645,7 @@ int ensure_grouped(m2d_engine *h, hipStream_t st)
         h->grp_cap_rows = cap_rows;
         h->grp_ew = EW;
     }
-    int32_t *blk_hist = h->grp_work, *grp = h->grp_work + (size_t)nblk * GRP_KEYS, *flags = grp + 32;
+    int32_t *blk_hist = h->grp_work, *grp = grouped_grp(h), *flags = grp + 32;
     float *stat = reinterpret_cast<float *>(grp + GRP_STAT);
     double *acc = reinterpret_cast<double *>(grp + GRP_WORDS);           // 8-byte aligned: nblk * GRP_KEYS and GRP_WORDS are even
     float *norm = reinterpret_cast<float *>(grp + GRP_WORDS + 4);
@@ -790,7 +784,7 @@ int launch_grouped(m2d_engine *h, const int E8, const int KR, const bool BF16X3,
     GroupedArgs a;
     a.pm = h->pm; a.ce = h->ce; a.rs = h->grp_rs; a.rs16 = reinterpret_cast<const __bf16 *>(h->grp_rs16);
     a.perm = h->grp_perm; a.tile_info = h->grp_tile_info;
-    a.grp = h->grp_work + (size_t)((h->I + 255) / 256) * GRP_KEYS;
+    a.grp = grouped_grp(h);
     a.users = users; a.nU = nU; a.U = h->U; a.user_base = h->user_base; a.k = k; a.tiles = h->grp_tiles;
     a.a = h->a; a.b = h->b; a.err = h->err_dev; a.dbg = g_m2d_diag_buffer; a.e_real = h->E;
     a.prog_limit = h->opt_variant == 15 ? 0 : (1 << 24);   // "variant" 15: test hook of the progress-word timeout
@@ -828,20 +822,16 @@ int launch_grouped(m2d_engine *h, const int E8, const int KR, const bool BF16X3,
         if (nsplit > 64) nsplit &= ~63;                      // two-pass merge: whole groups of 64 (6 or 7 blocks: 85 / 73 -> 64)
     }
     a.nsplit = nsplit;
-    // tie values (floats): per (user, split), per (user, group of 64 splits) when the merge takes two passes, per user;
-    // behind them the repair list (int32: count, users) and the repair's partial lists
-    const size_t tie_vals = (size_t)nU * (nsplit > 1 ? nsplit + (nsplit > 64 ? nsplit / 64 : 0) + 1 : 1);
-    const size_t tie_need = tie_vals + 1 + (size_t)nU + (size_t)2 * REPAIR_CAP * REPAIR_SPLITS * k;
-    if (h->topk_flags_cap < tie_need) {
-        h->topk_tie_list = nullptr; h->topk_tie_final = nullptr;     // (inside the buffer freed below)
-        if (h->topk_flags) M2D_HIP_TRY(h, hipFree(h->topk_flags));
-        h->topk_flags = nullptr; h->topk_flags_cap = 0;
-        M2D_HIP_TRY(h, hipMalloc((void **)&h->topk_flags, tie_need * sizeof(float)));
-        h->topk_flags_cap = tie_need;
-    }
-    float *tie_final = h->topk_flags + (nsplit > 1 ? (size_t)nU * (nsplit + (nsplit > 64 ? nsplit / 64 : 0)) : 0);
+    // What is kept per (user, dish range) -- a tie value, the left-out record -- has one layout: per user `nsplit` slots of the
+    // ranges, `nsplit / 64` slots of the groups of 64 when the merge takes two passes, then one final slot per user
+    const size_t slots_before = nsplit > 1 ? (size_t)nU * (nsplit + (nsplit > 64 ? nsplit / 64 : 0)) : 0, slots = slots_before + (size_t)nU;
+    int rc;
+    // tie values (a float per slot); behind them the repair list (int32: count, users) and the repair's partial lists
+    const size_t tie_need = slots + 1 + (size_t)nU + (size_t)2 * REPAIR_CAP * REPAIR_SPLITS * k;
+    if ((rc = m2d_grow(h, h->topk_flags, h->topk_flags_cap, tie_need, sizeof(float), h->topk_tie_list, h->topk_tie_final)) != M2D_OK) return rc;
+    float *tie_final = h->topk_flags + slots_before;
     a.tie_val = h->topk_flags;
-    int32_t *tie_list = reinterpret_cast<int32_t *>(h->topk_flags + tie_vals);
+    int32_t *tie_list = reinterpret_cast<int32_t *>(h->topk_flags + slots);
     const bool planned = !BF16X3 || pipe;                    // (the first-form bf16 kernel takes no plan)
     if (!planned) M2D_HIP_TRY(h, hipMemsetAsync(tie_list, 0, sizeof(int32_t), st));
     h->topk_tie_final = tie_final;
@@ -853,16 +843,10 @@ int launch_grouped(m2d_engine *h, const int E8, const int KR, const bool BF16X3,
                      (BF16X3 ? (pipe && !(E == 128 && KR == 16)) : E8 <= 16);
     float *ex_final = nullptr;
     if (ext) {
-        const size_t ex_need = ((size_t)nU * (nsplit > 1 ? nsplit + (nsplit > 64 ? nsplit / 64 : 0) + 1 : 1)) * 8 + (size_t)nU + 8;
-        if (h->topk_ex_cap < ex_need) {
-            h->topk_refine_counter = nullptr;                // (it points into the buffer freed below: nothing may read it if the allocation fails)
-            if (h->topk_ex) M2D_HIP_TRY(h, hipFree(h->topk_ex));
-            h->topk_ex = nullptr; h->topk_ex_cap = 0;
-            M2D_HIP_TRY(h, hipMalloc((void **)&h->topk_ex, ex_need * sizeof(float)));
-            h->topk_ex_cap = ex_need;
-        }
+        const size_t ex_need = slots * 8 + (size_t)nU + 8;   // records of 8 floats in the tie values' layout | counters | a word per user
+        if ((rc = m2d_grow(h, h->topk_ex, h->topk_ex_cap, ex_need, sizeof(float), h->topk_refine_counter)) != M2D_OK) return rc;
         a.ex_out = h->topk_ex;
-        ex_final = h->topk_ex + (nsplit > 1 ? (size_t)nU * (nsplit + (nsplit > 64 ? nsplit / 64 : 0)) * 8 : 0);
+        ex_final = h->topk_ex + slots_before * 8;
         h->topk_refine_counter = reinterpret_cast<int32_t *>(h->topk_ex + ex_need - (size_t)nU - 8);     // [0] refined [1] sent to the repair; [8 + u] user u's word
                                                                                                        // (zeroed by the plan kernel: no memset launch)
     } else {
@@ -871,12 +855,7 @@ int launch_grouped(m2d_engine *h, const int E8, const int KR, const bool BF16X3,
     const size_t tmp_entries = nsplit > 64 ? (size_t)nU * (nsplit / 64) * k : 0;
     if (nsplit > 1) {
         const size_t need = ((size_t)nU * nsplit * k + tmp_entries) * 8 + 256;
-        if (h->scratch_bytes < need) {
-            if (h->scratch) M2D_HIP_TRY(h, hipFree(h->scratch));
-            h->scratch = nullptr; h->scratch_bytes = 0;
-            M2D_HIP_TRY(h, hipMalloc((void **)&h->scratch, need));
-            h->scratch_bytes = need;
-        }
+        if ((rc = m2d_grow(h, h->scratch, h->scratch_bytes, need, 1)) != M2D_OK) return rc;
         a.out_scores = h->scratch;
         a.out_ids = reinterpret_cast<int32_t *>(h->scratch + (size_t)nU * nsplit * k);
     } else {
@@ -892,13 +871,7 @@ int launch_grouped(m2d_engine *h, const int E8, const int KR, const bool BF16X3,
         // top-k; users sorted by mask so that a block's 256 users share their patterns (a single block: no sort)
         const size_t nitems = (size_t)ublocks * nsplit;
         const size_t need = (size_t)nU * 8 + (size_t)nU + PLAN_KEYS + 8 + 2 * nitems;
-        if (h->topk_plan_cap < need) {
-            h->topk_tiles_counter = nullptr;                 // (inside the buffer freed below)
-            if (h->topk_plan) M2D_HIP_TRY(h, hipFree(h->topk_plan));
-            h->topk_plan = nullptr; h->topk_plan_cap = 0;
-            M2D_HIP_TRY(h, hipMalloc((void **)&h->topk_plan, need * sizeof(float)));
-            h->topk_plan_cap = need;
-        }
+        if ((rc = m2d_grow(h, h->topk_plan, h->topk_plan_cap, need, sizeof(float), h->topk_tiles_counter)) != M2D_OK) return rc;
         float *plan = h->topk_plan;
         int32_t *order = reinterpret_cast<int32_t *>(plan + (size_t)nU * 8), *hist = order + ((nU + 3) & ~(int64_t)3);      // hist: 16-B aligned
         unsigned long long *counter = reinterpret_cast<unsigned long long *>(hist + PLAN_KEYS);
@@ -918,14 +891,8 @@ int launch_grouped(m2d_engine *h, const int E8, const int KR, const bool BF16X3,
         a.plan = plan;
         // dish ranges of a user share their thresholds (pipelined kernel; "topk_prune" = 7 keeps them apart: A/B)
         if (BF16X3 && pipe && !HV && E == 64 && nsplit > 1 && h->opt_topk_prune != 7) a.shared_thr = reinterpret_cast<int32_t *>(plan) + 6;
-        if (sorted) {
-            const size_t tab = (size_t)PLAN_KEYS * sizeof(int32_t);
-            const unsigned sblocks = (unsigned)((nU + 1023) / 1024 < 4 * h->num_cu ? (nU + 1023) / 1024 : 4 * h->num_cu);
-            M2D_HIP_TRY(h, m2d_lds_limit((const void *)m2d_plan_hist, (int)tab));
-            M2D_HIP_TRY(h, m2d_lds_limit((const void *)m2d_plan_scatter, (int)tab));
-            hipLaunchKernelGGL(m2d_plan_hist, dim3(sblocks), dim3(1024), tab, st, plan, nU, hist);
-            hipLaunchKernelGGL(m2d_plan_scan, dim3(1), dim3(1024), 0, st, hist);
-            hipLaunchKernelGGL(m2d_plan_scatter, dim3(sblocks), dim3(1024), tab, st, plan, nU, hist, order);
+        if (sorted) {                                        // (the plan kernel has zeroed the histogram: three memset launches less per call)
+            if ((rc = m2d_plan_sort_launch(h, plan, nU, hist, order, st, true)) != M2D_OK) return rc;
             a.order = order;
         }
         if (a.order && nitems > (size_t)h->num_cu && h->opt_topk_prune != 5) {      // 5: grid order (A/B)
@@ -944,7 +911,7 @@ int launch_grouped(m2d_engine *h, const int E8, const int KR, const bool BF16X3,
     {
         const ScanShape shape{E, KR, BF16X3, HV, PAD, pipe, WV, a.ex_out != nullptr, apx};
         h->topk_apx_last = apx;
-        const int rc = BF16X3 ? m2d_topk_scan_bf16_launch(h, a, shape, grid, lds, st) : m2d_topk_scan_f32_launch(h, a, shape, grid, lds, st);
+        rc = BF16X3 ? m2d_topk_scan_bf16_launch(h, a, shape, grid, lds, st) : m2d_topk_scan_f32_launch(h, a, shape, grid, lds, st);
         if (rc != M2D_OK) return rc;
     }
     M2D_HIP_TRY(h, hipGetLastError());
@@ -966,13 +933,13 @@ int launch_grouped(m2d_engine *h, const int E8, const int KR, const bool BF16X3,
         r.plan = a.plan;
         r.all_patterns = h->opt_topk_prune == 9 ? 1 : 0;                     // "topk_prune" = 9: the repair reads every pattern (A/B)
         r.cap = h->opt_variant == 13 ? 2 : REPAIR_CAP;      // test hook: send all but two listed users to the one-block-per-user kernel
-        r.part_s = h->topk_flags + tie_vals + 1 + (size_t)nU;
+        r.part_s = h->topk_flags + slots + 1 + (size_t)nU;
         r.part_i = reinterpret_cast<int32_t *>(r.part_s + (size_t)REPAIR_CAP * REPAIR_SPLITS * k);
         if (nsplit == 1)                                     // (with dish ranges the last merge pass has listed the tied users)
             m2d_topk_launch_tie_compact(tie_final, nU, tie_list, final_s, final_i, (int)k, h->I, ext ? 1 : 0, st);
         if (ext)                                             // (may add to the repair's list; with dish ranges the last merge pass has
             m2d_topk_launch_refine(f, nsplit == 1, st);      //  flagged the near-tied users)
-        const int rc = m2d_topk_launch_repair(h, r, HV, st);
+        rc = m2d_topk_launch_repair(h, r, HV, st);
         if (rc != M2D_OK) return rc;
     }
     h->last_kernel = BF16X3 ? "m2d_topk_grouped_bf16x3" : "m2d_topk_grouped";      // both bf16 forms report this name
@@ -990,13 +957,13 @@ int m2d_grouped_tables(m2d_engine *h, hipStream_t st)
     return refresh_grouped_nonfinite(h, st);
 }
 
-// the counting sort of plan records (stride 8) by word 5, as a retrieval call sorts its users: `hist` holds PLAN_SORT_KEYS words
-int m2d_plan_sort_launch(m2d_engine *h, const float *plan, int64_t nU, int32_t *hist, int32_t *order, hipStream_t st)
+// the counting sort of plan records (stride 8) by word 5: `hist` holds PLAN_KEYS words, zeroed here unless the caller's kernels
+// have done so (`hist_zeroed`)
+int m2d_plan_sort_launch(m2d_engine *h, const float *plan, int64_t nU, int32_t *hist, int32_t *order, hipStream_t st, bool hist_zeroed)
 {
-    static_assert(PLAN_SORT_KEYS == PLAN_KEYS, "m2d_catalogue.h: PLAN_SORT_KEYS");
     const size_t tab = (size_t)PLAN_KEYS * sizeof(int32_t);
     const unsigned sblocks = (unsigned)((nU + 1023) / 1024 < 4 * h->num_cu ? (nU + 1023) / 1024 : 4 * h->num_cu);
-    M2D_HIP_TRY(h, hipMemsetAsync(hist, 0, tab, st));
+    if (!hist_zeroed) M2D_HIP_TRY(h, hipMemsetAsync(hist, 0, tab, st));
     M2D_HIP_TRY(h, m2d_lds_limit((const void *)m2d_plan_hist, (int)tab));
     M2D_HIP_TRY(h, m2d_lds_limit((const void *)m2d_plan_scatter, (int)tab));
     hipLaunchKernelGGL(m2d_plan_hist, dim3(sblocks), dim3(1024), tab, st, plan, nU, hist);

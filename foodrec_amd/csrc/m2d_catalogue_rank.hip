@@ -51,13 +51,13 @@ __global__ __launch_bounds__(256) void m2d_rank_plan(RankArgs p)
     const int32_t uid = p.users[q];
     int64_t ul = (int64_t)uid - p.user_base;
     if (ul < 0 || ul >= p.U) {
-        if (j == 0) rank_latch(p.err, M2D_ERR_BAD_USER_ID, uid, q);
+        if (j == 0) latch_error(p.err, M2D_ERR_BAD_USER_ID, uid, q);
         ul = 0;
         bad = true;
     }
     int32_t it = p.items[q];
     if (it < 0 || (int64_t)it >= p.I) {
-        if (j == 0) rank_latch(p.err, M2D_ERR_BAD_ITEM_ID, it, q);
+        if (j == 0) latch_error(p.err, M2D_ERR_BAD_ITEM_ID, it, q);
         it = 0;
         bad = true;
     }
@@ -158,7 +158,7 @@ __global__ __launch_bounds__(256) void m2d_rank_count(RankArgs p)
         cum += nt;
         if (lo_t >= hi_t) continue;
         const bool straddle = (mask >> q) & 1u;
-        const RankBound rb = rank_bound_terms(hc, ha, G, q, p.a, p.b, p.E);
+        const PatternBoundTerms rb = pattern_bound_terms(hc, ha, G, q, p.a, p.b, p.E);
         const float alpha = repair_alpha(p.a, hc, q);
         const float npat = (float)__builtin_popcount(q);
         v4f w[E4MAX];
@@ -167,7 +167,7 @@ __global__ __launch_bounds__(256) void m2d_rank_count(RankArgs p)
             const int64_t tile = tfirst + (t - c0);
             const int nrows = p.tile_info[tile] >> 8;
             float blo, bhi;
-            rank_bound(rb, p.tnorm[tile], blo, bhi);
+            pattern_bound(rb, p.tnorm[tile], blo, bhi);
             const bool ahead_t = straddle && blo > s;
             const bool need = straddle && !ahead_t && !(bhi < s);
             count += ahead_t ? nrows : 0;
@@ -237,31 +237,12 @@ __global__ __launch_bounds__(256) void m2d_rank_exclude(RankArgs p)
     const int64_t g0 = ((int64_t)blockIdx.x * 256 + threadIdx.x) >> 4, ng = ((int64_t)gridDim.x * 256) >> 4;
     const int E4 = p.E >> 2;
     // the offsets themselves: non-decreasing from 0
-    for (int64_t q = (int64_t)blockIdx.x * 256 + threadIdx.x; q <= p.n; q += (int64_t)gridDim.x * 256) {
-        const int64_t o = p.excl_off[q];
-        if ((q == 0 && o != 0) || (q > 0 && o < p.excl_off[q - 1])) rank_latch(p.err, M2D_ERR_INVALID_ARG, (int32_t)o, q);
-    }
+    for (int64_t q = (int64_t)blockIdx.x * 256 + threadIdx.x; q <= p.n; q += (int64_t)gridDim.x * 256) csr_check_offset(p.excl_off, q, p.err);
     const int64_t nnz = p.excl_off[p.n];
     for (int64_t i = g0; i < nnz; i += ng) {                // 16-lane-uniform
-        const int32_t x = p.excl_ids[i];
-        if (x < 0 || (int64_t)x >= p.I) {
-            if (j == 0) rank_latch(p.err, M2D_ERR_BAD_ITEM_ID, x, i);
-            continue;
-        }
-        int64_t lo = 0, hi = p.n;                           // the query: the last q with excl_off[q] <= i
-        while (hi - lo > 1) {
-            const int64_t mid = (lo + hi) >> 1;
-            if (p.excl_off[mid] <= i) lo = mid; else hi = mid;
-        }
-        const int64_t q = lo;
-        if (i > p.excl_off[q]) {
-            const int32_t prev = p.excl_ids[i - 1];
-            if (prev > x) {
-                if (j == 0) rank_latch(p.err, M2D_ERR_INVALID_ARG, x, i);
-                continue;
-            }
-            if (prev == x) continue;                        // a repeated id counts once
-        }
+        int32_t x;
+        int64_t q;                                          // the query
+        if (csr_check_id(p.excl_off, p.excl_ids, p.n, p.I, i, j == 0, p.err, x, q) != 1) continue;     // (a repeated id counts once)
         const float *rec = p.plan + (size_t)q * 8;
         const int32_t pd = __float_as_int(rec[6]);
         if (x == pd) continue;                              // p in its own list: ignored
@@ -302,30 +283,13 @@ __global__ __launch_bounds__(256) void m2d_rank_tile_norms(const float *rs, int6
 
 }  // namespace
 
-// h->rank_tnorm for the sorted table as it stands: rebuilt when the table was (grp_gen); also m2d_topk_users_excluding's tile bounds
-int m2d_rank_tile_norms_ensure(m2d_engine *h, hipStream_t st)
-{
-    const int64_t tiles = h->grp_tiles;
-    if (h->rank_tnorm_gen != h->grp_gen) {
-        if (h->rank_tnorm_cap < tiles + 1) {
-            if (h->rank_tnorm) M2D_HIP_TRY(h, hipFree(h->rank_tnorm));
-            h->rank_tnorm = nullptr; h->rank_tnorm_cap = 0;
-            M2D_HIP_TRY(h, hipMalloc((void **)&h->rank_tnorm, (size_t)(tiles + 1) * sizeof(float)));
-            h->rank_tnorm_cap = tiles + 1;
-        }
-        if (tiles > 0)
-            hipLaunchKernelGGL(m2d_rank_tile_norms, dim3((unsigned)((tiles + 3) / 4)), dim3(256), 0, st, h->grp_rs, tiles, h->E, h->grp_ew, h->rank_tnorm);
-        M2D_HIP_TRY(h, hipGetLastError());
-        h->rank_tnorm_gen = h->grp_gen;
-    }
-    return M2D_OK;
-}
-
-int m2d_launch_catalogue_rank(m2d_engine *h, const int32_t *users, const int32_t *items, int64_t n, const int64_t *excl_off,
-                              const int32_t *excl_ids, int32_t *out_rank, float *out_scores, hipStream_t st)
+// What m2d_catalogue_rank and m2d_topk_users_excluding (`entry`: the name their refusals carry) need before they launch: a model
+// the ranking arithmetic covers, the sorted dish table, and h->rank_tnorm for that table as it stands (rebuilt when the table
+// was: grp_gen)
+int m2d_rank_prepare(m2d_engine *h, const char *entry, hipStream_t st)
 {
     auto refuse = [&](const char *why) {
-        h->last_error = std::string("m2d_catalogue_rank: ") + why;
+        h->last_error = std::string(entry) + ": " + why;
         return M2D_ERR_UNSUPPORTED;
     };
     if (h->C != 4) return refuse("needs C = 4 categories");
@@ -337,29 +301,38 @@ int m2d_launch_catalogue_rank(m2d_engine *h, const int32_t *users, const int32_t
     if ((rc = m2d_grouped_tables(h, st)) != M2D_OK) return rc;
     if (!h->grp_binary) return refuse("needs 0/1 dish masks (a mask weight is neither 0 nor 1)");
     if (h->grp_nonfinite) return refuse("needs finite tables (a table value is inf or NaN)");
-    if ((rc = m2d_rank_tile_norms_ensure(h, st)) != M2D_OK) return rc;
+    const int64_t tiles = h->grp_tiles;
+    if (h->rank_tnorm_gen != h->grp_gen) {
+        if ((rc = m2d_grow(h, h->rank_tnorm, h->rank_tnorm_cap, (size_t)(tiles + 1), sizeof(float))) != M2D_OK) return rc;
+        if (tiles > 0)
+            hipLaunchKernelGGL(m2d_rank_tile_norms, dim3((unsigned)((tiles + 3) / 4)), dim3(256), 0, st, h->grp_rs, tiles, h->E, h->grp_ew, h->rank_tnorm);
+        M2D_HIP_TRY(h, hipGetLastError());
+        h->rank_tnorm_gen = h->grp_gen;
+    }
+    return M2D_OK;
+}
+
+int m2d_launch_catalogue_rank(m2d_engine *h, const int32_t *users, const int32_t *items, int64_t n, const int64_t *excl_off,
+                              const int32_t *excl_ids, int32_t *out_rank, float *out_scores, hipStream_t st)
+{
+    int rc;
+    if ((rc = m2d_rank_prepare(h, "m2d_catalogue_rank", st)) != M2D_OK) return rc;
     // records [n, 8] | bound sums [n, 16] | order [n] | sort histogram | counters
     const size_t n4 = ((size_t)n + 3) & ~(size_t)3;
-    const size_t need = (size_t)n * 24 + n4 + PLAN_SORT_KEYS + 8;
-    if (h->rank_cap < need) {
-        h->rank_counters = nullptr;
-        if (h->rank_buf) M2D_HIP_TRY(h, hipFree(h->rank_buf));
-        h->rank_buf = nullptr; h->rank_cap = 0;
-        M2D_HIP_TRY(h, hipMalloc((void **)&h->rank_buf, need * sizeof(float)));
-        h->rank_cap = need;
-    }
+    const size_t need = (size_t)n * 24 + n4 + PLAN_KEYS + 8;
+    if ((rc = m2d_grow(h, h->rank_buf, h->rank_cap, need, sizeof(float), h->rank_counters)) != M2D_OK) return rc;
     RankArgs a;
     a.pm = h->pm; a.re = h->re; a.ce = h->ce; a.cats = h->dish_cats; a.rs = h->grp_rs; a.tnorm = h->rank_tnorm;
     a.perm = h->grp_perm; a.tile_info = h->grp_tile_info;
     a.blk_hist = h->grp_work;                                // per 256-dish block: dishes of each key in the blocks before it
-    a.grp = h->grp_work + (size_t)((h->I + 255) / 256) * GRP_KEYS;
+    a.grp = grouped_grp(h);
     a.users = users; a.items = items; a.excl_off = excl_off; a.excl_ids = excl_ids;
     a.n = n; a.U = h->U; a.I = h->I; a.user_base = h->user_base; a.E = h->E; a.ew = h->grp_ew; a.a = h->a; a.b = h->b;
     a.plan = h->rank_buf;
     a.bnd = a.plan + (size_t)n * 8;
     int32_t *order = reinterpret_cast<int32_t *>(a.bnd + (size_t)n * 16);
     int32_t *hist = order + n4;
-    a.counters = reinterpret_cast<unsigned long long *>(hist + PLAN_SORT_KEYS);
+    a.counters = reinterpret_cast<unsigned long long *>(hist + PLAN_KEYS);
     h->rank_counters = a.counters;
     a.order = nullptr;
     a.out_rank = out_rank; a.out_scores = out_scores; a.err = h->err_dev;

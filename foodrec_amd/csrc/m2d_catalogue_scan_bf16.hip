@@ -40,11 +40,7 @@ __global__ __launch_bounds__(WAVES * 64) void m2d_topk_grouped_bf16(GroupedArgs 
         const int32_t uid = p.users[uidx];
         ul = (int64_t)uid - p.user_base;
         if (ul < 0 || ul >= p.U) {
-            if (atomicCAS(&p.err[0], 0, M2D_ERR_BAD_USER_ID) == 0) {
-                p.err[1] = uid;
-                p.err[2] = (int32_t)(uidx & 0xffffffff);
-                p.err[3] = (int32_t)(uidx >> 32);
-            }
+            latch_error(p.err, M2D_ERR_BAD_USER_ID, uid, uidx);
             ul = 0;
         }
     }
@@ -351,11 +347,7 @@ __global__ __launch_bounds__(WAVES * 64, 2) void m2d_topk_grouped_bf16_pipe2(Gro
         if (uvalid[g]) {
             ul = (int64_t)uid - p.user_base;
             if (ul < 0 || ul >= p.U) {
-                if (atomicCAS(&p.err[0], 0, M2D_ERR_BAD_USER_ID) == 0) {
-                    p.err[1] = uid;
-                    p.err[2] = uidx[g];
-                    p.err[3] = 0;
-                }
+                latch_error(p.err, M2D_ERR_BAD_USER_ID, uid, uidx[g]);
                 ul = 0;
             }
         }

@@ -46,11 +46,7 @@ __global__ __launch_bounds__(WAVES * 64) void m2d_topk_grouped(GroupedArgs p)
         const int64_t ul64 = (int64_t)uid - p.user_base;
         ul = (int)ul64;
         if (ul64 < 0 || ul64 >= p.U) {
-            if (atomicCAS(&p.err[0], 0, M2D_ERR_BAD_USER_ID) == 0) {
-                p.err[1] = uid;
-                p.err[2] = uidx;
-                p.err[3] = 0;
-            }
+            latch_error(p.err, M2D_ERR_BAD_USER_ID, uid, uidx);
             ul = 0;
         }
     }

@@ -164,6 +164,22 @@ struct m2d_engine {
         }                                                                                      \
     } while (0)
 
+// Grow one of the engine's device buffers to `need` units of `unit` bytes (`cap` counts the same units); nothing happens while
+// the capacity suffices.  `inside` are the engine's pointers into the old block: they are null before it is freed and stay null
+// when the allocation fails -- m2d_get_option reads through them -- and the buffer is then null with capacity 0.
+template <typename T, typename Cap, typename... Inside>
+static inline int m2d_grow(m2d_engine *h, T *&buf, Cap &cap, const size_t need, const size_t unit, Inside *&...inside)
+{
+    if ((size_t)cap >= need) return M2D_OK;
+    ((inside = nullptr), ...);
+    if (buf) M2D_HIP_TRY(h, hipFree(buf));
+    buf = nullptr;
+    cap = 0;
+    M2D_HIP_TRY(h, hipMalloc((void **)&buf, need * unit));
+    cap = (Cap)need;
+    return M2D_OK;
+}
+
 // hipFuncSetAttribute(MaxDynamicSharedMemorySize) once per kernel and size: a retrieval call makes six such calls, each a
 // trip into the runtime, for a value that does not change (8 us of a 50 us host-side call)
 // (The attribute belongs to the function ON A DEVICE, and a process may hold engines on several -- m2d_create(device): the
@@ -187,7 +203,7 @@ static inline hipError_t m2d_lds_limit(const void *fn, int bytes)
 // a * x + b * y as TF's Mul, Mul, Add compute Model_Recommender.py:95-96: two rounded products, one rounded sum.
 // __fadd_rn(__fmul_rn(a, x), __fmul_rn(b, y)) does not guarantee that -- the device library's bodies carry the `contract` flag,
 // and hipcc 7.2 fused the second product into the add (v_fmac, one rounding fewer) in SOME copies of an unrolled loop: the same
-// (user, dish) then scored one ulp apart depending on the slot it was computed in (m2d_catalogue.hip, repair scan).  Plain
+// (user, dish) then scored one ulp apart depending on the slot it was computed in (m2d_catalogue_repair.hip, repair scan).  Plain
 // operators under `fp contract(off)` carry no such flag, also after inlining.
 __device__ __forceinline__ float m2d_blend_unfused(const float a, const float x, const float b, const float y)
 {
@@ -197,7 +213,7 @@ __device__ __forceinline__ float m2d_blend_unfused(const float a, const float x,
     return p + q;
 }
 
-// ---- device helpers shared by the LDS-DMA kernels (m2d_catalogue.hip, m2d_mlp.hip) ----
+// ---- device helpers shared by the LDS-DMA kernels (m2d_catalogue_*.hip, m2d_mlp.hip) ----
 // vmcnt(0) twice over: the builtin is an s_waitcnt the compiler's own counter model sees (so it stops assuming that
 // loads from a previous loop trip are still in flight), the asm one cannot be optimised away on the grounds that
 // the compiler knows of nothing outstanding (the DMA ops below are hidden from it).

@@ -1228,13 +1228,7 @@ int m2d_launch_score_pairs_mlp(m2d_engine *h, const int32_t *users, const int32_
         if (group) {
             tiles_max += npat;
             const size_t need = (size_t)(PG_MAXPAT + 4) + (size_t)tiles_max + (size_t)tiles_max * PC_PAIRS;
-            if (need > h->mlp_pg_cap) {
-                if (h->mlp_pg) M2D_HIP_TRY(h, hipFree(h->mlp_pg));
-                h->mlp_pg = nullptr;
-                h->mlp_pg_cap = 0;
-                M2D_HIP_TRY(h, hipMalloc((void **)&h->mlp_pg, need * sizeof(int32_t)));
-                h->mlp_pg_cap = need;
-            }
+            if (int rc = m2d_grow(h, h->mlp_pg, h->mlp_pg_cap, need, sizeof(int32_t))) return rc;
             if (!h->mlp_pat8 || h->mlp_pat8_gen != h->dish_vec_gen || h->mlp_pat8_rows != h->I) {      // once per mask table
                 if (h->mlp_pat8 && h->mlp_pat8_rows != h->I) { M2D_HIP_TRY(h, hipFree(h->mlp_pat8)); h->mlp_pat8 = nullptr; }
                 if (!h->mlp_pat8) M2D_HIP_TRY(h, hipMalloc((void **)&h->mlp_pat8, (size_t)h->I));

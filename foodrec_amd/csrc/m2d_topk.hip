@@ -10,13 +10,7 @@ namespace {
 int ensure_scratch(m2d_engine *h, size_t bytes)
 {
     if (h->scratch_bytes >= bytes) return M2D_OK;
-    if (h->scratch) M2D_HIP_TRY(h, hipFree(h->scratch));
-    h->scratch = nullptr;
-    h->scratch_bytes = 0;
-    size_t want = bytes + (bytes >> 2);
-    M2D_HIP_TRY(h, hipMalloc((void **)&h->scratch, want));
-    h->scratch_bytes = want;
-    return M2D_OK;
+    return m2d_grow(h, h->scratch, h->scratch_bytes, bytes + (bytes >> 2), 1);      // a quarter more than asked for
 }
 
 // users[s] -> one id per candidate slot; padded slots (pos >= len) score dish 0 and are ignored later

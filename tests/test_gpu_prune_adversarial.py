@@ -1,5 +1,5 @@
 """Retrieval's pruning bounds under cancellation (`m2d_topk_users`, option "topk_prune"; bounds in
-csrc/m2d_catalogue.hip::grouped_pattern_terms).
+csrc/m2d_catalogue.h::grouped_pattern_terms).
 
 A pruned call leaves out every mask pattern whose upper bound alpha_P + |w_P| max|r| is below a scan-start bound of the
 user's k-th score (Model_Recommender.py:82-96 collapsed per pattern; the ranking itself is evaluate.py:63).  The bounds
