@@ -749,7 +749,7 @@ int launch_grouped(m2d_engine *h, const int E8, const int KR, const bool BF16X3,
                            h->user_base, h->E, grouped_first_ids(h), (int)k, h->a, h->I, final_s, final_i, h->err_dev);
         M2D_HIP_TRY(h, hipGetLastError());
         h->topk_tie_list = nullptr; h->topk_refine_counter = nullptr; h->topk_tiles_counter = nullptr;      // (diagnostics: nothing was scanned)
-        h->topk_tiles_full = 0; h->topk_flags_used = nU;
+        h->topk_tiles_full = 0;
         h->last_kernel = "m2d_topk_high_level_only";
         return M2D_OK;
     }
@@ -836,7 +836,6 @@ int launch_grouped(m2d_engine *h, const int E8, const int KR, const bool BF16X3,
     if (!planned) M2D_HIP_TRY(h, hipMemsetAsync(tie_list, 0, sizeof(int32_t), st));
     h->topk_tie_final = tie_final;
     h->topk_tie_list = tie_list;
-    h->topk_flags_used = nU;
     // what the lists leave out, for m2d_topk_refine (kernels that keep it: see EXT in the scan kernels)
     // (a user's word is its position in the call | left-out dishes to take along << 30: calls of 2^30 users or more go without)
     const bool ext = planned && h->opt_topk_refine != 0 && !HV && !PAD && nU < ((int64_t)1 << 30) &&
@@ -986,7 +985,7 @@ int m2d_launch_topk_users(m2d_engine *h, const int32_t *users, int64_t nU, int32
     const int roww = grouped_row_width(h->E);
     const bool padded = !(h->E == 32 || h->E == 64 || h->E == 128);   // e.g. the reference's embed_size 200: rows padded to 256
     if (h->C == 4 && (!h->dish_high || (hv_ok && !padded)) && k <= 16 && roww != 0 &&
-        h->opt_topk_grouped != 0 && h->opt_variant != 7 && h->opt_variant != 8 && h->opt_variant != 9) {
+        h->opt_topk_grouped != 0 && h->opt_variant != 7 && h->opt_variant != 9) {
         if ((rc = ensure_grouped(h, stream)) != M2D_OK) return rc;
         if ((rc = refresh_grouped_nonfinite(h, stream)) != M2D_OK) return rc;
         const int KR = k <= 10 ? 10 : 16;                    // list slots per lane

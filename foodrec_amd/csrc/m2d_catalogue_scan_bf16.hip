@@ -242,13 +242,13 @@ __global__ __launch_bounds__(WAVES * 64) void m2d_topk_grouped_bf16(GroupedArgs 
 //     tree's result; its row is the map's set bit) is parked as (px, pid) and inserted by the NEXT step -- slot
 //     ranges of an in-place sorted insert placed between that step's MFMA groups.  Only a tile in which one lane
 //     holds two or more candidates (the first tiles of a scan, then rare) takes the immediate per-row path.
-// G = groups of 32 users per wave (8 / G waves per block, always 256 users per block).  G = 1 is what is launched.
-// G = 2 (one wave per SIMD, every A fragment feeding two independent MFMA chains) was measured slower (100 k dishes
-// E = 64: 4.7 ms against 3.7) and is kept only as a template parameter.
+// A wave owns 32 users (lanes l and l ^ 32 share a user and split each tile's dishes); a block is 8 waves (256 users) or, E = 64
+// only, 4 waves (128 users) -- see WAVES below.  There is no form with two groups of 32 users per wave: one wave per SIMD with
+// every A fragment feeding two independent MFMA chains measured slower (100 k dishes, E = 64: 4.7 ms against 3.7).
 // Thresholds are one insertion stale when tile q-2 is compared: more candidates, never fewer.
 // HV = true: the ingredient extension.  Dish rows are [H[d] | RE[d]] (E = 2 x the embedding width) and the user operand
 // is [a U_high | w_P]: score = <a U_high, H[d]> + <w_P, RE[d]>, no alpha_P term.
-// WAVES: 8 / G (a block of 256 users, 128 KiB of LDS, one block per CU), or 4 with G = 1: a block of 128 users over stages of
+// WAVES: 8 (a block of 256 users, 128 KiB of LDS, one block per CU), or 4: a block of 128 users over stages of
 // half the tiles (64 KiB of LDS), TWO blocks per CU -- a stage barrier then holds up four waves, not eight, and the CU's other
 // block keeps the matrix pipes busy meanwhile (launch_grouped: pruned launches, where the waves of a block are unequal).
 #if M2D_DIAG & 256
@@ -276,15 +276,15 @@ __device__ __forceinline__ void diag_mfma16(v16f &acc, const int ks, const bf16x
 // gets its cross products then, from its rows still in LDS, and is handled from exact scores as before.  A score is the
 // hi x hi sums of all k-steps with the cross products added behind them: not the bits of the three-product kernels, so the launcher's
 // choice depends on the catalogue alone -- every launch shape of one problem takes the same arithmetic (lists bit for bit).
-template <int E, int KR, int G, bool HV = false, int WAVES = 8 / G, bool KEEP = false, bool APX = false>
+template <int E, int KR, bool HV = false, int WAVES = 8, bool KEEP = false, bool APX = false>
 __global__ __launch_bounds__(WAVES * 64, 2) void m2d_topk_grouped_bf16_pipe2(GroupedArgs p)
 {
-    static_assert(!APX || ((E == 64 || E == 128) && WAVES == 8 && G == 1), "the hi x hi first form: blocks of eight waves");
+    static_assert(!APX || ((E == 64 || E == 128) && WAVES == 8), "the hi x hi first form: blocks of eight waves");
     constexpr int C = 4;
     constexpr int KS = E / 16;                             // k-steps (16 k-values) per tile
     constexpr int S8 = E / 8;                              // 16-B slots per bf16 row
     constexpr int RPB = 256 / (E * 2) > 0 ? 256 / (E * 2) : 1;   // rows per 256-B bank row
-    constexpr int TPS = (E == 64 ? 8 : 4) * (WAVES * G) / 8;   // tiles per stage: 64 KiB stages (32 KiB for blocks of four waves)
+    constexpr int TPS = (E == 64 ? 8 : 4) * WAVES / 8;     // tiles per stage: 64 KiB stages (32 KiB for blocks of four waves)
     static_assert(TPS >= 4, "a stage holds at least four tiles (its pieces are issued in the steps before its last)");
     constexpr int ROW_BYTES = E * 2, TILE_BYTES = 64 * ROW_BYTES, STAGE_BYTES = TPS * TILE_BYTES;
     constexpr int PIECES = STAGE_BYTES / 1024;
@@ -322,43 +322,40 @@ __global__ __launch_bounds__(WAVES * 64, 2) void m2d_topk_grouped_bf16_pipe2(Gro
 
     // The users of a launch come in the order the call's plan sorted them into (by relevant-pattern mask, p.order):
     // uidx = the user's index in the CALL (users, plan, outputs), wherever the launch placed it.
-    int32_t uidx[G];                                       // 32-bit on purpose (a call holds < 2^31 users): a register less across the scan
-    bool uvalid[G];
-    const v4f *pmu[G];
-    float hc[G][C];                                        // <U_high, CE_c>   Model_Recommender.py:67-75 (from the plan)
-    float seed[G];                                         // scan-start bound of the user's final k-th score (from the plan)
-    float dlt2[G];                                         // 2 delta: scores this close under a threshold still reach the insertion
-    LeftOut lout[G];                                       // what this lane's list leaves out (EXT)
-    uint32_t umask_lane = 0u;                              // patterns that can reach the top-k of this lane's user(s)
-#pragma unroll
-    for (int g = 0; g < G; ++g) {
-        const int64_t pos = (((int64_t)bx * WAVES + wave) * G + g) * 32 + j;
-        uvalid[g] = pos < p.nU;
-        uidx[g] = uvalid[g] ? (p.order ? p.order[pos] : (int32_t)pos) : 0;
-        // everything that hangs on the user's index is fetched in ONE round trip: the id, the plan record, the shared word
-        // (read one after the other -- id, its range check, record, word -- they were four in a row at the head of every item)
-        const float *rec = p.plan + (size_t)uidx[g] * 8;
-        const int32_t uid = uvalid[g] ? p.users[uidx[g]] : 0;
-        const float rec0 = rec[0], rec1 = rec[1], rec2 = rec[2], rec3 = rec[3], rec4 = rec[4], rec5 = rec[5], rec7 = rec[7];
-        int32_t shared_key = thr_key(-INFINITY);
-        if (SHARE && p.shared_thr && uvalid[g])             // what the user's other dish ranges have reached so far (see exchange_thresholds)
-            shared_key = __hip_atomic_load(p.shared_thr + (size_t)uidx[g] * 8, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        int64_t ul = 0;
-        if (uvalid[g]) {
-            ul = (int64_t)uid - p.user_base;
-            if (ul < 0 || ul >= p.U) {
-                latch_error(p.err, M2D_ERR_BAD_USER_ID, uid, uidx[g]);
-                ul = 0;
-            }
+    int32_t uidx;                                          // 32-bit on purpose (a call holds < 2^31 users): a register less across the scan
+    bool uvalid;
+    const v4f *pmu;
+    float hc[C];                                           // <U_high, CE_c>   Model_Recommender.py:67-75 (from the plan)
+    float seed;                                            // scan-start bound of the user's final k-th score (from the plan)
+    float dlt2;                                            // 2 delta: scores this close under a threshold still reach the insertion
+    LeftOut lout;                                          // what this lane's list leaves out (EXT)
+    uint32_t umask_lane = 0u;                              // patterns that can reach the top-k of this lane's user
+    const int64_t pos = ((int64_t)bx * WAVES + wave) * 32 + j;
+    uvalid = pos < p.nU;
+    uidx = uvalid ? (p.order ? p.order[pos] : (int32_t)pos) : 0;
+    // everything that hangs on the user's index is fetched in ONE round trip: the id, the plan record, the shared word
+    // (read one after the other -- id, its range check, record, word -- they were four in a row at the head of every item)
+    const float *rec = p.plan + (size_t)uidx * 8;
+    const int32_t uid = uvalid ? p.users[uidx] : 0;
+    const float rec0 = rec[0], rec1 = rec[1], rec2 = rec[2], rec3 = rec[3], rec4 = rec[4], rec5 = rec[5], rec7 = rec[7];
+    int32_t shared_key = thr_key(-INFINITY);
+    if (SHARE && p.shared_thr && uvalid)                   // what the user's other dish ranges have reached so far (see exchange_thresholds)
+        shared_key = __hip_atomic_load(p.shared_thr + (size_t)uidx * 8, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    int64_t ul = 0;
+    if (uvalid) {
+        ul = (int64_t)uid - p.user_base;
+        if (ul < 0 || ul >= p.U) {
+            latch_error(p.err, M2D_ERR_BAD_USER_ID, uid, uidx);
+            ul = 0;
         }
-        pmu[g] = reinterpret_cast<const v4f *>(p.pm) + (size_t)ul * ((C + 1) * S4);
-        hc[g][0] = rec1; hc[g][1] = rec2; hc[g][2] = rec3; hc[g][3] = rec4;
-        seed[g] = uvalid[g] ? rec0 : INFINITY;              // a lane without a user never has a candidate
-        dlt2[g] = (EXT && p.ex_out && uvalid[g]) ? 2.f * rec7 : 0.f;
-        lout[g] = M2D_LEFTOUT_NONE;
-        if (SHARE && p.shared_thr && uvalid[g]) seed[g] = fmaxf(seed[g], thr_unkey(shared_key));
-        umask_lane |= uvalid[g] ? __float_as_uint(rec5) : 0u;
     }
+    pmu = reinterpret_cast<const v4f *>(p.pm) + (size_t)ul * ((C + 1) * S4);
+    hc[0] = rec1; hc[1] = rec2; hc[2] = rec3; hc[3] = rec4;
+    seed = uvalid ? rec0 : INFINITY;                       // a lane without a user never has a candidate
+    dlt2 = (EXT && p.ex_out && uvalid) ? 2.f * rec7 : 0.f;
+    lout = M2D_LEFTOUT_NONE;
+    if (SHARE && p.shared_thr && uvalid) seed = fmaxf(seed, thr_unkey(shared_key));
+    umask_lane |= uvalid ? __float_as_uint(rec5) : 0u;
     // the block's patterns: the union over its users.  Tiles of every other pattern are not even fetched.
     __shared__ uint32_t s_umask;
     __shared__ __align__(16) uint32_t s_prog[8];           // (APX) stages whose step "sub 1" wave w has finished, see issue of pieces 6 and 7
@@ -377,35 +374,30 @@ __global__ __launch_bounds__(WAVES * 64, 2) void m2d_topk_grouped_bf16_pipe2(Gro
         g_rows = p.grp[40 + lane];
     }
 
-    bf16x8 wh[G][KS], wl[G][KS];                           // w_P[u] for k = 16 s + 8 h + (0..7), split hi / lo
-    float alpha[G], alpha_prev[G];                         // alpha_P of the tile being multiplied / being compared
-    float eps[G], eps_prev[G];                             // (APX) what the cross products can add to a score of that tile, at most
+    bf16x8 wh[KS], wl[KS];                                 // w_P[u] for k = 16 s + 8 h + (0..7), split hi / lo
+    float alpha, alpha_prev;                               // alpha_P of the tile being multiplied / being compared
+    float eps, eps_prev;                                   // (APX) what the cross products can add to a score of that tile, at most
     int cur_pat = -1;
     int gp = 0;                                            // group walk: pattern, its tile range and row count
     int64_t g_beg = 0, g_end = 0;
     int g_tot = 0;
 
-    float rs[G][KR];
-    int32_t ri[G][KR];
-    float thr[G], px[G];                                   // px, pid: parked candidate = this lane's best score of one tile
-    int32_t pid[G];
+    float rs[KR];
+    int32_t ri[KR];
+    float thr, px;                                         // px, pid: parked candidate = this lane's best score of one tile
+    int32_t pid;
 #pragma unroll
-    for (int g = 0; g < G; ++g) {
-#pragma unroll
-        for (int i = 0; i < KR; ++i) {
-            rs[g][i] = -INFINITY;
-            ri[g][i] = -1;
-        }
-        thr[g] = seed[g];
-        px[g] = -INFINITY;
-        pid[g] = -1;
-        alpha[g] = alpha_prev[g] = 0.f;
-        eps[g] = eps_prev[g] = 0.f;
+    for (int i = 0; i < KR; ++i) {
+        rs[i] = -INFINITY;
+        ri[i] = -1;
     }
+    thr = seed;
+    px = -INFINITY;
+    pid = -1;
+    alpha = alpha_prev = 0.f;
+    eps = eps_prev = 0.f;
     bool pend = false;                                     // wave-uniform: some (px, pid) waits to be inserted
-    unsigned long long tie_mask[G];                        // lanes with a tie event at their list's present last value (tie_update)
-#pragma unroll
-    for (int g = 0; g < G; ++g) tie_mask[g] = 0ull;
+    unsigned long long tie_mask = 0ull;                    // lanes with a tie event at their list's present last value (tie_update)
 
     const int64_t per = (p.tiles + p.nsplit - 1) / p.nsplit;
     const int64_t t_begin = (int64_t)by * per;
@@ -499,12 +491,9 @@ __global__ __launch_bounds__(WAVES * 64, 2) void m2d_topk_grouped_bf16_pipe2(Gro
     // (8 k-steps, 4 sets: 32 VGPRs instead of 64, which is what keeps this form under 256 registers there), the next
     // tile's at E = 64
     bf16x8 ah[AR], al[AR];
-    v16f acc0[G], acc1[G];
+    v16f acc0, acc1;
 #pragma unroll
-    for (int g = 0; g < G; ++g) {
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc0[g][r] = acc1[g][r] = -INFINITY;
-    }
+    for (int r = 0; r < 16; ++r) acc0[r] = acc1[r] = -INFINITY;
     const v16f zero16 = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
 
     // a pattern's operands: alpha_P[u], w_P[u] split hi / lo, (APX) the cross products' bound -- built where a scan reaches a pattern its
@@ -515,101 +504,98 @@ __global__ __launch_bounds__(WAVES * 64, 2) void m2d_topk_grouped_bf16_pipe2(Gro
         const float beta = p.b * inv_n;
         const float rmax_pat = APX ? __int_as_float(p.grp[GRP_RMAX + pat]) : 0.f;   // the pattern's largest row norm (NaN rows: +inf)
         const float rmax_re = (APX && HV) ? __int_as_float(p.grp[GRP_STAT + 2]) : 0.f;   // ingredient form: rmax_pat is of H[d], this the largest |RE[d]|
+        float hs = 0.f;
 #pragma unroll
-        for (int g = 0; g < G; ++g) {
-            float hs = 0.f;
+        for (int c = 0; c < C; ++c) hs += ((pat >> c) & 1) ? hc[c] : 0.f;
+        alpha = HV ? 0.f : p.a * (hs * inv_n);
+        // E = 64: the pattern's rows category by category -- a category's eight float4 in flight together, one wait,
+        // then the adds (the same sums in the same order).  Written k-step by k-step with the category test inside,
+        // the loads came out as sixteen exec-masked pairs, each waited for before the next was issued: sixteen
+        // round trips in a row at every pattern switch, with the block's matrix pipe idle
+        constexpr bool BYCAT = !HV && KS == 4;
+        v4f wacc[BYCAT ? KS : 1][2];
+        if constexpr (BYCAT) {
 #pragma unroll
-            for (int c = 0; c < C; ++c) hs += ((pat >> c) & 1) ? hc[g][c] : 0.f;
-            alpha[g] = HV ? 0.f : p.a * (hs * inv_n);
-            // E = 64: the pattern's rows category by category -- a category's eight float4 in flight together, one wait,
-            // then the adds (the same sums in the same order).  Written k-step by k-step with the category test inside,
-            // the loads came out as sixteen exec-masked pairs, each waited for before the next was issued: sixteen
-            // round trips in a row at every pattern switch, with the block's matrix pipe idle
-            constexpr bool BYCAT = !HV && KS == 4;
-            v4f wacc[BYCAT ? KS : 1][2];
+            for (int ks = 0; ks < KS; ++ks) wacc[ks][0] = wacc[ks][1] = v4f{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+            for (int c = 0; c < C; ++c) {
+                if ((pat >> c) & 1) {
+                    v4f ld[KS][2];
+#pragma unroll
+                    for (int ks = 0; ks < KS; ++ks) {
+                        const v4f *row = pmu + (c + 1) * S4 + 4 * ks + 2 * h;
+                        ld[ks][0] = row[0];
+                        ld[ks][1] = row[1];
+                    }
+#pragma unroll
+                    for (int ks = 0; ks < KS; ++ks) {
+                        wacc[ks][0] += ld[ks][0];
+                        wacc[ks][1] += ld[ks][1];
+                    }
+                }
+            }
+        }
+        float ww = 0.f, wmax = 0.f;                          // (APX) sum of squares and largest magnitude of this lane's half of w_P[u]
+        float wwh = 0.f, wmaxh = 0.f;                        // (APX, ingredient form) the same of a U_high, whose k-values meet H[d]
+#pragma unroll
+        for (int ks = 0; ks < KS; ++ks) {                   // unrolled: every register index is static
+            v4f w0 = {0.f, 0.f, 0.f, 0.f}, w1 = {0.f, 0.f, 0.f, 0.f};
             if constexpr (BYCAT) {
-#pragma unroll
-                for (int ks = 0; ks < KS; ++ks) wacc[ks][0] = wacc[ks][1] = v4f{0.f, 0.f, 0.f, 0.f};
+                w0 = wacc[ks][0] * beta;
+                w1 = wacc[ks][1] * beta;
+            } else
+            if (HV && ks < KS / 2) {                        // k < EU: a U_high against H[d]
+                const v4f *row = pmu + 4 * ks + 2 * h;
+                w0 = row[0] * p.a;
+                w1 = row[1] * p.a;
+            } else {
+                const int kk = HV ? ks - KS / 2 : ks;       // k - EU: w_P against RE[d]
 #pragma unroll
                 for (int c = 0; c < C; ++c) {
                     if ((pat >> c) & 1) {
-                        v4f ld[KS][2];
+                        const v4f *row = pmu + (c + 1) * S4 + 4 * kk + 2 * h;
+                        w0 += row[0];
+                        w1 += row[1];
+                    }
+                }
+                w0 *= beta;
+                w1 *= beta;
+            }
+            const float xx[8] = {w0.x, w0.y, w0.z, w0.w, w1.x, w1.y, w1.z, w1.w};
+            bf16x8 vh, vl;
 #pragma unroll
-                        for (int ks = 0; ks < KS; ++ks) {
-                            const v4f *row = pmu[g] + (c + 1) * S4 + 4 * ks + 2 * h;
-                            ld[ks][0] = row[0];
-                            ld[ks][1] = row[1];
-                        }
-#pragma unroll
-                        for (int ks = 0; ks < KS; ++ks) {
-                            wacc[ks][0] += ld[ks][0];
-                            wacc[ks][1] += ld[ks][1];
-                        }
+            for (int i = 0; i < 8; ++i) {
+                const __bf16 xh = (__bf16)xx[i];
+                vh[i] = xh;
+                vl[i] = (__bf16)(xx[i] - (float)xh);
+                if (APX) {
+                    if (HV && ks < KS / 2) {
+                        wwh = fmaf(xx[i], xx[i], wwh);
+                        wmaxh = fmaxf(wmaxh, fabsf(xx[i]));
+                    } else {
+                        ww = fmaf(xx[i], xx[i], ww);
+                        wmax = fmaxf(wmax, fabsf(xx[i]));
                     }
                 }
             }
-            float ww = 0.f, wmax = 0.f;                          // (APX) sum of squares and largest magnitude of this lane's half of w_P[u]
-            float wwh = 0.f, wmaxh = 0.f;                        // (APX, ingredient form) the same of a U_high, whose k-values meet H[d]
-#pragma unroll
-            for (int ks = 0; ks < KS; ++ks) {                   // unrolled: every register index is static
-                v4f w0 = {0.f, 0.f, 0.f, 0.f}, w1 = {0.f, 0.f, 0.f, 0.f};
-                if constexpr (BYCAT) {
-                    w0 = wacc[ks][0] * beta;
-                    w1 = wacc[ks][1] * beta;
-                } else
-                if (HV && ks < KS / 2) {                        // k < EU: a U_high against H[d]
-                    const v4f *row = pmu[g] + 4 * ks + 2 * h;
-                    w0 = row[0] * p.a;
-                    w1 = row[1] * p.a;
-                } else {
-                    const int kk = HV ? ks - KS / 2 : ks;       // k - EU: w_P against RE[d]
-#pragma unroll
-                    for (int c = 0; c < C; ++c) {
-                        if ((pat >> c) & 1) {
-                            const v4f *row = pmu[g] + (c + 1) * S4 + 4 * kk + 2 * h;
-                            w0 += row[0];
-                            w1 += row[1];
-                        }
-                    }
-                    w0 *= beta;
-                    w1 *= beta;
-                }
-                const float xx[8] = {w0.x, w0.y, w0.z, w0.w, w1.x, w1.y, w1.z, w1.w};
-                bf16x8 vh, vl;
-#pragma unroll
-                for (int i = 0; i < 8; ++i) {
-                    const __bf16 xh = (__bf16)xx[i];
-                    vh[i] = xh;
-                    vl[i] = (__bf16)(xx[i] - (float)xh);
-                    if (APX) {
-                        if (HV && ks < KS / 2) {
-                            wwh = fmaf(xx[i], xx[i], wwh);
-                            wmaxh = fmaxf(wmaxh, fabsf(xx[i]));
-                        } else {
-                            ww = fmaf(xx[i], xx[i], ww);
-                            wmax = fmaxf(wmax, fabsf(xx[i]));
-                        }
-                    }
-                }
-                wh[g][ks] = vh;
-                wl[g][ks] = vl;
-            }
-            if constexpr (APX) {
-                // |x - hi| <= 2^-8 |x| for a dish value and for a w value: |sum (lo_d hi_w + hi_d lo_w)| <= 2^-7 (1 + 2^-8)
-                // sum |d_k| |w_k| <= that times |d| |w|; 1.02 covers the norms' and the accumulations' own roundings.
-                // |w|: the root of the sum of squares where that sum is a normal number (squares lost to underflow are then
-                // far below what the 1.02 covers), else sqrt(E) times the largest |w_k| -- never less than |w|
-                ww += __shfl_xor(ww, 32, 64);
-                wmax = fmaxf(wmax, __shfl_xor(wmax, 32, 64));
-                const float nw = (ww >= 1e-30f && ww < INFINITY) ? sqrtf(ww) : sqrtf((float)EU) * wmax;
-                if constexpr (HV) {                         // two operand halves, two row halves: |a U_high| against |H[d]|, |w_P| against |RE[d]|
-                    wwh += __shfl_xor(wwh, 32, 64);
-                    wmaxh = fmaxf(wmaxh, __shfl_xor(wmaxh, 32, 64));
-                    const float nh = (wwh >= 1e-30f && wwh < INFINITY) ? sqrtf(wwh) : sqrtf((float)EU) * wmaxh;
-                    eps[g] = 1.02f * 0.0078125f * (nh * rmax_pat + nw * rmax_re);
-                } else
-                    eps[g] = 1.02f * 0.0078125f * nw * rmax_pat;
-            }
+            wh[ks] = vh;
+            wl[ks] = vl;
+        }
+        if constexpr (APX) {
+            // |x - hi| <= 2^-8 |x| for a dish value and for a w value: |sum (lo_d hi_w + hi_d lo_w)| <= 2^-7 (1 + 2^-8)
+            // sum |d_k| |w_k| <= that times |d| |w|; 1.02 covers the norms' and the accumulations' own roundings.
+            // |w|: the root of the sum of squares where that sum is a normal number (squares lost to underflow are then
+            // far below what the 1.02 covers), else sqrt(E) times the largest |w_k| -- never less than |w|
+            ww += __shfl_xor(ww, 32, 64);
+            wmax = fmaxf(wmax, __shfl_xor(wmax, 32, 64));
+            const float nw = (ww >= 1e-30f && ww < INFINITY) ? sqrtf(ww) : sqrtf((float)EU) * wmax;
+            if constexpr (HV) {                         // two operand halves, two row halves: |a U_high| against |H[d]|, |w_P| against |RE[d]|
+                wwh += __shfl_xor(wwh, 32, 64);
+                wmaxh = fmaxf(wmaxh, __shfl_xor(wmaxh, 32, 64));
+                const float nh = (wwh >= 1e-30f && wwh < INFINITY) ? sqrtf(wwh) : sqrtf((float)EU) * wmaxh;
+                eps = 1.02f * 0.0078125f * (nh * rmax_pat + nw * rmax_re);
+            } else
+                eps = 1.02f * 0.0078125f * nw * rmax_pat;
         }
     };
 
@@ -638,17 +624,17 @@ __global__ __launch_bounds__(WAVES * 64, 2) void m2d_topk_grouped_bf16_pipe2(Gro
     const unsigned long long clk0 = __builtin_amdgcn_s_memtime(), rt0 = __builtin_amdgcn_s_memrealtime();
 #endif
 
-    auto share_threshold = [&](const int g) __attribute__((always_inline)) {
+    auto share_threshold = [&]() __attribute__((always_inline)) {
         // the user's other lane (l ^ 32): a score below the larger of the two lists' last entries cannot be in the user's
         // merged top-KR, nor can one below the smaller of their MIDDLE entries (KR / 2 entries of each list are at or above
         // it: KR scores in all) -- with the dishes dealt evenly to the two lanes that is about the merged list's last
         // entry itself, where each lane's own last is about its 2 KR-th (candidate tiles 17 % -> 15 %, insertions per
         // lane 110 -> 85 in scripts/diag/topk_scan_sim.py); and never below the scan-start bound
-        const float t = rs[g][KR - 1], m = rs[g][KR / 2 - 1];
+        const float t = rs[KR - 1], m = rs[KR / 2 - 1];
         const auto sw = __builtin_amdgcn_permlane32_swap(__float_as_uint(t), __float_as_uint(t), false, false);
         const auto sm = __builtin_amdgcn_permlane32_swap(__float_as_uint(m), __float_as_uint(m), false, false);
-        thr[g] = fmaxf(fmaxf(fmaxf(__uint_as_float(sw[0]), __uint_as_float(sw[1])),
-                             fminf(__uint_as_float(sm[0]), __uint_as_float(sm[1]))), seed[g]);
+        thr = fmaxf(fmaxf(fmaxf(__uint_as_float(sw[0]), __uint_as_float(sw[1])),
+                             fminf(__uint_as_float(sm[0]), __uint_as_float(sm[1]))), seed);
     };
 
     // A launch cut into dish ranges runs a user's ranges as separate workgroups, each with lists of its own -- and each
@@ -660,98 +646,78 @@ __global__ __launch_bounds__(WAVES * 64, 2) void m2d_topk_grouped_bf16_pipe2(Gro
     // for.  What the word holds when a lane looks depends on timing; the lists do not: a dish of the final top-k scores at or
     // above every lower bound of the k-th score, reaches its range's insertion whatever the floor, and stays in that
     // range's list; tie events at the final k-th value likewise involve scores at or above every floor.
-    int32_t pend_key[G];
-#pragma unroll
-    for (int g = 0; g < G; ++g) pend_key[g] = thr_key(-INFINITY);
+    int32_t pend_key = thr_key(-INFINITY);
     auto exchange_thresholds = [&]() __attribute__((always_inline)) {
-#pragma unroll
-        for (int g = 0; g < G; ++g) {
-            seed[g] = fmaxf(seed[g], thr_unkey(pend_key[g]));
-            thr[g] = fmaxf(thr[g], seed[g]);
-            if (uvalid[g]) {
-                int32_t *word = p.shared_thr + (size_t)uidx[g] * 8;
-                if (thr[g] > seed[g]) {                     // news: above everything this lane has heard or said (seed = that floor)
-                    pend_key[g] = __hip_atomic_fetch_max(word, thr_key(thr[g]), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    seed[g] = thr[g];
-                } else                                      // nothing to say: a read leaves the line shared between the XCDs' L2s
-                    pend_key[g] = __hip_atomic_load(word, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            }
+        seed = fmaxf(seed, thr_unkey(pend_key));
+        thr = fmaxf(thr, seed);
+        if (uvalid) {
+            int32_t *word = p.shared_thr + (size_t)uidx * 8;
+            if (thr > seed) {                     // news: above everything this lane has heard or said (seed = that floor)
+                pend_key = __hip_atomic_fetch_max(word, thr_key(thr), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                seed = thr;
+            } else                                      // nothing to say: a read leaves the line shared between the XCDs' L2s
+                pend_key = __hip_atomic_load(word, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         }
     };
 
     // the interleaved body: M(q-1) into accN, L(q), the max tree of tile q-2 (accP), and -- INS -- the parked insertion,
     // slot ranges from the end of the list up, one range per k-step group
-    auto body = [&](auto ins_tag, v16f (&accN)[G], const v16f (&accP)[G], const int img_prev, const int img_off,
-                    float (&mx)[G]) __attribute__((always_inline)) {
+    auto body = [&](auto ins_tag, v16f &accN, const v16f &accP, const int img_prev, const int img_off,
+                    float &mx) __attribute__((always_inline)) {
         constexpr bool INS = decltype(ins_tag)::value;
         constexpr bool PIN = WAVES == 4;
-        float x[G], old_last[G];
-        int32_t old_id[G];
-#pragma unroll
-        for (int g = 0; g < G; ++g) {
-            x[g] = fmaxf(px[g], -INFINITY);
-            mx[g] = -INFINITY;
-            old_last[g] = rs[g][KR - 1];
-            old_id[g] = ri[g][KR - 1];
-        }
+        const float x = fmaxf(px, -INFINITY), old_last = rs[KR - 1];
+        const int32_t old_id = ri[KR - 1];
+        mx = -INFINITY;
         __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
         for (int ks = 0; ks < KS; ++ks) {
             const int st = ks % AR;
-#pragma unroll
-            for (int g = 0; g < G; ++g) {
 #if M2D_DIAG & 256
-                // TIMING ONLY (wrong scores; scripts/diag/topk_diag.cpp): the k-step's flops as six v_mfma_f32_16x16x32_bf16 on the
-                // quarters of the same accumulator registers -- what the 2 x 2 arrangement of 16 x 16 tiles over the wave's 32 users
-                // x 32 dishes would issue (each A and each B fragment feeding two MFMAs: the same LDS reads, the same registers) --
-                // to read the clock the chip holds on that shape before anything is built for it (MI355X_MICROARCH "DVFS give-back" 7)
-                diag_mfma16<0>(accN[g], ks, al[st], wh[g][ks], ks < 2);
-                diag_mfma16<0>(accN[g], ks, ah[st], wl[g][ks], false);
-                diag_mfma16<0>(accN[g], ks, ah[st], wh[g][ks], false);
-                diag_mfma16<1>(accN[g], ks, ah[st], wl[g][ks], ks < 2);      // (another order: identical chains would be merged)
-                diag_mfma16<1>(accN[g], ks, ah[st], wh[g][ks], false);
-                diag_mfma16<1>(accN[g], ks, al[st], wh[g][ks], false);
+            // TIMING ONLY (wrong scores; scripts/diag/topk_diag.cpp): the k-step's flops as six v_mfma_f32_16x16x32_bf16 on the
+            // quarters of the same accumulator registers -- what the 2 x 2 arrangement of 16 x 16 tiles over the wave's 32 users
+            // x 32 dishes would issue (each A and each B fragment feeding two MFMAs: the same LDS reads, the same registers) --
+            // to read the clock the chip holds on that shape before anything is built for it (MI355X_MICROARCH "DVFS give-back" 7)
+            diag_mfma16<0>(accN, ks, al[st], wh[ks], ks < 2);
+            diag_mfma16<0>(accN, ks, ah[st], wl[ks], false);
+            diag_mfma16<0>(accN, ks, ah[st], wh[ks], false);
+            diag_mfma16<1>(accN, ks, ah[st], wl[ks], ks < 2);      // (another order: identical chains would be merged)
+            diag_mfma16<1>(accN, ks, ah[st], wh[ks], false);
+            diag_mfma16<1>(accN, ks, al[st], wh[ks], false);
 #else
-                if constexpr (APX) {
-                    accN[g] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[st], wh[g][ks], ks == 0 ? zero16 : accN[g], 0, 0, 0);
-                } else {
-                    accN[g] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al[st], wh[g][ks], ks == 0 ? zero16 : accN[g], 0, 0, 0);
-                    accN[g] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[st], wl[g][ks], accN[g], 0, 0, 0);
-                    accN[g] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[st], wh[g][ks], accN[g], 0, 0, 0);
-                }
-#endif
+            if constexpr (APX) {
+                accN = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[st], wh[ks], ks == 0 ? zero16 : accN, 0, 0, 0);
+            } else {
+                accN = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al[st], wh[ks], ks == 0 ? zero16 : accN, 0, 0, 0);
+                accN = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[st], wl[ks], accN, 0, 0, 0);
+                accN = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[st], wh[ks], accN, 0, 0, 0);
             }
+#endif
             // k-step ks + AR of this tile (q-1), or k-step ks + AR - KS of the next (q)
             const unsigned char *a = smem8 + (ks + AR < KS ? (img_prev ^ ((ks + AR) << 5)) : (img_off ^ ((ks + AR - KS) << 5)));
             ah[st] = *reinterpret_cast<const bf16x8 *>(a);
             if (!APX) al[st] = *reinterpret_cast<const bf16x8 *>(a + 32 * ROW_BYTES);
 #pragma unroll
-            for (int g = 0; g < G; ++g) {
-#pragma unroll
-                for (int r = ks * RPK; r < (ks + 1) * RPK; ++r) mx[g] = fmaxf(mx[g], accP[g][r]);      // the tile's maximum per lane: one
-                                                                       // compare of it against the threshold settles most tiles (below)
-                if (PIN && INS) asm volatile("" : "+v"(mx[g]));
-                if constexpr (INS) {
-                    // slots [lo, hi) of the list, highest ranges first
-                    constexpr int PER = (KR + KS - 1) / KS;
-                    constexpr int L0 = KR - PER > 0 ? KR - PER : 0, L1 = KR - 2 * PER > 0 ? KR - 2 * PER : 0,
-                                  L2 = KR - 3 * PER > 0 ? KR - 3 * PER : 0, L3 = KS == 4 ? 0 : (KR - 4 * PER > 0 ? KR - 4 * PER : 0);
-                    if (ks == 0) { sorted_insert_range<KR, L0, KR>(rs[g], ri[g], x[g], pid[g]); if (PIN) pin_range<KR, L0, KR>(rs[g]); }
-                    if (ks == 1) { sorted_insert_range<KR, L1, L0>(rs[g], ri[g], x[g], pid[g]); if (PIN) pin_range<KR, L1, L0>(rs[g]); }
-                    if (ks == 2) { sorted_insert_range<KR, L2, L1>(rs[g], ri[g], x[g], pid[g]); if (PIN) pin_range<KR, L2, L1>(rs[g]); }
-                    if (ks == 3) { sorted_insert_range<KR, L3, L2>(rs[g], ri[g], x[g], pid[g]); if (PIN) pin_range<KR, L3, L2>(rs[g]); }
-                    if (KS > 4 && ks == 4) sorted_insert_range<KR, 0, L3>(rs[g], ri[g], x[g], pid[g]);
-                }
+            for (int r = ks * RPK; r < (ks + 1) * RPK; ++r) mx = fmaxf(mx, accP[r]);      // the tile's maximum per lane: one
+                                                                   // compare of it against the threshold settles most tiles (below)
+            if (PIN && INS) asm volatile("" : "+v"(mx));
+            if constexpr (INS) {
+                // slots [lo, hi) of the list, highest ranges first
+                constexpr int PER = (KR + KS - 1) / KS;
+                constexpr int L0 = KR - PER > 0 ? KR - PER : 0, L1 = KR - 2 * PER > 0 ? KR - 2 * PER : 0,
+                              L2 = KR - 3 * PER > 0 ? KR - 3 * PER : 0, L3 = KS == 4 ? 0 : (KR - 4 * PER > 0 ? KR - 4 * PER : 0);
+                if (ks == 0) { sorted_insert_range<KR, L0, KR>(rs, ri, x, pid); if (PIN) pin_range<KR, L0, KR>(rs); }
+                if (ks == 1) { sorted_insert_range<KR, L1, L0>(rs, ri, x, pid); if (PIN) pin_range<KR, L1, L0>(rs); }
+                if (ks == 2) { sorted_insert_range<KR, L2, L1>(rs, ri, x, pid); if (PIN) pin_range<KR, L2, L1>(rs); }
+                if (ks == 3) { sorted_insert_range<KR, L3, L2>(rs, ri, x, pid); if (PIN) pin_range<KR, L3, L2>(rs); }
+                if (KS > 4 && ks == 4) sorted_insert_range<KR, 0, L3>(rs, ri, x, pid);
             }
             __builtin_amdgcn_sched_barrier(0);
         }
         if constexpr (INS) {
-#pragma unroll
-            for (int g = 0; g < G; ++g) {
-                if (!EXT) tie_mask[g] = tie_update(tie_mask[g], x[g], old_last[g], rs[g][KR - 1]);
-                if (EXT) left_out_note(lout[g], x[g], pid[g], old_last[g], old_id[g], rs[g][KR - 1] - dlt2[g]);
-                share_threshold(g);
-            }
+            if (!EXT) tie_mask = tie_update(tie_mask, x, old_last, rs[KR - 1]);
+            if (EXT) left_out_note(lout, x, pid, old_last, old_id, rs[KR - 1] - dlt2);
+            share_threshold();
         }
     };
 
@@ -760,7 +726,7 @@ __global__ __launch_bounds__(WAVES * 64, 2) void m2d_topk_grouped_bf16_pipe2(Gro
     // Accumulated onto the tile's hi x hi sums, k-step by k-step: one order for every tile, the same bits wherever it sits in a launch.
     bool accP_exact = false;                               // wave-uniform
     unsigned n_completed = 0;                              // (diagnostic) tiles this wave completed
-    auto complete = [&](v16f (&acc)[G], const int qt) __attribute__((always_inline)) {
+    auto complete = [&](v16f &acc, const int qt) __attribute__((always_inline)) {
         if (qt < 0) return;
         ++n_completed;
         const int img2 = (((qt / TPS) & 1) * STAGE_BYTES + (qt & (TPS - 1)) * TILE_BYTES) + lane_off;
@@ -768,11 +734,8 @@ __global__ __launch_bounds__(WAVES * 64, 2) void m2d_topk_grouped_bf16_pipe2(Gro
         for (int ks = 0; ks < KS; ++ks) {
             const unsigned char *a2 = smem8 + (img2 ^ (ks << 5));
             const bf16x8 h2 = *reinterpret_cast<const bf16x8 *>(a2), l2 = *reinterpret_cast<const bf16x8 *>(a2 + 32 * ROW_BYTES);
-#pragma unroll
-            for (int g = 0; g < G; ++g) {
-                acc[g] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(l2, wh[g][ks], acc[g], 0, 0, 0);
-                acc[g] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(h2, wl[g][ks], acc[g], 0, 0, 0);
-            }
+            acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(l2, wh[ks], acc, 0, 0, 0);
+            acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(h2, wl[ks], acc, 0, 0, 0);
         }
     };
     // (APX) Tile q - 2's rows must still be in LDS when a step completes it.  In a stage's steps "sub 0" and "sub 1" that tile is
@@ -819,9 +782,7 @@ __global__ __launch_bounds__(WAVES * 64, 2) void m2d_topk_grouped_bf16_pipe2(Gro
     // reasons: no candidates, and operands that are constants -- the part holds 2.39 GHz on those and 2.0-2.15 GHz on real rows.
     int plain_left = 0;
     bool thr_dirty = true;                                 // wave-uniform
-    float thr_rel[G];
-#pragma unroll
-    for (int g = 0; g < G; ++g) thr_rel[g] = INFINITY;
+    float thr_rel = INFINITY;
 
 #if M2D_DIAG & 4096
     // (diagnostic) time line of workgroup (0, 0)'s first steps: p.dbg + 7 000 000 + ((wave * 512 + q) * 4 + {0: step start, 1: body start,
@@ -831,7 +792,7 @@ __global__ __launch_bounds__(WAVES * 64, 2) void m2d_topk_grouped_bf16_pipe2(Gro
 #else
 #define TRACE(q_, k_)
 #endif
-    auto step = [&](v16f (&accN)[G], v16f (&accP)[G], const int q) __attribute__((always_inline)) {
+    auto step = [&](v16f &accN, v16f &accP, const int q) __attribute__((always_inline)) {
 #if M2D_DIAG & 16
         STAMP(t0_);
 #endif
@@ -898,18 +859,14 @@ __global__ __launch_bounds__(WAVES * 64, 2) void m2d_topk_grouped_bf16_pipe2(Gro
             // no threshold arithmetic, no candidate test -- to read what everything between two bodies costs a scan
             const int img_off_ = (int)(((q / TPS) & 1) * STAGE_BYTES + sub * TILE_BYTES) + lane_off;
             const int img_prev_ = (int)((((q - 1) / TPS) & 1) * STAGE_BYTES + ((q - 1) & (TPS - 1)) * TILE_BYTES) + lane_off;
-            float mx_[G];
+            float mx_;
             body(std::false_type{}, accN, accP, img_prev_, img_off_, mx_);
-#pragma unroll
-            for (int g = 0; g < G; ++g) asm volatile("" ::"v"(mx_[g]));
+            asm volatile("" ::"v"(mx_));
             return;
         }
 #endif
-#pragma unroll
-        for (int g = 0; g < G; ++g) {
-            alpha_prev[g] = alpha[g];                          // tile q-2 was multiplied under the previous step's alpha
-            eps_prev[g] = eps[g];
-        }
+        alpha_prev = alpha;                          // tile q-2 was multiplied under the previous step's alpha
+        eps_prev = eps;
         accP_exact = false;
         int nvalid = 32;
         const bool plain = (M2D_DIAG & 2048) ? false : plain_left > 0;
@@ -959,38 +916,30 @@ __global__ __launch_bounds__(WAVES * 64, 2) void m2d_topk_grouped_bf16_pipe2(Gro
         // (kept from step to step; redone after a general step -- alpha_prev follows alpha one step late, so also in the step after
         //  one -- and after anything that moved a threshold: an insertion, the exchange at a stage's start)
         if (thr_dirty || !plain) {
-#pragma unroll
-            for (int g = 0; g < G; ++g) {
-                const float d = thr[g] - alpha_prev[g];
-                thr_rel[g] = d - 2.4e-7f * (fabsf(thr[g]) + fabsf(alpha_prev[g])) - dlt2[g];   // 2^-22 (|thr| + |alpha|); thr = +inf: NaN, no candidate
-            }
+            const float d = thr - alpha_prev;
+            thr_rel = d - 2.4e-7f * (fabsf(thr) + fabsf(alpha_prev)) - dlt2;   // 2^-22 (|thr| + |alpha|); thr = +inf: NaN, no candidate
         }
         thr_dirty = !plain || pend;                        // pend: this step's body inserts, and ends on share_threshold
         const int img_off = (((q / TPS) & 1) * STAGE_BYTES + sub * TILE_BYTES) + lane_off;   // tile q
         const int img_prev = ((((q - 1) / TPS) & 1) * STAGE_BYTES + ((q - 1) & (TPS - 1)) * TILE_BYTES) + lane_off;
-        unsigned long long m[G][16];                       // lane masks: row r of tile q-2 beats the lane's threshold
-        float mx[G];
+        unsigned long long m[16];                          // lane masks: row r of tile q-2 beats the lane's threshold
+        float mx;
         TRACE(q, 1);
         if (pend) body(std::true_type{}, accN, accP, img_prev, img_off, mx);
         else body(std::false_type{}, accN, accP, img_prev, img_off, mx);
         TRACE(q, 2);
         if (nvalid < 32) {                                 // a group's last tile, or a dummy tile: padding rows never rank
 #pragma unroll
-            for (int g = 0; g < G; ++g) {
-#pragma unroll
-                for (int r = 0; r < 16; ++r)
-                    accN[g][r] = (4 * h + (r & 3) + 8 * (r >> 2) < nvalid) ? accN[g][r] : -INFINITY;
-            }
+            for (int r = 0; r < 16; ++r)
+                accN[r] = (4 * h + (r & 3) + 8 * (r >> 2) < nvalid) ? accN[r] : -INFINITY;
         }
-        unsigned long long anyc = 0ull;
-#pragma unroll
-        for (int g = 0; g < G; ++g) anyc |= __ballot(mx[g] >= (APX ? thr_rel[g] - eps_prev[g] : thr_rel[g]));   // (APX: mx is of hi x hi scores)
+        const unsigned long long anyc = __ballot(mx >= (APX ? thr_rel - eps_prev : thr_rel));   // (APX: mx is of hi x hi scores)
 #if M2D_DIAG & 16
         STAMP(t1_); if (!(M2D_DIAG & 512)) t_body += t1_ - t0_; t0_ = t1_; ++n_step;
 #endif
         pend = false;
 #if M2D_DIAG & 8
-        asm volatile("" ::"s"(anyc), "v"(mx[0]), "v"(mx[G - 1]));
+        asm volatile("" ::"s"(anyc), "v"(mx));
 #endif
         bool cand_step = (M2D_DIAG & 8) ? false : anyc != 0ull;
         if constexpr (APX) {
@@ -999,16 +948,11 @@ __global__ __launch_bounds__(WAVES * 64, 2) void m2d_topk_grouped_bf16_pipe2(Gro
                 ++n_ins;                                    // (APX builds: d[1] counts the tiles completed, not the multi-candidate tiles)
 #endif
                 if (!accP_exact) complete(accP, q - 2);
-                unsigned long long any2 = 0ull;
+                float m2 = -INFINITY;
 #pragma unroll
-                for (int g = 0; g < G; ++g) {
-                    float m2 = -INFINITY;
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) m2 = fmaxf(m2, accP[g][r]);
-                    mx[g] = m2;
-                    any2 |= __ballot(m2 >= thr_rel[g]);
-                }
-                cand_step = any2 != 0ull;
+                for (int r = 0; r < 16; ++r) m2 = fmaxf(m2, accP[r]);
+                mx = m2;
+                cand_step = __ballot(m2 >= thr_rel) != 0ull;
             }
         }
         if (cand_step) {                                    // some lane of tile q-2 beat its threshold
@@ -1022,105 +966,91 @@ __global__ __launch_bounds__(WAVES * 64, 2) void m2d_topk_grouped_bf16_pipe2(Gro
             // step and wave for 768 of the SIMD's two waves' matrix work -- and 85 % of an every-tile scan's steps have no candidate.
             // Same masks, same lists; body 1 009 -> 910 cycles, every tile 2.38 -> 2.27 ms, pruned 0.508 -> 0.500 ms (round 5).
 #pragma unroll
-            for (int g = 0; g < G; ++g)
+            for (int r = 0; r < 16; ++r) m[r] = __ballot(accP[r] >= thr_rel);
+            uint32_t rowmap = 0u;
 #pragma unroll
-                for (int r = 0; r < 16; ++r) m[g][r] = __ballot(accP[g][r] >= thr_rel[g]);
-            uint32_t rowmap[G];
-            bool cand[G];
-            unsigned long long multi = 0ull;
-#pragma unroll
-            for (int g = 0; g < G; ++g) {
-                rowmap[g] = 0u;
-#pragma unroll
-                for (int r = 0; r < 16; ++r)
-                    asm("v_addc_co_u32_e64 %0, vcc, %1, %1, %2" : "=v"(rowmap[g]) : "v"(rowmap[g]), "s"(m[g][r]) : "vcc");
-                cand[g] = rowmap[g] != 0u;
-                multi |= __ballot((rowmap[g] & (rowmap[g] - 1u)) != 0u);                      // two or more bits set
-            }
+            for (int r = 0; r < 16; ++r)
+                asm("v_addc_co_u32_e64 %0, vcc, %1, %1, %2" : "=v"(rowmap) : "v"(rowmap), "s"(m[r]) : "vcc");
+            const bool cand = rowmap != 0u;
+            const unsigned long long multi = __ballot((rowmap & (rowmap - 1u)) != 0u);                      // two or more bits set
             // one candidate per lane at most: it is the lane's maximum, its row is the map's only set bit, and it is parked
             // for the next step's body (written ahead of the branch, not as its else-arm: as the two arms of a diamond the
             // compiler gave the lists other registers in the multi-candidate arm and paid for it in THIS arm -- 26 v_mov into
             // those registers and 26 back at the merge, in every step with a candidate)
-#pragma unroll
-            for (int g = 0; g < G; ++g) {
-                const int r = __builtin_clz(rowmap[g] | 1u) - 16;          // bit 15 - r  ->  r  (lanes without a candidate: any)
-                px[g] = cand[g] ? mx[g] + alpha_prev[g] : -INFINITY;
-                pid[g] = sbase + (r & 3) + 8 * (r >> 2);
-            }
-            pend = (M2D_DIAG & 128) ? (__ballot(px[0] == 12345.678f) != 0ull) : true;
+            const int r = __builtin_clz(rowmap | 1u) - 16;          // bit 15 - r  ->  r  (lanes without a candidate: any)
+            px = cand ? mx + alpha_prev : -INFINITY;
+            pid = sbase + (r & 3) + 8 * (r >> 2);
+            pend = (M2D_DIAG & 128) ? (__ballot(px == 12345.678f) != 0ull) : true;
             if ((M2D_DIAG & 64) ? false : __builtin_expect(multi != 0ull, 0)) { // immediate path: some lane holds two or more candidates of this tile
                 pend = false;
+                // Two ways to get them in.  Row by row: every row in which SOME lane has a candidate is inserted by the
+                // whole wave (about 55 VALU a row) -- the first tiles of a scan, where every lane wants most rows.
+                // Lane by lane: each lane takes its own next candidate row (its map's highest bit), the value is
+                // picked out of the sixteen accumulators by sixteen compares and selects, one insertion per pass
+                // (about 85 VALU a pass, passes = the most candidates any lane holds).  In the tiles of a pattern the
+                // block's users all want -- the only tiles a pruned scan still visits -- nearly every row has a taker
+                // but a lane has two or three: 16 x 55 against 3 x 85.
+                // (Which is cheaper was worked out per tile from the number of rows with a taker -- sixteen scalar
+                //  compares the compiler turned into 32 VALU + 32 SALU, more than the choice ever saved: row by row wins
+                //  only when at most 3 / 4 / 6 rows have takers while a lane holds 2 / 3 / 4.  Now: lane by lane up to
+                //  four candidates per lane.)
+                const uint32_t pc = (uint32_t)__builtin_popcount(rowmap);
+                const bool b5 = __ballot(pc >= 5u) != 0ull;
+                // (No loop and no else-arm below: plain ifs.  As a `while` beside an else-arm the compiler moved the lists
+                //  into other registers on the way in and back on the way out, 50 v_mov per multi-candidate tile.)
+                uint32_t rm = rowmap;
+                if (b5) {
 #pragma unroll
-                for (int g = 0; g < G; ++g) {
-                    // Two ways to get them in.  Row by row: every row in which SOME lane has a candidate is inserted by the
-                    // whole wave (about 55 VALU a row) -- the first tiles of a scan, where every lane wants most rows.
-                    // Lane by lane: each lane takes its own next candidate row (its map's highest bit), the value is
-                    // picked out of the sixteen accumulators by sixteen compares and selects, one insertion per pass
-                    // (about 85 VALU a pass, passes = the most candidates any lane holds).  In the tiles of a pattern the
-                    // block's users all want -- the only tiles a pruned scan still visits -- nearly every row has a taker
-                    // but a lane has two or three: 16 x 55 against 3 x 85.
-                    // (Which is cheaper was worked out per tile from the number of rows with a taker -- sixteen scalar
-                    //  compares the compiler turned into 32 VALU + 32 SALU, more than the choice ever saved: row by row wins
-                    //  only when at most 3 / 4 / 6 rows have takers while a lane holds 2 / 3 / 4.  Now: lane by lane up to
-                    //  four candidates per lane.)
-                    const uint32_t pc = (uint32_t)__builtin_popcount(rowmap[g]);
-                    const bool b5 = __ballot(pc >= 5u) != 0ull;
-                    // (No loop and no else-arm below: plain ifs.  As a `while` beside an else-arm the compiler moved the lists
-                    //  into other registers on the way in and back on the way out, 50 v_mov per multi-candidate tile.)
-                    uint32_t rm = rowmap[g];
-                    if (b5) {
-#pragma unroll
-                        for (int r = 0; r < 16; ++r) {
-                            if (m[g][r] != 0ull) {
-                                const float ol = rs[g][KR - 1], xv = accP[g][r] + alpha_prev[g];
-                                const int32_t oi = ri[g][KR - 1];
-                                sorted_insert_inplace<KR>(rs[g], ri[g], xv, sbase + (r & 3) + 8 * (r >> 2));
-                                if (!EXT) tie_mask[g] = tie_update(tie_mask[g], xv, ol, rs[g][KR - 1]);
-                                if (EXT) left_out_note(lout[g], fmaxf(xv, -INFINITY), sbase + (r & 3) + 8 * (r >> 2), ol, oi, rs[g][KR - 1] - dlt2[g]);
-                            }
-                        }
-                        rm = 0u;
-                    }
-                    auto pass = [&]() __attribute__((always_inline)) {     // a lane's rows in ascending order, one per pass
-                        const bool has = rm != 0u;
-                        const int r = __builtin_clz(rm | 1u) - 16;
-                        // the lane's row r out of its sixteen accumulators: a binary tree of selects on the bits of r (four
-                        // lane masks + fifteen v_cndmask; sixteen compares + sixteen selects before)
-                        const unsigned long long b0 = __ballot((r & 1) != 0), b1 = __ballot((r & 2) != 0), b2 = __ballot((r & 4) != 0),
-                                                 b3 = __ballot((r & 8) != 0);
-                        float t8[8], t4[4], t2[2];
-#pragma unroll
-                        for (int q = 0; q < 8; ++q) t8[q] = __int_as_float(lane_select(b0, __float_as_int(accP[g][2 * q + 1]), __float_as_int(accP[g][2 * q])));
-#pragma unroll
-                        for (int q = 0; q < 4; ++q) t4[q] = __int_as_float(lane_select(b1, __float_as_int(t8[2 * q + 1]), __float_as_int(t8[2 * q])));
-#pragma unroll
-                        for (int q = 0; q < 2; ++q) t2[q] = __int_as_float(lane_select(b2, __float_as_int(t4[2 * q + 1]), __float_as_int(t4[2 * q])));
-                        float xv = __int_as_float(lane_select(b3, __float_as_int(t2[1]), __float_as_int(t2[0])));
-                        xv = has ? xv + alpha_prev[g] : -INFINITY;    // a lane without a candidate inserts nothing
-                        const float ol = rs[g][KR - 1];
-                        const int32_t oi = ri[g][KR - 1];
-                        sorted_insert_inplace<KR>(rs[g], ri[g], xv, sbase + (r & 3) + 8 * (r >> 2));
-                        if (!EXT) tie_mask[g] = tie_update(tie_mask[g], xv, ol, rs[g][KR - 1]);
-                        if (EXT) left_out_note(lout[g], xv, sbase + (r & 3) + 8 * (r >> 2), ol, oi, rs[g][KR - 1] - dlt2[g]);
-                        rm &= ~(0x8000u >> r);
-                    };
-                    if (__ballot(rm != 0u) != 0ull) {               // (not b5: some lane holds two to four)
-                        pass();
-                        pass();
-                        if (__ballot(rm != 0u) != 0ull) {
-                            pass();
-                            if (__ballot(rm != 0u) != 0ull) pass();
+                    for (int r = 0; r < 16; ++r) {
+                        if (m[r] != 0ull) {
+                            const float ol = rs[KR - 1], xv = accP[r] + alpha_prev;
+                            const int32_t oi = ri[KR - 1];
+                            sorted_insert_inplace<KR>(rs, ri, xv, sbase + (r & 3) + 8 * (r >> 2));
+                            if (!EXT) tie_mask = tie_update(tie_mask, xv, ol, rs[KR - 1]);
+                            if (EXT) left_out_note(lout, fmaxf(xv, -INFINITY), sbase + (r & 3) + 8 * (r >> 2), ol, oi, rs[KR - 1] - dlt2);
                         }
                     }
-                    share_threshold(g);
+                    rm = 0u;
                 }
+                auto pass = [&]() __attribute__((always_inline)) {     // a lane's rows in ascending order, one per pass
+                    const bool has = rm != 0u;
+                    const int r = __builtin_clz(rm | 1u) - 16;
+                    // the lane's row r out of its sixteen accumulators: a binary tree of selects on the bits of r (four
+                    // lane masks + fifteen v_cndmask; sixteen compares + sixteen selects before)
+                    const unsigned long long b0 = __ballot((r & 1) != 0), b1 = __ballot((r & 2) != 0), b2 = __ballot((r & 4) != 0),
+                                             b3 = __ballot((r & 8) != 0);
+                    float t8[8], t4[4], t2[2];
+#pragma unroll
+                    for (int q = 0; q < 8; ++q) t8[q] = __int_as_float(lane_select(b0, __float_as_int(accP[2 * q + 1]), __float_as_int(accP[2 * q])));
+#pragma unroll
+                    for (int q = 0; q < 4; ++q) t4[q] = __int_as_float(lane_select(b1, __float_as_int(t8[2 * q + 1]), __float_as_int(t8[2 * q])));
+#pragma unroll
+                    for (int q = 0; q < 2; ++q) t2[q] = __int_as_float(lane_select(b2, __float_as_int(t4[2 * q + 1]), __float_as_int(t4[2 * q])));
+                    float xv = __int_as_float(lane_select(b3, __float_as_int(t2[1]), __float_as_int(t2[0])));
+                    xv = has ? xv + alpha_prev : -INFINITY;    // a lane without a candidate inserts nothing
+                    const float ol = rs[KR - 1];
+                    const int32_t oi = ri[KR - 1];
+                    sorted_insert_inplace<KR>(rs, ri, xv, sbase + (r & 3) + 8 * (r >> 2));
+                    if (!EXT) tie_mask = tie_update(tie_mask, xv, ol, rs[KR - 1]);
+                    if (EXT) left_out_note(lout, xv, sbase + (r & 3) + 8 * (r >> 2), ol, oi, rs[KR - 1] - dlt2);
+                    rm &= ~(0x8000u >> r);
+                };
+                if (__ballot(rm != 0u) != 0ull) {               // (not b5: some lane holds two to four)
+                    pass();
+                    pass();
+                    if (__ballot(rm != 0u) != 0ull) {
+                        pass();
+                        if (__ballot(rm != 0u) != 0ull) pass();
+                    }
+                }
+                share_threshold();
                 thr_dirty = true;
 #if M2D_DIAG & 16
                 if (!APX) ++n_ins;
 #endif
             }
 #if M2D_DIAG & 16
-            asm volatile("" ::"v"(thr[0]), "v"(px[0]));
+            asm volatile("" ::"v"(thr), "v"(px));
             STAMP(t1_); if (!(M2D_DIAG & 512)) { t_slow += t1_ - t0_; ++n_slow; }
             if (q <= TPS + 2) { t_slow_first += t1_ - t0_; ++n_slow_first; }
 #endif
@@ -1132,23 +1062,17 @@ __global__ __launch_bounds__(WAVES * 64, 2) void m2d_topk_grouped_bf16_pipe2(Gro
         step(acc0, acc1, q);
         step(acc1, acc0, q + 1);
     }
-    if (pend) {                                            // the last parked candidates
-#pragma unroll
-        for (int g = 0; g < G; ++g) {
-            const float ol = rs[g][KR - 1];
-            const int32_t oi = ri[g][KR - 1];
-            sorted_insert_inplace<KR>(rs[g], ri[g], px[g], pid[g]);
-            if (!EXT) tie_mask[g] = tie_update(tie_mask[g], fmaxf(px[g], -INFINITY), ol, rs[g][KR - 1]);
-            if (EXT) left_out_note(lout[g], fmaxf(px[g], -INFINITY), pid[g], ol, oi, rs[g][KR - 1] - dlt2[g]);
-        }
+    if (pend) {                                            // the last parked candidate
+        const float ol = rs[KR - 1];
+        const int32_t oi = ri[KR - 1];
+        sorted_insert_inplace<KR>(rs, ri, px, pid);
+        if (!EXT) tie_mask = tie_update(tie_mask, fmaxf(px, -INFINITY), ol, rs[KR - 1]);
+        if (EXT) left_out_note(lout, fmaxf(px, -INFINITY), pid, ol, oi, rs[KR - 1] - dlt2);
     }
     if (SHARE && p.shared_thr && n > 0) {                  // what this range ends with: ranges of the user that start later begin there
-#pragma unroll
-        for (int g = 0; g < G; ++g) {
-            share_threshold(g);
-            if (uvalid[g])
-                __hip_atomic_fetch_max(p.shared_thr + (size_t)uidx[g] * 8, thr_key(thr[g]), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
+        share_threshold();
+        if (uvalid)
+            __hip_atomic_fetch_max(p.shared_thr + (size_t)uidx * 8, thr_key(thr), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
     wait_all_vmem();                                       // no LDS-DMA may land after the lists are published below
     __syncthreads();
@@ -1177,12 +1101,9 @@ __global__ __launch_bounds__(WAVES * 64, 2) void m2d_topk_grouped_bf16_pipe2(Gro
     }
 #endif
 
-#pragma unroll
-    for (int g = 0; g < G; ++g) {
-        float *ls = reinterpret_cast<float *>(smem8) + (size_t)(wave * G + g) * 2 * KR * 64;   // aliases stage 0
-        int32_t *li = reinterpret_cast<int32_t *>(ls + (size_t)KR * 64);
-        grouped_publish<KR>(ls, li, rs[g], ri[g], p, lane, uidx[g], uvalid[g], tie_mask[g], by, lout[g]);
-    }
+    float *ls = reinterpret_cast<float *>(smem8) + (size_t)wave * 2 * KR * 64;   // aliases stage 0
+    int32_t *li = reinterpret_cast<int32_t *>(ls + (size_t)KR * 64);
+    grouped_publish<KR>(ls, li, rs, ri, p, lane, uidx, uvalid, tie_mask, by, lout);
     (void)k;
 }
 
@@ -1210,21 +1131,21 @@ int M2D_SCAN_LAUNCH(m2d_engine *h, const GroupedArgs &a, const ScanShape &s, dim
 #define M2D_SCAN_BF16(EV, KRV)                                                                                                   \
     if (s.E == EV && s.KR == KRV) {                                                                                               \
         constexpr bool CAN_KEEP = !(EV == 128 && KRV == 16);                                                                      \
-        if (s.hv && s.apx) M2D_SCAN_GO((m2d_topk_grouped_bf16_pipe2<EV, KRV, 1, true, 8, false, true>), 512)                      \
-        if (s.hv) M2D_SCAN_GO((m2d_topk_grouped_bf16_pipe2<EV, KRV, 1, true>), 512)                                               \
+        if (s.hv && s.apx) M2D_SCAN_GO((m2d_topk_grouped_bf16_pipe2<EV, KRV, true, 8, false, true>), 512)                         \
+        if (s.hv) M2D_SCAN_GO((m2d_topk_grouped_bf16_pipe2<EV, KRV, true>), 512)                                                  \
         if (!s.pipe) M2D_SCAN_GO((m2d_topk_grouped_bf16<EV, 8, KRV>), 512)                                                        \
         if constexpr (EV == 64) {                                                                                                 \
-            if (s.apx && s.keep) M2D_SCAN_GO((m2d_topk_grouped_bf16_pipe2<EV, KRV, 1, false, 8, true, true>), 512)                \
-            if (s.apx) M2D_SCAN_GO((m2d_topk_grouped_bf16_pipe2<EV, KRV, 1, false, 8, false, true>), 512)                         \
-            if (s.waves == 4 && s.keep) M2D_SCAN_GO((m2d_topk_grouped_bf16_pipe2<EV, KRV, 1, false, 4, true>), 256)               \
-            if (s.waves == 4) M2D_SCAN_GO((m2d_topk_grouped_bf16_pipe2<EV, KRV, 1, false, 4>), 256)                               \
+            if (s.apx && s.keep) M2D_SCAN_GO((m2d_topk_grouped_bf16_pipe2<EV, KRV, false, 8, true, true>), 512)                   \
+            if (s.apx) M2D_SCAN_GO((m2d_topk_grouped_bf16_pipe2<EV, KRV, false, 8, false, true>), 512)                            \
+            if (s.waves == 4 && s.keep) M2D_SCAN_GO((m2d_topk_grouped_bf16_pipe2<EV, KRV, false, 4, true>), 256)                  \
+            if (s.waves == 4) M2D_SCAN_GO((m2d_topk_grouped_bf16_pipe2<EV, KRV, false, 4>), 256)                                  \
         }                                                                                                                         \
         if constexpr (EV == 128) {                                                                                                \
-            if (CAN_KEEP && s.apx && s.keep) M2D_SCAN_GO((m2d_topk_grouped_bf16_pipe2<EV, KRV, 1, false, 8, CAN_KEEP, true>), 512)    \
-            if (s.apx && !s.keep) M2D_SCAN_GO((m2d_topk_grouped_bf16_pipe2<EV, KRV, 1, false, 8, false, true>), 512)              \
+            if (CAN_KEEP && s.apx && s.keep) M2D_SCAN_GO((m2d_topk_grouped_bf16_pipe2<EV, KRV, false, 8, CAN_KEEP, true>), 512)   \
+            if (s.apx && !s.keep) M2D_SCAN_GO((m2d_topk_grouped_bf16_pipe2<EV, KRV, false, 8, false, true>), 512)                 \
         }                                                                                                                         \
-        if (CAN_KEEP && s.keep) M2D_SCAN_GO((m2d_topk_grouped_bf16_pipe2<EV, KRV, 1, false, 8, CAN_KEEP>), 512)                   \
-        M2D_SCAN_GO((m2d_topk_grouped_bf16_pipe2<EV, KRV, 1>), 512)                                                               \
+        if (CAN_KEEP && s.keep) M2D_SCAN_GO((m2d_topk_grouped_bf16_pipe2<EV, KRV, false, 8, CAN_KEEP>), 512)                      \
+        M2D_SCAN_GO((m2d_topk_grouped_bf16_pipe2<EV, KRV>), 512)                                                                  \
     }
 #if !defined(M2D_SCAN_E) || M2D_SCAN_E == 64
     M2D_SCAN_BF16(64, 10) M2D_SCAN_BF16(64, 16)
