@@ -35,6 +35,7 @@ struct WriteArgs {
     int32_t C, E, L;
     float beta_1, beta_2, alpha;
     int32_t *err;
+    const int32_t *nonfinite;   // device word: some table value is inf / NaN -> 0 * row is not 0 (:111), no row is left out
 };
 
 __device__ __forceinline__ void latch(int32_t *err, int code, int64_t value, int64_t index)
@@ -55,6 +56,7 @@ __global__ __launch_bounds__(256) void m2d_write_memory_kernel(WriteArgs p)
     const int64_t wave0 = (int64_t)blockIdx.x * 4 + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int64_t nwaves = (int64_t)gridDim.x * 4;
     const int C = p.C, E = p.E, L = p.L;
+    const bool finite_tables = PASS != 0 && __builtin_amdgcn_readfirstlane(*p.nonfinite) == 0;
     for (int64_t b = wave0; b < p.B; b += nwaves) {
         const int32_t uid = p.users[b], did = p.items[b];
         const int64_t ul = (int64_t)uid - p.user_base;
@@ -95,8 +97,10 @@ __global__ __launch_bounds__(256) void m2d_write_memory_kernel(WriteArgs p)
         if (PASS == 0) each_label([&](int l) { ysum += y[l]; });             // :180 -- the zero weights add nothing
         const float lo = p.beta_1 * s, hi = p.beta_2 * s;                    // :115, :141
         for (int r = 0; r <= C; ++r) {
-            // General_Memory passes: the row of a category whose weight is 0 is a row of zeros -- nothing to add
-            if (PASS != 0 && r > 0 && m[r - 1] == 0.f) continue;
+            // General_Memory passes: the row of a category whose weight is 0 is (0 * RE[d]) * lo -- a row of zeros, nothing to
+            // add, WHILE every table value and lo are finite.  Otherwise it is 0 * inf = NaN (:111, :119), which
+            // m2d_write_gm_gather and pass 0 add: so does this pass.
+            if (PASS != 0 && r > 0 && m[r - 1] == 0.f && finite_tables && lo * 0.f == 0.f) continue;
             for (int e = lane; e < E; e += 64) {
                 float v;
                 if (r == 0) {
@@ -190,8 +194,12 @@ int m2d_launch_write_memory(m2d_engine *h, const int32_t *users, const int32_t *
     a.pm = const_cast<float *>(h->pm); a.re = h->re; a.ce = h->ce; a.gm = gm;
     a.users = users; a.items = items; a.cats = cats; a.sign = sign; a.labels = labels;
     a.B = B; a.U = h->U; a.I = h->I; a.user_base = h->user_base; a.C = h->C; a.E = h->E; a.L = L;
-    a.beta_1 = beta_1; a.beta_2 = beta_2; a.alpha = alpha; a.err = h->err_dev;
+    a.beta_1 = beta_1; a.beta_2 = beta_2; a.alpha = alpha; a.err = h->err_dev; a.nonfinite = h->nonfinite_dev;
     if (B > 0) {
+        if ((which & M2D_WRITE_GENERAL) && B > 2048) {          // the atomics form leaves zero-weight rows out on the word's say-so
+            const int rc = m2d_ensure_finite_scan(h, stream);
+            if (rc != M2D_OK) return rc;
+        }
         int64_t blocks = (B + 3) / 4;
         if (blocks > (int64_t)h->num_cu * 8) blocks = (int64_t)h->num_cu * 8;
         // each pass runs only when its assign is fetched (`personal` -> :167/:198, `general` -> :215); a GM-only call

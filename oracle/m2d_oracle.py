@@ -201,6 +201,52 @@ def write_memory(PM, RE, CE, GM, users, items, categories, write_sign, user_one_
     return PM2, GM2, PM2.mean(), GM2.mean()
 
 
+def write_memory_scatter(PM, RE, CE, GM, users, items, categories, write_sign, user_one_hot_label,
+                         beta_1=0.01, beta_2=0.01, alpha=0.01, dtype=np.float64, personal=True, general=True):
+    """`write_memory` as the scatter-add the engine documents: a plain loop over the pairs, in batch order,
+
+        v_b = [ beta_2 s_b (sum_c m_bc CE_c) / n_b ; (m_bc RE[d_b]) beta_1 s_b , c = 0..C-1 ]
+        g_b = (sum_{l: y_bl != 0} y_bl GM[l]) / (sum_l y_bl)                 GM = General_Memory before the call
+        PM[u_b] += v_b + alpha g_b ;   GM[l] += y_bl v_b  for every l with y_bl != 0
+
+    with each term grouped as the reference groups it (:111, :119, :134, :145).  Same arguments and return value as
+    `write_memory`.  On finite inputs the two agree to rounding; they part where a value is inf / NaN: the dense one-hot
+    matmuls multiply such a row by the zeros of every other user and label (0 * inf = NaN everywhere), this form keeps it
+    in the rows the pair addresses -- and inside those rows keeps the reference's own arithmetic, so the row of a category
+    with weight 0 still receives 0 * inf = NaN (:111).  No [B, U, .] intermediates: usable at any batch size."""
+    PM2 = np.array(PM, dtype=dtype); RE = np.asarray(RE, dtype=dtype); CE = np.asarray(CE, dtype=dtype)
+    GM0 = np.asarray(GM, dtype=dtype)
+    GM2 = GM0.copy()
+    U, C1, E = PM2.shape
+    C = C1 - 1
+    users = _as_ids(users, U, "user"); items = _as_ids(items, RE.shape[0], "item")
+    B = len(users)
+    cat = _as_mask(categories, C).astype(dtype)[:, :, 0]                          # [B, C]
+    s = np.asarray(write_sign, dtype=dtype).reshape(B)
+    y = np.asarray(user_one_hot_label, dtype=dtype).reshape(B, -1)
+    b1, b2, al = dtype(beta_1), dtype(beta_2), dtype(alpha)
+    with np.errstate(divide="ignore", invalid="ignore", over="ignore"):
+        for b in range(B):
+            m = cat[b]
+            v = np.empty((C1, E), dtype=dtype)
+            v[0] = ((m[:, None] * CE).sum(axis=0) / m.sum()) * (b2 * s[b])        # :124-145
+            v[1:] = (m[:, None] * RE[items[b]][None, :]) * (b1 * s[b])            # :111-119
+            lab = np.flatnonzero(y[b] != 0)
+            if personal:
+                g = np.zeros((C1, E), dtype=dtype)
+                for l in lab:
+                    g = g + y[b, l] * GM0[l]                                      # :172-178
+                PM2[users[b]] += v + al * (g / y[b, lab].sum())                   # :162, :180-198
+            if general:
+                for l in lab:
+                    GM2[l] += y[b, l] * v                                         # :200-215
+    if not personal:
+        PM2 = np.asarray(PM, dtype=dtype)
+    if not general:
+        GM2 = GM0
+    return PM2, GM2, PM2.mean(), GM2.mean()
+
+
 # ----------------------------------------------------------------------------------------------
 # Build-defined extensions (NO reference counterpart; BASELINE.json configs 2-5).  These restate the
 # build's own definitions (DESIGN.md section 8); nothing in the reference pins them.

@@ -63,3 +63,34 @@ def random_case(U, I, C, E, B, seed, zero_rows=True):
     if not zero_rows:
         cats[cats.sum(1) == 0, 0] = 1.0
     return PM, RE, CE, users, items, cats
+
+
+def write_case(U, I, C, E, L, B, seed, weighted=False):
+    """Inputs of one Write_Memory call: random_case's tables and pairs, a General_Memory, +-1 write signs and labels
+    (every pair has at least one).  `weighted`: label weights from {0, 0.5, 1, 2} and each pair's mask scaled by
+    uniform(0.5, 2) -- the placeholders are float, the kernels multiply by them."""
+    PM, RE, CE, users, items, cats = random_case(U, I, C, E, B, seed, zero_rows=False)
+    rng = np.random.default_rng(seed + 1000)
+    GM = (rng.standard_normal((L, C + 1, E)) / 4).astype(np.float32)
+    sign = np.where(rng.random(B) < 0.6, 1.0, -1.0).astype(np.float32)
+    if weighted:
+        y = rng.choice(np.array([0, 0, 0, 0.5, 1, 2], np.float32), (B, L))
+        cats = (cats * rng.uniform(0.5, 2.0, (B, 1))).astype(np.float32)
+    else:
+        y = (rng.random((B, L)) < 0.2).astype(np.float32)
+    y[y.sum(1) == 0, 0] = 1
+    return PM, RE, CE, GM, users, items, cats, sign, y
+
+
+def containment_case(U, I, C, E, L, B, seed, bad=np.inf, zero=0.0):
+    """write_case with one non-finite element: Recipe_Embedding[5, 3] = `bad`.  Dish 5 is written by pair 7 alone, whose mask
+    is [1, zero, 1, zero] (C = 4), whose one label is 4 and whose user, U - 1, no other pair of the batch has."""
+    PM, RE, CE, GM, users, items, cats, sign, y = write_case(U, I, C, E, L, B, seed)
+    items[items == 5] = 6
+    users[users == U - 1] = 0
+    users[7], items[7] = U - 1, 5
+    cats[7] = [1.0, zero, 1.0, zero]
+    y[7] = 0
+    y[7, 4] = 1
+    RE[5, 3] = bad
+    return PM, RE, CE, GM, users, items, cats, sign, y

@@ -148,3 +148,45 @@ def test_write_memory_restatement_by_hand():
     assert np.allclose(PM2[1, :, 0], [0.5 + 0.55, 1 + 1.1, 1 + 1.65]) and np.all(PM2[0] == 0)
     assert np.allclose(GM2[:, :, 0], GM[:, :, 0] + [0.5, 1, 1])
     assert mp == pytest.approx(PM2.mean()) and mg == pytest.approx(GM2.mean())
+
+
+@pytest.mark.parametrize("personal,general", [(True, True), (True, False), (False, True)])
+def test_write_memory_scatter_agrees_with_the_dense_restatement(personal, general):
+    """Finite inputs, weighted masks and weighted labels: the per-pair scatter loop and the dense one-hot matmuls are the
+    same sums in another order (float64: 1e-12)."""
+    from helpers import write_case
+    args = write_case(40, 30, 4, 32, 9, 600, seed=21, weighted=True)
+    assert len(np.unique(args[8])) == 4 and len(np.unique(args[6])) > 100          # the weights are there
+    d = oracle.write_memory(*args, 0.01, 0.02, 0.03, personal=personal, general=general)
+    s = oracle.write_memory_scatter(*args, 0.01, 0.02, 0.03, personal=personal, general=general)
+    for a, b in zip(d, s):
+        assert np.all(np.isfinite(a)) and np.abs(np.asarray(a) - np.asarray(b)).max() <= 1e-12
+    assert np.array_equal(s[0], args[0]) == (not personal) and np.array_equal(s[1], args[3]) == (not general)
+
+
+def test_write_memory_scatter_keeps_non_finite_values_in_the_rows_a_pair_addresses():
+    """One inf in one dish row.  The pair that writes the dish has mask [1, 0, 1, 0]: element 3 of rows 1 and 3
+    of its user's block and of its label's block becomes +-inf, of rows 2 and 4 NaN (0 * inf, Model_Recommender.py:111), and
+    nothing else is non-finite.  The dense restatement is no reference here: it leaves no user or label finite there."""
+    from helpers import containment_case
+    U, L = 40, 9
+    PM, RE, CE, GM, users, items, cats, sign, y = args = containment_case(U, 30, 4, 32, L, 64, seed=8)
+    assert (items == 5).sum() == 1 and (users == U - 1).sum() == 1 and items[7] == 5
+    PM2, GM2, mp, mg = oracle.write_memory_scatter(*args, 0.01, 0.02, 0.03)
+    inf = np.float64(sign[7]) * np.inf
+    for T, row in ((PM2, U - 1), (GM2, 4)):
+        bad = ~np.isfinite(T)
+        want = np.zeros_like(bad)
+        want[row, 1:, 3] = True
+        assert np.array_equal(bad, want)
+        assert T[row, 1, 3] == inf and T[row, 3, 3] == inf and np.isnan(T[row, 2, 3]) and np.isnan(T[row, 4, 3])
+    assert np.isnan(mp) and np.isnan(mg)
+    # everything finite is what the batch gives with a finite value in that place
+    RE0 = RE.copy(); RE0[5, 3] = 0.25
+    PMf, GMf, _, _ = oracle.write_memory_scatter(PM, RE0, CE, GM, *args[4:], 0.01, 0.02, 0.03)
+    ok = np.isfinite(PM2)
+    assert np.array_equal(PM2[ok], PMf[ok])
+    ok = np.isfinite(GM2)
+    assert np.array_equal(GM2[ok], GMf[ok])
+    PMd, GMd, _, _ = oracle.write_memory(*args, 0.01, 0.02, 0.03)
+    assert not np.isfinite(PMd[:, 1:, 3]).any() and not np.isfinite(GMd[:, 1:, 3]).any()
