@@ -94,3 +94,203 @@ def containment_case(U, I, C, E, L, B, seed, bad=np.inf, zero=0.0):
     y[7, 4] = 1
     RE[5, 3] = bad
     return PM, RE, CE, GM, users, items, cats, sign, y
+
+
+# ---- training step (tests/test_gpu_train.py, tests/test_train_oracle.py) ------------------------------------------------
+# |got - ref| <= rho |ref - ini| + phi max(1, |ref|).  (rho, phi): 4 x what the float32-mode oracle needs against the float64
+# one over every case of the training tests -- the measured maxima and the procedure are in test_gpu_train.py's docstring.
+TRAIN_RHO, TRAIN_PHI = 5.8e-3, 6.5e-7                # sgd, adagrad, rmsprop
+TRAIN_RHO_ADAM, TRAIN_PHI_ADAM = 1.0e-3, 4.5e-6      # adam: m / (sqrt(v) + eps) magnifies the last bits of gradients that cancel
+TRAIN_SLOT_RHO, TRAIN_SLOT_PHI = 7.2e-4, 1.4e-6      # optimizer slots, phi on the slot's own scale (assert_train_slots)
+TRAIN_PARTS = ("PM high", "PM low", "RE", "CE")
+
+
+def train_parts(tables):
+    """The four gradient paths of a step as views of (Personal_Memory, Recipe_Embedding, Category_Embedding)."""
+    PM, RE, CE = tables
+    return (("PM high", PM[:, :1, :]), ("PM low", PM[:, 1:, :]), ("RE", RE), ("CE", CE))
+
+
+def train_batches(U, I, C, B, steps, seed, fractional=False, distinct=False, user_base=0):
+    """`steps` batches of B pairs: a quarter of the pairs on one user and three eighths on one dish (duplicate ids: their rows
+    must be summed), 0/1 masks with one pair's halved (masks are weights).  `fractional`: a few labels of 0.25 / 0.75.
+    `distinct`: ids drawn without replacement apart from a hot block of 64 pairs (needs U, I >= B)."""
+    rng = np.random.default_rng(seed)
+    out = []
+    for _ in range(steps):
+        if distinct:
+            users = rng.permutation(U)[:B].astype(np.int32)
+            items = rng.permutation(I)[:B].astype(np.int32)
+            users[:64] = users[0]
+            items[32:96] = items[32]
+        else:
+            users = rng.integers(0, U, B).astype(np.int32)
+            items = rng.integers(0, I, B).astype(np.int32)
+            users[: B // 4] = users[0]
+            items[B // 8: B // 2] = items[B // 8]
+        cats = rng.integers(0, 2, (B, C)).astype(np.float32)
+        cats[cats.sum(1) == 0, rng.integers(0, C)] = 1.0
+        cats[B // 3] *= 0.5
+        labels = rng.integers(0, 2, B).astype(np.float32)
+        if fractional:
+            labels[1::7] = 0.25
+            labels[B // 2] = 0.75
+        out.append((users + np.int32(user_base), items, cats, labels))
+    return out
+
+
+def train_bound(ref, ini, learner, rho=None, phi=None):
+    rho = (TRAIN_RHO_ADAM if learner == "adam" else TRAIN_RHO) if rho is None else rho
+    phi = (TRAIN_PHI_ADAM if learner == "adam" else TRAIN_PHI) if phi is None else phi
+    return rho * np.abs(ref - ini) + phi * np.maximum(1.0, np.abs(ref))
+
+
+def train_visibility(ref, ini, learner, rho=None, phi=None):
+    """Per part: the share of the elements the oracle moved that moved by more than 10 times their bound (None: none moved)."""
+    out = {}
+    for (name, r), (_, i) in zip(train_parts(ref), train_parts(ini)):
+        r = np.asarray(r, np.float64); i = np.asarray(i, np.float64)
+        moved = r != i
+        out[name] = float((np.abs(r - i)[moved] > 10.0 * train_bound(r, i, learner, rho, phi)[moved]).mean()) if moved.any() else None
+    return out
+
+
+def assert_train_tables(got, ref, ini, learner, visible=TRAIN_PARTS, rho=None, phi=None, what=""):
+    """Tables after some training steps against the float64 restatement's.  got / ref / ini: (Personal_Memory,
+    Recipe_Embedding, Category_Embedding) as the engine left them, as the oracle left them, as both started.
+
+    Per part (Personal_Memory's high row, its low rows, Recipe_Embedding, Category_Embedding):
+      * |got - ref| <= rho |ref - ini| + phi max(1, |ref|), element by element;
+      * what the oracle did not move is bit-equal to `ini` -- element by element for sgd / adagrad / rmsprop (a zero gradient
+        is an exact zero), whole rows for adam (TF 1.x Adam moves every element of a row that has history);
+      * for the parts named in `visible`: at least 90 % of the moved elements moved by more than 10 bounds, so an engine that
+        halves, doubles, drops or misplaces that part's gradient cannot pass.  Asserted on ref and ini alone."""
+    vis = train_visibility(ref, ini, learner, rho, phi)
+    stats = {}
+    for (name, g), (_, r), (_, i) in zip(train_parts(got), train_parts(ref), train_parts(ini)):
+        g = np.asarray(g); r = np.asarray(r, np.float64); i32 = np.asarray(i); i = i32.astype(np.float64)
+        assert g.shape == r.shape == i.shape, (what, name, g.shape, r.shape)
+        moved = r != i
+        if name in visible:
+            assert vis[name] is None or vis[name] >= 0.9, "%s %s: only %.2f of the moved elements are visible" % (what, name, vis[name])
+        still = ~moved if learner != "adam" else np.broadcast_to(~moved.any(axis=-1, keepdims=True), moved.shape)
+        assert np.array_equal(g[still], i32[still].astype(g.dtype)), "%s %s: %d elements the oracle left alone changed" % (
+            what, name, int((g[still] != i32[still]).sum()))
+        err = np.abs(g.astype(np.float64) - r)
+        bound = train_bound(r, i, learner, rho, phi)
+        bad = err > bound
+        assert not bad.any(), "%s %s: %d of %d outside the bound, worst err %.3e (moved %.3e, bound %.3e)" % (
+            what, name, int(bad.sum()), bad.size, err[bad].max(), np.abs(r - i)[bad][err[bad].argmax()], bound[bad][err[bad].argmax()])
+        stats[name] = {"moved": int(moved.sum()), "visible": vis[name], "err": float(err.max())}
+    return stats
+
+
+TRAIN_SLOT_INIT = {"adam": (0.0, 0.0), "adagrad": (0.1,), "rmsprop": (1.0, 0.0), "sgd": ()}
+
+
+def assert_train_slots(got, ref, learner, rho=None, phi=None, what=""):
+    """Optimizer slots against the oracle's, [table][slot]: adam m, v (start at 0); adagrad's accumulator (0.1); rmsprop's rms
+    (1) and momentum (0).  The same form of bound on the slot's OWN scale -- Adam's v is g^2, 1e-9 to 3e-6, and a floor of
+    phi max(1, |ref|) would let a v that was never written pass:
+
+        |got - ref| <= rho |ref - ini| + phi S,     S = max(|ini|, max |ref| over that slot of that table)
+
+    and what the oracle left at its initial value is bit-equal to it.  TRAIN_SLOT_RHO / TRAIN_SLOT_PHI: 4 x what the float32
+    oracle needs, measured like the tables' pair over the same cases."""
+    rho = TRAIN_SLOT_RHO if rho is None else rho
+    phi = TRAIN_SLOT_PHI if phi is None else phi
+    for tb, (gs, rs) in enumerate(zip(got, ref)):
+        assert len(gs) == len(rs) == len(TRAIN_SLOT_INIT[learner]), (what, tb)
+        for sl, (g, r, v0) in enumerate(zip(gs, rs, TRAIN_SLOT_INIT[learner])):
+            g = np.asarray(g, np.float64).reshape(np.shape(r)); r = np.asarray(r, np.float64)
+            i = np.full_like(r, np.float64(np.float32(v0)))
+            still = (r == v0) | (r == i)                    # (the float64 oracle starts adagrad at the double 0.1)
+            assert np.array_equal(g[still], i[still]), "%s slot %d of table %d: values the oracle left alone changed" % (what, sl, tb)
+            err = np.abs(g - r)
+            bound = rho * np.abs(r - i) + phi * max(abs(float(np.float32(v0))), float(np.abs(r).max()))
+            bad = err > bound
+            assert not bad.any(), "%s slot %d of table %d: %d of %d outside the bound, worst err %.3e (bound there %.3e)" % (
+                what, sl, tb, int(bad.sum()), bad.size, err[bad].max(), bound[bad][err[bad].argmax()])
+
+
+def _train_lr(B, E=0):
+    """sgd / adagrad / rmsprop move a row by about lr * g, and g falls with 1 / B and with the table scale 1 / sqrt(E)."""
+    return (0.5 if B <= 128 else 8.0) * (8.0 if E >= 512 and B <= 128 else 1.0)
+
+
+def train_lr(lr, learner):
+    """Adam moves every element by about lr whatever the gradient: it keeps the small rate."""
+    return 0.01 if learner == "adam" else lr
+
+
+ALL_LEARNERS = ("adam", "sgd", "adagrad", "rmsprop")
+# test_train_steps_match_restatement's shapes (U, I, C, E, B, "variant" option)
+TRAIN_SHAPES = [(300, 100, 4, 32, 128, 0), (64, 40, 4, 200, 8, 0), (50, 30, 3, 6, 257, 0), (2000, 500, 4, 64, 4096, 0),
+                (300, 100, 4, 32, 128, 14), (64, 40, 4, 200, 1000, 0), (64, 40, 4, 200, 1000, 14)]
+FUSED, NINE = "m2d_train_grad_fused", "m2d_train_grad"
+
+
+def train_launch_cases(cus=256):
+    """The cases of test_gpu_train.py::test_train_launches_that_never_ran, by name.  `cus`: the device's compute units (the
+    grad kernel's grid stops at 8 blocks = 32 waves per unit).  Every case: blend 0.5, lr by batch size (see
+    assert_train_tables: what makes every gradient path visible), three steps of every learner unless it says otherwise."""
+    W = 32 * cus
+    case = lambda U, I, C, E, B, kernel, **kw: dict(dict(U=U, I=I, C=C, E=E, B=B, kernel=kernel, form=0, steps=3, learners=ALL_LEARNERS,
+                                                         coef=0.5, lr=_train_lr(B, E), distinct=False, user_base=0, then_fused=False), **kw)
+    return {
+        # rows that are no multiple of 4 floats in the nine-launch form: m2d_train_apply<*, 1>
+        "vec1_re_ce": case(50, 30, 3, 6, 1100, NINE),
+        "vec1_all": case(40, 30, 4, 7, 257, NINE, form=14),
+        # 16 C E bytes above 48 KiB: dCE through global atomics, no m2d_train_reduce_ce, the fused form refused
+        "ce_global_b200": case(600, 200, 4, 772, 200, NINE),
+        "ce_global_b1100": case(600, 200, 4, 772, 1100, NINE),
+        "ce_global_c13": case(600, 200, 13, 250, 300, NINE),
+        # the fused form at its LDS limit, and the first E past it
+        "fused_lds_limit": case(300, 100, 4, 768, 128, FUSED),
+        "past_lds_limit": case(300, 100, 4, 772, 128, NINE, steps=1),
+        # waves of the grad kernel own 2 or 3 pairs
+        "pairs_per_wave": case(3000, 700, 3, 6, 2 * W + 77, NINE),
+        "pairs_per_wave_e64": case(3000, 700, 4, 64, 2 * W + 77, NINE, learners=("sgd", "adam"), steps=2, lr=32.0),
+        # more rows than waves: m2d_train_apply<true, 4> over all users; <false, 4> and both cleanups over the claimed rows
+        "adam_rows_loop": case(W + 1500, 300, 4, 8, 1100, NINE, learners=("adam",), then_fused=True),
+        "claimed_rows_loop": case(3 * W, 3 * W, 4, 8, 2 * W + 77, NINE, learners=("sgd", "adagrad"), steps=2, distinct=True,
+                                  then_fused=True, lr=32.0),
+        # one user-range shard
+        "shard_nine": case(300, 100, 4, 32, 1100, NINE, user_base=7000),
+        "shard_fused": case(300, 100, 4, 32, 128, FUSED, user_base=7000),
+    }
+
+
+def train_visible_cases():
+    """test_train_steps_every_path_visible: every shape of TRAIN_SHAPES at blend 0.5, three at 0 (no high-level gradient: the
+    high row and Category_Embedding stay bit-equal), one at 1.25 (a negative low-level weight) and two at the default 0.99."""
+    out = [(s, 0.5) for s in TRAIN_SHAPES]
+    out += [(TRAIN_SHAPES[0], 0.0), (TRAIN_SHAPES[2], 0.0), (TRAIN_SHAPES[4], 0.0), (TRAIN_SHAPES[0], 1.25)]
+    out += [(TRAIN_SHAPES[0], 0.99), (TRAIN_SHAPES[3], 0.99)]      # the default blend: the high row and CE visible, the rest compared
+    return [s + (c, _train_lr(s[4], s[3]) * (4.0 if c > 1 else 1.0)) for s, c in out]
+
+
+def train_visible_parts(coef, learner, lr):
+    """The parts on which a case must meet assert_train_tables' visibility condition.  Adam moves every element by about lr:
+    all four.  The others move a row by lr * g: at the default blend the low-level gradient is 1 / 100 of the high-level one and
+    only the high row and Category_Embedding can be visible; at lr = 0.01 (the cases kept from before the condition) those two
+    meet it on some shapes and not on others (the high row 0.63 at (300, 100, 4, 32, 128)), so it is not asserted there."""
+    if learner == "adam":
+        return TRAIN_PARTS
+    if lr <= 0.01:
+        return ()
+    return ("PM high", "CE") if coef == 0.99 else TRAIN_PARTS
+
+
+def run_train_oracle(spec, learner, dtype=np.float64, cls=None):
+    """The oracle's side of one case of train_launch_cases: (initial tables, batches, state after the steps, [(loss, norm)])."""
+    from oracle import train_oracle as T
+    U, I, C, E, B = (spec[k] for k in "UICEB")
+    PM, RE, CE, *_ = random_case(U, I, C, E, 1, seed=U + E)
+    ini = (PM * 3, RE * 3, CE * 3)
+    batches = train_batches(U, I, C, B, spec["steps"], seed=B, fractional=True, distinct=spec["distinct"])
+    if spec["then_fused"]:
+        batches += train_batches(U, I, C, 64, 1, seed=B + 1, fractional=True)
+    st = (cls or T.TrainState)(*ini, learner, train_lr(spec["lr"], learner), coef=spec["coef"], dtype=dtype)
+    outs = [st.step(*b) for b in batches]
+    return ini, batches, st, outs

@@ -158,11 +158,11 @@ def test_training_step_any_shape(seed, learner, C, E, B):
     out = eng.train_step(dev(users), dev(items), dev(cats), dev(labels)).cpu().numpy(); eng.check()
     assert abs(out[0] - ref_loss) <= 1e-5 * max(1.0, abs(ref_loss))
     assert abs(out[1] - ref_norm) <= 1e-5 * max(1.0, ref_norm)
-    tol = 1e-3 * lr if learner in ("adam", "rmsprop") else None
-    for got, ref in ((eng.pm, st_.PM), (eng.re, st_.RE), (eng.ce, st_.CE)):
-        err = np.abs(got.cpu().numpy().astype(np.float64) - ref)
-        bound = tol if tol is not None else 1e-5 * np.maximum(1.0, np.abs(ref))
-        assert np.all(err <= bound), (learner, C, E, B, err.max())
+    # test_gpu_train.py's bound (every element against what the step did to it), without its visibility condition: at lr 0.01
+    # and the default blend the quiet parts cannot meet it
+    from helpers import assert_train_tables
+    assert_train_tables(tuple(t.cpu().numpy() for t in (eng.pm, eng.re, eng.ce)), (st_.PM, st_.RE, st_.CE), (PM, RE, CE), learner,
+                        visible=(), what=str((learner, C, E, B)))
     eng.close()
 
 
