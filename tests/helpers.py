@@ -96,6 +96,113 @@ def containment_case(U, I, C, E, L, B, seed, bad=np.inf, zero=0.0):
     return PM, RE, CE, GM, users, items, cats, sign, y
 
 
+# ---- the MLP head (tests/test_gpu_mlp.py, tests/test_mlp_checks_cpu.py, tests/test_gpu_readers_after_writers.py) ---------
+# The share of pairs that must move by more than 10 bounds when one 32-value k-period of one block is lost.  A condition on
+# the INPUTS of a comparison (tables, masks, head, blend), evaluated with the oracle alone; not a tolerance on any kernel.
+MLP_VISIBLE = 0.8
+
+
+def mlp_head(K, H1, H2, rng, scale=1.0):
+    """A random head (W1, b1, W2, b2, w3, b3); scale 4 makes the head's share of the score a large one."""
+    W1 = (rng.standard_normal((K, H1)) * scale / np.sqrt(K)).astype(np.float32)
+    b1 = (rng.standard_normal(H1) * 0.1).astype(np.float32)
+    W2 = (rng.standard_normal((H1, H2)) * scale / np.sqrt(H1)).astype(np.float32)
+    b2 = (rng.standard_normal(H2) * 0.1).astype(np.float32)
+    w3 = (rng.standard_normal(H2) * scale / np.sqrt(H2)).astype(np.float32)
+    return W1, b1, W2, b2, w3, 0.25
+
+
+def mlp_periods(E):
+    """The k-periods of one block of E values: whole periods of 32, a remainder joined to the last one (E < 32: one period).
+    The kernels that walk a block period by period exist for E % 32 == 0 only; elsewhere a lost period has no counterpart in
+    the code and the remainder alone (8 values of E = 200) would measure the table scale, not the inputs' visibility."""
+    n = max(1, E // 32)
+    return [(32 * p, 32 * (p + 1) if p < n - 1 else E) for p in range(n)]
+
+
+def mlp_visibility(PM, RE, CE, cats, head, users, items, coef, dish_high=None, detail=False):
+    """How visible a lost k-period is in the scores of these pairs, in float64 with the oracle's expressions only.
+
+    For every block b in 0 .. C and every period of that block (mlp_periods): that period of PM[:, b] zeroed -- which is what
+    a stale pattern byte, a skipped ring stage or a z set from another tile does to a score -- and the share of the AFFECTED
+    pairs whose score moves by more than 10 TOL max(1, |ref|).  Affected: every pair with a finite score for block 0, those
+    with cats[d, b - 1] != 0 for a low-level block (elsewhere the block's z is zero whatever the user row holds).  Returns the
+    minimum share over (block, period); `detail`: the whole {(block, period): share}.  Block 0 is skipped when an ingredient
+    table (`dish_high`) replaces it.
+
+    Zeroing PM[:, b, lo:hi] zeroes z there, and layer 1 is linear in z: the altered score comes from the pre-activations
+    minus that period's product instead of from a second pass over all K (test_mlp_checks_cpu.py checks the identity
+    against oracle.inference_mlp on altered tables)."""
+    from oracle import m2d_oracle as oracle
+    W1, b1, W2, b2, w3 = (np.asarray(x, np.float64) for x in head[:5])
+    b3 = float(head[5])
+    PMd = np.asarray(PM, np.float64)
+    cats = np.asarray(cats).reshape(len(RE), -1)
+    C, E = cats.shape[1], PMd.shape[2]
+    users = np.asarray(users, np.int64); items = np.asarray(items, np.int64)
+    Dt = oracle.dish_vectors(RE, CE, cats, coef, np.float64)
+    if dish_high is not None:
+        Dt[:, :E] = np.float64(oracle.blend_coefficients(coef)[0]) * np.asarray(dish_high, np.float64)
+    with np.errstate(invalid="ignore"):
+        z = PMd[users].reshape(len(users), -1) * Dt[items]
+        pre1 = z @ W1 + b1
+        tail = lambda pre: np.maximum(np.maximum(pre, 0) @ W2 + b2, 0) @ w3 + b3
+        base = z.sum(axis=1)
+        ref = base + tail(pre1)
+    finite = np.isfinite(ref)
+    out = {}
+    for b in range(C + 1):
+        if b == 0 and dish_high is not None:
+            continue
+        aff = finite if b == 0 else finite & (cats[items, b - 1] != 0)
+        if not aff.any():
+            continue
+        thr = 10.0 * TOL * np.maximum(1.0, np.abs(ref[aff]))
+        for p, (lo, hi) in enumerate(mlp_periods(E)):
+            ks = slice(b * E + lo, b * E + hi)
+            zz = z[aff, ks]
+            alt = base[aff] - zz.sum(axis=1) + tail(pre1[aff] - zz @ W1[ks])
+            out[(b, p)] = float(np.mean(np.abs(alt - ref[aff]) > thr))
+    assert out, "mlp_visibility: no pair with a finite score"
+    return out if detail else min(out.values())
+
+
+def mlp_case(PM, RE, CE, cats, head, users, items, coef, dish_high=None):
+    """What assert_mlp_scores compares against: tables, masks by dish, head, the pairs (GLOBAL user ids into PM) and the blend.
+    `cache`: references by pick, so that tests which share a case compute each once."""
+    import types
+    return types.SimpleNamespace(PM=PM, RE=RE, CE=CE, cats=cats, head=head, users=np.asarray(users), items=np.asarray(items),
+                                 coef=coef, dish_high=dish_high, cache={})
+
+
+def assert_mlp_scores(got, case, pick=None, what=""):
+    """Scores of the MLP head against oracle.inference_mlp (float64) (`got`: one score per pair of the case; `pick`: the
+    positions compared, all of them if None), under assert_scores_close's bound -- AND the condition that makes
+    that bound mean something for the low-level blocks: on at most 2 048 of the compared pairs, evenly spaced,
+    mlp_visibility >= MLP_VISIBLE.  At the default blend 0.99 the C low-level blocks carry weight 0.01 and a kernel that loses
+    a whole period of one stays inside the bound for a third to two thirds of the pairs it touches; such
+    inputs are refused here whatever the kernel returned.  Returns (max error, visibility)."""
+    from oracle import m2d_oracle as oracle
+    got = np.asarray(got)
+    users, items = case.users, case.items
+    if pick is not None:
+        pick = np.asarray(pick, np.int64)
+        got, users, items = got[pick], users[pick], items[pick]
+    key = None if pick is None else (pick.shape[0], hash(pick.tobytes()))
+    if key not in case.cache:
+        ref = oracle.inference_mlp(case.PM, case.RE, case.CE, case.cats, *case.head, users, items, coef=case.coef,
+                                   dish_high=case.dish_high)
+        n = len(users)
+        sub = np.arange(n) if n <= 2048 else np.linspace(0, n - 1, 2048).astype(np.int64)
+        vis = mlp_visibility(case.PM, case.RE, case.CE, case.cats, case.head, users[sub], items[sub], case.coef, case.dish_high)
+        case.cache[key] = (ref, vis)
+    ref, vis = case.cache[key]
+    err = assert_scores_close(got, ref, what=what)
+    assert vis >= MLP_VISIBLE, "%s: visibility %.2f < %.1f -- at these inputs (blend %g) a lost k-period stays inside the bound" % (
+        what, vis, MLP_VISIBLE, case.coef)
+    return err, vis
+
+
 # ---- training step (tests/test_gpu_train.py, tests/test_train_oracle.py) ------------------------------------------------
 # |got - ref| <= rho |ref - ini| + phi max(1, |ref|).  (rho, phi): 4 x what the float32-mode oracle needs against the float64
 # one over every case of the training tests -- the measured maxima and the procedure are in test_gpu_train.py's docstring.

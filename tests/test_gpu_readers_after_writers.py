@@ -3,9 +3,9 @@
 The engine keeps derived state behind hand-set flags and generation counters -- the factored dish vectors (dish_vec_valid,
 dish_vec_gen -> the MLP head's pattern bytes), the pattern-sorted dish rows (grp_valid, grp_gen -> catalogue_rank's tile norms,
 grp_ew = E or 2 E), the <U_high, CE_c> table (user_high_valid), the "a table value is inf / NaN" word (finite_scan_pending,
-grp_nonfinite_known) and the lazily built images of the MLP head's weights.  The flags are reset by hand in m2d_write_memory, in
-the two forms of the training step, in m2d_tables_updated and in the setters.  A reset that goes missing serves yesterday's
-lists without any error, so each test here follows one pattern:
+grp_nonfinite_known), the lazily built images of the MLP head's weights and the scratch of its pattern-grouped launch.  The
+flags are reset by hand in m2d_write_memory, in the two forms of the training step, in m2d_tables_updated and in the setters.
+A reset that goes missing serves yesterday's lists without any error, so each test here follows one pattern:
 
     snapshot (every reader; this also warms every cache) -> one writer -> snapshot -> the same snapshot on a FRESH engine built
     from the written engine's own tables
@@ -21,7 +21,7 @@ import types
 import numpy as np
 import pytest
 
-from helpers import TOL, assert_scores_close
+from helpers import TOL, assert_mlp_scores, assert_scores_close, mlp_case
 
 pytestmark = pytest.mark.gpu
 
@@ -79,12 +79,15 @@ def _inputs():
 
 
 def _cfg(E, cats=None, head=None, ing=None, user_base=0, mlp_x3=1):
-    return types.SimpleNamespace(E=E, cats=_masks(3) if cats is None else cats, head=head, ing=ing, user_base=user_base, mlp_x3=mlp_x3)
+    """A configuration with a head runs at blend 0.5: at the default 0.99 the low-level blocks of z carry weight 0.01 and the
+    oracle check of the grouped MLP reader could not see a stale pattern byte (helpers.assert_mlp_scores refuses such inputs)."""
+    return types.SimpleNamespace(E=E, cats=_masks(3) if cats is None else cats, head=head, ing=ing, user_base=user_base, mlp_x3=mlp_x3,
+                                 coef=0.99 if head is None else 0.5)
 
 
 def _engine(tabs, cfg):
     from foodrec_amd import ScoringEngine
-    eng = ScoringEngine(*tabs, user_base=cfg.user_base)
+    eng = ScoringEngine(*tabs, coef=cfg.coef, user_base=cfg.user_base)
     eng.set_dish_categories(cfg.cats)
     if cfg.head is not None:
         eng.set_mlp_head(*cfg.head)
@@ -145,6 +148,8 @@ def _snapshot(eng, cfg):
                 want = "m2d_mlp_pc_bf16x3" if form == 0 and E in (64, 128) else "m2d_mlp_mfma_bf16x3"
             run("mlp_form%d" % form, lambda: eng.score_pairs_mlp(users, items), want)
         eng.set_option("mlp_form", 0)
+        if cfg.mlp_x3 and E in (64, 128):                    # NBIG >= 16 384 pairs: bucketed by mask pattern -- mlp_pat8, the mlp_pg scratch
+            run("mlp_big", lambda: eng.score_pairs_mlp(t(inp.big_users + cfg.user_base), t(inp.big_items)), "m2d_mlp_pc_bf16x3")
         return out
     eng.set_option("topk_bf16x3", 0)
     run("topk_f32", topk, "m2d_topk_grouped" if binary else dense)
@@ -223,14 +228,17 @@ def _assert_oracle(eng, snap, cfg):
         assert_scores_close(snap["ingredient_pairs"][0], ref, what="ingredient pairs")
         return
     _check(eng, PM, RE, CE, cfg.cats, np.arange(0, U, 37), K, user_base=cfg.user_base)
-    ref = oracle.inference_f64(PM, RE, CE, inp.users, inp.items, cfg.cats[inp.items])
+    ref = oracle.inference_f64(PM, RE, CE, inp.users, inp.items, cfg.cats[inp.items], cfg.coef)
     assert_scores_close(snap["pairs"][0], ref, what="pairs")
     if "bydish" in snap:
         assert_scores_close(snap["bydish"][0], ref, what="bydish")
     if cfg.head is not None:
-        ref = oracle.inference_mlp(PM, RE, CE, cfg.cats, *cfg.head, inp.users, inp.items)
+        ref = oracle.inference_mlp(PM, RE, CE, cfg.cats, *cfg.head, inp.users, inp.items, coef=cfg.coef)
         for form in (0, 1):
             assert_scores_close(snap["mlp_form%d" % form][0], ref, what="mlp form %d" % form)
+        if "mlp_big" in snap:                                # a sample, and the condition that a lost k-period would show in it
+            case = mlp_case(PM, RE, CE, cfg.cats, cfg.head, inp.big_users, inp.big_items, cfg.coef)
+            assert_mlp_scores(snap["mlp_big"][0], case, np.arange(0, NBIG, 64), what="mlp, grouped launch")
 
 
 def _after(eng, cfg, before, what, expect="changed", only=None):
