@@ -52,6 +52,16 @@ __global__ __launch_bounds__(256) void m2d_scan_nonfinite(const float *p, int64_
     if (s != s) *flag = 1;
 }
 
+// H[d] of the ingredient table: +-inf only.  A NaN row (a dish without ingredients, 0 / 0) is NaN in every form of every kernel;
+// an inf is not -- the split-bf16 retrieval rows hold hi = inf and lo = inf - inf = NaN where the product with U_high is +-inf
+__global__ __launch_bounds__(256) void m2d_scan_inf(const float *p, int64_t n, int32_t *flag)
+{
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    bool hit = false;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) hit = hit || __builtin_isinf(p[i]);
+    if (hit) *flag = 1;
+}
+
 // the Personal_Memory blocks of a batch's users (after a writer that adds into them with atomics)
 __global__ __launch_bounds__(256) void m2d_rows_nonfinite(const float *pm, const int32_t *users, int64_t B, int64_t U, int64_t user_base,
                                                           int32_t W, int32_t *flag)
@@ -146,8 +156,9 @@ void release(m2d_engine *h)
 
 }  // namespace
 
-// The scan queued by m2d_create / m2d_tables_updated: one streaming pass over the three tables on the caller's stream, in
-// front of the launch that needs its answer (1.28 GB of Personal_Memory: 0.2 ms, once per table change).
+// The scan queued by m2d_create / m2d_tables_updated / m2d_set_ingredients / m2d_clear_ingredients: one streaming pass over the
+// three tables, and over H[d] when the ingredient table is set, on the caller's stream, in front of the launch that needs its
+// answer (1.28 GB of Personal_Memory: 0.2 ms, once per table change).
 int m2d_ensure_finite_scan(m2d_engine *h, hipStream_t st)
 {
     if (!h->finite_scan_pending) return M2D_OK;
@@ -160,7 +171,14 @@ int m2d_ensure_finite_scan(m2d_engine *h, hipStream_t st)
         if (blocks < 1) blocks = 1;
         hipLaunchKernelGGL(m2d_scan_nonfinite, dim3((unsigned)blocks), dim3(256), 0, st, t[i], n[i], h->nonfinite_dev);
     }
+    if (h->dish_high) {                 // (set / cleared by m2d_set_ingredients / m2d_clear_ingredients, which queue this scan again)
+        const int64_t nh = h->I * (int64_t)h->E;
+        int64_t blocks = (nh + 1023) / 1024;
+        if (blocks > (int64_t)h->num_cu * 8) blocks = (int64_t)h->num_cu * 8;
+        hipLaunchKernelGGL(m2d_scan_inf, dim3((unsigned)blocks), dim3(256), 0, st, h->dish_high, nh, h->nonfinite_dev);
+    }
     M2D_HIP_TRY(h, hipGetLastError());
+    h->grp_nonfinite_known = false;     // the retrieval launcher's host copy of the word
     h->finite_scan_pending = false;
     return M2D_OK;
 }
@@ -549,6 +567,7 @@ int m2d_clear_ingredients(m2d_engine *h)
     h->own_ing = false; h->ing_rows = 0; h->ing_nnz = 0;
     h->dish_vec_valid = false;
     h->grp_valid = false;               // the pattern-grouped retrieval rows carry H[d] when it is set
+    h->finite_scan_pending = true;      // H[d] was part of the scan
     return M2D_OK;
 }
 
@@ -602,6 +621,7 @@ int m2d_set_ingredients(m2d_engine *h, const float *ing, int64_t R, const int32_
     }
     h->dish_vec_valid = false;
     h->grp_valid = false;
+    h->finite_scan_pending = true;      // H[d] is part of the scan
     return M2D_OK;
 }
 

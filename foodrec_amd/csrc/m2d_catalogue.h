@@ -145,6 +145,9 @@ M2D_INTERNAL int m2d_topk_launch_repair(m2d_engine *h, const RepairArgs &r, bool
 // sort of 8-float plan records by their word-5 pattern mask (m2d_plan_hist / _scan / _scatter; `hist`: PLAN_KEYS words)
 constexpr int PLAN_KEYS = 1 << 15;                         // a mask holds bits 1..15: key = mask >> 1
 M2D_INTERNAL int m2d_grouped_tables(m2d_engine *h, hipStream_t st);
+// m2d_catalogue_dense.hip: retrieval on tables that hold inf / NaN -- the reference formula as written, one block per user
+M2D_INTERNAL int m2d_topk_literal_launch(m2d_engine *h, const int32_t *users, int64_t nU, int32_t k, float *out_scores, int32_t *out_ids,
+                                         hipStream_t stream);
 M2D_INTERNAL int m2d_plan_sort_launch(m2d_engine *h, const float *plan, int64_t nU, int32_t *hist, int32_t *order, hipStream_t st,
                                       bool hist_zeroed = false);
 // m2d_catalogue_rank.hip, also for m2d_topk_users_excluding (`entry`): the refusals of a model the ranking arithmetic does not cover, the

@@ -383,6 +383,89 @@ __global__ __launch_bounds__(256) void m2d_topk_generic(TopkArgs p, int K)
     }
 }
 
+// Tables that hold inf / NaN (the engine's "a table value is not finite" word is set): the reference formula as written, one block
+// per user.  The factored dish vectors above sum m_c CE_c[e] over c BEFORE the product with U_high[e] -- U_high[u][e] = inf then
+// gives +-inf where Model_Recommender.py:71 gives inf * (0 * CE_c[e]) = NaN for every dish that lacks a category -- and the
+// register lists of m2d_topk_mfma start at -inf and insert on v > thr, so a dish that scores -inf never enters.  Here: the layout of
+// m2d_topk_generic (waves stride over the dishes, lane 0 of each keeps an ahead() list in LDS: descending, -inf before NaN, ties
+// and NaN in id order; k <= 64), the score of m2d_score_pairs_generic<BYDISH = true> with no row left out (m2d_pair_score_wave),
+// the ingredient vector H[d] included.  Not tuned: a diverged run is not a serving path.
+struct LiteralArgs {
+    const float *pm, *re, *ce, *cats, *hv;
+    const int32_t *users;
+    int64_t U, I, user_base;
+    int32_t C, E, k;
+    float a, b;
+    float *out_scores;     // [nU, k]
+    int32_t *out_ids;
+    int32_t *err;
+};
+
+__global__ __launch_bounds__(256) void m2d_topk_literal(LiteralArgs p)
+{
+    extern __shared__ __align__(16) float smem[];
+    __shared__ int s_cnt[4];
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
+    const int k = p.k, C = p.C, E = p.E;
+    float *ls = smem + (size_t)wave * 2 * k;
+    int32_t *li = reinterpret_cast<int32_t *>(ls + k);
+    const int64_t uidx = blockIdx.x;
+    const int32_t uid = p.users[uidx];
+    int64_t ul = (int64_t)uid - p.user_base;
+    if (ul < 0 || ul >= p.U) {
+        if (threadIdx.x == 0 && atomicCAS(&p.err[0], 0, M2D_ERR_BAD_USER_ID) == 0) {
+            p.err[1] = uid;
+            p.err[2] = (int32_t)(uidx & 0xffffffff);
+            p.err[3] = (int32_t)(uidx >> 32);
+        }
+        ul = 0;
+    }
+    const float *um = p.pm + (size_t)ul * (size_t)(C + 1) * E;
+    int cnt = 0;
+    for (int64_t d = wave; d < p.I; d += 4) {
+        const float s = m2d_pair_score_wave(um, p.re + (size_t)d * E, p.cats + (size_t)d * C, p.ce, p.hv ? p.hv + (size_t)d * E : nullptr,
+                                            C, E, p.a, p.b, false, lane);
+        if (lane == 0) {
+            const bool cand = cnt < k || ahead(s, ls[k - 1]);
+            if (cand) {
+                int pos = cnt < k ? cnt : k - 1;
+                while (pos > 0 && ahead(s, ls[pos - 1])) {
+                    ls[pos] = ls[pos - 1];
+                    li[pos] = li[pos - 1];
+                    --pos;
+                }
+                ls[pos] = s;
+                li[pos] = (int32_t)d;
+                if (cnt < k) ++cnt;
+            }
+        }
+    }
+    if (lane == 0) s_cnt[wave] = cnt;
+    __syncthreads();
+    if (threadIdx.x == 0) {                      // merge of the four lists: (score by ahead(), id)
+        int ptr[4] = {0, 0, 0, 0};
+        for (int o = 0; o < k; ++o) {
+            int best = -1;
+            for (int w = 0; w < 4; ++w) {
+                if (ptr[w] >= s_cnt[w]) continue;
+                if (best < 0) { best = w; continue; }
+                const float sv = smem[(size_t)w * 2 * k + ptr[w]], bv = smem[(size_t)best * 2 * k + ptr[best]];
+                const int32_t si = reinterpret_cast<int32_t *>(smem + (size_t)w * 2 * k + k)[ptr[w]];
+                const int32_t bi = reinterpret_cast<int32_t *>(smem + (size_t)best * 2 * k + k)[ptr[best]];
+                if (ahead(sv, bv) || (!ahead(bv, sv) && si < bi)) best = w;
+            }
+            if (best < 0) {                      // (k <= I: not reached)
+                p.out_scores[uidx * k + o] = __builtin_nanf("");
+                p.out_ids[uidx * k + o] = -1;
+            } else {
+                p.out_scores[uidx * k + o] = smem[(size_t)best * 2 * k + ptr[best]];
+                p.out_ids[uidx * k + o] = reinterpret_cast<int32_t *>(smem + (size_t)best * 2 * k + k)[ptr[best]];
+                ++ptr[best];
+            }
+        }
+    }
+}
+
 template <int NB, int WAVES, int KR>
 int launch_mfma(m2d_engine *h, TopkArgs &a, float *final_s, int32_t *final_i, hipStream_t st)
 {
@@ -453,7 +536,24 @@ int m2d_ensure_dish_vectors(m2d_engine *h, hipStream_t st)
     return M2D_OK;
 }
 
-// Dispatch of the kernels of this file: weighted masks, k > 16, category counts other than 4, embedding sizes without a
+int m2d_topk_literal_launch(m2d_engine *h, const int32_t *users, int64_t nU, int32_t k, float *out_scores, int32_t *out_ids, hipStream_t stream)
+{
+    if (k > 64 || h->C > 64) {
+        h->last_error = "m2d_topk_users on non-finite tables: needs k <= 64 and num_categories <= 64";
+        return M2D_ERR_UNSUPPORTED;
+    }
+    LiteralArgs a;
+    a.pm = h->pm; a.re = h->re; a.ce = h->ce; a.cats = h->dish_cats; a.hv = h->dish_high; a.users = users;
+    a.U = h->U; a.I = h->I; a.user_base = h->user_base; a.C = h->C; a.E = h->E; a.k = k; a.a = h->a; a.b = h->b;
+    a.out_scores = out_scores; a.out_ids = out_ids; a.err = h->err_dev;
+    h->topk_tie_list = nullptr; h->topk_refine_counter = nullptr; h->topk_tiles_counter = nullptr; h->topk_tiles_full = 0;
+    hipLaunchKernelGGL(m2d_topk_literal, dim3((unsigned)nU), dim3(256), (size_t)4 * 2 * k * sizeof(float), stream, a);
+    M2D_HIP_TRY(h, hipGetLastError());
+    h->last_kernel = "m2d_topk_literal";
+    return M2D_OK;
+}
+
+// Dispatch of the kernels of this file (finite tables): weighted masks, k > 16, category counts other than 4, embedding sizes without a
 // pattern-grouped kernel -- and 0/1 masks under option "topk_grouped" = 0.
 int m2d_topk_dense_launch(m2d_engine *h, const int32_t *users, int64_t nU, int32_t k, float *out_scores, int32_t *out_ids,
                           hipStream_t stream)

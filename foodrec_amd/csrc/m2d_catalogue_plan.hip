@@ -673,7 +673,7 @@ int ensure_grouped(m2d_engine *h, hipStream_t st)
     h->grp_tiles = host[0];
     h->grp_binary = host[2] == 0;
     // w_P = sum of the pattern's U_low rows leaves out the 0 * U_low[c] products of the other categories: with inf / NaN in
-    // a table those are NaN in the reference formula, and the dense kernel (which multiplies them) serves the call
+    // a table those are NaN in the reference formula, and the literal kernel (m2d_topk_literal, which multiplies them) serves the call
     h->grp_nonfinite = host[3] != 0;
     h->grp_nonfinite_known = true;
     h->grp_valid = true;
@@ -683,7 +683,8 @@ int ensure_grouped(m2d_engine *h, hipStream_t st)
 
 // m2d_write_memory adds into Personal_Memory: the sorted dish rows stay valid, but the device word "a table value is
 // inf / NaN" may have been set by its row check -- read it again before choosing between the pattern-grouped kernels
-// (which leave out the 0 * U_low[c] products) and the dense one
+// (which leave out the 0 * U_low[c] products) and the literal one.  A table scan (m2d_ensure_finite_scan) makes the host's copy
+// stale in the same way.
 int refresh_grouped_nonfinite(m2d_engine *h, hipStream_t st)
 {
     if (h->grp_nonfinite_known) return M2D_OK;
@@ -984,14 +985,18 @@ int m2d_launch_topk_users(m2d_engine *h, const int32_t *users, int64_t nU, int32
     const bool hv_ok = h->dish_high && h->opt_topk_bf16x3 != 0 && (h->E == 32 || h->E == 64);
     const int roww = grouped_row_width(h->E);
     const bool padded = !(h->E == 32 || h->E == 64 || h->E == 128);   // e.g. the reference's embed_size 200: rows padded to 256
-    if (h->C == 4 && (!h->dish_high || (hv_ok && !padded)) && k <= 16 && roww != 0 &&
-        h->opt_topk_grouped != 0 && h->opt_variant != 7 && h->opt_variant != 9) {
-        if ((rc = ensure_grouped(h, stream)) != M2D_OK) return rc;
-        if ((rc = refresh_grouped_nonfinite(h, stream)) != M2D_OK) return rc;
+    const bool grouped = h->C == 4 && (!h->dish_high || (hv_ok && !padded)) && k <= 16 && roww != 0 &&
+                         h->opt_topk_grouped != 0 && h->opt_variant != 7 && h->opt_variant != 9;
+    if (grouped && (rc = ensure_grouped(h, stream)) != M2D_OK) return rc;
+    if ((rc = refresh_grouped_nonfinite(h, stream)) != M2D_OK) return rc;
+    // a table value is inf / NaN: neither the pattern-grouped kernels (they leave the 0 * U_low[c] products out) nor the factored
+    // dense ones (sum_c m_c CE_c before the product with U_high; -inf never enters their lists) return the graph's lists
+    if (h->grp_nonfinite) return m2d_topk_literal_launch(h, users, nU, k, out_scores, out_ids, stream);
+    if (grouped) {
         const int KR = k <= 10 ? 10 : 16;                    // list slots per lane
-        if (hv_ok && h->grp_binary && h->grp_tiles > 0 && !h->grp_nonfinite)       // rows [H[d] | RE[d]]: width 2 E
+        if (hv_ok && h->grp_binary && h->grp_tiles > 0)       // rows [H[d] | RE[d]]: width 2 E
             return launch_grouped(h, 2 * h->E / 8, KR, true, true, false, users, nU, k, out_scores, out_ids, stream);
-        if (!h->dish_high && h->grp_binary && h->grp_tiles > 0 && !h->grp_nonfinite) {
+        if (!h->dish_high && h->grp_binary && h->grp_tiles > 0) {
             // "topk_bf16x3" option: 1 = split-bf16 MFMA (E = 64 / 128), 0 = exact-f32 MFMA; embedding sizes without a kernel of
             // their own (`padded`) run exact f32 on rows zero-padded to `roww` floats
             const bool x3 = h->opt_topk_bf16x3 != 0 && (h->E == 64 || h->E == 128);

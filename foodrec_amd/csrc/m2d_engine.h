@@ -32,8 +32,8 @@ struct m2d_engine {
     int32_t *err_dev = nullptr;
     int32_t *err_host = nullptr;  // pinned
 
-    // "some value of Personal_Memory / Recipe_Embedding / Category_Embedding is not finite" (device word, sticky until the
-    // next full scan).  Model_Recommender.py:82-90 multiplies the row of a category a dish does not have by 0, and
+    // "some value of Personal_Memory / Recipe_Embedding / Category_Embedding is not finite, or some H[d] of the ingredient table is
+    // +-inf" (device word, sticky until the next full scan).  Model_Recommender.py:82-90 multiplies the row of a category a dish does not have by 0, and
     // 0 * inf = NaN: every kernel that leaves such rows out (option skip_masked, the pattern-grouped forms) reads this
     // word and fetches / multiplies everything when it is set.  Set by m2d_scan_tables (queued by m2d_create and
     // m2d_tables_updated, run by the next scoring call on its stream) and by the engine's own writers (training step,
@@ -208,6 +208,33 @@ __device__ __forceinline__ float m2d_blend_unfused(const float a, const float x,
     const float p = a * x;
     const float q = b * y;
     return p + q;
+}
+
+// One wave, one (user, dish) pair, any C and E: Model_Recommender.py:67-96 as written -- every product of every category, the rows
+// of weight-0 categories included unless `skipm` (0 * inf = NaN, :82) -- lanes striding over e, one xor butterfly per sum.  Every
+// lane returns the score.  um: the user's (C + 1) E floats, it: RE[d], mrow: the pair's C weights, hv: H[d] of the ingredient
+// table or null.  Shared by m2d_score_pairs_generic (m2d_score.hip) and m2d_topk_literal (m2d_catalogue_dense.hip): the same
+// (user, dish, mask) scores the same bits in both.
+__device__ __forceinline__ float m2d_pair_score_wave(const float *um, const float *it, const float *mrow, const float *ce, const float *hv,
+                                                     const int C, const int E, const float a, const float b, const bool skipm, const int lane)
+{
+    float hs = 0.f, ls = 0.f, n = 0.f;
+    for (int c = 0; c < C; ++c) {
+        const float mc = mrow[c];
+        n += mc;                               // :77
+        if (skipm && mc == 0.f) continue;      // 0 * row = 0: the row is not fetched
+        for (int e = lane; e < E; e += 64) {
+            if (!hv) hs = fmaf(um[e], mc * ce[(size_t)c * E + e], hs);          // :67, :71, :75
+            ls = fmaf(it[e], mc * um[(size_t)(c + 1) * E + e], ls);             // :82, :86, :90
+        }
+    }
+    if (hv)
+        for (int e = lane; e < E; e += 64) hs = fmaf(um[e], hv[e], hs);
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) hs += __shfl_xor(hs, off, 64);
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) ls += __shfl_xor(ls, off, 64);
+    return m2d_blend_unfused(a, hv ? hs : hs / n, b, ls / n);                   // :79, :92, :95-96
 }
 
 // ---- device helpers shared by the LDS-DMA kernels (m2d_catalogue_*.hip, m2d_mlp.hip) ----

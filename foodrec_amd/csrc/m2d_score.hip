@@ -103,6 +103,11 @@ __global__ __launch_bounds__(256) void m2d_score_pairs_c4(ScoreArgs p)
     const int E4 = FULL ? LPP : (p.E >> 2);
     const bool col_ok = FULL || (j < E4);
     const int jc = col_ok ? j : 0;  // idle lanes re-read column 0 (in bounds), contribution zeroed
+    // Idle lanes hold U_high's column 0 and cef = 0: 0 * inf would be NaN, so their `hs` is dropped like their `ls`.  As an AND
+    // with a lane mask the compiler cannot see through: written as a select, it moved the whole high-level chain under the lane
+    // condition and the default instantiations took 10 to 60 more VGPRs (LPP 16, PF 2: 144 -> 204); this form takes 2.
+    int32_t keep = col_ok ? -1 : 0;
+    asm volatile("" : "+v"(keep));
     const int64_t nchunks = (p.B + 63) >> 6;
     // wave-uniform loop control lives in SGPRs: no shuffle below ever runs under a partial EXEC mask
     const int64_t wave0 = (int64_t)blockIdx.x * (blockDim.x >> 6) + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -198,10 +203,8 @@ __global__ __launch_bounds__(256) void m2d_score_pairs_c4(ScoreArgs p)
                     ls = dot4(ib[k], dish_memory, ls);                         // :86, :90
                 }
                 if constexpr (HV) hs = dot4(ub[k][0], hb[k], hs);
-                if (!FULL && !col_ok) {
-                    ls = 0.f;
-                    if (HV) hs = 0.f;
-                }
+                if (!FULL && !col_ok) ls = 0.f;
+                if constexpr (!FULL) hs = __builtin_bit_cast(float, __builtin_bit_cast(int32_t, hs) & keep);
                 if (s + PF < LPP) issue(s + PF, k);
                 if constexpr (HV || !use_uh) hs = group_sum<LPP>(hs);
                 ls = group_sum<LPP>(ls);
@@ -244,7 +247,7 @@ __global__ __launch_bounds__(256) void m2d_build_user_high(const float *pm, cons
         const v4f x = reinterpret_cast<const v4f *>(pm)[(size_t)(ok ? u : 0) * (C + 1) * E4 + jc];
         float h[C];
 #pragma unroll
-        for (int c = 0; c < C; ++c) h[c] = group_sum<LPP>(dot4(x, cef[c], 0.f));
+        for (int c = 0; c < C; ++c) h[c] = group_sum<LPP>(col_ok ? dot4(x, cef[c], 0.f) : 0.f);   // idle lanes: not 0 * U_high[u][0..3]
         if (ok && j == 0) reinterpret_cast<v4f *>(out)[u] = v4f{h[0], h[1], h[2], h[3]};
     }
 }
@@ -262,6 +265,8 @@ __global__ __launch_bounds__(256) void m2d_score_pairs_c4_small(ScoreArgs p)
     const int E4 = FULL ? LPP : (p.E >> 2);
     const bool col_ok = FULL || (j < E4);
     const int jc = col_ok ? j : 0;
+    int32_t keep = col_ok ? -1 : 0;   // idle lanes drop `hs` too: see m2d_score_pairs_c4
+    asm volatile("" : "+v"(keep));
     const int64_t wave0 = (int64_t)blockIdx.x * (blockDim.x >> 6) + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int64_t nwaves = (int64_t)gridDim.x * (blockDim.x >> 6);
     const v4f *pm4 = reinterpret_cast<const v4f *>(p.pm);
@@ -322,10 +327,8 @@ __global__ __launch_bounds__(256) void m2d_score_pairs_c4_small(ScoreArgs p)
             ls = dot4(ib, dish_memory, ls);                            // :86, :90
         }
         if constexpr (HV) hs = dot4(ub[0], hb, hs);
-        if (!FULL && !col_ok) {
-            ls = 0.f;
-            if (HV) hs = 0.f;
-        }
+        if (!FULL && !col_ok) ls = 0.f;
+        if constexpr (!FULL) hs = __builtin_bit_cast(float, __builtin_bit_cast(int32_t, hs) & keep);
         hs = group_sum<LPP>(hs);
         ls = group_sum<LPP>(ls);
         if (valid && j == 0) {
@@ -494,22 +497,8 @@ __global__ __launch_bounds__(256) void m2d_score_pairs_generic(ScoreArgs p)
         const float *um = p.pm + (size_t)ul * (size_t)(C + 1) * E;
         const float *it = p.re + (size_t)did * E;
         const float *mrow = p.cats + (BYDISH ? (size_t)did * C : (size_t)pi * C);
-        float hs = 0.f, ls = 0.f, n = 0.f;
-        for (int c = 0; c < C; ++c) {
-            const float mc = mrow[c];
-            n += mc;
-            if (skipm && mc == 0.f) continue;      // 0 * row = 0: the row is not fetched
-            for (int e = lane; e < E; e += 64) {
-                if (!p.hv) hs = fmaf(um[e], mc * p.ce[(size_t)c * E + e], hs);
-                ls = fmaf(it[e], mc * um[(size_t)(c + 1) * E + e], ls);
-            }
-        }
-        if (p.hv)
-            for (int e = lane; e < E; e += 64) hs = fmaf(um[e], p.hv[(size_t)did * E + e], hs);
-        hs = group_sum<64>(hs);
-        ls = group_sum<64>(ls);
+        float score = m2d_pair_score_wave(um, it, mrow, p.ce, p.hv ? p.hv + (size_t)did * E : nullptr, C, E, p.a, p.b, skipm, lane);
         if (lane == 0) {
-            float score = m2d_blend_unfused(p.a, p.hv ? hs : hs / n, p.b, ls / n);
             if (bad) score = __builtin_nanf("");
             p.out[pi] = score;
         }

@@ -743,6 +743,7 @@ int m2d_launch_train_step(m2d_engine *h, const int32_t *users, const int32_t *it
         t->parity ^= 1;
         h->dish_vec_valid = false;      // everything derived from the tables is stale now
         h->grp_valid = false;
+        h->grp_nonfinite_known = false; // (a step may set the "not finite" word: retrieval reads it again, whatever kernel it takes)
         h->user_high_valid = false;
         return M2D_OK;
     }
@@ -809,6 +810,7 @@ int m2d_launch_train_step(m2d_engine *h, const int32_t *users, const int32_t *it
     // everything derived from Recipe_Embedding / Category_Embedding is stale now
     h->dish_vec_valid = false;
     h->grp_valid = false;
+    h->grp_nonfinite_known = false;
     h->user_high_valid = false;
     return M2D_OK;
 }

@@ -105,9 +105,13 @@ int m2d_rank_candidates(m2d_engine *h, const int32_t *users, const int32_t *item
 
 /* Full-catalogue retrieval (build-defined generalisation of evaluate.py:39-63 to every dish; BASELINE
  * config 5): for each of nU users the k best dishes over all I, descending score, ties to the lower
- * dish id, NaN scores last.  out_scores f32[nU, k], out_ids i32[nU, k].  1 <= k <= 64.
+ * dish id, NaN scores last (after every -inf score).  out_scores f32[nU, k], out_ids i32[nU, k].  1 <= k <= 64.
  * Scores agree with m2d_score_pairs_bydish within the 1e-4 bar, not bit for bit (factored form; see the
  * "topk_bf16x3" option below).
+ * While a table value is inf / NaN (the engine's "not finite" word: Personal_Memory, Recipe_Embedding, Category_Embedding; +-inf
+ * in H[d] of the ingredient table) every call runs m2d_topk_literal instead, whatever the options: the formula as written, one
+ * block per user, untuned.  Its lists are the graph's -- +inf first, -inf after every finite score, NaN last, each in id order --
+ * and a listed score is m2d_score_pairs_bydish's under "variant" = 9 bit for bit.
  * Kernels: 0/1 masks, C = 4, k <= 16 and E a multiple of 4 up to 256 run the pattern-grouped MFMA kernels (E = 64 / 128
  * on split bf16 by default; other sizes, e.g. the reference's embed_size 200, exact f32 on dish rows zero-padded to
  * 32 / 64 / 128 / 256 floats); other masks or k run the dense MFMA kernel where (C + 1) E / 8 is 20, 40 or 80, and a

@@ -369,19 +369,24 @@ def evaluate_model(score_fn, testRatings, testNegatives, K, dish_to_category):
 
 
 def topk_catalogue(PM, RE, CE, dish_categories, users: Iterable[int], k: int,
-                   coef: float = DEFAULT_COEF, dtype=np.float64):
+                   coef: float = DEFAULT_COEF, dtype=np.float64, ingredients=None):
     """Full-catalogue retrieval (build-defined generalisation of evaluate.py:39-63 to every dish):
     score every dish with `inference`, rank with the reference's ``heapq.nlargest`` rule --
-    descending score, ties to the earlier (lower) dish id.  NaN scores (0/0, :79/:92) rank last."""
+    descending score, ties to the earlier (lower) dish id.  NaN scores (0/0, :79/:92) rank last: strictly after every
+    -inf score (include/m2d.h; a table that holds inf gives both), by id among themselves.  `ingredients`: (ING, offsets, ids,
+    weights) of the ingredient extension -- the scores are then `inference_ingredients`'."""
     PM = np.asarray(PM)
     I = np.asarray(RE).shape[0]
     m = _as_mask(dish_categories, np.asarray(CE).shape[0])
     all_items = np.arange(I)
     out_s, out_i = [], []
     for u in users:
-        s = inference(PM, RE, CE, np.full(I, int(u)), all_items, m, coef, dtype)
+        if ingredients is None:
+            s = inference(PM, RE, CE, np.full(I, int(u)), all_items, m, coef, dtype)
+        else:
+            s = inference_ingredients(PM, RE, *ingredients, np.full(I, int(u)), all_items, m, coef, dtype)
         key = np.where(np.isnan(s), -np.inf, s)
-        order = np.lexsort((all_items, -key))[:k]
+        order = np.lexsort((all_items, -key, np.isnan(s)))[:k]
         out_i.append(order.astype(np.int64))
         out_s.append(s[order])
     return np.asarray(out_s), np.asarray(out_i)

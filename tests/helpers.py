@@ -401,3 +401,148 @@ def run_train_oracle(spec, learner, dtype=np.float64, cls=None):
     st = (cls or T.TrainState)(*ini, learner, train_lr(spec["lr"], learner), coef=spec["coef"], dtype=dtype)
     outs = [st.step(*b) for b in batches]
     return ini, batches, st, outs
+
+
+# ---- non-finite tables (tests/test_nonfinite_cases_cpu.py, tests/test_gpu_nonfinite.py) ---------------------------------
+NONFINITE_TABLES = ("U_high", "U_low", "RE", "CE")
+NONFINITE_COLS = ("first", "last")
+NONFINITE_VALUES = (np.inf, -np.inf, np.nan)
+NONFINITE_U, NONFINITE_I = 400, 300
+# E of the C = 4 pair kernels: partial lane groups (E / 4 of 8 / 16 / 32 / 64 lanes) and full ones
+NONFINITE_E_PARTIAL, NONFINITE_E_FULL = (24, 48, 100, 200), (32, 64, 128, 256)
+_NONFINITE_BASE = {}
+
+
+def nonfinite_patterns(C, rng):
+    """The 20 masks of the hand-built pairs: all categories, four weighted masks with every weight non-zero, the empty mask,
+    then 14 more 0/1 patterns (C = 4: with the first one, all 15 non-empty ones).  The masks a +-inf score needs come first, so
+    that 64 pairs that cycle through the list hold them in pairs 0..7 and in pairs 56..63."""
+    full = 2 ** C - 1
+    rest = list(range(1, full)) if full - 1 <= 14 else [1 << c for c in range(C)] + [int(x) for x in rng.choice(
+        np.setdiff1d(np.arange(1, full), 1 << np.arange(C)), 14 - C, replace=False)]
+    rest = (rest * 14)[:14]                                        # C = 3 has 6 of them: repeated
+    bits = lambda p: (p >> np.arange(C) & 1).astype(np.float32)
+    out = [bits(full)] + [rng.uniform(0.5, 2.0, C).astype(np.float32) for _ in range(4)] + [bits(0)] + [bits(p) for p in rest]
+    return np.stack(out)
+
+
+def _nonfinite_base(C, E, B, seed, U, I):
+    key = (C, E, B, seed, U, I)
+    if key not in _NONFINITE_BASE:
+        PM, RE, CE, users, items, cats = random_case(U, I, C, E, B, seed)
+        rng = np.random.default_rng(seed + 7919)
+        u, d, c = int(rng.integers(0, U)), int(rng.integers(0, I)), int(rng.integers(0, C))
+        for e in (1, E - 1):                                       # one-signed partners of the element that is poisoned:
+            CE[:, e] = np.abs(CE[:, e])                            # U_high[u, e] = inf -> sum_c m_c CE_c[e] inf is inf, not inf - inf
+            PM[u, 1:, e] = np.abs(PM[u, 1:, e])                    # RE[d, e] = inf -> sum_c m_c U_low[u, c, e] inf likewise
+        pat = nonfinite_patterns(C, rng)
+        n = min(64, B)
+        users[:n] = u
+        items[:n] = d                                              # (U_high / U_low / CE: any dish would do)
+        cats[:n] = pat[np.arange(n) % len(pat)]
+        users[n:n + 8] = u                                         # other pairs of the poisoned user and of the poisoned dish
+        items[n + 8:n + 16] = d
+        for a in (PM, RE, CE, users, items, cats):
+            a.setflags(write=False)
+        _NONFINITE_BASE[key] = (PM, RE, CE, users, items, cats, u, d, c, {})
+        if len(_NONFINITE_BASE) > 4:                               # (tests walk the shapes one after another)
+            del _NONFINITE_BASE[next(iter(_NONFINITE_BASE))]
+    return _NONFINITE_BASE[key]
+
+
+def nonfinite_case(C, E, B, table, col, value, seed, U=NONFINITE_U, I=NONFINITE_I, ref_on=None, dish_cats=None):
+    """random_case(U, I, C, E, B, seed) with ONE table element set to `value` (+inf, -inf or NaN), and the float64 reference.
+
+    table: "U_high" (PM[u, 0, e]), "U_low" (PM[u, 1 + c, e]), "RE" (RE[d, e]), "CE" (CE[c, e]) for one user u, dish d and
+    category c drawn from the seed.  col: "first" -- e = 1, inside the float4 column that the idle lanes of a partial lane group
+    read again -- or "last", e = E - 1.
+
+    The first 64 pairs are (u, d) under nonfinite_patterns' 20 masks in turn: the pairs of the first and of the last lane group of
+    a wavefront hold the masks whose score is +-inf.  So that it is +-inf and not inf - inf, the partner factors are one-signed
+    at e = 1 and e = E - 1 in the clean tables already: |CE[:, e]| (U_high) and |PM[u, 1:, e]| (RE).  The rest of the batch is
+    random_case's, with 8 more pairs of u and 8 more of d.
+
+    Returns a namespace: PM, RE, CE (poisoned), PM0, RE0, CE0 (clean), users, items, cats, u, d, c, e, ref (float64,
+    oracle.inference_f64 on the poisoned tables), ref0 (on the clean ones), touched (pairs that read the poisoned element's
+    row).  ref_on: pair indices; ref / ref0 / touched then cover those pairs only (large batches).  dish_cats [I, C]: the masks
+    come from this table by dish instead (`score_pairs_bydish`; the hand-built pairs then all carry dish d's mask)."""
+    import types
+    from oracle import m2d_oracle as oracle
+    assert table in NONFINITE_TABLES and col in NONFINITE_COLS
+    PM0, RE0, CE0, users, items, cats, u, d, c, cache = _nonfinite_base(C, E, B, seed, U, I)
+    if dish_cats is not None:
+        cats = np.asarray(dish_cats, np.float32).reshape(I, C)[items]
+    e = 1 if col == "first" else E - 1
+    PM, RE, CE = PM0, RE0, CE0
+    if table in ("U_high", "U_low"):
+        PM = PM0.copy(); PM[u, 0 if table == "U_high" else 1 + c, e] = value
+    elif table == "RE":
+        RE = RE0.copy(); RE[d, e] = value
+    else:
+        CE = CE0.copy(); CE[c, e] = value
+    sel = np.arange(B) if ref_on is None else np.asarray(ref_on, np.int64)
+    rkey = (None if ref_on is None else sel.tobytes(), None if dish_cats is None else np.asarray(dish_cats, np.float32).tobytes())
+    if rkey not in cache:
+        ref0 = oracle.inference_f64(PM0, RE0, CE0, users[sel], items[sel], cats[sel])
+        ref0.setflags(write=False)
+        cache[rkey] = ref0
+    ref0 = cache[rkey]
+    touched = {"U_high": users[sel] == u, "U_low": users[sel] == u, "RE": items[sel] == d, "CE": np.ones(len(sel), bool)}[table]
+    ref = ref0.copy()
+    t = sel[touched]
+    ref[touched] = oracle.inference_f64(PM, RE, CE, users[t], items[t], cats[t])
+    return types.SimpleNamespace(PM=PM, RE=RE, CE=CE, PM0=PM0, RE0=RE0, CE0=CE0, users=users, items=items, cats=cats,
+                                 u=u, d=d, c=c, e=e, ref=ref, ref0=ref0, touched=touched, table=table, col=col, value=value)
+
+
+def nonfinite_case_conditions(case):
+    """What a case must hold to be worth a launch (the float64 reference alone): see test_nonfinite_cases_cpu.py."""
+    ref, ref0 = case.ref, case.ref0
+    by_poison = np.isnan(ref) & np.isfinite(ref0)
+    assert by_poison.sum() >= 8, (case.table, case.col, case.value, int(by_poison.sum()))
+    assert np.array_equal(ref[~case.touched], ref0[~case.touched], equal_nan=True)
+    if np.isinf(case.value):
+        assert np.isinf(ref).sum() >= 8, (case.table, case.col, case.value, int(np.isinf(ref).sum()))
+        n = min(64, len(ref))
+        assert np.isinf(ref[:8]).any() and np.isinf(ref[n - 8:n]).any()     # first and last lane group of the hand-built wave
+    if case.table != "CE":
+        assert np.isfinite(ref).mean() >= 0.5
+
+
+def c4_lane_standin(PM, RE, CE, users, items, cats, coef=0.99, zero_idle_hs=True):
+    """numpy stand-in of one lane group of the C = 4 pair kernels (m2d_score.hip): LPP = 8 / 16 / 32 / 64 lanes, lane j holds
+    float4 column j of every row, lanes with j >= E / 4 read column 0 again with cef = 0; their `ls` is zeroed, their `hs` is
+    zeroed or kept (`zero_idle_hs`); the group's sum is the xor butterfly.  float32 throughout (products and sums rounded
+    separately where the kernel uses fma: far inside the 1e-4 bound)."""
+    from oracle import m2d_oracle as oracle
+    C, E = CE.shape
+    assert C == 4 and E % 4 == 0 and E <= 256
+    E4 = E // 4
+    LPP = 8 if E4 <= 8 else 16 if E4 <= 16 else 32 if E4 <= 32 else 64
+    j = np.arange(LPP)
+    idle = j >= E4
+    col = (np.where(idle, 0, j)[:, None] * 4 + np.arange(4)[None, :])                  # [LPP, 4] element index
+    f = np.float32
+    with np.errstate(invalid="ignore", over="ignore", divide="ignore"):
+        ub = PM[users][:, :, col]                                                      # [B, C + 1, LPP, 4]
+        ib = RE[items][:, col]                                                         # [B, LPP, 4]
+        cef = np.where(idle[None, :, None], f(0), CE[:, col])                          # [C, LPP, 4]
+        m = cats.astype(f)
+        hs = np.zeros((len(users), LPP), f); ls = np.zeros_like(hs)
+        for c in range(C):
+            dc = m[:, c, None, None] * cef[None, c]
+            dm = m[:, c, None, None] * ub[:, c + 1]
+            for q in range(4):
+                hs = (hs + ub[:, 0, :, q] * dc[:, :, q]).astype(f)
+                ls = (ls + ib[:, :, q] * dm[:, :, q]).astype(f)
+        ls[:, idle] = 0
+        if zero_idle_hs:
+            hs[:, idle] = 0
+        off = LPP // 2
+        while off >= 1:
+            hs = (hs + hs[:, j ^ off]).astype(f)
+            ls = (ls + ls[:, j ^ off]).astype(f)
+            off //= 2
+        n = ((m[:, 0] + m[:, 1]) + (m[:, 2] + m[:, 3])).astype(f)
+        a, b = oracle.blend_coefficients(coef)
+        return (a * (hs[:, 0] / n) + b * (ls[:, 0] / n)).astype(f)

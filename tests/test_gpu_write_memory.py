@@ -363,8 +363,8 @@ def test_write_memory_non_finite_dish_row_at_a_zero_weight_category(personal, ge
         rest = args[:4] + tuple(np.delete(a, 7, axis=0) for a in args[4:])
         _close(gm[4, [2, 4]], _scatter(rest, False, True)[1][4, [2, 4]])
     elif personal:
-        # Personal_Memory now holds inf / NaN: retrieval takes the dense kernel
+        # Personal_Memory now holds inf / NaN: retrieval takes the literal kernel
         dish_cats = (np.random.default_rng(3).integers(1, 16, I)[:, None] >> np.arange(C)[None, :] & 1).astype(np.float32)
         eng.set_dish_categories(dish_cats)
         eng.topk_users(torch.arange(U, dtype=torch.int32, device="cuda"), 5); eng.check()
-        assert eng.last_kernel() == "m2d_topk_mfma"
+        assert eng.last_kernel() == "m2d_topk_literal"
