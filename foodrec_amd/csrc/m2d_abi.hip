@@ -9,8 +9,6 @@
 
 namespace {
 
-typedef float v4f __attribute__((ext_vector_type(4)));
-
 // plain streaming read: 4 x 16 B in flight per lane, non-temporal, the four loads a whole grid stride apart, TWO workgroups per CU.
 // Round 6 sweep on MI355X over the 1.28 GB Personal_Memory (profiles/r06_stream_probe_sweep.txt):
 // this form 6 970-7 000 GB/s at 2-3 workgroups per CU against 5 560-5 840 at 4-16 (round 1-5's launch: 8 per CU), 6 250 at 32;
@@ -130,11 +128,7 @@ void release(m2d_engine *h)
         for (const float *q : {h->mlp_w1, h->mlp_b1, h->mlp_w2, h->mlp_b2, h->mlp_w3})
             if (q) (void)hipFree((void *)q);
     }
-    if (h->mlp_w1x3) (void)hipFree(h->mlp_w1x3);
-    if (h->mlp_w1pad) (void)hipFree(h->mlp_w1pad);
-    if (h->mlp_w1pc) (void)hipFree(h->mlp_w1pc);
-    if (h->mlp_pg) (void)hipFree(h->mlp_pg);
-    if (h->mlp_pat8) (void)hipFree(h->mlp_pat8);
+    m2d_mlp_free_derived(h, true);
     if (h->user_high) (void)hipFree(h->user_high);
     if (h->dish_high) (void)hipFree(h->dish_high);
     if (h->own_ing) {
@@ -664,12 +658,7 @@ int m2d_clear_mlp_head(m2d_engine *h)
         for (const float *q : {h->mlp_w1, h->mlp_b1, h->mlp_w2, h->mlp_b2, h->mlp_w3})
             if (q) (void)hipFree((void *)q);
     }
-    if (h->mlp_w1x3) (void)hipFree(h->mlp_w1x3);
-    h->mlp_w1x3 = nullptr;
-    if (h->mlp_w1pad) (void)hipFree(h->mlp_w1pad);
-    h->mlp_w1pad = nullptr;
-    if (h->mlp_w1pc) (void)hipFree(h->mlp_w1pc);
-    h->mlp_w1pc = nullptr;
+    m2d_mlp_free_derived(h, false);
     h->mlp_w1 = h->mlp_b1 = h->mlp_w2 = h->mlp_b2 = h->mlp_w3 = nullptr;
     h->own_mlp = false;
     h->mlp_h1 = h->mlp_h2 = 0;

@@ -44,9 +44,6 @@ __attribute__((unused)) static unsigned long long *g_m2d_diag_buffer = nullptr; 
 
 #define M2D_INTERNAL __attribute__((visibility("hidden")))
 
-typedef float v4f __attribute__((ext_vector_type(4)));
-typedef float v16f __attribute__((ext_vector_type(16)));
-
 // ---- argument blocks that cross translation units (global namespace: one type for every unit) ------------------------------
 struct GroupedArgs {
     const float *pm;         // [U, (C+1) E]
@@ -155,16 +152,6 @@ M2D_INTERNAL int m2d_plan_sort_launch(m2d_engine *h, const float *plan, int64_t 
 M2D_INTERNAL int m2d_rank_prepare(m2d_engine *h, const char *entry, hipStream_t st);
 
 namespace {
-
-// the engine's id-error latch (m2d_engine::err_dev): the first error of a call wins -- its code, the bad value, where it stood
-__device__ __forceinline__ void latch_error(int32_t *err, const int32_t code, const int32_t value, const int64_t pos)
-{
-    if (atomicCAS(&err[0], 0, code) == 0) {
-        err[1] = value;
-        err[2] = (int32_t)(pos & 0xffffffff);
-        err[3] = (int32_t)(pos >> 32);
-    }
-}
 
 __device__ __forceinline__ bool ahead(float v, float w)
 {
@@ -636,7 +623,7 @@ __device__ __forceinline__ void grouped_publish(float *ls, int32_t *li, const fl
 __device__ __forceinline__ void csr_check_offset(const int64_t *off, const int64_t q, int32_t *err)
 {
     const int64_t o = off[q];
-    if ((q == 0 && o != 0) || (q > 0 && o < off[q - 1])) latch_error(err, M2D_ERR_INVALID_ARG, (int32_t)o, q);
+    if ((q == 0 && o != 0) || (q > 0 && o < off[q - 1])) m2d_latch_error(err, M2D_ERR_INVALID_ARG, (int32_t)o, q);
 }
 
 // the segment position i lies in: the last q with off[q] <= i
@@ -659,13 +646,13 @@ __device__ __forceinline__ int csr_check_id(const int64_t *off, const int32_t *i
     x = ids[i];
     int r = 1;
     if (x < 0 || (int64_t)x >= I) {
-        if (report) latch_error(err, M2D_ERR_BAD_ITEM_ID, x, i);
+        if (report) m2d_latch_error(err, M2D_ERR_BAD_ITEM_ID, x, i);
         r = 0;
     } else {
         q = csr_owner(off, n, i);
         if (i > off[q]) {
             const int32_t prev = ids[i - 1];
-            if (prev > x && report) latch_error(err, M2D_ERR_INVALID_ARG, x, i);
+            if (prev > x && report) m2d_latch_error(err, M2D_ERR_INVALID_ARG, x, i);
             r = prev > x ? 0 : (prev == x ? 2 : 1);
         }
     }

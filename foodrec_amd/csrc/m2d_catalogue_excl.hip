@@ -152,7 +152,7 @@ __global__ __launch_bounds__(256) void m2d_topk_excl_filter(ExclArgs p)
     const int32_t uid = p.users[u];
     int64_t ul = (int64_t)uid - p.user_base;
     if (ul < 0 || ul >= p.U) {
-        if (j == 0) latch_error(p.err, M2D_ERR_BAD_USER_ID, uid, u);
+        if (j == 0) m2d_latch_error(p.err, M2D_ERR_BAD_USER_ID, uid, u);
         return;                                             // (the rows of a call with a latched error are unspecified)
     }
     int64_t x0, x1;
@@ -195,7 +195,7 @@ __global__ __launch_bounds__(256) void m2d_topk_excl_plan(ExclArgs p)
         const int32_t uid = p.users[u];
         ul = (int64_t)uid - p.user_base;
         if (ul < 0 || ul >= p.U) {
-            if (j == 0) latch_error(p.err, M2D_ERR_BAD_USER_ID, uid, u);
+            if (j == 0) m2d_latch_error(p.err, M2D_ERR_BAD_USER_ID, uid, u);
             u = -1;
         }
     }

@@ -568,7 +568,7 @@ __global__ __launch_bounds__(256) void m2d_topk_high_level_only(const float *pm,
         const int32_t uid = users[u];
         ul = (int64_t)uid - user_base;
         if (ul < 0 || ul >= U) {
-            if (j == 0) latch_error(err, M2D_ERR_BAD_USER_ID, uid, u);
+            if (j == 0) m2d_latch_error(err, M2D_ERR_BAD_USER_ID, uid, u);
             ul = 0;
         }
     }

@@ -51,13 +51,13 @@ __global__ __launch_bounds__(256) void m2d_rank_plan(RankArgs p)
     const int32_t uid = p.users[q];
     int64_t ul = (int64_t)uid - p.user_base;
     if (ul < 0 || ul >= p.U) {
-        if (j == 0) latch_error(p.err, M2D_ERR_BAD_USER_ID, uid, q);
+        if (j == 0) m2d_latch_error(p.err, M2D_ERR_BAD_USER_ID, uid, q);
         ul = 0;
         bad = true;
     }
     int32_t it = p.items[q];
     if (it < 0 || (int64_t)it >= p.I) {
-        if (j == 0) latch_error(p.err, M2D_ERR_BAD_ITEM_ID, it, q);
+        if (j == 0) m2d_latch_error(p.err, M2D_ERR_BAD_ITEM_ID, it, q);
         it = 0;
         bad = true;
     }

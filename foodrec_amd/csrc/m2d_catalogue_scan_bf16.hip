@@ -14,8 +14,6 @@ namespace {
 // error <= ~1.2e-5, so the score error is ~1e-5 of sqrt(sum (a_k b_k)^2) -- inside the 1e-4 parity bar, and
 // checked against the float64 restatement by the same tests as the exact kernel.  3 MFMAs of 16 k-values
 // in 96 cycles replace 8 f32 MFMAs in 512.
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-
 template <int E, int WAVES, int KR>
 __global__ __launch_bounds__(WAVES * 64) void m2d_topk_grouped_bf16(GroupedArgs p)
 {
@@ -40,7 +38,7 @@ __global__ __launch_bounds__(WAVES * 64) void m2d_topk_grouped_bf16(GroupedArgs 
         const int32_t uid = p.users[uidx];
         ul = (int64_t)uid - p.user_base;
         if (ul < 0 || ul >= p.U) {
-            latch_error(p.err, M2D_ERR_BAD_USER_ID, uid, uidx);
+            m2d_latch_error(p.err, M2D_ERR_BAD_USER_ID, uid, uidx);
             ul = 0;
         }
     }
@@ -345,7 +343,7 @@ __global__ __launch_bounds__(WAVES * 64, 2) void m2d_topk_grouped_bf16_pipe2(Gro
     if (uvalid) {
         ul = (int64_t)uid - p.user_base;
         if (ul < 0 || ul >= p.U) {
-            latch_error(p.err, M2D_ERR_BAD_USER_ID, uid, uidx);
+            m2d_latch_error(p.err, M2D_ERR_BAD_USER_ID, uid, uidx);
             ul = 0;
         }
     }

@@ -46,7 +46,7 @@ __global__ __launch_bounds__(WAVES * 64) void m2d_topk_grouped(GroupedArgs p)
         const int64_t ul64 = (int64_t)uid - p.user_base;
         ul = (int)ul64;
         if (ul64 < 0 || ul64 >= p.U) {
-            latch_error(p.err, M2D_ERR_BAD_USER_ID, uid, uidx);
+            m2d_latch_error(p.err, M2D_ERR_BAD_USER_ID, uid, uidx);
             ul = 0;
         }
     }

@@ -13,6 +13,10 @@
 
 struct m2d_train_state;   // csrc/m2d_train.hip
 
+typedef float v4f __attribute__((ext_vector_type(4)));
+typedef float v16f __attribute__((ext_vector_type(16)));
+typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+
 struct m2d_engine {
     // tables in HBM, row-major, float32 (Model_Recommender.py:45-53)
     const float *pm = nullptr;  // [U, C+1, E]
@@ -28,7 +32,7 @@ struct m2d_engine {
     int device = 0;
     int num_cu = 256;
 
-    // id-error latch: {code, bad value, index lo, index hi}; cleared by m2d_check
+    // id-error latch: {code, bad value, index lo, index hi}; cleared by m2d_check (kernels write it with m2d_latch_error below)
     int32_t *err_dev = nullptr;
     int32_t *err_host = nullptr;  // pinned
 
@@ -61,7 +65,6 @@ struct m2d_engine {
     int32_t *mlp_pg = nullptr;          // per-launch pair grouping of that kernel: histogram | tile count | tile blocks | slot -> pair
     uint8_t *mlp_pat8 = nullptr;        // [I] a dish's pattern of non-zero mask weights (all blocks for n = 0 / NaN): what the grouping reads per pair
     uint64_t mlp_pat8_gen = 0;          // the dish-vector build it belongs to (dish_vec_gen)
-    int64_t mlp_pat8_rows = 0;
     size_t mlp_pg_cap = 0;              // ints
 
     // derived table for pair scoring: <U_high[u], CE_c> per user and category (built lazily by large m2d_score_pairs calls;
@@ -151,6 +154,16 @@ struct m2d_engine {
     std::string last_error;
     const char *last_kernel = "";
 };
+
+// the id-error latch (m2d_engine::err_dev): the first error of a call wins -- its code, the bad value, where it stood
+__device__ __forceinline__ void m2d_latch_error(int32_t *err, int code, int32_t value, int64_t index)
+{
+    if (atomicCAS(&err[0], 0, code) == 0) {
+        err[1] = value;
+        err[2] = (int32_t)(index & 0xffffffff);
+        err[3] = (int32_t)(index >> 32);
+    }
+}
 
 #define M2D_HIP_TRY(h, expr)                                                                   \
     do {                                                                                       \
@@ -288,6 +301,9 @@ int m2d_train_get_slot(m2d_engine *h, int32_t table, int32_t slot, float **dev, 
 int m2d_train_step_count(m2d_engine *h, int64_t *steps, int32_t set);
 int m2d_launch_score_pairs_mlp(m2d_engine *h, const int32_t *users, const int32_t *items, int64_t B, float *out,
                                hipStream_t stream);
+// m2d_mlp.hip: frees what is derived from the head's weights (mlp_w1x3, mlp_w1pad, mlp_w1pc: a new head rebuilds them), and with
+// `grouping` the pair grouping's buffers as well (mlp_pg, mlp_pat8: they outlive a head)
+void m2d_mlp_free_derived(m2d_engine *h, bool grouping);
 int m2d_launch_rank_candidates(m2d_engine *h, const int32_t *users, const int32_t *items,
                                const int32_t *lens, int64_t nseg, int32_t L, int32_t k, float *out_scores,
                                int32_t *out_items, int32_t *out_flags, hipStream_t stream);

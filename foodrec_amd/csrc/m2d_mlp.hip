@@ -45,9 +45,6 @@ static unsigned long long *g_m2d_mlp_diag_buffer = nullptr;
 
 namespace {
 
-typedef float v4f __attribute__((ext_vector_type(4)));
-typedef float v16f __attribute__((ext_vector_type(16)));
-
 struct MlpArgs {
     const float *pm;   // [U, K]
     const float *dt;   // [rows, K]
@@ -73,19 +70,8 @@ struct MlpArgs {
     int32_t pshift;              // log2(periods of 32 k-values per block)
 };
 
-__device__ __forceinline__ void latch(int32_t *err, int code, int64_t value, int64_t index)
-{
-    if (atomicCAS(&err[0], 0, code) == 0) {
-        err[1] = (int32_t)value;
-        err[2] = (int32_t)(index & 0xffffffff);
-        err[3] = (int32_t)(index >> 32);
-    }
-}
-
 constexpr int MH1 = 256, MH2 = 64, MWAVES = 8;
 constexpr int RING_FLOATS = 64 * MH1;   // one stage: 64 k-rows of W1 (= all of W2: 256 x 64)
-
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 
 // hidden unit held by accumulator tile nt, register r, lane half h (see the two layer-1 forms below)
 template <bool X3>
@@ -192,8 +178,8 @@ __global__ __launch_bounds__(MWAVES * 64) void m2d_mlp_mfma(MlpArgs p)
         int32_t did = valid ? p.items[pi] : 0;
         int64_t ul = (int64_t)uid - p.user_base;
         bad = false;
-        if (ul < 0 || ul >= p.U) { latch(p.err, M2D_ERR_BAD_USER_ID, uid, pi); ul = 0; bad = true; }
-        if (did < 0 || (int64_t)did >= p.I) { latch(p.err, M2D_ERR_BAD_ITEM_ID, did, pi); did = 0; bad = true; }
+        if (ul < 0 || ul >= p.U) { m2d_latch_error(p.err, M2D_ERR_BAD_USER_ID, uid, pi); ul = 0; bad = true; }
+        if (did < 0 || (int64_t)did >= p.I) { m2d_latch_error(p.err, M2D_ERR_BAD_ITEM_ID, did, pi); did = 0; bad = true; }
         if (M2D_MLP_DIAG & 8) { ul = 0; did = 0; }          // diag bit 3: every pair reads row 0 (loads issue, no HBM traffic)
         // f32 form: the lane owns k = 64 kc + 32 h + t; bf16 form: k = 64 kc + 16 ks + 8 h + j (fragment order)
         pu = reinterpret_cast<const v4f *>(p.pm) + (size_t)ul * K4 + (X3 ? 2 : 8) * h;
@@ -490,13 +476,12 @@ __global__ __launch_bounds__(256) void m2d_mlp_image_pc_w2(const float *w2, __bf
 // that are not a power-of-two number of periods): the pairs as they come, every block.
 constexpr int PG_MAXPAT = 64;             // C <= 6: up to 7 blocks fit the nibbles of a word beside their count
 
-// `group` points at the engine's "a table value is not finite" word: while it is set nothing is left out (0 * inf = NaN in
-// the literal z), every pair goes to the all-blocks bucket.  So does a dish whose weights sum to 0 or NaN: its dish-vector
+// A dish's pattern of non-zero mask weights.  A dish whose weights sum to 0 or NaN takes every block: its dish-vector
 // blocks are (1 - a) m_c RE[d] / n = NaN even where m_c = 0 (with an ingredient table block 0 is finite, so the score
 // is not NaN for some other reason), and the ungrouped kernels return NaN for it.
-__device__ __forceinline__ int pg_pattern(const float *cats, int C, int64_t I, int32_t did, const int32_t *group)
+__device__ __forceinline__ int pg_pattern(const float *cats, int C, int64_t I, int32_t did)
 {
-    if (*group != 0 || did < 0 || (int64_t)did >= I) return (1 << C) - 1;      // bad ids: any bucket (the gatherer reports them)
+    if (did < 0 || (int64_t)did >= I) return (1 << C) - 1;      // no row of the mask table (an index past the 32-bit ids)
     int pat = 0;
     float n = 0.f;
     for (int c = 0; c < C; ++c) {
@@ -508,15 +493,14 @@ __device__ __forceinline__ int pg_pattern(const float *cats, int C, int64_t I, i
 }
 
 // the per-dish pattern byte, once per mask table: what m2d_mlp_pg_hist / _scatter read per pair instead of the dish's C mask weights
-__global__ __launch_bounds__(256) void m2d_mlp_pg_pat8(const float *cats, int C, int64_t I, const int32_t *nogroup, uint8_t *pat8)
+__global__ __launch_bounds__(256) void m2d_mlp_pg_pat8(const float *cats, int C, int64_t I, const int32_t * /* not read */, uint8_t *pat8)
 {
-    const int32_t zero = 0;
     const int64_t d = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (d < I) pat8[d] = (uint8_t)pg_pattern(cats, C, I, (int32_t)d, &zero);
-    (void)nogroup;
+    if (d < I) pat8[d] = (uint8_t)pg_pattern(cats, C, I, (int32_t)d);
 }
 
-// a pair's bucket: the dish's pattern byte; every block while a table value is not finite (`group`, see pg_pattern) or for a bad id
+// a pair's bucket: the dish's pattern byte; every block for a bad id (any bucket would do: the gatherer reports them) and while
+// `nogroup`, the engine's "a table value is not finite" word, is set: nothing is left out then (0 * inf = NaN in the literal z)
 __device__ __forceinline__ int pg_bucket(const uint8_t *pat8, int C, int64_t I, int32_t did, int nogroup)
 {
     return (nogroup || did < 0 || (int64_t)did >= I) ? (1 << C) - 1 : (int)pat8[did];
@@ -620,24 +604,9 @@ __device__ __forceinline__ void pc_barrier()
 }
 #endif
 
-// Cross-lane sums without the LDS crossbar.  __shfl_xor compiles to ds_bpermute_b32 + s_waitcnt lgkmcnt(0): an LDS round trip
-// per step, queued behind the consumers' ds_read_b128 streams.  The gatherers' 24 of them (8 rows x 3 steps, serial) were the
-// 5 000-cycle barrier interval of every tile in round 6's arrival trace (profiles/r06_mlp_slack.txt, bars 7 / 17 / 27 ...) --
-// tables in L2 or not.  DPP / permlane swaps stay in the VALU; the sums associate as before (same bits).
-template <int CTRL>
-__device__ __forceinline__ float pc_dpp(float x)
-{
-    return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x), CTRL, 0xf, 0xf, true));
-}
-// sum over the 8 lanes 8 r .. 8 r + 7 of a row, in every one of them: lane ^ 1, lane ^ 2 (quad_perm), then lane 7 - i of the
-// half row (row_half_mirror: the other quad's sum, which is the same value in each of its lanes)
-__device__ __forceinline__ float pc_sum8(float b)
-{
-    b += pc_dpp<0xB1>(b);                                   // quad_perm [1, 0, 3, 2]
-    b += pc_dpp<0x4E>(b);                                   // quad_perm [2, 3, 0, 1]
-    b += pc_dpp<0x141>(b);                                  // row_half_mirror
-    return b;
-}
+// Cross-lane sums without the LDS crossbar, for the consumers' layer 3 and reference-score sums over a pair's four row groups
+// (lanes c, 16 + c, 32 + c, 48 + c).  __shfl_xor compiles to ds_bpermute_b32 + s_waitcnt lgkmcnt(0): an LDS round trip per step,
+// queued behind the consumers' own ds_read_b128 streams.  Permlane swaps stay in the VALU; the sums associate as before (same bits).
 // x[lane] + x[lane ^ 16], x[lane] + x[lane ^ 32]: v_permlane16_swap / v_permlane32_swap of a value with itself leave the row's
 // (half's) own value in one result and its partner's in the other
 __device__ __forceinline__ float pc_add_xor16(float x)
@@ -991,7 +960,7 @@ __global__ __launch_bounds__(512) void m2d_mlp_pc(MlpArgs p)
                 nd[i] = (uint32_t)p.items[pi];
             }
         };
-        auto convert_ids = [&](int64_t) __attribute__((always_inline)) {
+        auto convert_ids = [&]() __attribute__((always_inline)) {
             nbadmask = 0;
 #pragma unroll
             for (int i = 0; i < 8; ++i) {
@@ -1000,8 +969,8 @@ __global__ __launch_bounds__(512) void m2d_mlp_pc(MlpArgs p)
                 const int32_t uid = (int32_t)nu[i], did = (int32_t)nd[i];
                 int64_t ul = (int64_t)uid - p.user_base;
                 int32_t dl = did;
-                if (valid && (ul < 0 || ul >= p.U)) { if (s == 0) latch(p.err, M2D_ERR_BAD_USER_ID, uid, pi); nbadmask |= 1u << i; }
-                if (valid && (did < 0 || (int64_t)did >= p.I)) { if (s == 0) latch(p.err, M2D_ERR_BAD_ITEM_ID, did, pi); nbadmask |= 1u << i; }
+                if (valid && (ul < 0 || ul >= p.U)) { if (s == 0) m2d_latch_error(p.err, M2D_ERR_BAD_USER_ID, uid, pi); nbadmask |= 1u << i; }
+                if (valid && (did < 0 || (int64_t)did >= p.I)) { if (s == 0) m2d_latch_error(p.err, M2D_ERR_BAD_ITEM_ID, did, pi); nbadmask |= 1u << i; }
                 if (!valid || ul < 0 || ul >= p.U) ul = 0;
                 if (!valid || did < 0 || (int64_t)did >= p.I) dl = 0;
                 nu[i] = ((uint32_t)ul * (uint32_t)(K / 4) + (uint32_t)s) * (OFF32 ? 16u : 1u);
@@ -1036,13 +1005,13 @@ __global__ __launch_bounds__(512) void m2d_mlp_pc(MlpArgs p)
         auto next_of = [&](int64_t t) { return t + gridDim.x < ntiles ? t + gridDim.x : t; };   // none left: any valid rows
         load_ids(tile0);
         pc_wait_vmem<0>();
-        convert_ids(tile0);
+        convert_ids();
 #pragma unroll
         for (int i = 0; i < 8; ++i) { cu[i] = nu[i]; cd[i] = nd[i]; }
         badmask = nbadmask;
         load_ids(next_of(tile0));
         pc_wait_vmem<0>();
-        convert_ids(next_of(tile0));
+        convert_ids();
         gather(0, cu, cd, 0);
         gather(1, cu, cd, 1);
 #if M2D_MLP_DIAG
@@ -1115,7 +1084,7 @@ __global__ __launch_bounds__(512) void m2d_mlp_pc(MlpArgs p)
             GSTAMP(0);
             pc_wait_vmem<0>();
             GSTAMP(1);
-            convert_ids(t2);
+            convert_ids();
             GSTAMP(2);
             GSTAMP(4);
             pc_barrier();
@@ -1132,7 +1101,6 @@ __global__ __launch_bounds__(512) void m2d_mlp_pc(MlpArgs p)
     }
 }
 
-// (diag epilogue is emitted by the macro below, inside the kernel)
 // Any K / H1 / H2: one wave per pair, activations in LDS.  Slow; for shapes the MFMA kernel does not cover.
 __global__ __launch_bounds__(256) void m2d_mlp_generic(MlpArgs p)
 {
@@ -1145,8 +1113,8 @@ __global__ __launch_bounds__(256) void m2d_mlp_generic(MlpArgs p)
         int32_t uid = p.users[pi], did = p.items[pi];
         int64_t ul = (int64_t)uid - p.user_base;
         bool bad = false;
-        if (ul < 0 || ul >= p.U) { if (lane == 0) latch(p.err, M2D_ERR_BAD_USER_ID, uid, pi); ul = 0; bad = true; }
-        if (did < 0 || (int64_t)did >= p.I) { if (lane == 0) latch(p.err, M2D_ERR_BAD_ITEM_ID, did, pi); did = 0; bad = true; }
+        if (ul < 0 || ul >= p.U) { if (lane == 0) m2d_latch_error(p.err, M2D_ERR_BAD_USER_ID, uid, pi); ul = 0; bad = true; }
+        if (did < 0 || (int64_t)did >= p.I) { if (lane == 0) m2d_latch_error(p.err, M2D_ERR_BAD_ITEM_ID, did, pi); did = 0; bad = true; }
         float base = 0.f;
         for (int k = lane; k < p.K; k += 64) {
             const float v = p.pm[(size_t)ul * p.K + k] * p.dt[(size_t)did * p.K + k];
@@ -1180,7 +1148,170 @@ __global__ __launch_bounds__(256) void m2d_mlp_generic(MlpArgs p)
     }
 }
 
+// ---- the launcher: which kernel family serves a call, then one function per family -----------------------------------------
+typedef void (*MlpKernel)(MlpArgs);
+enum MlpForm { MLP_PC, MLP_GATHER, MLP_GENERIC };   // m2d_mlp_pc, m2d_mlp_mfma (every wave gathers its rows), m2d_mlp_generic
+struct MlpChoice {
+    MlpForm form;
+    int kch;            // the 64-wide chunks of K that the kernel is instantiated for (not MLP_GENERIC)
+    bool padded;        // MLP_GATHER: K % 64 != 0 (e.g. the reference's embed_size 200: K = 1000), W1 zero-padded to 64 kch rows
+    bool x3;            // MLP_GATHER: split-bf16 arithmetic (MLP_PC has no other)
+    bool off32;         // MLP_PC: row offsets as 32-bit byte offsets where both gathered tables allow it (see the kernel's OFF32)
+};
+
+MlpChoice mlp_choose(const m2d_engine *h, const int K, const int64_t B)
+{
+    MlpChoice c = {MLP_GENERIC, K / 64, false, h->opt_mlp_bf16x3 != 0, false};
+    const bool mfma_ok = h->mlp_h1 == MH1 && h->mlp_h2 == MH2 && K % 64 == 0 && h->opt_variant != 9;
+    int pad_kch = 0;                          // K % 64 != 0: chunks of the zero-padded form (0 = none instantiated)
+    if (h->mlp_h1 == MH1 && h->mlp_h2 == MH2 && K % 64 != 0 && K % 4 == 0 && h->opt_variant != 9) {
+        const int need = (K + 63) / 64;
+        pad_kch = need <= 5 ? 5 : (need <= 10 ? 10 : (need <= 16 ? 16 : (need <= 20 ? 20 : 0)));
+    }
+    const bool pc_ok = (uint64_t)h->U * K * 4 < (1ull << 36) && (uint64_t)h->I * K * 4 < (1ull << 36) &&   // 32-bit row offsets in 16-B units
+                       h->E % 32 == 0 && ((h->E / 32) & (h->E / 32 - 1)) == 0 && h->C <= 6 && h->dish_cats &&      // k-blocks of whole periods
+                       B < (1ll << 31) - (1 << 16);                                                             // 32-bit pair slots
+    // ("variant" 16: the 16-byte-unit offsets whatever the sizes -- the tests' way to run the large-table instantiation)
+    c.off32 = (uint64_t)h->U * K * 4 <= (1ull << 32) && (uint64_t)h->I * K * 4 <= (1ull << 32) && h->opt_variant != 16;
+    if (mfma_ok && (c.kch == 5 || c.kch == 10 || c.kch == 20 || c.kch == 3)) {
+        c.form = h->opt_mlp_bf16x3 != 0 && h->opt_mlp_form == 0 && pc_ok ? MLP_PC : MLP_GATHER;
+    } else if (pad_kch != 0) {
+        c.form = MLP_GATHER;
+        c.kch = pad_kch;
+        c.padded = true;
+    }
+    return c;
+}
+
+// the producer / consumer form's own image of W1 | W2: (2 kch + 2) ring stages of 32 KiB, built once per head
+int mlp_ensure_pc_image(m2d_engine *h, const int K, hipStream_t stream)
+{
+    if (h->mlp_w1pc) return M2D_OK;
+    M2D_HIP_TRY(h, hipMalloc((void **)&h->mlp_w1pc, (size_t)(2 * (K / 64) + 2) * PC_STAGE));
+    hipLaunchKernelGGL(m2d_mlp_image_pc_w1, dim3((unsigned)(((int64_t)K * MH1 + 255) / 256)), dim3(256), 0, stream,
+                       h->mlp_w1, K, reinterpret_cast<__bf16 *>(h->mlp_w1pc));
+    hipLaunchKernelGGL(m2d_mlp_image_pc_w2, dim3(MH1 * MH2 / 256), dim3(256), 0, stream, h->mlp_w2,
+                       reinterpret_cast<__bf16 *>(h->mlp_w1pc) + (size_t)(2 * (K / 64)) * (PC_STAGE / 2));
+    M2D_HIP_TRY(h, hipGetLastError());
+    return M2D_OK;
+}
+
+// pairs bucketed by the dish's pattern of non-zero mask weights, every bucket padded to whole tiles (`tiles_max` in all, at most)
+int mlp_group_pairs(m2d_engine *h, MlpArgs &a, const int64_t tiles_max, hipStream_t stream)
+{
+    const size_t need = (size_t)(PG_MAXPAT + 4) + (size_t)tiles_max + (size_t)tiles_max * PC_PAIRS;
+    if (int rc = m2d_grow(h, h->mlp_pg, h->mlp_pg_cap, need, sizeof(int32_t))) return rc;
+    if (!h->mlp_pat8 || h->mlp_pat8_gen != h->dish_vec_gen) {      // once per mask table
+        if (!h->mlp_pat8) M2D_HIP_TRY(h, hipMalloc((void **)&h->mlp_pat8, (size_t)h->I));
+        hipLaunchKernelGGL(m2d_mlp_pg_pat8, dim3((unsigned)((h->I + 255) / 256)), dim3(256), 0, stream, h->dish_cats, h->C, h->I,
+                           h->nonfinite_dev, h->mlp_pat8);
+        M2D_HIP_TRY(h, hipGetLastError());
+        h->mlp_pat8_gen = h->dish_vec_gen;
+    }
+    int32_t *hist = h->mlp_pg, *ntl = hist + PG_MAXPAT, *perm = ntl + 4 + tiles_max;
+    uint32_t *tblocks = reinterpret_cast<uint32_t *>(ntl + 4);
+    M2D_HIP_TRY(h, hipMemsetAsync(hist, 0, (PG_MAXPAT + 4) * sizeof(int32_t), stream));
+    M2D_HIP_TRY(h, hipMemsetAsync(perm, 0xFF, (size_t)tiles_max * PC_PAIRS * sizeof(int32_t), stream));
+    const unsigned gcap = (unsigned)h->num_cu * 8;
+    const int64_t hb = (a.B + 255) / 256, sb = (a.B + 4095) / 4096;
+    hipLaunchKernelGGL(m2d_mlp_pg_hist, dim3((unsigned)(hb < gcap ? hb : gcap)), dim3(256), 0, stream, a.items, a.B, h->I,
+                       h->mlp_pat8, h->C, h->nonfinite_dev, hist);
+    hipLaunchKernelGGL(m2d_mlp_pg_scan, dim3(1), dim3(256), 0, stream, hist, h->C, tblocks, ntl);
+    hipLaunchKernelGGL(m2d_mlp_pg_scatter, dim3((unsigned)(sb < gcap ? sb : gcap)), dim3(256), 0, stream, a.items, a.B, h->I,
+                       h->mlp_pat8, h->C, h->nonfinite_dev, hist, perm);
+    M2D_HIP_TRY(h, hipGetLastError());
+    a.perm = perm; a.tile_blocks = tblocks; a.ntiles_dev = ntl;
+    return M2D_OK;
+}
+
+int mlp_launch_pc(m2d_engine *h, MlpArgs &a, const MlpChoice &c, hipStream_t stream)
+{
+    if (int rc = mlp_ensure_pc_image(h, a.K, stream)) return rc;
+    a.w1x3 = reinterpret_cast<const __bf16 *>(h->mlp_w1pc);
+    a.pshift = __builtin_ctz((unsigned)(h->E / 32));
+    // E = 32: a block is one period, keep every block; small batches: three more launches and mostly-empty tiles
+    // cost more than the skipped periods save
+    const bool group = h->opt_skip_masked != 0 && a.pshift >= 1 && a.B >= 16384;
+    int64_t tiles_max = (a.B + PC_PAIRS - 1) / PC_PAIRS;
+    if (group) {
+        tiles_max += 1 << h->C;
+        if (int rc = mlp_group_pairs(h, a, tiles_max, stream)) return rc;
+    }
+    const unsigned grid = (unsigned)(tiles_max < h->num_cu ? tiles_max : h->num_cu);
+    MlpKernel fn = nullptr;
+#define M2D_MLP_PC_CASE(N) \
+    if (c.kch == N) fn = c.off32 ? m2d_mlp_pc<N, true> : m2d_mlp_pc<N, false>;
+    M2D_MLP_PC_CASE(3) M2D_MLP_PC_CASE(5) M2D_MLP_PC_CASE(10) M2D_MLP_PC_CASE(20)
+#undef M2D_MLP_PC_CASE
+    M2D_HIP_TRY(h, m2d_lds_limit((const void *)fn, PC_LDS_BYTES));
+    hipLaunchKernelGGL(fn, dim3(grid), dim3(512), PC_LDS_BYTES, stream, a);
+    h->last_kernel = "m2d_mlp_pc_bf16x3";
+    return M2D_OK;
+}
+
+// K a multiple of 64 or not: the kernel sees a W1 of 64 kch rows -- the head's own, or its zero-padded copy
+int mlp_launch_gather(m2d_engine *h, MlpArgs &a, const MlpChoice &c, hipStream_t stream)
+{
+    const int Kp = c.kch * 64;
+    const size_t lds = (size_t)(2 * RING_FLOATS + MH1 + 2 * MH2) * sizeof(float);
+    const int64_t ntiles = (a.B + 32 * MWAVES - 1) / (32 * MWAVES);
+    const unsigned grid = (unsigned)(ntiles < h->num_cu ? ntiles : h->num_cu);
+    if (c.padded && !h->mlp_w1pad) {       // built once per head (m2d_set_mlp_head resets it)
+        M2D_HIP_TRY(h, hipMalloc((void **)&h->mlp_w1pad, (size_t)Kp * MH1 * sizeof(float)));
+        M2D_HIP_TRY(h, hipMemsetAsync(h->mlp_w1pad, 0, (size_t)Kp * MH1 * sizeof(float), stream));
+        M2D_HIP_TRY(h, hipMemcpyAsync(h->mlp_w1pad, h->mlp_w1, (size_t)a.K * MH1 * sizeof(float), hipMemcpyDeviceToDevice, stream));
+    }
+    if (c.padded) a.w1 = h->mlp_w1pad;
+    if (c.x3 && !h->mlp_w1x3) {            // built once per head, from the W1 the kernel reads
+        M2D_HIP_TRY(h, hipMalloc((void **)&h->mlp_w1x3, (size_t)Kp * MH1 * 4 + (size_t)MH1 * MH2 * 4));
+        hipLaunchKernelGGL(m2d_mlp_split_w1, dim3((unsigned)(((int64_t)Kp * MH1 + 255) / 256)), dim3(256), 0, stream,
+                           a.w1, Kp, reinterpret_cast<__bf16 *>(h->mlp_w1x3));
+        hipLaunchKernelGGL(m2d_mlp_split_w2, dim3(MH1 * MH2 / 256), dim3(256), 0, stream, h->mlp_w2,
+                           reinterpret_cast<__bf16 *>(h->mlp_w1x3) + (size_t)Kp * MH1 * 2);
+        M2D_HIP_TRY(h, hipGetLastError());
+    }
+    a.w1x3 = reinterpret_cast<const __bf16 *>(h->mlp_w1x3);
+    a.w2x3 = a.w1x3 ? a.w1x3 + (size_t)Kp * MH1 * 2 : nullptr;
+    MlpKernel fn = nullptr;
+#define M2D_MLP_CASE(N, PADK) \
+    if (c.kch == N && c.padded == PADK) fn = c.x3 ? m2d_mlp_mfma<N, true, PADK> : m2d_mlp_mfma<N, false, PADK>;
+    M2D_MLP_CASE(3, false) M2D_MLP_CASE(5, false) M2D_MLP_CASE(10, false) M2D_MLP_CASE(20, false)
+    M2D_MLP_CASE(5, true) M2D_MLP_CASE(10, true) M2D_MLP_CASE(16, true) M2D_MLP_CASE(20, true)
+#undef M2D_MLP_CASE
+    M2D_HIP_TRY(h, m2d_lds_limit((const void *)fn, (int)lds));
+    hipLaunchKernelGGL(fn, dim3(grid), dim3(MWAVES * 64), lds, stream, a);
+    h->last_kernel = c.x3 ? "m2d_mlp_mfma_bf16x3" : "m2d_mlp_mfma";
+    return M2D_OK;
+}
+
+int mlp_launch_generic(m2d_engine *h, const MlpArgs &a, hipStream_t stream)
+{
+    const size_t lds = (size_t)4 * (a.K + a.H1 + a.H2) * sizeof(float);
+    if (lds > 160 * 1024) {
+        h->last_error = "m2d_score_pairs_mlp: K + H1 + H2 too large for the generic kernel";
+        return M2D_ERR_UNSUPPORTED;
+    }
+    int64_t blocks = (a.B + 3) / 4;
+    if (blocks > (int64_t)h->num_cu * 4) blocks = (int64_t)h->num_cu * 4;
+    M2D_HIP_TRY(h, m2d_lds_limit((const void *)m2d_mlp_generic, (int)lds));
+    hipLaunchKernelGGL(m2d_mlp_generic, dim3((unsigned)blocks), dim3(256), lds, stream, a);
+    h->last_kernel = "m2d_mlp_generic";
+    return M2D_OK;
+}
+
 }  // namespace
+
+void m2d_mlp_free_derived(m2d_engine *h, const bool grouping)
+{
+    auto drop = [](auto *&p) {
+        if (p) (void)hipFree(p);
+        p = nullptr;
+    };
+    drop(h->mlp_w1x3); drop(h->mlp_w1pad); drop(h->mlp_w1pc);
+    if (!grouping) return;
+    drop(h->mlp_pg); drop(h->mlp_pat8);
+    h->mlp_pg_cap = 0;
+}
 
 int m2d_launch_score_pairs_mlp(m2d_engine *h, const int32_t *users, const int32_t *items, int64_t B, float *out,
                                hipStream_t stream)
@@ -1197,157 +1328,10 @@ int m2d_launch_score_pairs_mlp(m2d_engine *h, const int32_t *users, const int32_
     a.dbg = g_m2d_mlp_diag_buffer;
     a.w1x3 = a.w2x3 = nullptr;
     a.perm = nullptr; a.tile_blocks = nullptr; a.ntiles_dev = nullptr; a.pshift = 0;
-    const bool mfma_ok = a.H1 == MH1 && a.H2 == MH2 && a.K % 64 == 0 && h->opt_variant != 9;
-    const int kch = a.K / 64;
-    int pad_kch = 0;                          // K % 64 != 0: chunks of the zero-padded form (0 = none instantiated)
-    if (a.H1 == MH1 && a.H2 == MH2 && a.K % 64 != 0 && a.K % 4 == 0 && h->opt_variant != 9) {
-        const int need = (a.K + 63) / 64;
-        pad_kch = need <= 5 ? 5 : (need <= 10 ? 10 : (need <= 16 ? 16 : (need <= 20 ? 20 : 0)));
-    }
-    const bool pc_ok = (uint64_t)h->U * a.K * 4 < (1ull << 36) && (uint64_t)h->I * a.K * 4 < (1ull << 36) &&   // 32-bit row offsets in 16-B units
-                       h->E % 32 == 0 && ((h->E / 32) & (h->E / 32 - 1)) == 0 && h->C <= 6 && h->dish_cats &&      // k-blocks of whole periods
-                       B < (1ll << 31) - (1 << 16);                                                             // 32-bit pair slots
-    if (mfma_ok && (kch == 5 || kch == 10 || kch == 20 || kch == 3) && h->opt_mlp_bf16x3 != 0 && h->opt_mlp_form == 0 && pc_ok) {
-        // producer / consumer form: its own image of W1 | W2, (2 kch + 2) ring stages of 32 KiB, built once per head
-        if (!h->mlp_w1pc) {
-            M2D_HIP_TRY(h, hipMalloc((void **)&h->mlp_w1pc, (size_t)(2 * kch + 2) * PC_STAGE));
-            hipLaunchKernelGGL(m2d_mlp_image_pc_w1, dim3((unsigned)(((int64_t)a.K * MH1 + 255) / 256)), dim3(256), 0, stream,
-                               h->mlp_w1, a.K, reinterpret_cast<__bf16 *>(h->mlp_w1pc));
-            hipLaunchKernelGGL(m2d_mlp_image_pc_w2, dim3(MH1 * MH2 / 256), dim3(256), 0, stream, h->mlp_w2,
-                               reinterpret_cast<__bf16 *>(h->mlp_w1pc) + (size_t)(2 * kch) * (PC_STAGE / 2));
-            M2D_HIP_TRY(h, hipGetLastError());
-        }
-        a.w1x3 = reinterpret_cast<const __bf16 *>(h->mlp_w1pc);
-        // pairs bucketed by the dish's pattern of non-zero mask weights; every bucket padded to whole tiles
-        const int npat = 1 << h->C;
-        a.pshift = __builtin_ctz((unsigned)(h->E / 32));
-        // E = 32: a block is one period, keep every block; small batches: three more launches and mostly-empty tiles
-        // cost more than the skipped periods save
-        const bool group = h->opt_skip_masked != 0 && a.pshift >= 1 && B >= 16384;
-        int64_t tiles_max = (B + PC_PAIRS - 1) / PC_PAIRS;
-        if (group) {
-            tiles_max += npat;
-            const size_t need = (size_t)(PG_MAXPAT + 4) + (size_t)tiles_max + (size_t)tiles_max * PC_PAIRS;
-            if (int rc = m2d_grow(h, h->mlp_pg, h->mlp_pg_cap, need, sizeof(int32_t))) return rc;
-            if (!h->mlp_pat8 || h->mlp_pat8_gen != h->dish_vec_gen || h->mlp_pat8_rows != h->I) {      // once per mask table
-                if (h->mlp_pat8 && h->mlp_pat8_rows != h->I) { M2D_HIP_TRY(h, hipFree(h->mlp_pat8)); h->mlp_pat8 = nullptr; }
-                if (!h->mlp_pat8) M2D_HIP_TRY(h, hipMalloc((void **)&h->mlp_pat8, (size_t)h->I));
-                h->mlp_pat8_rows = h->I;
-                hipLaunchKernelGGL(m2d_mlp_pg_pat8, dim3((unsigned)((h->I + 255) / 256)), dim3(256), 0, stream, h->dish_cats, h->C, h->I,
-                                   h->nonfinite_dev, h->mlp_pat8);
-                M2D_HIP_TRY(h, hipGetLastError());
-                h->mlp_pat8_gen = h->dish_vec_gen;
-            }
-            int32_t *hist = h->mlp_pg, *ntl = hist + PG_MAXPAT, *perm = ntl + 4 + tiles_max;
-            uint32_t *tblocks = reinterpret_cast<uint32_t *>(ntl + 4);
-            M2D_HIP_TRY(h, hipMemsetAsync(hist, 0, (PG_MAXPAT + 4) * sizeof(int32_t), stream));
-            M2D_HIP_TRY(h, hipMemsetAsync(perm, 0xFF, (size_t)tiles_max * PC_PAIRS * sizeof(int32_t), stream));
-            const unsigned gcap = (unsigned)h->num_cu * 8;
-            const int64_t hb = (B + 255) / 256, sb = (B + 4095) / 4096;
-            hipLaunchKernelGGL(m2d_mlp_pg_hist, dim3((unsigned)(hb < gcap ? hb : gcap)), dim3(256), 0, stream, items, B, h->I,
-                               h->mlp_pat8, h->C, h->nonfinite_dev, hist);
-            hipLaunchKernelGGL(m2d_mlp_pg_scan, dim3(1), dim3(256), 0, stream, hist, h->C, tblocks, ntl);
-            hipLaunchKernelGGL(m2d_mlp_pg_scatter, dim3((unsigned)(sb < gcap ? sb : gcap)), dim3(256), 0, stream, items, B, h->I,
-                               h->mlp_pat8, h->C, h->nonfinite_dev, hist, perm);
-            M2D_HIP_TRY(h, hipGetLastError());
-            a.perm = perm; a.tile_blocks = tblocks; a.ntiles_dev = ntl;
-        }
-        const unsigned grid = (unsigned)(tiles_max < h->num_cu ? tiles_max : h->num_cu);
-        // row offsets as 32-bit byte offsets where both gathered tables allow it (see the kernel's OFF32)
-        // ("variant" 16: the 16-byte-unit offsets whatever the sizes -- the tests' way to run the large-table instantiation)
-        const bool off32 = (uint64_t)h->U * a.K * 4 <= (1ull << 32) && (uint64_t)h->I * a.K * 4 <= (1ull << 32) && h->opt_variant != 16;
-#define M2D_MLP_PC_CASE(N)                                                                                  \
-    if (kch == N && off32) {                                                                                \
-        M2D_HIP_TRY(h, m2d_lds_limit((const void *)m2d_mlp_pc<N, true>, PC_LDS_BYTES));                     \
-        hipLaunchKernelGGL((m2d_mlp_pc<N, true>), dim3(grid), dim3(512), PC_LDS_BYTES, stream, a);          \
-    } else if (kch == N) {                                                                                  \
-        M2D_HIP_TRY(h, m2d_lds_limit((const void *)m2d_mlp_pc<N, false>, PC_LDS_BYTES));                    \
-        hipLaunchKernelGGL((m2d_mlp_pc<N, false>), dim3(grid), dim3(512), PC_LDS_BYTES, stream, a);         \
-    }
-        M2D_MLP_PC_CASE(3) M2D_MLP_PC_CASE(5) M2D_MLP_PC_CASE(10) M2D_MLP_PC_CASE(20)
-#undef M2D_MLP_PC_CASE
-        h->last_kernel = "m2d_mlp_pc_bf16x3";
-    } else if (mfma_ok && (kch == 5 || kch == 10 || kch == 20 || kch == 3)) {
-        const size_t lds = (size_t)(2 * RING_FLOATS + MH1 + 2 * MH2) * sizeof(float);
-        const int64_t ntiles = (B + 32 * MWAVES - 1) / (32 * MWAVES);
-        const unsigned grid = (unsigned)(ntiles < h->num_cu ? ntiles : h->num_cu);
-        const bool x3 = h->opt_mlp_bf16x3 != 0;
-        if (x3 && !h->mlp_w1x3) {          // built once per head (m2d_set_mlp_head resets it)
-            M2D_HIP_TRY(h, hipMalloc((void **)&h->mlp_w1x3, (size_t)a.K * MH1 * 4 + (size_t)MH1 * MH2 * 4));
-            hipLaunchKernelGGL(m2d_mlp_split_w1, dim3((unsigned)(((int64_t)a.K * MH1 + 255) / 256)), dim3(256), 0, stream,
-                               h->mlp_w1, a.K, reinterpret_cast<__bf16 *>(h->mlp_w1x3));
-            hipLaunchKernelGGL(m2d_mlp_split_w2, dim3(MH1 * MH2 / 256), dim3(256), 0, stream, h->mlp_w2,
-                               reinterpret_cast<__bf16 *>(h->mlp_w1x3) + (size_t)a.K * MH1 * 2);
-            M2D_HIP_TRY(h, hipGetLastError());
-        }
-        a.w1x3 = reinterpret_cast<const __bf16 *>(h->mlp_w1x3);
-        a.w2x3 = a.w1x3 ? a.w1x3 + (size_t)a.K * MH1 * 2 : nullptr;
-#define M2D_MLP_CASE(N)                                                                                     \
-    if (kch == N) {                                                                                         \
-        if (x3) {                                                                                           \
-            M2D_HIP_TRY(h, hipFuncSetAttribute((const void *)m2d_mlp_mfma<N, true>,                         \
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));      \
-            hipLaunchKernelGGL((m2d_mlp_mfma<N, true>), dim3(grid), dim3(MWAVES * 64), lds, stream, a);     \
-        } else {                                                                                            \
-            M2D_HIP_TRY(h, hipFuncSetAttribute((const void *)m2d_mlp_mfma<N, false>,                        \
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));      \
-            hipLaunchKernelGGL((m2d_mlp_mfma<N, false>), dim3(grid), dim3(MWAVES * 64), lds, stream, a);    \
-        }                                                                                                   \
-    }
-        M2D_MLP_CASE(3) M2D_MLP_CASE(5) M2D_MLP_CASE(10) M2D_MLP_CASE(20)
-#undef M2D_MLP_CASE
-        h->last_kernel = x3 ? "m2d_mlp_mfma_bf16x3" : "m2d_mlp_mfma";
-    } else if (pad_kch != 0) {
-        // K not a multiple of 64 (e.g. the reference's embed_size 200: K = 1000): the every-wave-gathers kernel on a W1 copy
-        // zero-padded to 64 pad_kch rows; a lane reads zeros for the k-values past the end of its rows
-        const int Kp = pad_kch * 64;
-        const size_t lds = (size_t)(2 * RING_FLOATS + MH1 + 2 * MH2) * sizeof(float);
-        const int64_t ntiles = (B + 32 * MWAVES - 1) / (32 * MWAVES);
-        const unsigned grid = (unsigned)(ntiles < h->num_cu ? ntiles : h->num_cu);
-        const bool x3 = h->opt_mlp_bf16x3 != 0;
-        if (!h->mlp_w1pad) {               // built once per head (m2d_set_mlp_head resets it)
-            M2D_HIP_TRY(h, hipMalloc((void **)&h->mlp_w1pad, (size_t)Kp * MH1 * sizeof(float)));
-            M2D_HIP_TRY(h, hipMemsetAsync(h->mlp_w1pad, 0, (size_t)Kp * MH1 * sizeof(float), stream));
-            M2D_HIP_TRY(h, hipMemcpyAsync(h->mlp_w1pad, h->mlp_w1, (size_t)a.K * MH1 * sizeof(float), hipMemcpyDeviceToDevice, stream));
-        }
-        a.w1 = h->mlp_w1pad;
-        if (x3 && !h->mlp_w1x3) {
-            M2D_HIP_TRY(h, hipMalloc((void **)&h->mlp_w1x3, (size_t)Kp * MH1 * 4 + (size_t)MH1 * MH2 * 4));
-            hipLaunchKernelGGL(m2d_mlp_split_w1, dim3((unsigned)(((int64_t)Kp * MH1 + 255) / 256)), dim3(256), 0, stream,
-                               h->mlp_w1pad, Kp, reinterpret_cast<__bf16 *>(h->mlp_w1x3));
-            hipLaunchKernelGGL(m2d_mlp_split_w2, dim3(MH1 * MH2 / 256), dim3(256), 0, stream, h->mlp_w2,
-                               reinterpret_cast<__bf16 *>(h->mlp_w1x3) + (size_t)Kp * MH1 * 2);
-            M2D_HIP_TRY(h, hipGetLastError());
-        }
-        a.w1x3 = reinterpret_cast<const __bf16 *>(h->mlp_w1x3);
-        a.w2x3 = a.w1x3 ? a.w1x3 + (size_t)Kp * MH1 * 2 : nullptr;
-#define M2D_MLP_PAD_CASE(N)                                                                                 \
-    if (pad_kch == N) {                                                                                     \
-        if (x3) {                                                                                           \
-            M2D_HIP_TRY(h, hipFuncSetAttribute((const void *)m2d_mlp_mfma<N, true, true>,                   \
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));      \
-            hipLaunchKernelGGL((m2d_mlp_mfma<N, true, true>), dim3(grid), dim3(MWAVES * 64), lds, stream, a); \
-        } else {                                                                                            \
-            M2D_HIP_TRY(h, hipFuncSetAttribute((const void *)m2d_mlp_mfma<N, false, true>,                  \
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));      \
-            hipLaunchKernelGGL((m2d_mlp_mfma<N, false, true>), dim3(grid), dim3(MWAVES * 64), lds, stream, a); \
-        }                                                                                                   \
-    }
-        M2D_MLP_PAD_CASE(5) M2D_MLP_PAD_CASE(10) M2D_MLP_PAD_CASE(16) M2D_MLP_PAD_CASE(20)
-#undef M2D_MLP_PAD_CASE
-        h->last_kernel = x3 ? "m2d_mlp_mfma_bf16x3" : "m2d_mlp_mfma";
-    } else {
-        const size_t lds = (size_t)4 * (a.K + a.H1 + a.H2) * sizeof(float);
-        if (lds > 160 * 1024) {
-            h->last_error = "m2d_score_pairs_mlp: K + H1 + H2 too large for the generic kernel";
-            return M2D_ERR_UNSUPPORTED;
-        }
-        int64_t blocks = (B + 3) / 4;
-        if (blocks > (int64_t)h->num_cu * 4) blocks = (int64_t)h->num_cu * 4;
-        M2D_HIP_TRY(h, m2d_lds_limit((const void *)m2d_mlp_generic, (int)lds));
-        hipLaunchKernelGGL(m2d_mlp_generic, dim3((unsigned)blocks), dim3(256), lds, stream, a);
-        h->last_kernel = "m2d_mlp_generic";
-    }
+    const MlpChoice c = mlp_choose(h, a.K, B);
+    rc = c.form == MLP_PC ? mlp_launch_pc(h, a, c, stream)
+       : c.form == MLP_GATHER ? mlp_launch_gather(h, a, c, stream) : mlp_launch_generic(h, a, stream);
+    if (rc != M2D_OK) return rc;
     M2D_HIP_TRY(h, hipGetLastError());
     return M2D_OK;
 }

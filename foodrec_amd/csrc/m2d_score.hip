@@ -43,23 +43,12 @@ struct ScoreArgs {
     const float *uh;       // [U, 4] derived table <U_high[u], CE_c> (m2d_build_user_high), or null: read U_high and multiply
 };
 
-__device__ __forceinline__ void latch_error(int32_t *err, int code, int64_t value, int64_t index)
-{
-    if (atomicCAS(&err[0], 0, code) == 0) {
-        err[1] = (int32_t)value;
-        err[2] = (int32_t)(index & 0xffffffff);
-        err[3] = (int32_t)(index >> 32);
-    }
-}
-
 // Rows of weight-0 categories may be left out only while every table value is finite: 0 * inf = NaN at
 // Model_Recommender.py:82-90.  One scalar load per wave (the word is set by the table scan / the engine's writers).
 __device__ __forceinline__ bool skip_rows(const ScoreArgs &p)
 {
     return p.skip_masked != 0 && __builtin_amdgcn_readfirstlane(*p.nonfinite) == 0;
 }
-
-typedef float v4f __attribute__((ext_vector_type(4)));
 
 template <bool NT>
 __device__ __forceinline__ v4f ld4(const v4f *p)
@@ -135,12 +124,12 @@ __global__ __launch_bounds__(256) void m2d_score_pairs_c4(ScoreArgs p)
         int64_t ul = (int64_t)uid - p.user_base;
         bool bad = false;
         if (ul < 0 || ul >= p.U) {
-            latch_error(p.err, M2D_ERR_BAD_USER_ID, uid, pi);
+            m2d_latch_error(p.err, M2D_ERR_BAD_USER_ID, uid, pi);
             ul = 0;
             bad = true;
         }
         if (did < 0 || (int64_t)did >= p.I) {
-            latch_error(p.err, M2D_ERR_BAD_ITEM_ID, did, pi);
+            m2d_latch_error(p.err, M2D_ERR_BAD_ITEM_ID, did, pi);
             did = 0;
             bad = true;
         }
@@ -289,12 +278,12 @@ __global__ __launch_bounds__(256) void m2d_score_pairs_c4_small(ScoreArgs p)
         int64_t ul = (int64_t)uid - p.user_base;
         bool bad = false;
         if (ul < 0 || ul >= p.U) {
-            if (j == 0) latch_error(p.err, M2D_ERR_BAD_USER_ID, uid, pi);
+            if (j == 0) m2d_latch_error(p.err, M2D_ERR_BAD_USER_ID, uid, pi);
             ul = 0;
             bad = true;
         }
         if (did < 0 || (int64_t)did >= p.I) {
-            if (j == 0) latch_error(p.err, M2D_ERR_BAD_ITEM_ID, did, pi);
+            if (j == 0) m2d_latch_error(p.err, M2D_ERR_BAD_ITEM_ID, did, pi);
             did = 0;
             bad = true;
         }
@@ -383,12 +372,12 @@ __global__ __launch_bounds__(256) void m2d_score_pairs_cn(ScoreArgs p)
         int64_t ul = (int64_t)uid - p.user_base;
         bool bad = false;
         if (ul < 0 || ul >= p.U) {
-            latch_error(p.err, M2D_ERR_BAD_USER_ID, uid, pi);
+            m2d_latch_error(p.err, M2D_ERR_BAD_USER_ID, uid, pi);
             ul = 0;
             bad = true;
         }
         if (did < 0 || (int64_t)did >= p.I) {
-            latch_error(p.err, M2D_ERR_BAD_ITEM_ID, did, pi);
+            m2d_latch_error(p.err, M2D_ERR_BAD_ITEM_ID, did, pi);
             did = 0;
             bad = true;
         }
@@ -485,12 +474,12 @@ __global__ __launch_bounds__(256) void m2d_score_pairs_generic(ScoreArgs p)
         int64_t ul = (int64_t)uid - p.user_base;
         bool bad = false;
         if (ul < 0 || ul >= p.U) {
-            if (lane == 0) latch_error(p.err, M2D_ERR_BAD_USER_ID, uid, pi);
+            if (lane == 0) m2d_latch_error(p.err, M2D_ERR_BAD_USER_ID, uid, pi);
             ul = 0;
             bad = true;
         }
         if (did < 0 || (int64_t)did >= p.I) {
-            if (lane == 0) latch_error(p.err, M2D_ERR_BAD_ITEM_ID, did, pi);
+            if (lane == 0) m2d_latch_error(p.err, M2D_ERR_BAD_ITEM_ID, did, pi);
             did = 0;
             bad = true;
         }

@@ -71,15 +71,6 @@ struct TrainArgs {
     int32_t learner, parity;
 };
 
-__device__ __forceinline__ void train_latch(int32_t *err, int code, int64_t value, int64_t index)
-{
-    if (atomicCAS(&err[0], 0, code) == 0) {
-        err[1] = (int32_t)value;
-        err[2] = (int32_t)(index & 0xffffffff);
-        err[3] = (int32_t)(index >> 32);
-    }
-}
-
 __device__ __forceinline__ float wave_sum(float x)
 {
 #pragma unroll
@@ -93,8 +84,8 @@ __global__ __launch_bounds__(256) void m2d_train_claim(TrainArgs p)
     if (b >= p.B) return;
     const int32_t uid = p.users[b], did = p.items[b];
     const int64_t ul = (int64_t)uid - p.user_base;
-    if (ul < 0 || ul >= p.U) { train_latch(p.err, M2D_ERR_BAD_USER_ID, uid, b); return; }
-    if (did < 0 || (int64_t)did >= p.I) { train_latch(p.err, M2D_ERR_BAD_ITEM_ID, did, b); return; }
+    if (ul < 0 || ul >= p.U) { m2d_latch_error(p.err, M2D_ERR_BAD_USER_ID, uid, b); return; }
+    if (did < 0 || (int64_t)did >= p.I) { m2d_latch_error(p.err, M2D_ERR_BAD_ITEM_ID, did, b); return; }
     if (atomicCAS(&p.map_u[ul], -1, -2) == -1) {
         const int s = atomicAdd(&p.cnt[0], 1);
         p.slot_u[s] = (int32_t)ul;
@@ -130,7 +121,7 @@ __global__ __launch_bounds__(256) void m2d_train_grad(TrainArgs p, int ce_lds)
         const int64_t ul = (int64_t)uid - p.user_base;
         if (ul < 0 || ul >= p.U || did < 0 || (int64_t)did >= p.I) {      // latched by the claim pass / below
             if (!p.accumulate && lane == 0)
-                train_latch(p.err, (ul < 0 || ul >= p.U) ? M2D_ERR_BAD_USER_ID : M2D_ERR_BAD_ITEM_ID,
+                m2d_latch_error(p.err, (ul < 0 || ul >= p.U) ? M2D_ERR_BAD_USER_ID : M2D_ERR_BAD_ITEM_ID,
                             (ul < 0 || ul >= p.U) ? uid : did, b);
             continue;
         }
@@ -290,7 +281,6 @@ __device__ __forceinline__ void apply_one(const RuleArgs &r, float g, float &var
 // Rows of one table.  ALL = true (Adam): every row r < R, gradient row map[r] when >= 0, else zero.
 // ALL = false: claimed rows only, r = slot_row[s] for s < *count.  map == nullptr: dense gradient (row r of G).
 // W floats per row; a wave walks a row 64 (x4 when W % 4 == 0) floats at a time.
-typedef float v4f __attribute__((ext_vector_type(4)));
 template <int VEC> struct RowVec;
 template <> struct RowVec<1> { typedef float T; };
 template <> struct RowVec<4> { typedef v4f T; };
@@ -386,7 +376,7 @@ __global__ __launch_bounds__(256) void m2d_train_grad_fused(TrainArgs p)
         const int64_t ul = (int64_t)uid - p.user_base;
         if (ul < 0 || ul >= p.U || did < 0 || (int64_t)did >= p.I) {      // TF raises from the gather: the step applies nothing
             if (lane == 0)
-                train_latch(p.err, (ul < 0 || ul >= p.U) ? M2D_ERR_BAD_USER_ID : M2D_ERR_BAD_ITEM_ID,
+                m2d_latch_error(p.err, (ul < 0 || ul >= p.U) ? M2D_ERR_BAD_USER_ID : M2D_ERR_BAD_ITEM_ID,
                             (ul < 0 || ul >= p.U) ? uid : did, b);
             continue;
         }

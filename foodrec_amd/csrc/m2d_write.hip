@@ -38,15 +38,6 @@ struct WriteArgs {
     const int32_t *nonfinite;   // device word: some table value is inf / NaN -> 0 * row is not 0 (:111), no row is left out
 };
 
-__device__ __forceinline__ void latch(int32_t *err, int code, int64_t value, int64_t index)
-{
-    if (atomicCAS(&err[0], 0, code) == 0) {
-        err[1] = (int32_t)value;
-        err[2] = (int32_t)(index & 0xffffffff);
-        err[3] = (int32_t)(index >> 32);
-    }
-}
-
 // PASS 0: PM[u_b] += v_b + alpha g_b.   PASS 1: GM[l] += y_bl v_b (after pass 0, which latched any id error).
 // PASS 2: the GM pass on its own (the `general`-only fetch): latches id errors itself.
 template <int PASS>
@@ -61,11 +52,11 @@ __global__ __launch_bounds__(256) void m2d_write_memory_kernel(WriteArgs p)
         const int32_t uid = p.users[b], did = p.items[b];
         const int64_t ul = (int64_t)uid - p.user_base;
         if (ul < 0 || ul >= p.U) {
-            if (PASS != 1 && lane == 0) latch(p.err, M2D_ERR_BAD_USER_ID, uid, b);
+            if (PASS != 1 && lane == 0) m2d_latch_error(p.err, M2D_ERR_BAD_USER_ID, uid, b);
             continue;   // wave-uniform: nothing is written for a bad pair
         }
         if (did < 0 || (int64_t)did >= p.I) {
-            if (PASS != 1 && lane == 0) latch(p.err, M2D_ERR_BAD_ITEM_ID, did, b);
+            if (PASS != 1 && lane == 0) m2d_latch_error(p.err, M2D_ERR_BAD_ITEM_ID, did, b);
             continue;
         }
         const float s = p.sign[b];
@@ -146,7 +137,7 @@ __global__ __launch_bounds__(256) void m2d_write_gm_gather(WriteArgs p)
         const int64_t ul = (int64_t)uid - p.user_base;
         const bool bad = ul < 0 || ul >= p.U || did < 0 || (int64_t)did >= p.I;
         if (LATCH && wv == 0 && in && bad)
-            latch(p.err, (ul < 0 || ul >= p.U) ? M2D_ERR_BAD_USER_ID : M2D_ERR_BAD_ITEM_ID, (ul < 0 || ul >= p.U) ? uid : did, bi);
+            m2d_latch_error(p.err, (ul < 0 || ul >= p.U) ? M2D_ERR_BAD_USER_ID : M2D_ERR_BAD_ITEM_ID, (ul < 0 || ul >= p.U) ? uid : did, bi);
         const float yw = (in && !bad) ? p.labels[(size_t)bi * L + l] : 0.f;   // nothing is written for a bad pair
         for (unsigned long long bits = __ballot(yw != 0.f); bits; bits &= bits - 1) {            // in batch order
             const int i = __builtin_ctzll(bits);
