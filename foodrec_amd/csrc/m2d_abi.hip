@@ -157,19 +157,14 @@ int m2d_ensure_finite_scan(m2d_engine *h, hipStream_t st)
 {
     if (!h->finite_scan_pending) return M2D_OK;
     M2D_HIP_TRY(h, hipMemsetAsync(h->nonfinite_dev, 0, sizeof(int32_t), st));
-    const int64_t n[3] = {h->U * (int64_t)(h->C + 1) * h->E, h->I * (int64_t)h->E, (int64_t)h->C * h->E};
     const float *t[3] = {h->pm, h->re, h->ce};
     for (int i = 0; i < 3; ++i) {
-        int64_t blocks = (n[i] / 4 + 1023) / 1024;
-        if (blocks > (int64_t)h->num_cu * 8) blocks = (int64_t)h->num_cu * 8;
-        if (blocks < 1) blocks = 1;
-        hipLaunchKernelGGL(m2d_scan_nonfinite, dim3((unsigned)blocks), dim3(256), 0, st, t[i], n[i], h->nonfinite_dev);
+        const int64_t n = m2d_table_floats(h, i);
+        hipLaunchKernelGGL(m2d_scan_nonfinite, dim3(m2d_blocks_for(h, n / 4, 1024)), dim3(256), 0, st, t[i], n, h->nonfinite_dev);
     }
     if (h->dish_high) {                 // (set / cleared by m2d_set_ingredients / m2d_clear_ingredients, which queue this scan again)
         const int64_t nh = h->I * (int64_t)h->E;
-        int64_t blocks = (nh + 1023) / 1024;
-        if (blocks > (int64_t)h->num_cu * 8) blocks = (int64_t)h->num_cu * 8;
-        hipLaunchKernelGGL(m2d_scan_inf, dim3((unsigned)blocks), dim3(256), 0, st, h->dish_high, nh, h->nonfinite_dev);
+        hipLaunchKernelGGL(m2d_scan_inf, dim3(m2d_blocks_for(h, nh, 1024)), dim3(256), 0, st, h->dish_high, nh, h->nonfinite_dev);
     }
     M2D_HIP_TRY(h, hipGetLastError());
     h->grp_nonfinite_known = false;     // the retrieval launcher's host copy of the word
@@ -180,9 +175,7 @@ int m2d_ensure_finite_scan(m2d_engine *h, hipStream_t st)
 int m2d_launch_rows_finite_check(m2d_engine *h, const int32_t *users, int64_t B, hipStream_t st)
 {
     if (B <= 0) return M2D_OK;
-    int64_t blocks = (B + 3) / 4;
-    if (blocks > (int64_t)h->num_cu * 8) blocks = (int64_t)h->num_cu * 8;
-    hipLaunchKernelGGL(m2d_rows_nonfinite, dim3((unsigned)blocks), dim3(256), 0, st, h->pm, users, B, h->U, h->user_base,
+    hipLaunchKernelGGL(m2d_rows_nonfinite, dim3(m2d_blocks_for(h, B, 4)), dim3(256), 0, st, h->pm, users, B, h->U, h->user_base,
                        (h->C + 1) * h->E, h->nonfinite_dev);
     M2D_HIP_TRY(h, hipGetLastError());
     return M2D_OK;
@@ -275,8 +268,7 @@ int m2d_set_dish_categories(m2d_engine *h, const float *cats, int table_flags)
     if (h->own_dish_cats && h->dish_cats) (void)hipFree((void *)h->dish_cats);
     h->dish_cats = nullptr;
     h->own_dish_cats = false;
-    h->dish_vec_valid = false;
-    h->grp_valid = false;
+    m2d_mark_written(h, M2D_TAB_MASKS, M2D_NO_VALUES);
     int rc = adopt_table(h, cats, (size_t)h->I * h->C, table_flags, &h->dish_cats, &h->own_dish_cats);
     if (rc != M2D_OK) return rc;
     if (!aligned16(h->dish_cats)) return fail(h, M2D_ERR_INVALID_ARG, "dish categories must be 16-byte aligned");
@@ -559,9 +551,7 @@ int m2d_clear_ingredients(m2d_engine *h)
     if (h->dish_high) (void)hipFree(h->dish_high);
     h->ing = nullptr; h->ing_off = nullptr; h->ing_ids = nullptr; h->ing_w = nullptr; h->dish_high = nullptr;
     h->own_ing = false; h->ing_rows = 0; h->ing_nnz = 0;
-    h->dish_vec_valid = false;
-    h->grp_valid = false;               // the pattern-grouped retrieval rows carry H[d] when it is set
-    h->finite_scan_pending = true;      // H[d] was part of the scan
+    m2d_mark_written(h, M2D_TAB_ING, M2D_BY_CALLER);       // H[d] was part of the scan
     return M2D_OK;
 }
 
@@ -613,9 +603,7 @@ int m2d_set_ingredients(m2d_engine *h, const float *ing, int64_t R, const int32_
         h->last_error = "m2d_set_ingredients: " + msg;
         return M2D_ERR_BAD_INGREDIENT;
     }
-    h->dish_vec_valid = false;
-    h->grp_valid = false;
-    h->finite_scan_pending = true;      // H[d] is part of the scan
+    m2d_mark_written(h, M2D_TAB_ING, M2D_BY_CALLER);       // H[d] is part of the scan
     return M2D_OK;
 }
 
@@ -741,10 +729,7 @@ int m2d_train_slot(m2d_engine *h, int32_t table, int32_t slot, float *buf, int32
 int m2d_tables_updated(m2d_engine *h)
 {
     if (!h) return M2D_ERR_INVALID_ARG;
-    h->dish_vec_valid = false;      // factored dish vectors (Recipe_Embedding, Category_Embedding)
-    h->user_high_valid = false;     // <U_high, CE_c> (Personal_Memory, Category_Embedding)
-    h->grp_valid = false;           // pattern-grouped retrieval tables (Recipe_Embedding)
-    h->finite_scan_pending = true;  // "every table value is finite" has to be established again
+    m2d_mark_written(h, M2D_TAB_PM | M2D_TAB_RE | M2D_TAB_CE, M2D_BY_CALLER);   // "every table value is finite" has to be established again
     return M2D_OK;
 }
 

@@ -165,6 +165,47 @@ __device__ __forceinline__ void m2d_latch_error(int32_t *err, int code, int32_t 
     }
 }
 
+// a pair's id error: the user id is looked at first (ul = uid - user_base, U rows), the caller has found one of the two out of range
+__device__ __forceinline__ void m2d_latch_bad_pair(int32_t *err, int64_t ul, int64_t U, int32_t uid, int32_t did, int64_t index)
+{
+    const bool user = ul < 0 || ul >= U;
+    m2d_latch_error(err, user ? M2D_ERR_BAD_USER_ID : M2D_ERR_BAD_ITEM_ID, user ? uid : did, index);
+}
+
+// floats of table 0 / 1 / 2: Personal_Memory [U, C+1, E], Recipe_Embedding [I, E], Category_Embedding [C, E]
+static inline int64_t m2d_table_floats(const m2d_engine *h, int table)
+{
+    return table == 0 ? h->U * (int64_t)(h->C + 1) * h->E : table == 1 ? h->I * (int64_t)h->E : (int64_t)h->C * h->E;
+}
+
+// grid of a grid-stride launch: one block per `per_block` items, at least one, at most eight per CU
+static inline unsigned m2d_blocks_for(const m2d_engine *h, int64_t items, int64_t per_block)
+{
+    const int64_t b = (items + per_block - 1) / per_block, cap = (int64_t)h->num_cu * 8;
+    return (unsigned)(b > cap ? cap : b < 1 ? 1 : b);
+}
+
+// What a write makes stale.  Every writer of something the derived state is built from says WHICH tables it wrote and what is
+// known about the new VALUES; the dependencies are here and nowhere else:
+//   user_high (<U_high, CE_c>)                                  hangs on Personal_Memory, Category_Embedding;
+//   dish_vec and the sorted retrieval tables (grp_*)            hang on Recipe_Embedding, Category_Embedding, the dish masks and
+//                                                               the ingredient table (H[d] rides in the sorted rows);
+//   the non-finite word (nonfinite_dev)                         covers every table value and H[d]:
+//     M2D_BY_ENGINE  one of the engine's own kernels wrote, and looked at what it wrote: the word is up to date on the device, but
+//                    the retrieval launcher's host copy of it (grp_nonfinite) is not -- it reads the word again;
+//     M2D_BY_CALLER  the caller wrote: nobody looked, the full scan is queued again (it resets the host copy when it runs);
+//     M2D_NO_VALUES  nothing the word covers changed (the dish masks).
+// State that follows a generation counter (mlp_pat8_gen, rank_tnorm_gen) rebuilds with what it was derived from.
+enum : unsigned { M2D_TAB_PM = 1, M2D_TAB_RE = 2, M2D_TAB_CE = 4, M2D_TAB_MASKS = 8, M2D_TAB_ING = 16 };
+enum m2d_written_by { M2D_BY_ENGINE, M2D_BY_CALLER, M2D_NO_VALUES };
+static inline void m2d_mark_written(m2d_engine *h, unsigned tables, m2d_written_by who)
+{
+    if (tables & (M2D_TAB_PM | M2D_TAB_CE)) h->user_high_valid = false;
+    if (tables & (M2D_TAB_RE | M2D_TAB_CE | M2D_TAB_MASKS | M2D_TAB_ING)) h->dish_vec_valid = h->grp_valid = false;
+    if (who == M2D_BY_ENGINE) h->grp_nonfinite_known = false;
+    if (who == M2D_BY_CALLER) h->finite_scan_pending = true;
+}
+
 #define M2D_HIP_TRY(h, expr)                                                                   \
     do {                                                                                       \
         hipError_t e_ = (expr);                                                                \

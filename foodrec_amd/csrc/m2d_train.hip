@@ -40,6 +40,11 @@
 // An out-of-range id is latched by the claim pass (m2d_check reports it) and the apply pass then leaves every
 // table and slot as it was -- TF raises InvalidArgumentError from the gather before anything is assigned.
 // Sums are float atomics: results are order-dependent in the last bits, like m2d_write_memory.
+//
+// Both forms run one copy of the arithmetic: pair_forward / pair_grad (a pair's forward pass and gradient rows; the grad kernels
+// differ in how slots are claimed, where dCE goes and who finishes the step) and apply_row<VEC> (one row's update; the apply
+// kernels differ in how rows are found and released).  m2d_launch_train_step chooses between train_step_fused / _staged; both
+// take the tables from apply_tabs and the learner from rule_args.  What a step makes stale: m2d_mark_written (m2d_engine.h).
 #include "m2d_engine.h"
 
 namespace {
@@ -76,6 +81,79 @@ __device__ __forceinline__ float wave_sum(float x)
 #pragma unroll
     for (int off = 32; off >= 1; off >>= 1) x += __shfl_xor(x, off, 64);
     return x;
+}
+
+// One pair, one wave: its mask row, the user's block and the dish's row; n = sum of the mask (:77).
+struct PairRows {
+    const float *m, *urow, *drow;
+    float n;
+};
+
+__device__ __forceinline__ PairRows pair_rows(const TrainArgs &p, int64_t b, int64_t ul, int32_t did)
+{
+    PairRows r = {p.cats + (size_t)b * p.C, p.pm + (size_t)ul * (p.C + 1) * p.E, p.re + (size_t)did * p.E, 0.f};
+    for (int c = 0; c < p.C; ++c) r.n += r.m[c];                                    // :77
+    return r;
+}
+
+// Model.inference for the pair (:56-97): every lane returns the score.
+__device__ __forceinline__ float pair_forward(const TrainArgs &p, const PairRows &r, const int lane)
+{
+    const int C = p.C, E = p.E;
+    float hi = 0.f, lo = 0.f;
+    for (int e = lane; e < E; e += 64) {
+        float H = 0.f, L = 0.f;
+        for (int c = 0; c < C; ++c) {
+            H = fmaf(r.m[c], p.ce[(size_t)c * E + e], H);                           // :67-75
+            L = fmaf(r.m[c], r.urow[(size_t)(1 + c) * E + e], L);                   // :82-90
+        }
+        hi = fmaf(r.urow[e], H, hi);
+        lo = fmaf(r.drow[e], L, lo);
+    }
+    hi = wave_sum(hi);
+    lo = wave_sum(lo);
+    return m2d_blend_unfused(p.a, hi / r.n, p.b, lo / r.n);        // :79, :93, :95-96
+}
+
+// The pair's loss term and gradient rows from its score s and label y: the rows are float-atomic-added into the compact rows gu / gd
+// (p.accumulate), dCE goes to this wave's LDS copy `dce` (ce_lds) or through atomics to p.gce; the loss term and the wave's sum
+// of squares of the per-pair values join loss_acc / sq_acc.
+__device__ __forceinline__ void pair_grad(const TrainArgs &p, const PairRows &r, const float s, const float y, const float invB,
+                                          float *gu, float *gd, float *dce, const bool ce_lds, const int lane,
+                                          double &loss_acc, double &sq_acc)
+{
+    const int C = p.C, E = p.E;
+    const float *m = r.m;
+    const float loss_b = fmaxf(s, 0.f) - s * y + log1pf(expf(-fabsf(s)));           // :101
+    const float gs = (1.0f / (1.0f + expf(-s)) - y) * invB;                         // d mean / d s_b
+    const float qh = gs * p.a / r.n, ql = gs * p.b / r.n;
+    float sq = 0.f;
+    for (int e = lane; e < E; e += 64) {
+        float H = 0.f, L = 0.f;
+        for (int c = 0; c < C; ++c) {
+            H = fmaf(m[c], p.ce[(size_t)c * E + e], H);
+            L = fmaf(m[c], r.urow[(size_t)(1 + c) * E + e], L);
+        }
+        const float uh = r.urow[e], it = r.drow[e];
+        const float v0 = qh * H, vd = ql * L;
+        sq = fmaf(v0, v0, sq);
+        sq = fmaf(vd, vd, sq);
+        if (p.accumulate) {
+            atomicAdd(gu + e, v0);
+            atomicAdd(gd + e, vd);
+        }
+        for (int c = 0; c < C; ++c) {
+            const float vc = (ql * m[c]) * it;
+            sq = fmaf(vc, vc, sq);
+            // a zero mask entry contributes an exact zero (unless RE holds inf / NaN -- not reproduced)
+            if (p.accumulate && m[c] != 0.f) atomicAdd(gu + (size_t)(1 + c) * E + e, vc);
+            const float w = (qh * m[c]) * uh;
+            if (ce_lds) dce[c * E + e] += w;                                        // this lane owns column e
+            else if (m[c] != 0.f) atomicAdd(p.gce + (size_t)c * E + e, w);
+        }
+    }
+    sq_acc += (double)wave_sum(sq);
+    loss_acc += (double)loss_b;
 }
 
 __global__ __launch_bounds__(256) void m2d_train_claim(TrainArgs p)
@@ -120,63 +198,13 @@ __global__ __launch_bounds__(256) void m2d_train_grad(TrainArgs p, int ce_lds)
         const int32_t uid = p.users[b], did = p.items[b];
         const int64_t ul = (int64_t)uid - p.user_base;
         if (ul < 0 || ul >= p.U || did < 0 || (int64_t)did >= p.I) {      // latched by the claim pass / below
-            if (!p.accumulate && lane == 0)
-                m2d_latch_error(p.err, (ul < 0 || ul >= p.U) ? M2D_ERR_BAD_USER_ID : M2D_ERR_BAD_ITEM_ID,
-                            (ul < 0 || ul >= p.U) ? uid : did, b);
+            if (!p.accumulate && lane == 0) m2d_latch_bad_pair(p.err, ul, p.U, uid, did, b);
             continue;
         }
-        const float *m = p.cats + (size_t)b * C;
-        const float *urow = p.pm + (size_t)ul * (C + 1) * E;
-        const float *drow = p.re + (size_t)did * E;
-        float n = 0.f;
-        for (int c = 0; c < C; ++c) n += m[c];                                      // :77
-        float hi = 0.f, lo = 0.f;
-        for (int e = lane; e < E; e += 64) {
-            float H = 0.f, L = 0.f;
-            for (int c = 0; c < C; ++c) {
-                H = fmaf(m[c], p.ce[(size_t)c * E + e], H);                         // :67-75
-                L = fmaf(m[c], urow[(size_t)(1 + c) * E + e], L);                   // :82-90
-            }
-            hi = fmaf(urow[e], H, hi);
-            lo = fmaf(drow[e], L, lo);
-        }
-        hi = wave_sum(hi);
-        lo = wave_sum(lo);
-        const float s = m2d_blend_unfused(p.a, hi / n, p.b, lo / n);  // :79, :93, :95-96
-        const float y = p.labels[b];
-        const float loss_b = fmaxf(s, 0.f) - s * y + log1pf(expf(-fabsf(s)));       // :101
-        const float gs = (1.0f / (1.0f + expf(-s)) - y) * invB;                     // d mean / d s_b
-        const float qh = gs * p.a / n, ql = gs * p.b / n;
+        const PairRows r = pair_rows(p, b, ul, did);
+        const float s = pair_forward(p, r, lane);
         const int su = p.accumulate ? p.map_u[ul] : 0, sd = p.accumulate ? p.map_d[did] : 0;
-        float *gu = p.gu + (size_t)su * (C + 1) * E;
-        float *gd = p.gd + (size_t)sd * E;
-        float sq = 0.f;
-        for (int e = lane; e < E; e += 64) {
-            float H = 0.f, L = 0.f;
-            for (int c = 0; c < C; ++c) {
-                H = fmaf(m[c], p.ce[(size_t)c * E + e], H);
-                L = fmaf(m[c], urow[(size_t)(1 + c) * E + e], L);
-            }
-            const float uh = urow[e], it = drow[e];
-            const float v0 = qh * H, vd = ql * L;
-            sq = fmaf(v0, v0, sq);
-            sq = fmaf(vd, vd, sq);
-            if (p.accumulate) {
-                atomicAdd(gu + e, v0);
-                atomicAdd(gd + e, vd);
-            }
-            for (int c = 0; c < C; ++c) {
-                const float vc = (ql * m[c]) * it;
-                sq = fmaf(vc, vc, sq);
-                // a zero mask entry contributes an exact zero (unless RE holds inf / NaN -- not reproduced)
-                if (p.accumulate && m[c] != 0.f) atomicAdd(gu + (size_t)(1 + c) * E + e, vc);
-                const float w = (qh * m[c]) * uh;
-                if (ce_lds) dce[c * E + e] += w;                                    // this lane owns column e
-                else if (m[c] != 0.f) atomicAdd(p.gce + (size_t)c * E + e, w);
-            }
-        }
-        sq_acc += (double)wave_sum(sq);
-        loss_acc += (double)loss_b;
+        pair_grad(p, r, s, p.labels[b], invB, p.gu + (size_t)su * (C + 1) * E, p.gd + (size_t)sd * E, dce, ce_lds != 0, lane, loss_acc, sq_acc);
     }
     __shared__ double wave_acc[4][2];
     if (lane == 0) { wave_acc[wv][0] = loss_acc; wave_acc[wv][1] = sq_acc; }
@@ -278,9 +306,7 @@ __device__ __forceinline__ void apply_one(const RuleArgs &r, float g, float &var
     }
 }
 
-// Rows of one table.  ALL = true (Adam): every row r < R, gradient row map[r] when >= 0, else zero.
-// ALL = false: claimed rows only, r = slot_row[s] for s < *count.  map == nullptr: dense gradient (row r of G).
-// W floats per row; a wave walks a row 64 (x4 when W % 4 == 0) floats at a time.
+// a lane's VEC floats: float or v4f, so that one row body serves both widths
 template <int VEC> struct RowVec;
 template <> struct RowVec<1> { typedef float T; };
 template <> struct RowVec<4> { typedef v4f T; };
@@ -289,13 +315,42 @@ __device__ __forceinline__ float lane_get(const float &v, int) { return v; }
 __device__ __forceinline__ void lane_set(v4f &v, int j, float x) { v[j] = x; }
 __device__ __forceinline__ void lane_set(float &v, int, float x) { v = x; }
 
+// One row of W floats, one wave, 64 x VEC floats at a time: the row starts at `base` of var / s0 / s1, g is its gradient row (null: zero).
+// fin gathers x * 0 over the values written: NaN iff one of them is inf / NaN.
+template <int VEC>
+__device__ __forceinline__ void apply_row(const RuleArgs &r, float *var, float *s0, float *s1, const size_t base, const float *g,
+                                          const int W, const float scale, const int lane, float &fin)
+{
+    typedef typename RowVec<VEC>::T vf;
+    const bool two = r.rule == M2D_LEARNER_ADAM || r.rule == M2D_LEARNER_RMSPROP, one = two || r.rule == M2D_LEARNER_ADAGRAD;
+    for (int e = lane * VEC; e < W; e += 64 * VEC) {
+        vf v = *reinterpret_cast<const vf *>(var + base + e);
+        vf a = vf(0.f), b = vf(0.f), gg = vf(0.f);
+        if (one) a = *reinterpret_cast<const vf *>(s0 + base + e);
+        if (two) b = *reinterpret_cast<const vf *>(s1 + base + e);
+        if (g) gg = *reinterpret_cast<const vf *>(g + e) * scale;
+#pragma unroll
+        for (int j = 0; j < VEC; ++j) {
+            float vv = lane_get(v, j), aa = lane_get(a, j), bb = lane_get(b, j);
+            apply_one(r, lane_get(gg, j), vv, aa, bb);
+            fin = fmaf(vv, 0.f, fin);
+            lane_set(v, j, vv); lane_set(a, j, aa); lane_set(b, j, bb);
+        }
+        *reinterpret_cast<vf *>(var + base + e) = v;
+        if (one) *reinterpret_cast<vf *>(s0 + base + e) = a;
+        if (two) *reinterpret_cast<vf *>(s1 + base + e) = b;
+    }
+}
+
+// Rows of one table.  ALL = true (Adam): every row r < R, gradient row map[r] when >= 0, else zero.
+// ALL = false: claimed rows only, r = slot_row[s] for s < *count.  map == nullptr: dense gradient (row r of G).
+// W floats per row; a wave walks a row 64 (x4 when W % 4 == 0) floats at a time.
 template <bool ALL, int VEC>
 __global__ __launch_bounds__(256) void m2d_train_apply(float *var, float *s0, float *s1, const float *G, const int32_t *map,
                                                        const int32_t *slot_row, const int32_t *count, int64_t R, int32_t W,
                                                        const float *scal, RuleArgs r, const int32_t *err, const OptState *st,
                                                        int32_t *nonfinite)
 {
-    typedef typename RowVec<VEC>::T vf;
     if (err[0] != 0) return;    // an id was out of range: like TF's InvalidArgumentError, the step applies nothing
     if (r.rule == M2D_LEARNER_ADAM) {                                     // AdamOptimizer._apply_dense; kept wave-uniform (SGPRs)
         const float b1p = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, st->b1p)));
@@ -307,31 +362,12 @@ __global__ __launch_bounds__(256) void m2d_train_apply(float *var, float *s0, fl
     const int64_t nwaves = (int64_t)gridDim.x * 4;
     const float scale = scal[2];
     const int64_t n = ALL ? R : (int64_t)*count;
-    const bool two = r.rule == M2D_LEARNER_ADAM || r.rule == M2D_LEARNER_RMSPROP, one = two || r.rule == M2D_LEARNER_ADAGRAD;
-    float fin = 0.f;                // x * 0 summed over the values written: NaN iff one of them is inf / NaN
+    float fin = 0.f;
     for (int64_t i = wave0; i < n; i += nwaves) {
         int64_t row, grow;
         if (ALL) { row = i; grow = map ? (int64_t)map[i] : i; }
         else { row = slot_row[i]; grow = i; }
-        const size_t base = (size_t)row * W;
-        const float *g = grow >= 0 ? G + (size_t)grow * W : nullptr;
-        for (int e = lane * VEC; e < W; e += 64 * VEC) {
-            vf v = *reinterpret_cast<const vf *>(var + base + e);
-            vf a = vf(0.f), b = vf(0.f), gg = vf(0.f);
-            if (one) a = *reinterpret_cast<const vf *>(s0 + base + e);
-            if (two) b = *reinterpret_cast<const vf *>(s1 + base + e);
-            if (g) gg = *reinterpret_cast<const vf *>(g + e) * scale;
-#pragma unroll
-            for (int j = 0; j < VEC; ++j) {
-                float vv = lane_get(v, j), aa = lane_get(a, j), bb = lane_get(b, j);
-                apply_one(r, lane_get(gg, j), vv, aa, bb);
-                fin = fmaf(vv, 0.f, fin);
-                lane_set(v, j, vv); lane_set(a, j, aa); lane_set(b, j, bb);
-            }
-            *reinterpret_cast<vf *>(var + base + e) = v;
-            if (one) *reinterpret_cast<vf *>(s0 + base + e) = a;
-            if (two) *reinterpret_cast<vf *>(s1 + base + e) = b;
-        }
+        apply_row<VEC>(r, var, s0, s1, (size_t)row * W, grow >= 0 ? G + (size_t)grow * W : nullptr, W, scale, lane, fin);
     }
     // a diverged run: the forward kernels stop leaving out the rows of weight-0 categories (0 * inf = NaN, :82)
     if (fin != fin) *nonfinite = 1;
@@ -375,9 +411,7 @@ __global__ __launch_bounds__(256) void m2d_train_grad_fused(TrainArgs p)
         const int32_t uid = p.users[b], did = p.items[b];
         const int64_t ul = (int64_t)uid - p.user_base;
         if (ul < 0 || ul >= p.U || did < 0 || (int64_t)did >= p.I) {      // TF raises from the gather: the step applies nothing
-            if (lane == 0)
-                m2d_latch_error(p.err, (ul < 0 || ul >= p.U) ? M2D_ERR_BAD_USER_ID : M2D_ERR_BAD_ITEM_ID,
-                            (ul < 0 || ul >= p.U) ? uid : did, b);
+            if (lane == 0) m2d_latch_bad_pair(p.err, ul, p.U, uid, did, b);
             continue;
         }
         // The pair's two claims go out together (lane 0: the user's slot, lane 1: the dish's) and are looked at only after the
@@ -388,24 +422,8 @@ __global__ __launch_bounds__(256) void m2d_train_grad_fused(TrainArgs p)
         int seen = 0;
         if (claimer) seen = atomicCAS(&cmap[crow], -1, -2);
         const float y = p.labels[b];
-        const float *m = p.cats + (size_t)b * C;
-        const float *urow = p.pm + (size_t)ul * (C + 1) * E;
-        const float *drow = p.re + (size_t)did * E;
-        float n = 0.f;
-        for (int c = 0; c < C; ++c) n += m[c];                                      // :77
-        float hi = 0.f, lo = 0.f;
-        for (int e = lane; e < E; e += 64) {
-            float H = 0.f, L = 0.f;
-            for (int c = 0; c < C; ++c) {
-                H = fmaf(m[c], p.ce[(size_t)c * E + e], H);                         // :67-75
-                L = fmaf(m[c], urow[(size_t)(1 + c) * E + e], L);                   // :82-90
-            }
-            hi = fmaf(urow[e], H, hi);
-            lo = fmaf(drow[e], L, lo);
-        }
-        hi = wave_sum(hi);
-        lo = wave_sum(lo);
-        const float s = m2d_blend_unfused(p.a, hi / n, p.b, lo / n);  // :79, :93, :95-96
+        const PairRows r = pair_rows(p, b, ul, did);
+        const float s = pair_forward(p, r, lane);
         // -1: the row was free and this lane numbers it; anything else: the number, once it is there.  Two statements, in this
         // order, not the two arms of one `if`: a wave whose lane 0 numbers a row while its lane 1 waits for another wave's
         // number must publish BEFORE it waits -- with the arms in the other order two such waves, each holding the row the
@@ -423,35 +441,8 @@ __global__ __launch_bounds__(256) void m2d_train_grad_fused(TrainArgs p)
         if (claimer && seen != -1)
             while (slot < 0) slot = __hip_atomic_load(&cmap[crow], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         const int su = __builtin_amdgcn_readlane(slot, 0), sd = __builtin_amdgcn_readlane(slot, 1);
-        const float loss_b = fmaxf(s, 0.f) - s * y + log1pf(expf(-fabsf(s)));       // :101
-        const float gs = (1.0f / (1.0f + expf(-s)) - y) * invB;                     // d mean / d s_b
-        const float qh = gs * p.a / n, ql = gs * p.b / n;
-        float *gu = p.gu + (size_t)su * (C + 1) * E;
-        float *gd = p.gd + (size_t)sd * E;
-        float sq = 0.f;
-        for (int e = lane; e < E; e += 64) {
-            float H = 0.f, L = 0.f;
-            for (int c = 0; c < C; ++c) {
-                H = fmaf(m[c], p.ce[(size_t)c * E + e], H);
-                L = fmaf(m[c], urow[(size_t)(1 + c) * E + e], L);
-            }
-            const float uh = urow[e], it = drow[e];
-            const float v0 = qh * H, vd = ql * L;
-            sq = fmaf(v0, v0, sq);
-            sq = fmaf(vd, vd, sq);
-            if (p.accumulate) {
-                atomicAdd(gu + e, v0);
-                atomicAdd(gd + e, vd);
-            }
-            for (int c = 0; c < C; ++c) {
-                const float vc = (ql * m[c]) * it;
-                sq = fmaf(vc, vc, sq);
-                if (p.accumulate && m[c] != 0.f) atomicAdd(gu + (size_t)(1 + c) * E + e, vc);
-                dce[c * E + e] += (qh * m[c]) * uh;                                 // this lane owns column e
-            }
-        }
-        sq_acc += (double)wave_sum(sq);
-        loss_acc += (double)loss_b;
+        // (true: the global-atomics arm folds away)
+        pair_grad(p, r, s, y, invB, p.gu + (size_t)su * (C + 1) * E, p.gd + (size_t)sd * E, dce, true, lane, loss_acc, sq_acc);
     }
     __shared__ double wave_acc[4][2];
     __shared__ int s_ticket;
@@ -539,7 +530,6 @@ __global__ __launch_bounds__(256) void m2d_train_apply_fused(ApplyArgs p)
     RuleArgs r = p.r;
     const float scale = p.scal[2];
     r.lr = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, p.scal[4])));   // Adam: lr_t of this step
-    const bool two = r.rule == M2D_LEARNER_ADAM || r.rule == M2D_LEARNER_RMSPROP, one = two || r.rule == M2D_LEARNER_ADAGRAD;
     float fin = 0.f;
     int64_t n[3], tot = 0;
 #pragma unroll
@@ -560,33 +550,9 @@ __global__ __launch_bounds__(256) void m2d_train_apply_fused(ApplyArgs p)
         // rows of whole, 16-B aligned float4 (every embedding size that is a multiple of 4; the caller's table may start anywhere)
         const bool vec = (W & 3) == 0 && (reinterpret_cast<uintptr_t>(tb.var) & 15) == 0;
         if (ok && (g || r.rule == M2D_LEARNER_ADAM)) {     // Adam decays and moves every row; the others touch rows with a gradient
-            if (vec) {                                      // 16 B per lane: the dense Adam pass is a stream over var / m / v
-                for (int e = lane * 4; e < W; e += 256) {
-                    v4f v = *reinterpret_cast<const v4f *>(tb.var + base + e), a = v4f(0.f), b = v4f(0.f), gg = v4f(0.f);
-                    if (one) a = *reinterpret_cast<const v4f *>(tb.s0 + base + e);
-                    if (two) b = *reinterpret_cast<const v4f *>(tb.s1 + base + e);
-                    if (g) gg = *reinterpret_cast<const v4f *>(g + e) * scale;
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) {
-                        float vv = v[j], aa = a[j], bb = b[j];
-                        apply_one(r, gg[j], vv, aa, bb);
-                        fin = fmaf(vv, 0.f, fin);
-                        v[j] = vv; a[j] = aa; b[j] = bb;
-                    }
-                    *reinterpret_cast<v4f *>(tb.var + base + e) = v;
-                    if (one) *reinterpret_cast<v4f *>(tb.s0 + base + e) = a;
-                    if (two) *reinterpret_cast<v4f *>(tb.s1 + base + e) = b;
-                }
-            } else {
-                for (int e = lane; e < W; e += 64) {
-                    float v = tb.var[base + e], a = one ? tb.s0[base + e] : 0.f, b = two ? tb.s1[base + e] : 0.f;
-                    apply_one(r, g ? g[e] * scale : 0.f, v, a, b);
-                    fin = fmaf(v, 0.f, fin);
-                    tb.var[base + e] = v;
-                    if (one) tb.s0[base + e] = a;
-                    if (two) tb.s1[base + e] = b;
-                }
-            }
+            // 16 B per lane where it can: the dense Adam pass is a stream over var / m / v
+            if (vec) apply_row<4>(r, tb.var, tb.s0, tb.s1, base, g, W, scale, lane, fin);
+            else apply_row<1>(r, tb.var, tb.s0, tb.s1, base, g, W, scale, lane, fin);
         }
         if (g && (tb.map || t == 2)) {                      // release: the gradient row back to zero, the slot back to free
             if (vec) { for (int e = lane * 4; e < W; e += 256) *reinterpret_cast<v4f *>(g + e) = v4f(0.f); }
@@ -605,15 +571,6 @@ __global__ __launch_bounds__(256) void m2d_fill_kernel(float *x, int64_t n, floa
 __global__ __launch_bounds__(256) void m2d_fill_i32_kernel(int32_t *x, int64_t n, int32_t v)
 {
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) x[i] = v;
-}
-
-unsigned blocks_for(const m2d_engine *h, int64_t waves)
-{
-    int64_t b = (waves + 3) / 4;
-    const int64_t cap = (int64_t)h->num_cu * 8;
-    if (b > cap) b = cap;
-    if (b < 1) b = 1;
-    return (unsigned)b;
 }
 
 }  // namespace
@@ -652,19 +609,19 @@ int m2d_train_setup(m2d_engine *h, int32_t learner, float lr, float clip_norm, h
     m2d_train_state *t = new m2d_train_state;
     h->train = t;
     t->learner = learner; t->lr = lr; t->clip = clip_norm;
-    const int64_t n[3] = {h->U * (int64_t)(h->C + 1) * h->E, h->I * (int64_t)h->E, (int64_t)h->C * h->E};
+    const int64_t n[3] = {m2d_table_floats(h, 0), m2d_table_floats(h, 1), m2d_table_floats(h, 2)};
     const int nslots = (learner == M2D_LEARNER_ADAM || learner == M2D_LEARNER_RMSPROP) ? 2 : learner == M2D_LEARNER_ADAGRAD ? 1 : 0;
     for (int tb = 0; tb < 3; ++tb)
         for (int s = 0; s < nslots; ++s) {
             M2D_HIP_TRY(h, hipMalloc((void **)&t->slot[tb][s], (size_t)n[tb] * 4));
             // slot initial values: adam m = v = 0; adagrad accumulator 0.1; rmsprop rms = 1, momentum = 0
             const float v0 = learner == M2D_LEARNER_ADAGRAD ? 0.1f : (learner == M2D_LEARNER_RMSPROP && s == 0) ? 1.0f : 0.0f;
-            hipLaunchKernelGGL(m2d_fill_kernel, dim3(blocks_for(h, n[tb] / 64 + 1)), dim3(256), 0, stream, t->slot[tb][s], n[tb], v0);
+            hipLaunchKernelGGL(m2d_fill_kernel, dim3(m2d_blocks_for(h, n[tb] / 64 + 1, 4)), dim3(256), 0, stream, t->slot[tb][s], n[tb], v0);
         }
     M2D_HIP_TRY(h, hipMalloc((void **)&t->map_u, (size_t)h->U * 4));
     M2D_HIP_TRY(h, hipMalloc((void **)&t->map_d, (size_t)h->I * 4));
-    hipLaunchKernelGGL(m2d_fill_i32_kernel, dim3(blocks_for(h, h->U / 64 + 1)), dim3(256), 0, stream, t->map_u, h->U, -1);
-    hipLaunchKernelGGL(m2d_fill_i32_kernel, dim3(blocks_for(h, h->I / 64 + 1)), dim3(256), 0, stream, t->map_d, h->I, -1);
+    hipLaunchKernelGGL(m2d_fill_i32_kernel, dim3(m2d_blocks_for(h, h->U / 64 + 1, 4)), dim3(256), 0, stream, t->map_u, h->U, -1);
+    hipLaunchKernelGGL(m2d_fill_i32_kernel, dim3(m2d_blocks_for(h, h->I / 64 + 1, 4)), dim3(256), 0, stream, t->map_d, h->I, -1);
     M2D_HIP_TRY(h, hipMalloc((void **)&t->cnt, 4 * 4));                 // two pairs: the fused form alternates between them
     M2D_HIP_TRY(h, hipMemsetAsync(t->cnt, 0, 16, stream));
     M2D_HIP_TRY(h, hipMalloc((void **)&t->done, 4));
@@ -683,72 +640,92 @@ int m2d_train_setup(m2d_engine *h, int32_t learner, float lr, float clip_norm, h
     return M2D_OK;
 }
 
-int m2d_launch_train_step(m2d_engine *h, const int32_t *users, const int32_t *items, const float *cats, const float *labels,
-                          int64_t B, int32_t apply, float *out, hipStream_t stream)
+namespace {
+
+// compact gradient rows: at most one per pair.  The four blocks share one capacity, which counts again once all of them hold B pairs.
+int grow_compact(m2d_engine *h, m2d_train_state *t, int64_t B, hipStream_t stream)
 {
-    m2d_train_state *t = h->train;
-    const int C = h->C, E = h->E, W = (C + 1) * E;
-    if (apply && B > t->cap) {          // compact gradient rows: at most one per pair
-        M2D_HIP_TRY(h, hipStreamSynchronize(stream));
-        for (void *q : {(void *)t->slot_u, (void *)t->slot_d, (void *)t->gu, (void *)t->gd})
-            if (q) (void)hipFree(q);
-        t->slot_u = t->slot_d = nullptr; t->gu = t->gd = nullptr;
-        M2D_HIP_TRY(h, hipMalloc((void **)&t->slot_u, (size_t)B * 4));
-        M2D_HIP_TRY(h, hipMalloc((void **)&t->slot_d, (size_t)B * 4));
-        M2D_HIP_TRY(h, hipMalloc((void **)&t->gu, (size_t)B * W * 4));
-        M2D_HIP_TRY(h, hipMalloc((void **)&t->gd, (size_t)B * E * 4));
-        M2D_HIP_TRY(h, hipMemsetAsync(t->gu, 0, (size_t)B * W * 4, stream));
-        M2D_HIP_TRY(h, hipMemsetAsync(t->gd, 0, (size_t)B * E * 4, stream));
-        t->cap = B;
-    }
+    if (B <= t->cap) return M2D_OK;
+    const size_t W = (size_t)(h->C + 1) * h->E, E = (size_t)h->E;
+    M2D_HIP_TRY(h, hipStreamSynchronize(stream));      // steps in flight use the blocks about to be freed
+    t->cap = 0;
+    auto grow = [&](auto *&buf, size_t unit) { int64_t held = 0; return m2d_grow(h, buf, held, (size_t)B, unit); };   // (frees what buf holds)
+    int rc;
+    if ((rc = grow(t->slot_u, 4)) != M2D_OK || (rc = grow(t->slot_d, 4)) != M2D_OK || (rc = grow(t->gu, W * 4)) != M2D_OK ||
+        (rc = grow(t->gd, E * 4)) != M2D_OK)
+        return rc;
+    M2D_HIP_TRY(h, hipMemsetAsync(t->gu, 0, (size_t)B * W * 4, stream));
+    M2D_HIP_TRY(h, hipMemsetAsync(t->gd, 0, (size_t)B * E * 4, stream));
+    t->cap = B;
+    return M2D_OK;
+}
+
+TrainArgs train_args(const m2d_engine *h, const m2d_train_state *t, const int32_t *users, const int32_t *items, const float *cats,
+                     const float *labels, int64_t B, int32_t apply, float *out)
+{
     TrainArgs a;
     a.pm = const_cast<float *>(h->pm); a.re = const_cast<float *>(h->re); a.ce = const_cast<float *>(h->ce);
     a.users = users; a.items = items; a.cats = cats; a.labels = labels;
-    a.B = B; a.U = h->U; a.I = h->I; a.user_base = h->user_base; a.C = C; a.E = E; a.a = h->a; a.b = h->b;
+    a.B = B; a.U = h->U; a.I = h->I; a.user_base = h->user_base; a.C = h->C; a.E = h->E; a.a = h->a; a.b = h->b;
     a.map_u = t->map_u; a.map_d = t->map_d; a.slot_u = t->slot_u; a.slot_d = t->slot_d; a.cnt = t->cnt;
     a.gu = t->gu; a.gd = t->gd; a.gce = t->gce; a.scal = t->scal; a.err = h->err_dev;
     a.accumulate = apply ? 1 : 0; a.clip = t->clip; a.lr = t->lr;      // Global_Step never moves (:240): lr is constant
     a.done = t->done; a.out = out; a.opt = t->opt; a.learner = t->learner; a.parity = t->parity;
     a.part_ce = t->part_ce; a.part_acc = t->part_acc;
-    const size_t lds_f = (size_t)4 * C * E * 4;
-    if (B <= 1024 && lds_f <= 48 * 1024 && h->opt_variant != 14) {     // the fused form ("variant" = 14: the nine-launch form, A/B)
-        a.nblocks = (int32_t)blocks_for(h, B);
-        hipLaunchKernelGGL(m2d_train_grad_fused, dim3((unsigned)a.nblocks), dim3(256), lds_f, stream, a);
-        M2D_HIP_TRY(h, hipGetLastError());
-        h->last_kernel = "m2d_train_grad_fused";
-        if (!apply) return M2D_OK;
-        ApplyArgs ap;
-        const bool adam = t->learner == M2D_LEARNER_ADAM;
-        int32_t *cnt = t->cnt + 2 * t->parity;
-        ap.t[0] = {a.pm, t->slot[0][0], t->slot[0][1], t->gu, t->map_u, t->slot_u, cnt + 0, h->U, W, adam ? 1 : 0};
-        ap.t[1] = {a.re, t->slot[1][0], t->slot[1][1], t->gd, t->map_d, t->slot_d, cnt + 1, h->I, E, adam ? 1 : 0};
-        ap.t[2] = {a.ce, t->slot[2][0], t->slot[2][1], t->gce, nullptr, nullptr, nullptr, C, E, 1};
-        ap.scal = t->scal; ap.err = h->err_dev; ap.nonfinite = h->nonfinite_dev;
-        ap.r.rule = t->learner; ap.r.lr = t->lr; ap.r.b1 = ap.r.b2 = ap.r.eps = 0.f;
-        if (adam) { ap.r.b1 = 0.9f; ap.r.b2 = 0.999f; ap.r.eps = 1e-8f; }
-        else if (t->learner == M2D_LEARNER_RMSPROP) { ap.r.b1 = 0.9f; ap.r.b2 = 0.0f; ap.r.eps = 1e-10f; }
-        const int64_t rows = adam ? h->U + h->I + C : 2 * B + C;
-        hipLaunchKernelGGL(m2d_train_apply_fused, dim3(blocks_for(h, rows)), dim3(256), 0, stream, ap);
-        M2D_HIP_TRY(h, hipGetLastError());
-        t->parity ^= 1;
-        h->dish_vec_valid = false;      // everything derived from the tables is stale now
-        h->grp_valid = false;
-        h->grp_nonfinite_known = false; // (a step may set the "not finite" word: retrieval reads it again, whatever kernel it takes)
-        h->user_high_valid = false;
-        return M2D_OK;
-    }
-    int32_t *cnt_now = t->cnt + 2 * t->parity;              // (the fused form may have left the other pair in use)
-    a.cnt = cnt_now;
-    M2D_HIP_TRY(h, hipMemsetAsync(cnt_now, 0, 8, stream));
+    a.nblocks = (int32_t)m2d_blocks_for(h, B, 4);          // grid of either grad kernel: one wave per pair
+    return a;
+}
+
+// the learner's constants (TF 1.x defaults, as Model.train constructs the optimizers, :228-235)
+RuleArgs rule_args(const m2d_train_state *t)
+{
+    RuleArgs r = {t->learner, t->lr, 0.f, 0.f, 0.f};
+    if (t->learner == M2D_LEARNER_ADAM) { r.b1 = 0.9f; r.b2 = 0.999f; r.eps = 1e-8f; }
+    else if (t->learner == M2D_LEARNER_RMSPROP) { r.b1 = 0.9f; r.b2 = 0.0f; r.eps = 1e-10f; }
+    return r;
+}
+
+// The three tables as the apply pass sees them, in the order PM, RE, CE (cnt: this step's pair of slot counters).  Adam walks
+// every row; so does the dense Category_Embedding gradient, which has no map.
+void apply_tabs(const m2d_engine *h, const m2d_train_state *t, const int32_t *cnt, ApplyTab tb[3])
+{
+    const int32_t all = t->learner == M2D_LEARNER_ADAM, W = (h->C + 1) * h->E;
+    tb[0] = {const_cast<float *>(h->pm), t->slot[0][0], t->slot[0][1], t->gu, t->map_u, t->slot_u, cnt + 0, h->U, W, all};
+    tb[1] = {const_cast<float *>(h->re), t->slot[1][0], t->slot[1][1], t->gd, t->map_d, t->slot_d, cnt + 1, h->I, h->E, all};
+    tb[2] = {const_cast<float *>(h->ce), t->slot[2][0], t->slot[2][1], t->gce, nullptr, nullptr, nullptr, h->C, h->E, 1};
+}
+
+// two launches (batches of up to 1024 pairs whose dCE fits in LDS four times)
+int train_step_fused(m2d_engine *h, const TrainArgs &a, size_t lds, hipStream_t stream)
+{
+    m2d_train_state *t = h->train;
+    hipLaunchKernelGGL(m2d_train_grad_fused, dim3((unsigned)a.nblocks), dim3(256), lds, stream, a);
+    M2D_HIP_TRY(h, hipGetLastError());
+    h->last_kernel = "m2d_train_grad_fused";
+    if (!a.accumulate) return M2D_OK;
+    ApplyArgs ap;
+    apply_tabs(h, t, t->cnt + 2 * t->parity, ap.t);
+    ap.scal = t->scal; ap.err = h->err_dev; ap.nonfinite = h->nonfinite_dev; ap.r = rule_args(t);
+    const int64_t rows = ap.t[0].all ? h->U + h->I + h->C : 2 * a.B + h->C;
+    hipLaunchKernelGGL(m2d_train_apply_fused, dim3(m2d_blocks_for(h, rows, 4)), dim3(256), 0, stream, ap);
+    M2D_HIP_TRY(h, hipGetLastError());
+    t->parity ^= 1;
+    return M2D_OK;
+}
+
+// nine launches (any batch; "variant" = 14 keeps it for small ones too, A/B)
+int train_step_staged(m2d_engine *h, TrainArgs a, size_t lds, hipStream_t stream)
+{
+    m2d_train_state *t = h->train;
+    const int C = h->C, E = h->E;
+    a.cnt = t->cnt + 2 * t->parity;                         // (the fused form may have left the other pair in use)
+    M2D_HIP_TRY(h, hipMemsetAsync(a.cnt, 0, 8, stream));
     M2D_HIP_TRY(h, hipMemsetAsync(t->gce, 0, (size_t)C * E * 4, stream));
-    if (apply) {
-        hipLaunchKernelGGL(m2d_train_claim, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, stream, a);
+    if (a.accumulate) {
+        hipLaunchKernelGGL(m2d_train_claim, dim3((unsigned)((a.B + 255) / 256)), dim3(256), 0, stream, a);
         M2D_HIP_TRY(h, hipGetLastError());
     }
-    const size_t lds = (size_t)4 * C * E * 4;
     const int ce_lds = lds <= 48 * 1024;
-    a.part_ce = t->part_ce; a.part_acc = t->part_acc;
-    a.nblocks = (int32_t)blocks_for(h, B);
     hipLaunchKernelGGL(m2d_train_grad, dim3((unsigned)a.nblocks), dim3(256), ce_lds ? lds : 0, stream, a, ce_lds);
     M2D_HIP_TRY(h, hipGetLastError());
     if (ce_lds) {
@@ -758,51 +735,50 @@ int m2d_launch_train_step(m2d_engine *h, const int32_t *users, const int32_t *it
     }
     hipLaunchKernelGGL(m2d_train_finalize, dim3(1), dim3(256), 0, stream, a);
     M2D_HIP_TRY(h, hipGetLastError());
-    if (out) M2D_HIP_TRY(h, hipMemcpyAsync(out, t->scal, 16, hipMemcpyDeviceToDevice, stream));
+    if (a.out) M2D_HIP_TRY(h, hipMemcpyAsync(a.out, t->scal, 16, hipMemcpyDeviceToDevice, stream));
     h->last_kernel = "m2d_train_grad";
-    if (!apply) {
+    if (!a.accumulate) {
         M2D_HIP_TRY(h, hipMemsetAsync(t->gce, 0, (size_t)C * E * 4, stream));   // (the fused form expects the dense gradient at zero)
         return M2D_OK;
     }
-
-    RuleArgs r;
-    r.rule = t->learner; r.lr = t->lr; r.b1 = r.b2 = r.eps = 0.f;
-    if (t->learner == M2D_LEARNER_ADAM) {
-        r.b1 = 0.9f; r.b2 = 0.999f; r.eps = 1e-8f;
-    } else if (t->learner == M2D_LEARNER_RMSPROP) {
-        r.b1 = 0.9f; r.b2 = 0.0f; r.eps = 1e-10f;
-    }
-    struct Tab { float *var; float *G; int32_t *map; int32_t *slot_row; int32_t *count; int64_t R; int32_t W; int idx; };
-    const Tab tabs[3] = {{a.pm, t->gu, t->map_u, t->slot_u, a.cnt + 0, h->U, W, 0},
-                         {a.re, t->gd, t->map_d, t->slot_d, a.cnt + 1, h->I, E, 1},
-                         {a.ce, t->gce, nullptr, nullptr, nullptr, C, E, 2}};
-    for (const Tab &tb : tabs) {
-        float *s0 = t->slot[tb.idx][0], *s1 = t->slot[tb.idx][1];
-        const bool all = t->learner == M2D_LEARNER_ADAM || !tb.map;       // dense gradient: every row
-        const int64_t rows = all ? tb.R : B;
-        const unsigned grid = blocks_for(h, rows);
+    const RuleArgs r = rule_args(t);
+    ApplyTab tabs[3];
+    apply_tabs(h, t, a.cnt, tabs);
+    for (const ApplyTab &tb : tabs) {
+        const unsigned grid = m2d_blocks_for(h, tb.all ? tb.R : a.B, 4);
         const bool v4 = tb.W % 4 == 0;
-#define M2D_APPLY(ALL, VEC)                                                                                               \
-    hipLaunchKernelGGL((m2d_train_apply<ALL, VEC>), dim3(grid), dim3(256), 0, stream, tb.var, s0, s1, tb.G, tb.map, tb.slot_row, \
+#define M2D_APPLY(ALL, VEC)                                                                                                        \
+    hipLaunchKernelGGL((m2d_train_apply<ALL, VEC>), dim3(grid), dim3(256), 0, stream, tb.var, tb.s0, tb.s1, tb.G, tb.map, tb.slot_row, \
                        tb.count, tb.R, tb.W, t->scal, r, h->err_dev, t->opt, h->nonfinite_dev)
-        if (all) { if (v4) M2D_APPLY(true, 4); else M2D_APPLY(true, 1); }
+        if (tb.all) { if (v4) M2D_APPLY(true, 4); else M2D_APPLY(true, 1); }
         else { if (v4) M2D_APPLY(false, 4); else M2D_APPLY(false, 1); }
 #undef M2D_APPLY
         M2D_HIP_TRY(h, hipGetLastError());
     }
-    hipLaunchKernelGGL(m2d_train_cleanup, dim3(blocks_for(h, B)), dim3(256), 0, stream, t->map_u, t->slot_u, a.cnt + 0, t->gu, W,
-                       h->err_dev, (OptState *)nullptr);
-    hipLaunchKernelGGL(m2d_train_cleanup, dim3(blocks_for(h, B)), dim3(256), 0, stream, t->map_d, t->slot_d, a.cnt + 1, t->gd, E,
-                       h->err_dev, t->opt);               // also advances the step count / beta powers if the step applied
+    for (int i = 0; i < 2; ++i)     // the second one also advances the step count / beta powers if the step applied
+        hipLaunchKernelGGL(m2d_train_cleanup, dim3((unsigned)a.nblocks), dim3(256), 0, stream, tabs[i].map, tabs[i].slot_row, tabs[i].count,
+                           tabs[i].G, tabs[i].W, h->err_dev, i == 1 ? t->opt : (OptState *)nullptr);
     M2D_HIP_TRY(h, hipGetLastError());
-    M2D_HIP_TRY(h, hipMemsetAsync(cnt_now, 0, 8, stream));   // the fused form expects its slot counters ...
+    M2D_HIP_TRY(h, hipMemsetAsync(a.cnt, 0, 8, stream));   // the fused form expects its slot counters ...
     M2D_HIP_TRY(h, hipMemsetAsync(t->gce, 0, (size_t)C * E * 4, stream));   // ... and the dense gradient at zero
-    // everything derived from Recipe_Embedding / Category_Embedding is stale now
-    h->dish_vec_valid = false;
-    h->grp_valid = false;
-    h->grp_nonfinite_known = false;
-    h->user_high_valid = false;
     return M2D_OK;
+}
+
+}  // namespace
+
+int m2d_launch_train_step(m2d_engine *h, const int32_t *users, const int32_t *items, const float *cats, const float *labels,
+                          int64_t B, int32_t apply, float *out, hipStream_t stream)
+{
+    m2d_train_state *t = h->train;
+    int rc = apply ? grow_compact(h, t, B, stream) : M2D_OK;
+    if (rc != M2D_OK) return rc;
+    const TrainArgs a = train_args(h, t, users, items, cats, labels, B, apply, out);
+    const size_t lds = (size_t)4 * h->C * h->E * 4;        // dCE once per wave of a grad block
+    if (B <= 1024 && lds <= 48 * 1024 && h->opt_variant != 14) rc = train_step_fused(h, a, lds, stream);
+    else rc = train_step_staged(h, a, lds, stream);
+    // a step may also set the "not finite" word: retrieval reads it again, whatever kernel it takes
+    if (rc == M2D_OK && apply) m2d_mark_written(h, M2D_TAB_PM | M2D_TAB_RE | M2D_TAB_CE, M2D_BY_ENGINE);
+    return rc;
 }
 
 // steps applied so far; setting it (checkpoint resume) also replays Adam's beta-power products, which TF keeps as
@@ -827,8 +803,7 @@ int m2d_train_step_count(m2d_engine *h, int64_t *steps, int32_t set)
 int m2d_train_get_slot(m2d_engine *h, int32_t table, int32_t slot, float **dev, int64_t *count)
 {
     m2d_train_state *t = h->train;
-    const int64_t n[3] = {h->U * (int64_t)(h->C + 1) * h->E, h->I * (int64_t)h->E, (int64_t)h->C * h->E};
     *dev = t->slot[table][slot];
-    *count = *dev ? n[table] : 0;
+    *count = *dev ? m2d_table_floats(h, table) : 0;
     return M2D_OK;
 }

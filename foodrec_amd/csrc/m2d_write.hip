@@ -137,7 +137,7 @@ __global__ __launch_bounds__(256) void m2d_write_gm_gather(WriteArgs p)
         const int64_t ul = (int64_t)uid - p.user_base;
         const bool bad = ul < 0 || ul >= p.U || did < 0 || (int64_t)did >= p.I;
         if (LATCH && wv == 0 && in && bad)
-            m2d_latch_error(p.err, (ul < 0 || ul >= p.U) ? M2D_ERR_BAD_USER_ID : M2D_ERR_BAD_ITEM_ID, (ul < 0 || ul >= p.U) ? uid : did, bi);
+            m2d_latch_bad_pair(p.err, ul, p.U, uid, did, bi);
         const float yw = (in && !bad) ? p.labels[(size_t)bi * L + l] : 0.f;   // nothing is written for a bad pair
         for (unsigned long long bits = __ballot(yw != 0.f); bits; bits &= bits - 1) {            // in batch order
             const int i = __builtin_ctzll(bits);
@@ -177,10 +177,8 @@ int m2d_launch_write_memory(m2d_engine *h, const int32_t *users, const int32_t *
                             const float *sign, const float *labels, int64_t B, int32_t L, float *gm, float beta_1,
                             float beta_2, float alpha, int32_t which, double *out_sums, hipStream_t stream)
 {
-    if (which & M2D_WRITE_PERSONAL) {
-        h->user_high_valid = false;                             // Personal_Memory is about to change
-        h->grp_nonfinite_known = false;                         // ... and may receive inf / NaN: retrieval reads the device word again
-    }
+    // Personal_Memory is about to change, and may receive inf / NaN: retrieval reads the device word again
+    if (which & M2D_WRITE_PERSONAL) m2d_mark_written(h, M2D_TAB_PM, M2D_BY_ENGINE);
     WriteArgs a;
     a.pm = const_cast<float *>(h->pm); a.re = h->re; a.ce = h->ce; a.gm = gm;
     a.users = users; a.items = items; a.cats = cats; a.sign = sign; a.labels = labels;
@@ -191,12 +189,11 @@ int m2d_launch_write_memory(m2d_engine *h, const int32_t *users, const int32_t *
             const int rc = m2d_ensure_finite_scan(h, stream);
             if (rc != M2D_OK) return rc;
         }
-        int64_t blocks = (B + 3) / 4;
-        if (blocks > (int64_t)h->num_cu * 8) blocks = (int64_t)h->num_cu * 8;
+        const unsigned blocks = m2d_blocks_for(h, B, 4);
         // each pass runs only when its assign is fetched (`personal` -> :167/:198, `general` -> :215); a GM-only call
         // still validates the ids (the gathers at :107 / one_hot at :149 are shared by both branches)
         if (which & M2D_WRITE_PERSONAL) {
-            hipLaunchKernelGGL(m2d_write_memory_kernel<0>, dim3((unsigned)blocks), dim3(256), 0, stream, a);
+            hipLaunchKernelGGL(m2d_write_memory_kernel<0>, dim3(blocks), dim3(256), 0, stream, a);
             M2D_HIP_TRY(h, hipGetLastError());
             // the blocks just added into: an inf / NaN there ends the forward kernels' row skipping (0 * inf = NaN, :82)
             const int rc = m2d_launch_rows_finite_check(h, users, B, stream);
@@ -209,9 +206,9 @@ int m2d_launch_write_memory(m2d_engine *h, const int32_t *users, const int32_t *
                 if (which & M2D_WRITE_PERSONAL) hipLaunchKernelGGL(m2d_write_gm_gather<false>, g2, dim3(256), 0, stream, a);
                 else hipLaunchKernelGGL(m2d_write_gm_gather<true>, g2, dim3(256), 0, stream, a);
             } else if (which & M2D_WRITE_PERSONAL)
-                hipLaunchKernelGGL(m2d_write_memory_kernel<1>, dim3((unsigned)blocks), dim3(256), 0, stream, a);
+                hipLaunchKernelGGL(m2d_write_memory_kernel<1>, dim3(blocks), dim3(256), 0, stream, a);
             else
-                hipLaunchKernelGGL(m2d_write_memory_kernel<2>, dim3((unsigned)blocks), dim3(256), 0, stream, a);
+                hipLaunchKernelGGL(m2d_write_memory_kernel<2>, dim3(blocks), dim3(256), 0, stream, a);
             M2D_HIP_TRY(h, hipGetLastError());
         }
     }
