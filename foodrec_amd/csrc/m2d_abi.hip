@@ -144,6 +144,9 @@ void release(m2d_engine *h)
     if (h->rank_buf) (void)hipFree(h->rank_buf);
     if (h->rank_tnorm) (void)hipFree(h->rank_tnorm);
     if (h->excl_buf) (void)hipFree(h->excl_buf);
+    if (h->topk_mlp_ids) (void)hipFree(h->topk_mlp_ids);
+    if (h->topk_mlp_scores) (void)hipFree(h->topk_mlp_scores);
+    if (h->topk_mlp_cand) (void)hipFree(h->topk_mlp_cand);
     if (h->err_dev) (void)hipFree(h->err_dev);
     if (h->err_host) (void)hipHostFree(h->err_host);
 }
@@ -691,6 +694,38 @@ int m2d_score_pairs_mlp(m2d_engine *h, const int32_t *users, const int32_t *item
     return m2d_launch_score_pairs_mlp(h, users, items, B, out, (hipStream_t)stream);
 }
 
+int m2d_topk_users_mlp(m2d_engine *h, const int32_t *users, int64_t nU, int32_t k, int32_t candidates, float *out_scores,
+                       int32_t *out_ids, void *stream)
+{
+    if (!h) return M2D_ERR_INVALID_ARG;
+    if (nU < 0 || k < 1 || k > 64 || (int64_t)k > h->I)
+        return fail(h, M2D_ERR_INVALID_ARG, "m2d_topk_users_mlp: need nU >= 0 and 1 <= k <= min(64, I)");
+    if (candidates != 0 && (candidates < k || candidates > 64 || (int64_t)candidates > h->I))
+        return fail(h, M2D_ERR_INVALID_ARG, "m2d_topk_users_mlp: candidates must be 0 (exact) or k <= candidates <= min(64, I)");
+    if (nU == 0) return M2D_OK;
+    if (!users || !out_scores || !out_ids) return fail(h, M2D_ERR_INVALID_ARG, "m2d_topk_users_mlp: null buffer");
+    if (!h->mlp_w1) return fail(h, M2D_ERR_NOT_CONFIGURED, "call m2d_set_mlp_head first");
+    if (!h->dish_cats) return fail(h, M2D_ERR_NOT_CONFIGURED, "call m2d_set_dish_categories first");
+    M2D_HIP_TRY(h, hipSetDevice(h->device));
+    return m2d_launch_topk_users_mlp(h, users, nU, k, candidates, out_scores, out_ids, (hipStream_t)stream);
+}
+
+int m2d_rank_candidates_mlp(m2d_engine *h, const int32_t *users, const int32_t *items, const int32_t *lens, int64_t nseg, int32_t L,
+                            int32_t k, float *out_scores, int32_t *out_items, int32_t *out_flags, void *stream)
+{
+    if (!h) return M2D_ERR_INVALID_ARG;
+    if (nseg < 0 || L < 1 || L > 1024 || k < 1 || k > 64)
+        return fail(h, M2D_ERR_INVALID_ARG, "m2d_rank_candidates_mlp: need nseg >= 0, 1 <= L <= 1024, 1 <= k <= 64");
+    if (nseg == 0) return M2D_OK;
+    if (!users || !items || !out_scores || !out_items || !out_flags)
+        return fail(h, M2D_ERR_INVALID_ARG, "m2d_rank_candidates_mlp: null buffer");
+    if (!h->mlp_w1) return fail(h, M2D_ERR_NOT_CONFIGURED, "call m2d_set_mlp_head first");
+    if (!h->dish_cats) return fail(h, M2D_ERR_NOT_CONFIGURED, "call m2d_set_dish_categories first");
+    M2D_HIP_TRY(h, hipSetDevice(h->device));
+    return m2d_launch_rank_candidates(h, users, items, lens, nseg, L, k, out_scores, out_items, out_flags, (hipStream_t)stream,
+                                      /*head=*/true);
+}
+
 int m2d_train_begin(m2d_engine *h, int32_t learner, float lr, float clip_norm, void *stream)
 {
     if (!h) return M2D_ERR_INVALID_ARG;
@@ -806,6 +841,10 @@ int m2d_set_option(m2d_engine *h, const char *name, int64_t value)
     else if (!strcmp(name, "topk_refine")) h->opt_topk_refine = (int)value;
     else if (!strcmp(name, "topk_grouped")) h->opt_topk_grouped = (int)value;
     else if (!strcmp(name, "topk_excl_tier")) h->opt_topk_excl_tier = (int)value;
+    else if (!strcmp(name, "topk_mlp_chunk_pairs")) {
+        if (value < 256 || value > (1 << 24)) return fail(h, M2D_ERR_INVALID_ARG, "m2d_set_option: topk_mlp_chunk_pairs takes 256 ... 2^24");
+        h->opt_topk_mlp_chunk_pairs = value;
+    }
     else if (!strcmp(name, "mlp_bf16x3")) h->opt_mlp_bf16x3 = (int)value;
     else if (!strcmp(name, "mlp_form")) h->opt_mlp_form = (int)value;
     else if (!strcmp(name, "skip_masked")) h->opt_skip_masked = (int)value;
@@ -881,6 +920,8 @@ int m2d_get_option(const m2d_engine *h, const char *name, int64_t *value)
         }
     }
     else if (!strcmp(name, "topk_grouped")) *value = h->opt_topk_grouped;
+    else if (!strcmp(name, "topk_mlp_chunk_pairs")) *value = h->opt_topk_mlp_chunk_pairs;
+    else if (!strcmp(name, "topk_mlp_launches")) *value = h->topk_mlp_launches;
     else if (!strcmp(name, "mlp_bf16x3")) *value = h->opt_mlp_bf16x3;
     else if (!strcmp(name, "mlp_form")) *value = h->opt_mlp_form;
     else if (!strcmp(name, "skip_masked")) *value = h->opt_skip_masked;

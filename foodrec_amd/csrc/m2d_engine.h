@@ -67,6 +67,15 @@ struct m2d_engine {
     uint64_t mlp_pat8_gen = 0;          // the dish-vector build it belongs to (dish_vec_gen)
     size_t mlp_pg_cap = 0;              // ints
 
+    // m2d_topk_users_mlp (m2d_topk_mlp.hip): a chunk's pair ids (users | items), its head scores and, in the two-stage form, stage 1's
+    // candidate ids -- buffers of their own: stage 1 writes `scratch`, the head's pair grouping writes mlp_pg
+    int32_t *topk_mlp_ids = nullptr;
+    float *topk_mlp_scores = nullptr;
+    int32_t *topk_mlp_cand = nullptr;
+    size_t topk_mlp_ids_cap = 0, topk_mlp_scores_cap = 0, topk_mlp_cand_cap = 0;   // ints / floats / ints
+    int64_t opt_topk_mlp_chunk_pairs = 1 << 22;   // pairs per head launch of that call (diagnostic: the lists do not depend on it)
+    int64_t topk_mlp_launches = 0;                // head launches of the last call
+
     // derived table for pair scoring: <U_high[u], CE_c> per user and category (built lazily by large m2d_score_pairs calls;
     // stale after any write to Personal_Memory / Category_Embedding: the engine's own writers and m2d_tables_updated reset it)
     float *user_high = nullptr;  // [U, 4]
@@ -347,7 +356,9 @@ int m2d_launch_score_pairs_mlp(m2d_engine *h, const int32_t *users, const int32_
 void m2d_mlp_free_derived(m2d_engine *h, bool grouping);
 int m2d_launch_rank_candidates(m2d_engine *h, const int32_t *users, const int32_t *items,
                                const int32_t *lens, int64_t nseg, int32_t L, int32_t k, float *out_scores,
-                               int32_t *out_items, int32_t *out_flags, hipStream_t stream);
+                               int32_t *out_items, int32_t *out_flags, hipStream_t stream, bool head = false);
+int m2d_launch_topk_users_mlp(m2d_engine *h, const int32_t *users, int64_t nU, int32_t k, int32_t candidates, float *out_scores,
+                              int32_t *out_ids, hipStream_t stream);
 int m2d_launch_topk_users(m2d_engine *h, const int32_t *users, int64_t nU, int32_t k, float *out_scores,
                           int32_t *out_ids, hipStream_t stream);
 int m2d_launch_catalogue_rank(m2d_engine *h, const int32_t *users, const int32_t *items, int64_t n, const int64_t *excl_off,

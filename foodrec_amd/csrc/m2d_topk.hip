@@ -104,7 +104,7 @@ __global__ __launch_bounds__(RANK_WAVES * 64) void m2d_rank_segments(
 
 int m2d_launch_rank_candidates(m2d_engine *h, const int32_t *users, const int32_t *items,
                                const int32_t *lens, int64_t nseg, int32_t L, int32_t k, float *out_scores,
-                               int32_t *out_items, int32_t *out_flags, hipStream_t stream)
+                               int32_t *out_items, int32_t *out_flags, hipStream_t stream, bool head)
 {
     if (nseg == 0) return M2D_OK;
     const int64_t total = nseg * (int64_t)L;
@@ -120,7 +120,9 @@ int m2d_launch_rank_candidates(m2d_engine *h, const int32_t *users, const int32_
     hipLaunchKernelGGL(m2d_expand_segments, dim3((unsigned)eb), dim3(256), 0, stream, users, items, lens, nseg,
                        L, users_x, items_x);
     M2D_HIP_TRY(h, hipGetLastError());
-    rc = m2d_launch_score_pairs(h, users_x, items_x, h->dish_cats, /*by_dish=*/true, total, scores, stream);
+    // `head`: the segment scores are the 3-layer head's (m2d_rank_candidates_mlp; it writes neither this scratch nor the outputs)
+    rc = head ? m2d_launch_score_pairs_mlp(h, users_x, items_x, total, scores, stream)
+              : m2d_launch_score_pairs(h, users_x, items_x, h->dish_cats, /*by_dish=*/true, total, scores, stream);
     if (rc != M2D_OK) return rc;
     const int64_t rb = (nseg + RANK_WAVES - 1) / RANK_WAVES;
     const size_t lds = (size_t)RANK_WAVES * 3 * L * 4;

@@ -390,8 +390,9 @@ class ScoringEngine:
         return out
 
     def rank_candidates(self, users: torch.Tensor, items: torch.Tensor, k: int,
-                        lens: Optional[torch.Tensor] = None):
-        """users i32[nseg], items i32[nseg, L] -> (scores f32[nseg, k], items i32[nseg, k], flags i32[nseg])."""
+                        lens: Optional[torch.Tensor] = None, head: bool = False):
+        """users i32[nseg], items i32[nseg, L] -> (scores f32[nseg, k], items i32[nseg, k], flags i32[nseg]).
+        `head`: the segments are scored under the MLP head (``m2d_rank_candidates_mlp``; needs ``set_mlp_head``)."""
         if items.dim() != 2 or users.numel() != items.shape[0]:
             raise ValueError("rank_candidates: items must be [nseg, L] with one user per row")
         self._check_ids(users, items)
@@ -403,9 +404,9 @@ class ScoringEngine:
         out_i = torch.empty((nseg, k), dtype=torch.int32, device=self.device)
         out_f = torch.empty((nseg,), dtype=torch.int32, device=self.device)
         with torch.cuda.device(self.device):
-            rc = _native.lib().m2d_rank_candidates(self._h, users.data_ptr(), items.data_ptr(),
-                                                   lens.data_ptr() if lens is not None else None, nseg, L, k,
-                                                   out_s.data_ptr(), out_i.data_ptr(), out_f.data_ptr(), _stream_ptr())
+            fn = _native.lib().m2d_rank_candidates_mlp if head else _native.lib().m2d_rank_candidates
+            rc = fn(self._h, users.data_ptr(), items.data_ptr(), lens.data_ptr() if lens is not None else None, nseg, L, k,
+                    out_s.data_ptr(), out_i.data_ptr(), out_f.data_ptr(), _stream_ptr())
         _native.raise_for(rc, self._h)
         return out_s, out_i, out_f
 
@@ -430,6 +431,23 @@ class ScoringEngine:
             rc = _native.lib().m2d_topk_users(self._h, users.data_ptr(), nU, k, out_s.data_ptr(), out_i.data_ptr(),
                                               _stream_ptr())
         _native.raise_for(rc, self._h)
+        return out_s, out_i
+
+    def topk_users_mlp(self, users: torch.Tensor, k: int, candidates: int = 0):
+        """``topk_users`` under the MLP head (``m2d_topk_users_mlp``, include/m2d.h): users i32[nU] -> (scores f32[nU, k],
+        dish ids i32[nU, k]).  ``candidates`` = 0: every dish is scored under the head (exact); K1 = ``candidates`` >= k: the K1
+        best by the reference score (``topk_users``) are reranked under the head.  Does not synchronise."""
+        if users.dtype != torch.int32 or users.device != self.device:
+            raise TypeError("topk_users_mlp: users must be an int32 tensor on %s" % self.device)
+        users = users.contiguous()
+        nU, k, candidates = users.numel(), int(k), int(candidates)
+        out_s = torch.empty((nU, max(k, 0)), dtype=torch.float32, device=self.device)
+        out_i = torch.empty((nU, max(k, 0)), dtype=torch.int32, device=self.device)
+        with torch.cuda.device(self.device):
+            rc = _native.lib().m2d_topk_users_mlp(self._h, users.data_ptr(), nU, k, candidates, out_s.data_ptr(), out_i.data_ptr(),
+                                                  _stream_ptr())
+        _native.raise_for(rc, self._h)
+        self._topk_mlp_keep = users                      # stays alive until the queued kernels have read it
         return out_s, out_i
 
     def catalogue_rank(self, users, items, exclude=None):
@@ -574,6 +592,17 @@ def topk_users_op(engine: int, users: torch.Tensor, k: int) -> tuple[torch.Tenso
 
 @topk_users_op.register_fake
 def _(engine, users, k):
+    return (users.new_empty((users.numel(), k), dtype=torch.float32),
+            users.new_empty((users.numel(), k), dtype=torch.int32))
+
+
+@torch.library.custom_op("m2d::topk_users_mlp", mutates_args=(), device_types="cuda")
+def topk_users_mlp_op(engine: int, users: torch.Tensor, k: int, candidates: int = 0) -> tuple[torch.Tensor, torch.Tensor]:
+    return _engine(engine).topk_users_mlp(users, k, candidates)
+
+
+@topk_users_mlp_op.register_fake
+def _(engine, users, k, candidates=0):
     return (users.new_empty((users.numel(), k), dtype=torch.float32),
             users.new_empty((users.numel(), k), dtype=torch.int32))
 

@@ -333,7 +333,7 @@ class Model:
 
 
     # -- retrieval and build-defined extensions (no reference counterpart; DESIGN.md sections 4.3-4.4, 8) ---
-    def topk(self, users, k: int = 10, exclude=None):
+    def topk(self, users, k: int = 10, exclude=None, head: bool = False, candidates: int = 0):
         """The k best dishes of every user in `users` over the whole catalogue -- the ranking rule of
         evaluate.py:63 applied to all dishes instead of 51 candidates.  Needs `set_dish_categories`.
         Returns (scores float32 [n, k], dish ids int32 [n, k]).
@@ -341,7 +341,15 @@ class Model:
         `exclude` leaves out dishes per user (the ones already had): a dict such as ``Dataset.trainMatrix`` keyed by the user as
         given in `users` (a missing key excludes nothing), or a list aligned with `users`.  The lists are then those
         ``evaluate_model_full`` measures (``ScoringEngine.topk_users_excluding``: k <= 16; rows end in id -1 / NaN when fewer than k
-        dishes remain).  None: the unfiltered lists, as before."""
+        dishes remain).  None: the unfiltered lists, as before.
+
+        EXTENSION, `head=True`: the lists under the MLP head (`set_mlp_head`), the score `predict_extended(head=True)` returns --
+        `candidates` = 0 scores every dish under the head, K1 = `candidates` >= k reranks the K1 best by the reference score
+        (``ScoringEngine.topk_users_mlp``).  Exclusions under the head are not served: `head=True` with `exclude` raises."""
+        if head and exclude is not None:
+            raise ValueError("topk: head=True together with exclude is not supported (exclusions under the MLP head)")
+        if candidates and not head:
+            raise ValueError("topk: candidates is the head's rerank width; it needs head=True")
         if exclude is not None:
             from .ops import topk_excluding_args
             if isinstance(exclude, dict):
@@ -353,6 +361,8 @@ class Model:
         ut = u.to(self.device, torch.int32) if isinstance(u, torch.Tensor) else torch.from_numpy(u).to(self.device)
         if exclude is not None:
             s, i = self.engine.topk_users_excluding(ut, int(k), (torch.from_numpy(off).to(self.device), torch.from_numpy(ids).to(self.device)))
+        elif head:
+            s, i = torch.ops.m2d.topk_users_mlp(self.engine.id, ut, int(k), int(candidates))
         else:
             s, i = torch.ops.m2d.topk_users(self.engine.id, ut, int(k))
         self.engine.check()

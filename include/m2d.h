@@ -272,6 +272,32 @@ int m2d_clear_mlp_head(m2d_engine *h);
 int m2d_score_pairs_mlp(m2d_engine *h, const int32_t *users, const int32_t *items, int64_t B, float *out,
                         void *stream);
 
+/* Retrieval and candidate ranking under the head (build-defined, like the head).  The score of a (user, dish) pair is
+ * m2d_score_pairs_mlp's in every mode -- the head added to the reference score, masks from the resident dish table, the ingredient
+ * table feeding Dt's high-level part when it is set -- and every score comes from that call's launcher, whichever kernel family
+ * the shape selects.  The order is m2d_topk_users' applied to those scores: score descending, bit-equal scores and -0 / +0 to the
+ * lower dish id, NaN scores last (after every -inf) in id order.  (m2d_topk_users itself ignores the head, as before.)
+ *
+ * m2d_topk_users_mlp, candidates == 0 (exact): every dish of [0, I) is scored under the head for every listed user; the first k of
+ * the order go to out_ids i32[nU, k] / out_scores f32[nU, k].  1 <= k <= min(64, I).  The work runs in chunks of at most
+ * "topk_mlp_chunk_pairs" pairs (P): dish ranges of W = min(I, P) dishes, user blocks of max(1, P / W) rows; for each user block, for
+ * each dish range: the pairs are written, scored, and m2d_topk_mlp_select merges the range into the rows' running lists (kept in
+ * the output buffers).  The lists do not depend on P: same ids, same score bits.
+ * m2d_topk_users_mlp, k <= candidates <= min(64, I) (two-stage, K1 = candidates): stage 1 is m2d_topk_users as it runs with default
+ * options -- K1 dishes per user by the reference / ingredient score --, stage 2 scores those nU x K1 pairs under the head and returns
+ * the first k of the same order among them.  Any other `candidates`: M2D_ERR_INVALID_ARG.
+ * m2d_rank_candidates_mlp: m2d_rank_candidates with the segment scores taken from the head; dict collapse, tie order, padding and
+ * the NaN flag are that call's, unchanged.
+ * No head or no dish masks: M2D_ERR_NOT_CONFIGURED.  A bad user id is latched (m2d_check; the position reported is the pair's inside
+ * its chunk), that call's rows are unspecified and the engine stays usable.  m2d_set_user_base is honoured (ids stay global);
+ * users may repeat.  Neither call synchronises more than m2d_topk_users / m2d_score_pairs_mlp do; after the first call of a size
+ * they allocate only on growth.  Diagnostic: "topk_mlp_launches". */
+int m2d_topk_users_mlp(m2d_engine *h, const int32_t *users, int64_t nU, int32_t k, int32_t candidates,
+                       float *out_scores, int32_t *out_ids, void *stream);
+int m2d_rank_candidates_mlp(m2d_engine *h, const int32_t *users, const int32_t *items, const int32_t *lens,
+                            int64_t nseg, int32_t L, int32_t k, float *out_scores, int32_t *out_items,
+                            int32_t *out_flags, void *stream);
+
 /* Synchronise `stream` and report (then clear) the first id error latched by kernels since the
  * previous check: M2D_OK, M2D_ERR_BAD_USER_ID or M2D_ERR_BAD_ITEM_ID.  TF-CPU GatherV2 raises
  * InvalidArgument for such ids; the kernels never read out of bounds and write NaN for the pair.
@@ -331,6 +357,8 @@ int m2d_check(m2d_engine *h, void *stream, int64_t *bad_value, int64_t *bad_inde
  * topk_block       0        0 128 256    users per block of a pruned pipelined launch (0 = the launcher's choice)
  * topk_excl_tier   0        0 / 2        m2d_topk_users_excluding: 0 = m2d_topk_users' lists filtered where they are index-exact, the exact scan
  *                                        for the users left short and for every other case; 2 = the exact scan for every user.  Same ids, same score bits.
+ * topk_mlp_chunk_pairs  4194304  256 ... 2^24  m2d_topk_users_mlp: pairs per head launch (the --workload mlp batch by default); other values are
+ *                                        M2D_ERR_INVALID_ARG.  Same ids, same score bits.
  * variant          0        7 9 11 12 13 14 15 16, 100 + n
  *                                        7 / 9: retrieval on the dense MFMA kernel / on the one-block-per-user kernel; 9 also forces the generic pair
  *                                        and head kernels; 11 / 12: the pair kernel's throughput / latency form whatever the batch size; 13: tie
@@ -355,6 +383,9 @@ int m2d_check(m2d_engine *h, void *stream, int64_t *bad_value, int64_t *bad_inde
  * topk_excl_short          users sent to the exact scan: those the filter left with fewer than k dishes, or all of them
  * topk_excl_tiles_scanned  32-dish tiles the exact scan multiplied
  * (the "topk_*" diagnostics above then describe the call's internal m2d_topk_users retrieval, if its first tier ran)
+ *
+ * ---- read-only diagnostic of the last m2d_topk_users_mlp call (host counter, no synchronisation) --------------------------------------------
+ * topk_mlp_launches        head launches: user blocks x dish ranges (two-stage: user blocks; the "topk_*" diagnostics then describe stage 1)
  */
 int m2d_set_option(m2d_engine *h, const char *name, int64_t value);
 int m2d_get_option(const m2d_engine *h, const char *name, int64_t *value);
