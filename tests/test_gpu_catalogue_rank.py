@@ -5,7 +5,9 @@ import numpy as np
 import pytest
 import torch
 
-from helpers import COEFS, TOL
+from helpers import COEFS
+from seen_dish_cases import assert_rank_band, exact_tables as _exact_tables, host_rank as _host_rank, masks as _masks, \
+    normal_tables as _normal_tables, oracle_scores as _oracle_scores
 
 pytestmark = pytest.mark.gpu
 
@@ -17,52 +19,11 @@ def _engine(PM, RE, CE, cats, coef):
     return eng
 
 
-def _masks(rng, I, C=4, allowed=None):
-    if allowed is None:
-        m = rng.integers(0, 2, (I, C)).astype(np.float32)
-        z = m.sum(1) == 0
-        m[z, rng.integers(0, C, int(z.sum()))] = 1.0
-        return m
-    pats = np.asarray(allowed)
-    bits = pats[rng.integers(0, len(pats), I)]
-    return ((bits[:, None] >> np.arange(C)[None, :]) & 1).astype(np.float32)
-
-
-def _normal_tables(rng, U, I, E, C=4):
-    s = 1.0 / math.sqrt(E)
-    PM = (rng.standard_normal((U, C + 1, E)) * s).astype(np.float32)
-    RE = (rng.standard_normal((I, E)) * s).astype(np.float32)
-    CE = (rng.standard_normal((C, E)) * s).astype(np.float32)
-    return PM, RE, CE
-
-
 def _rank(eng, users, items, exclude=None):
     r, s = eng.catalogue_rank(torch.as_tensor(np.asarray(users, np.int32)).cuda(), torch.as_tensor(np.asarray(items, np.int32)).cuda(),
                               exclude)
     eng.check()
     return r.cpu().numpy(), s.cpu().numpy()
-
-
-def _oracle_scores(PM, RE, CE, cats, u, coef):
-    from oracle import m2d_oracle as oracle
-    I = RE.shape[0]
-    return oracle.inference_f64(PM, RE, CE, np.full(I, u, np.int32), np.arange(I, dtype=np.int32), cats, coef)
-
-
-def _host_rank(s64, p, excl=()):
-    """rank of p over d != p, d not in excl: score desc, NaN last, equal scores to the lower id"""
-    I = s64.size
-    d = np.arange(I)
-    keep = d != p
-    if len(excl):
-        keep[np.asarray(list(excl), dtype=np.int64)] = False
-        keep[p] = False
-    sp = s64[p]
-    if np.isnan(sp):
-        prec = ~np.isnan(s64) | (d < p)
-    else:
-        prec = (s64 > sp) | ((s64 == sp) & (d < p))
-    return int((prec & keep).sum())
 
 
 # 1. agreement with retrieval, as exact integers ----------------------------------------------------------------------------------------
@@ -101,23 +62,10 @@ def test_rank_within_oracle_band(E):
     items = rng.integers(0, I, 48)
     r, s = _rank(eng, users, items)
     for q in range(users.size):
-        s64 = _oracle_scores(PM, RE, CE, cats, int(users[q]), coef)
-        p = int(items[q])
-        sp = s64[p]
-        t = 1e-5 * max(1.0, abs(sp))
-        d = np.arange(I) != p
-        lo = int(((s64 > sp + t) & d).sum())
-        hi = int(((s64 >= sp - t) & d).sum())
-        assert lo <= r[q] <= hi, (q, lo, r[q], hi)
-        assert abs(float(s[q]) - sp) <= TOL * max(1.0, abs(sp)), (q, s[q], sp)
+        assert_rank_band(_oracle_scores(PM, RE, CE, cats, int(users[q]), coef), int(items[q]), r[q], s[q])
 
 
 # 3. exact-arithmetic tables: exact ranks; the two protocols agree ----------------------------------------------------------------------
-def _exact_tables(rng, U, I, E):
-    f = lambda shape: (rng.integers(-16, 17, shape) / 16.0).astype(np.float32)      # noqa: E731
-    return f((U, 5, E)), f((I, E)), f((4, E)), _masks(rng, I, allowed=[1, 2, 4, 8, 3, 5, 6, 9, 10, 12, 15])
-
-
 @pytest.mark.parametrize("E", [8, 32, 64])
 def test_exact_tables_exact_ranks(E):
     rng = np.random.default_rng(100 + E)

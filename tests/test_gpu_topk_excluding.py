@@ -10,7 +10,9 @@ import numpy as np
 import pytest
 import torch
 
-from helpers import COEFS, TOL
+from helpers import COEFS
+from seen_dish_cases import assert_list_band, exact_tables as _exact_tables, host_topk, masks as _masks, normal_tables as _normal_tables, \
+    oracle_scores as _oracle_scores, per_query_csr as _per_query_csr
 
 pytestmark = pytest.mark.gpu
 
@@ -20,42 +22,6 @@ def _engine(PM, RE, CE, cats, coef):
     eng = foodrec_amd.ScoringEngine(PM, RE, CE, coef=coef, device=torch.device("cuda", 0))
     eng.set_dish_categories(cats)
     return eng
-
-
-def _masks(rng, I, C=4, allowed=None):
-    if allowed is None:
-        m = rng.integers(0, 2, (I, C)).astype(np.float32)
-        z = m.sum(1) == 0
-        m[z, rng.integers(0, C, int(z.sum()))] = 1.0
-        return m
-    pats = np.asarray(allowed)
-    bits = pats[rng.integers(0, len(pats), I)]
-    return ((bits[:, None] >> np.arange(C)[None, :]) & 1).astype(np.float32)
-
-
-def _normal_tables(rng, U, I, E, C=4):
-    s = 1.0 / math.sqrt(E)
-    PM = (rng.standard_normal((U, C + 1, E)) * s).astype(np.float32)
-    RE = (rng.standard_normal((I, E)) * s).astype(np.float32)
-    CE = (rng.standard_normal((C, E)) * s).astype(np.float32)
-    return PM, RE, CE
-
-
-def _exact_tables(rng, U, I, E):
-    f = lambda shape: (rng.integers(-16, 17, shape) / 16.0).astype(np.float32)      # noqa: E731
-    return f((U, 5, E)), f((I, E)), f((4, E)), _masks(rng, I, allowed=[1, 2, 4, 8, 3, 5, 6, 9, 10, 12, 15])
-
-
-def _oracle_scores(PM, RE, CE, cats, u, coef):
-    from oracle import m2d_oracle as oracle
-    I = RE.shape[0]
-    return oracle.inference_f64(PM, RE, CE, np.full(I, u, np.int32), np.arange(I, dtype=np.int32), cats, coef)
-
-
-def host_topk(s64, k, excl):          # s64: oracle.inference_f64 over the whole catalogue for one user
-    keep = np.ones(s64.size, bool); keep[list(excl)] = False
-    d = np.flatnonzero(keep); key = np.where(np.isnan(s64[d]), -np.inf, s64[d])
-    return d[np.lexsort((d, -key))[:k]]
 
 
 def _users(U):
@@ -105,16 +71,6 @@ def _own_top_plus_random(eng, rng, U, I, jmod, nrand):
     rnd = rng.integers(0, I, (U, nrand))
     lists = [top[u, :u % jmod].tolist() + rnd[u].tolist() for u in range(U)]
     return exclusion_csr(lists, U)
-
-
-def _per_query_csr(off, ids, k):
-    """the CSR of U users -> the CSR of U k queries, user u's segment repeated for its k queries"""
-    lens = np.repeat(np.diff(off), k)
-    starts = np.repeat(off[:-1], k)
-    qoff = np.zeros(lens.size + 1, np.int64)
-    np.cumsum(lens, out=qoff[1:])
-    idx = np.repeat(starts - qoff[:-1], lens) + np.arange(qoff[-1])
-    return qoff, ids[idx]
 
 
 def _assert_rank_equals_position(eng, U, I, k, off, ids):
@@ -196,15 +152,7 @@ def test_lists_within_oracle_band(E):
     off, ids = _own_top_plus_random(eng, rng, U, I, 20, 20)
     sc, li = _topk_excl(eng, _users(U), k, (off, ids))
     for u in range(U):
-        s64 = _oracle_scores(PM, RE, CE, cats, u, coef)
-        ls = s64[li[u]]
-        t = 1e-5 * np.maximum(1.0, np.abs(ls))
-        assert (ls[1:] <= ls[:-1] + t[:-1]).all(), (u, ls)    # non-increasing within t
-        rest = np.ones(I, bool)
-        rest[ids[off[u]:off[u + 1]]] = False
-        rest[li[u]] = False
-        assert (s64[rest] <= ls[-1] + t[-1]).all(), (u, s64[rest].max(), ls[-1])
-        assert (np.abs(sc[u] - ls) <= TOL * np.maximum(1.0, np.abs(ls))).all(), (u, sc[u], ls)
+        assert_list_band(_oracle_scores(PM, RE, CE, cats, u, coef), ids[off[u]:off[u + 1]], li[u], sc[u])
 
 
 # 5. with no exclusions it is topk_users ----------------------------------------------------------------------------------------------
