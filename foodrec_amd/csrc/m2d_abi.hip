@@ -130,6 +130,7 @@ void release(m2d_engine *h)
     }
     m2d_mlp_free_derived(h, true);
     if (h->user_high) (void)hipFree(h->user_high);
+    if (h->pm_bf16) (void)hipFree(h->pm_bf16);
     if (h->dish_high) (void)hipFree(h->dish_high);
     if (h->own_ing) {
         if (h->ing) (void)hipFree((void *)h->ing);
@@ -228,13 +229,14 @@ int m2d_create(const float *pm, const float *re, const float *ce, int64_t U, int
         h->last_error = "m2d_create: device tables must be 16-byte aligned";
         return bail(M2D_ERR_INVALID_ARG);
     }
-    if (hipMalloc((void **)&h->err_dev, 8 * sizeof(int32_t)) != hipSuccess ||       // id-error latch [4] | non-finite word | pad
+    if (hipMalloc((void **)&h->err_dev, 8 * sizeof(int32_t)) != hipSuccess ||       // id-error latch [4] | non-finite word | the bf16 mirror's | pad
         hipMemset(h->err_dev, 0, 8 * sizeof(int32_t)) != hipSuccess ||
         hipHostMalloc((void **)&h->err_host, 4 * sizeof(int32_t)) != hipSuccess) {
         h->last_error = "m2d_create: could not allocate the error latch";
         return bail(M2D_ERR_HIP);
     }
     h->nonfinite_dev = h->err_dev + 4;
+    h->pm_bf16_nonfinite = h->err_dev + 5;
     h->finite_scan_pending = true;      // the first scoring call scans the tables on its stream
     *out = h;
     return M2D_OK;
@@ -761,6 +763,17 @@ int m2d_train_slot(m2d_engine *h, int32_t table, int32_t slot, float *buf, int32
     return M2D_OK;
 }
 
+int m2d_pm_bf16(m2d_engine *h, uint16_t *buf, void *stream)
+{
+    if (!h) return M2D_ERR_INVALID_ARG;
+    if (!buf) return fail(h, M2D_ERR_INVALID_ARG, "m2d_pm_bf16: null buffer");
+    M2D_HIP_TRY(h, hipSetDevice(h->device));
+    const int rc = m2d_ensure_pm_bf16(h, (hipStream_t)stream);
+    if (rc != M2D_OK) return rc;
+    M2D_HIP_TRY(h, hipMemcpyAsync(buf, h->pm_bf16, (size_t)m2d_table_floats(h, 0) * sizeof(uint16_t), hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    return M2D_OK;
+}
+
 int m2d_tables_updated(m2d_engine *h)
 {
     if (!h) return M2D_ERR_INVALID_ARG;
@@ -849,6 +862,10 @@ int m2d_set_option(m2d_engine *h, const char *name, int64_t value)
     else if (!strcmp(name, "mlp_form")) h->opt_mlp_form = (int)value;
     else if (!strcmp(name, "skip_masked")) h->opt_skip_masked = (int)value;
     else if (!strcmp(name, "user_high_table")) h->opt_user_high = (int)value;
+    else if (!strcmp(name, "pm_bf16")) {
+        if (value != 0 && value != 1) return fail(h, M2D_ERR_INVALID_ARG, "m2d_set_option: pm_bf16 takes 0 or 1");
+        h->opt_pm_bf16 = (int)value;
+    }
     else if (!strcmp(name, "host_zero_copy")) h->opt_host_zero_copy = (int)value;
     else return fail(h, M2D_ERR_INVALID_ARG, "m2d_set_option: unknown option");
     return M2D_OK;
@@ -926,6 +943,7 @@ int m2d_get_option(const m2d_engine *h, const char *name, int64_t *value)
     else if (!strcmp(name, "mlp_form")) *value = h->opt_mlp_form;
     else if (!strcmp(name, "skip_masked")) *value = h->opt_skip_masked;
     else if (!strcmp(name, "user_high_table")) *value = h->opt_user_high;
+    else if (!strcmp(name, "pm_bf16")) *value = h->opt_pm_bf16;
     else if (!strcmp(name, "host_zero_copy")) *value = h->opt_host_zero_copy;
     else if (!strcmp(name, "num_cu")) *value = h->num_cu;
     else if (!strcmp(name, "topk_repaired")) {

@@ -81,6 +81,14 @@ struct m2d_engine {
     float *user_high = nullptr;  // [U, 4]
     bool user_high_valid = false;
 
+    // serving mirror of Personal_Memory (option "pm_bf16"): its round-to-nearest-even bf16 image, rows indexed like the table's own
+    // (u - user_base); built lazily by m2d_ensure_pm_bf16, stale after any write to Personal_Memory.  Rounding can make an inf the
+    // f32 table does not hold, so the mirror has a non-finite word of its own: the builder sets it from what it writes, and the
+    // mirror kernels leave out weight-0 rows only while this word and nonfinite_dev are both 0
+    uint16_t *pm_bf16 = nullptr;          // [U, C+1, E]
+    bool pm_bf16_valid = false;
+    int32_t *pm_bf16_nonfinite = nullptr; // device word (inside err_dev's allocation)
+
     // factored dish vectors for catalogue retrieval (built lazily by m2d_topk_users)
     float *dish_vec = nullptr;  // [I_pad, (C+1)*E]
     int64_t dish_vec_rows = 0;
@@ -144,6 +152,7 @@ struct m2d_engine {
     int opt_blocks_per_cu = 8;
     int opt_variant = 0;
     int opt_user_high = 0;              // opt-in: batches of >= 2^18 pairs take the high-level sum from the derived <U_high, CE_c> table
+    int opt_pm_bf16 = 0;                // opt-in: the C = 4 pair kernels read Personal_Memory's rows from the bf16 mirror (any batch size)
     int opt_host_zero_copy = 2;         // m2d_score_pairs_host, <= 65536 pairs: 1 = the kernel reads / writes the pinned staging block itself,
                                         // 2 = and the host spins on a completion word in that block before falling back to a stream wait; 0 = staged copies
     int opt_skip_masked = 1;            // pair kernels: rows of categories with mask weight 0 are not fetched (their products are 0)
@@ -197,6 +206,7 @@ static inline unsigned m2d_blocks_for(const m2d_engine *h, int64_t items, int64_
 // What a write makes stale.  Every writer of something the derived state is built from says WHICH tables it wrote and what is
 // known about the new VALUES; the dependencies are here and nowhere else:
 //   user_high (<U_high, CE_c>)                                  hangs on Personal_Memory, Category_Embedding;
+//   pm_bf16 (the bf16 mirror) and its non-finite word           hang on Personal_Memory (rebuilt as a whole, word included);
 //   dish_vec and the sorted retrieval tables (grp_*)            hang on Recipe_Embedding, Category_Embedding, the dish masks and
 //                                                               the ingredient table (H[d] rides in the sorted rows);
 //   the non-finite word (nonfinite_dev)                         covers every table value and H[d]:
@@ -210,6 +220,7 @@ enum m2d_written_by { M2D_BY_ENGINE, M2D_BY_CALLER, M2D_NO_VALUES };
 static inline void m2d_mark_written(m2d_engine *h, unsigned tables, m2d_written_by who)
 {
     if (tables & (M2D_TAB_PM | M2D_TAB_CE)) h->user_high_valid = false;
+    if (tables & M2D_TAB_PM) h->pm_bf16_valid = false;
     if (tables & (M2D_TAB_RE | M2D_TAB_CE | M2D_TAB_MASKS | M2D_TAB_ING)) h->dish_vec_valid = h->grp_valid = false;
     if (who == M2D_BY_ENGINE) h->grp_nonfinite_known = false;
     if (who == M2D_BY_CALLER) h->finite_scan_pending = true;
@@ -333,11 +344,12 @@ static __device__ __forceinline__ void lds_dma16_b(const void *src, void *lds_ba
 // launchers (m2d_score.hip / m2d_topk.hip); all enqueue on `stream` and return a status
 int m2d_launch_score_pairs(m2d_engine *h, const int32_t *users, const int32_t *items, const float *cats,
                            bool by_dish, int64_t B, float *out, hipStream_t stream,
-                           bool use_ingredients = false);
+                           bool use_ingredients = false, bool may_use_mirror = true);   // false: exact f32 rows whatever "pm_bf16" says
 int m2d_ensure_finite_scan(m2d_engine *h, hipStream_t stream);   // m2d_abi.hip: runs the queued table scan, if any
 int m2d_launch_rows_finite_check(m2d_engine *h, const int32_t *users, int64_t B, hipStream_t stream);   // Personal_Memory rows of a batch
 int m2d_launch_build_dish_high(m2d_engine *h, hipStream_t stream);
 int m2d_ensure_user_high(m2d_engine *h, hipStream_t stream);
+int m2d_ensure_pm_bf16(m2d_engine *h, hipStream_t stream);
 int m2d_launch_check_csr(m2d_engine *h, hipStream_t stream);
 int m2d_ensure_dish_vectors(m2d_engine *h, hipStream_t stream);
 int m2d_launch_write_memory(m2d_engine *h, const int32_t *users, const int32_t *items, const float *cats,

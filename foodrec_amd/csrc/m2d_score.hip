@@ -41,13 +41,18 @@ struct ScoreArgs {
     int32_t skip_masked;   // do not fetch the Personal_Memory rows of categories whose mask weight is 0 (their products are 0)
     const int32_t *nonfinite;   // device word: some table value is inf / NaN -> 0 * row is not 0 (:82), every row is fetched
     const float *uh;       // [U, 4] derived table <U_high[u], CE_c> (m2d_build_user_high), or null: read U_high and multiply
+    const uint16_t *pmh;   // [U, C+1, E] bf16 mirror of Personal_Memory (m2d_build_pm_bf16), or null: the BF kernel forms read it instead of pm
+    const int32_t *nonfinite_bf;   // device word: some value of the mirror is inf / NaN (rounding makes inf of finite values)
 };
 
 // Rows of weight-0 categories may be left out only while every table value is finite: 0 * inf = NaN at
 // Model_Recommender.py:82-90.  One scalar load per wave (the word is set by the table scan / the engine's writers).
+template <bool BF = false>
 __device__ __forceinline__ bool skip_rows(const ScoreArgs &p)
 {
-    return p.skip_masked != 0 && __builtin_amdgcn_readfirstlane(*p.nonfinite) == 0;
+    bool skip = p.skip_masked != 0 && __builtin_amdgcn_readfirstlane(*p.nonfinite) == 0;
+    if constexpr (BF) skip = skip && __builtin_amdgcn_readfirstlane(*p.nonfinite_bf) == 0;   // the mirror's own word as well
+    return skip;
 }
 
 template <bool NT>
@@ -57,6 +62,28 @@ __device__ __forceinline__ v4f ld4(const v4f *p)
         return __builtin_nontemporal_load(p);
     else
         return *p;
+}
+
+// A lane's four columns of a Personal_Memory row as they are loaded: a float4, or in the mirror forms (BF) the four bf16 halves in
+// one 8-byte word, kept packed until they are used (the row buffers are half the registers) and widened by shifts, which is exact.
+typedef uint32_t v2u __attribute__((ext_vector_type(2)));
+template <bool BF> struct pm_row { typedef v4f type; };
+template <> struct pm_row<true> { typedef v2u type; };
+
+template <bool NT>
+__device__ __forceinline__ v2u ld4(const v2u *p)
+{
+    if constexpr (NT)
+        return __builtin_nontemporal_load(p);
+    else
+        return *p;
+}
+
+__device__ __forceinline__ v4f widen(const v4f &x) { return x; }
+__device__ __forceinline__ v4f widen(const v2u &w)
+{
+    return v4f{__builtin_bit_cast(float, w.x << 16), __builtin_bit_cast(float, w.x & 0xffff0000u),
+               __builtin_bit_cast(float, w.y << 16), __builtin_bit_cast(float, w.y & 0xffff0000u)};
 }
 
 __device__ __forceinline__ float dot4(const v4f &x, const v4f &y, float acc)
@@ -83,9 +110,13 @@ __device__ __forceinline__ float group_sum(float v)
 // HV (build-defined extension): the high-level operand sum_c m_c CE_c / n of
 // Model_Recommender.py:67-79 is replaced by a resident per-dish vector H[d] (the normalised multi-hot
 // ingredient sum), i.e. high = <U_high, H[d]>; the low-level path is unchanged.
-template <int LPP, int PF, bool BYDISH, bool NT, bool FULL, bool HV, bool UH = false>
+// BF (option "pm_bf16"): the Personal_Memory rows come from the bf16 mirror, 8 bytes per lane and row; everything after the load is
+// the same code, so the scores are the f32 form's on the rounded table, bit for bit.
+template <int LPP, int PF, bool BYDISH, bool NT, bool FULL, bool HV, bool UH = false, bool BF = false>
 __global__ __launch_bounds__(256) void m2d_score_pairs_c4(ScoreArgs p)
 {
+    static_assert(!(UH && BF), "the mirror forms read U_high from the mirror");
+    typedef typename pm_row<BF>::type row_t;
     constexpr int C = 4;
     const int lane = threadIdx.x & 63;
     const int j = lane & (LPP - 1);
@@ -102,12 +133,12 @@ __global__ __launch_bounds__(256) void m2d_score_pairs_c4(ScoreArgs p)
     const int64_t wave0 = (int64_t)blockIdx.x * (blockDim.x >> 6) + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int64_t nwaves = (int64_t)gridDim.x * (blockDim.x >> 6);
 
-    const bool skipm = skip_rows(p);
-    const v4f *pm4 = reinterpret_cast<const v4f *>(p.pm);
+    const bool skipm = skip_rows<BF>(p);
+    const row_t *pm4 = BF ? reinterpret_cast<const row_t *>(p.pmh) : reinterpret_cast<const row_t *>(p.pm);
     const v4f *re4 = reinterpret_cast<const v4f *>(p.re);
     const v4f *ce4 = reinterpret_cast<const v4f *>(p.ce);
     const v4f *hv4 = reinterpret_cast<const v4f *>(p.hv);
-    const size_t urow4 = (size_t)(C + 1) * E4;  // float4 per user block
+    const size_t urow4 = (size_t)(C + 1) * E4;  // float4 (mirror: 8-byte words) per user block
 
     v4f cef[C];
 #pragma unroll
@@ -148,7 +179,7 @@ __global__ __launch_bounds__(256) void m2d_score_pairs_c4(ScoreArgs p)
         v4f uhv = {0.f, 0.f, 0.f, 0.f};
         if constexpr (use_uh) uhv = reinterpret_cast<const v4f *>(p.uh)[ul];
 
-        v4f ub[PF][C + 1];
+        row_t ub[PF][C + 1];
         v4f ib[PF];
         v4f hb[PF];
         float my_high = 0.f, my_low = 0.f;
@@ -157,12 +188,12 @@ __global__ __launch_bounds__(256) void m2d_score_pairs_c4(ScoreArgs p)
             const int32_t us = __shfl(ul32, s, LPP);
             const int32_t ds = __shfl(did, s, LPP);
             const int32_t as = __shfl(act, s, LPP);
-            const v4f *pu = pm4 + (size_t)us * urow4 + jc;
-            if constexpr (use_uh) ub[slot][0] = v4f{0.f, 0.f, 0.f, 0.f};
+            const row_t *pu = pm4 + (size_t)us * urow4 + jc;
+            if constexpr (use_uh) ub[slot][0] = row_t{};
             else ub[slot][0] = ld4<NT>(pu);
 #pragma unroll
             for (int r = 1; r <= C; ++r) {
-                ub[slot][r] = v4f{0.f, 0.f, 0.f, 0.f};
+                ub[slot][r] = row_t{};
                 if ((as >> (r - 1)) & 1) ub[slot][r] = ld4<NT>(pu + (size_t)r * E4);
             }
             ib[slot] = re4[(size_t)ds * E4 + jc];
@@ -182,16 +213,17 @@ __global__ __launch_bounds__(256) void m2d_score_pairs_c4(ScoreArgs p)
                 const float m3 = __shfl(m.w, s, LPP);
                 const float mc[C] = {m0, m1, m2, m3};
                 float hs = 0.f, ls = 0.f;
+                const v4f uhigh = widen(ub[k][0]);
 #pragma unroll
                 for (int c = 0; c < C; ++c) {
                     if constexpr (!HV && !use_uh) {
                         const v4f dish_category = scale4(mc[c], cef[c]);    // :67
-                        hs = dot4(ub[k][0], dish_category, hs);                // :71, :75
+                        hs = dot4(uhigh, dish_category, hs);                   // :71, :75
                     }
-                    const v4f dish_memory = scale4(mc[c], ub[k][c + 1]);    // :82
+                    const v4f dish_memory = scale4(mc[c], widen(ub[k][c + 1]));    // :82
                     ls = dot4(ib[k], dish_memory, ls);                         // :86, :90
                 }
-                if constexpr (HV) hs = dot4(ub[k][0], hb[k], hs);
+                if constexpr (HV) hs = dot4(uhigh, hb[k], hs);
                 if (!FULL && !col_ok) ls = 0.f;
                 if constexpr (!FULL) hs = __builtin_bit_cast(float, __builtin_bit_cast(int32_t, hs) & keep);
                 if (s + PF < LPP) issue(s + PF, k);
@@ -241,13 +273,43 @@ __global__ __launch_bounds__(256) void m2d_build_user_high(const float *pm, cons
     }
 }
 
+// Serving mirror (option "pm_bf16"): out[i] = bf16(pm[i]), round to nearest even in the integer form -- add 0x7fff and the kept
+// part's lowest bit, shift -- which rounds subnormals, keeps -0 and +-inf and turns finite values past the bf16 range into +-inf; a NaN
+// becomes the quiet NaN 0x7fc0 (what torch's float32 -> bfloat16 returns).  A grid-stride stream of 16-byte loads and 8-byte stores; the
+// n % 4 floats behind the last whole float4 go one by one.  *nonfinite (zeroed by the launcher) is set when a written value is inf / NaN.
+__device__ __forceinline__ uint32_t bf16_rne(const float x)
+{
+    const uint32_t u = __builtin_bit_cast(uint32_t, x);
+    if ((u & 0x7fffffffu) > 0x7f800000u) return 0x7fc0u;
+    return (u + 0x7fffu + ((u >> 16) & 1u)) >> 16;
+}
+
+__global__ __launch_bounds__(256) void m2d_build_pm_bf16(const float *pm, int64_t n, uint16_t *out, int32_t *nonfinite)
+{
+    const int64_t n4 = n >> 2, t0 = (int64_t)blockIdx.x * blockDim.x + threadIdx.x, stride = (int64_t)gridDim.x * blockDim.x;
+    uint32_t bad = 0;
+    for (int64_t i = t0; i < n4; i += stride) {
+        const v4f x = __builtin_nontemporal_load(reinterpret_cast<const v4f *>(pm) + i);
+        const uint32_t h0 = bf16_rne(x.x), h1 = bf16_rne(x.y), h2 = bf16_rne(x.z), h3 = bf16_rne(x.w);
+        bad |= (h0 & 0x7f80u) == 0x7f80u || (h1 & 0x7f80u) == 0x7f80u || (h2 & 0x7f80u) == 0x7f80u || (h3 & 0x7f80u) == 0x7f80u;
+        reinterpret_cast<v2u *>(out)[i] = v2u{h0 | (h1 << 16), h2 | (h3 << 16)};
+    }
+    for (int64_t i = (n4 << 2) + t0; i < n; i += stride) {
+        const uint32_t hh = bf16_rne(pm[i]);
+        bad |= (hh & 0x7f80u) == 0x7f80u;
+        out[i] = (uint16_t)hh;
+    }
+    if (bad) atomicOr(nonfinite, 1);
+}
+
 // Latency form of the kernel above for small batches (serving calls, the reference's own 51 pairs per sess.run):
 // a group of LPP lanes takes ONE pair per pass instead of walking LPP pairs one after another, so a batch of B
 // pairs is spread over B * LPP / 64 waves and finishes in about one row-gather latency instead of up to 64 of
 // them in sequence.  Same per-lane arithmetic and the same group reduction: bit-identical scores.
-template <int LPP, bool BYDISH, bool FULL, bool HV>
+template <int LPP, bool BYDISH, bool FULL, bool HV, bool BF = false>
 __global__ __launch_bounds__(256) void m2d_score_pairs_c4_small(ScoreArgs p)
 {
+    typedef typename pm_row<BF>::type row_t;                // BF: rows from the bf16 mirror, see m2d_score_pairs_c4
     constexpr int C = 4, GPW = 64 / LPP;                    // pairs per wave per pass
     const int lane = threadIdx.x & 63;
     const int j = lane & (LPP - 1);
@@ -258,12 +320,12 @@ __global__ __launch_bounds__(256) void m2d_score_pairs_c4_small(ScoreArgs p)
     asm volatile("" : "+v"(keep));
     const int64_t wave0 = (int64_t)blockIdx.x * (blockDim.x >> 6) + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int64_t nwaves = (int64_t)gridDim.x * (blockDim.x >> 6);
-    const v4f *pm4 = reinterpret_cast<const v4f *>(p.pm);
+    const row_t *pm4 = BF ? reinterpret_cast<const row_t *>(p.pmh) : reinterpret_cast<const row_t *>(p.pm);
     const v4f *re4 = reinterpret_cast<const v4f *>(p.re);
     const v4f *ce4 = reinterpret_cast<const v4f *>(p.ce);
     const v4f *hv4 = reinterpret_cast<const v4f *>(p.hv);
     const size_t urow4 = (size_t)(C + 1) * E4;
-    const bool skipm = skip_rows(p);
+    const bool skipm = skip_rows<BF>(p);
     v4f cef[C];
 #pragma unroll
     for (int c = 0; c < C; ++c) {
@@ -292,13 +354,13 @@ __global__ __launch_bounds__(256) void m2d_score_pairs_c4_small(ScoreArgs p)
             const v4f *cp = reinterpret_cast<const v4f *>(p.cats);
             m = BYDISH ? cp[did] : cp[pi];
         }
-        const v4f *pu = pm4 + (size_t)ul * urow4 + jc;
-        v4f ub[C + 1];
+        const row_t *pu = pm4 + (size_t)ul * urow4 + jc;
+        row_t ub[C + 1];
         const float mw[C] = {m.x, m.y, m.z, m.w};
         ub[0] = pu[0];
 #pragma unroll
         for (int r = 1; r <= C; ++r) {                     // a category of weight 0 contributes 0: its row is not fetched
-            ub[r] = v4f{0.f, 0.f, 0.f, 0.f};
+            ub[r] = row_t{};
             if (!skipm || mw[r - 1] != 0.f) ub[r] = pu[(size_t)r * E4];
         }
         const v4f ib = re4[(size_t)did * E4 + jc];
@@ -306,16 +368,17 @@ __global__ __launch_bounds__(256) void m2d_score_pairs_c4_small(ScoreArgs p)
         if constexpr (HV) hb = hv4[(size_t)did * E4 + jc];
         const float mc[C] = {m.x, m.y, m.z, m.w};
         float hs = 0.f, ls = 0.f;
+        const v4f uhigh = widen(ub[0]);
 #pragma unroll
         for (int c = 0; c < C; ++c) {
             if constexpr (!HV) {
                 const v4f dish_category = scale4(mc[c], cef[c]);    // :67
-                hs = dot4(ub[0], dish_category, hs);                   // :71, :75
+                hs = dot4(uhigh, dish_category, hs);                   // :71, :75
             }
-            const v4f dish_memory = scale4(mc[c], ub[c + 1]);       // :82
+            const v4f dish_memory = scale4(mc[c], widen(ub[c + 1]));   // :82
             ls = dot4(ib, dish_memory, ls);                            // :86, :90
         }
-        if constexpr (HV) hs = dot4(ub[0], hb, hs);
+        if constexpr (HV) hs = dot4(uhigh, hb, hs);
         if (!FULL && !col_ok) ls = 0.f;
         if constexpr (!FULL) hs = __builtin_bit_cast(float, __builtin_bit_cast(int32_t, hs) & keep);
         hs = group_sum<LPP>(hs);
@@ -494,31 +557,35 @@ __global__ __launch_bounds__(256) void m2d_score_pairs_generic(ScoreArgs p)
     }
 }
 
-template <int LPP, bool FULL, bool BYDISH>
+// BF: the forms that read the bf16 mirror (a.pmh), named as their f32 twins with "_bf16" behind
+template <int LPP, bool FULL, bool BYDISH, bool BF>
 void launch_c4(const ScoreArgs &a, int pf, bool nt, bool small, dim3 grid, hipStream_t st, const char **name)
 {
 #define M2D_CASE(PFV, NTV)                                                                           \
     if (pf == PFV && nt == NTV) {                                                                    \
-        hipLaunchKernelGGL((m2d_score_pairs_c4<LPP, PFV, BYDISH, NTV, FULL, false>), grid, dim3(256), 0, st, a); \
+        hipLaunchKernelGGL((m2d_score_pairs_c4<LPP, PFV, BYDISH, NTV, FULL, false, false, BF>), grid, dim3(256), 0, st, a); \
         return;                                                                                      \
     }
     if (small) {  // latency form: one pair per group per pass
-        *name = a.hv ? "m2d_score_pairs_c4_small_hv" : "m2d_score_pairs_c4_small";
-        if (a.hv) hipLaunchKernelGGL((m2d_score_pairs_c4_small<LPP, BYDISH, FULL, true>), grid, dim3(256), 0, st, a);
-        else hipLaunchKernelGGL((m2d_score_pairs_c4_small<LPP, BYDISH, FULL, false>), grid, dim3(256), 0, st, a);
+        *name = a.hv ? (BF ? "m2d_score_pairs_c4_small_hv_bf16" : "m2d_score_pairs_c4_small_hv")
+                     : (BF ? "m2d_score_pairs_c4_small_bf16" : "m2d_score_pairs_c4_small");
+        if (a.hv) hipLaunchKernelGGL((m2d_score_pairs_c4_small<LPP, BYDISH, FULL, true, BF>), grid, dim3(256), 0, st, a);
+        else hipLaunchKernelGGL((m2d_score_pairs_c4_small<LPP, BYDISH, FULL, false, BF>), grid, dim3(256), 0, st, a);
         return;
     }
     if (a.hv) {   // extension kernel: one configuration (PF 2, non-temporal user rows)
-        *name = "m2d_score_pairs_c4_hv";
-        hipLaunchKernelGGL((m2d_score_pairs_c4<LPP, 2, BYDISH, true, FULL, true>), grid, dim3(256), 0, st, a);
+        *name = BF ? "m2d_score_pairs_c4_hv_bf16" : "m2d_score_pairs_c4_hv";
+        hipLaunchKernelGGL((m2d_score_pairs_c4<LPP, 2, BYDISH, true, FULL, true, false, BF>), grid, dim3(256), 0, st, a);
         return;
     }
-    *name = "m2d_score_pairs_c4";
-    if (a.uh) {   // high-level sum from the derived table: one configuration (PF 2, non-temporal user rows), as the default
-        *name = "m2d_score_pairs_c4_uh";
-        if (pf == 4) hipLaunchKernelGGL((m2d_score_pairs_c4<LPP, 4, BYDISH, true, FULL, false, true>), grid, dim3(256), 0, st, a);
-        else hipLaunchKernelGGL((m2d_score_pairs_c4<LPP, 2, BYDISH, true, FULL, false, true>), grid, dim3(256), 0, st, a);
-        return;
+    *name = BF ? "m2d_score_pairs_c4_bf16" : "m2d_score_pairs_c4";
+    if constexpr (!BF) {
+        if (a.uh) {   // high-level sum from the derived table: one configuration (PF 2, non-temporal user rows), as the default
+            *name = "m2d_score_pairs_c4_uh";
+            if (pf == 4) hipLaunchKernelGGL((m2d_score_pairs_c4<LPP, 4, BYDISH, true, FULL, false, true>), grid, dim3(256), 0, st, a);
+            else hipLaunchKernelGGL((m2d_score_pairs_c4<LPP, 2, BYDISH, true, FULL, false, true>), grid, dim3(256), 0, st, a);
+            return;
+        }
     }
     M2D_CASE(1, false) M2D_CASE(1, true) M2D_CASE(2, false) M2D_CASE(2, true)
     M2D_CASE(4, false) M2D_CASE(4, true)
@@ -545,14 +612,20 @@ int launch_any(m2d_engine *h, const ScoreArgs &a, hipStream_t st)
         if (blocks < 1) blocks = 1;
         dim3 grid((unsigned)blocks);
         const char **nm = &h->last_kernel;
-        if (E4 == 8) launch_c4<8, true, BYDISH>(a, pf, nt, small, grid, st, nm);
-        else if (E4 == 16) launch_c4<16, true, BYDISH>(a, pf, nt, small, grid, st, nm);
-        else if (E4 == 32) launch_c4<32, true, BYDISH>(a, pf, nt, small, grid, st, nm);
-        else if (E4 == 64) launch_c4<64, true, BYDISH>(a, pf, nt, small, grid, st, nm);
-        else if (E4 < 8) launch_c4<8, false, BYDISH>(a, pf, nt, small, grid, st, nm);
-        else if (E4 < 16) launch_c4<16, false, BYDISH>(a, pf, nt, small, grid, st, nm);
-        else if (E4 < 32) launch_c4<32, false, BYDISH>(a, pf, nt, small, grid, st, nm);
-        else launch_c4<64, false, BYDISH>(a, pf, nt, small, grid, st, nm);
+#define M2D_C4(L, F)                                                                                     \
+    do {                                                                                                 \
+        if (a.pmh) launch_c4<L, F, BYDISH, true>(a, pf, nt, small, grid, st, nm);                        \
+        else launch_c4<L, F, BYDISH, false>(a, pf, nt, small, grid, st, nm);                             \
+    } while (0)
+        if (E4 == 8) M2D_C4(8, true);
+        else if (E4 == 16) M2D_C4(16, true);
+        else if (E4 == 32) M2D_C4(32, true);
+        else if (E4 == 64) M2D_C4(64, true);
+        else if (E4 < 8) M2D_C4(8, false);
+        else if (E4 < 16) M2D_C4(16, false);
+        else if (E4 < 32) M2D_C4(32, false);
+        else M2D_C4(64, false);
+#undef M2D_C4
     } else if (a.C <= 8 && (a.E % 4 == 0) && E4 <= 64 && !a.hv && a.B > 8192 && h->opt_variant != 9) {
         blocks = (nchunks + 3) / 4;
         if (blocks > cap) blocks = cap;
@@ -604,8 +677,22 @@ int m2d_ensure_user_high(m2d_engine *h, hipStream_t stream)
     return M2D_OK;
 }
 
+// The bf16 mirror of Personal_Memory, current: built on first use and again after a write (m2d_mark_written), a whole pass over the
+// table.  Its non-finite word is zeroed and set again with every build.
+int m2d_ensure_pm_bf16(m2d_engine *h, hipStream_t stream)
+{
+    if (h->pm_bf16_valid) return M2D_OK;
+    const int64_t n = m2d_table_floats(h, 0);
+    if (!h->pm_bf16) M2D_HIP_TRY(h, hipMalloc((void **)&h->pm_bf16, (size_t)n * sizeof(uint16_t)));
+    M2D_HIP_TRY(h, hipMemsetAsync(h->pm_bf16_nonfinite, 0, sizeof(int32_t), stream));
+    hipLaunchKernelGGL(m2d_build_pm_bf16, dim3(m2d_blocks_for(h, n / 4, 256)), dim3(256), 0, stream, h->pm, n, h->pm_bf16, h->pm_bf16_nonfinite);
+    M2D_HIP_TRY(h, hipGetLastError());
+    h->pm_bf16_valid = true;
+    return M2D_OK;
+}
+
 int m2d_launch_score_pairs(m2d_engine *h, const int32_t *users, const int32_t *items, const float *cats,
-                           bool by_dish, int64_t B, float *out, hipStream_t stream, bool use_ingredients)
+                           bool by_dish, int64_t B, float *out, hipStream_t stream, bool use_ingredients, bool may_use_mirror)
 {
     if (B == 0) return M2D_OK;
     {
@@ -621,10 +708,20 @@ int m2d_launch_score_pairs(m2d_engine *h, const int32_t *users, const int32_t *i
     a.E = h->E; a.C = h->C; a.a = h->a; a.b = h->b; a.err = h->err_dev;
     a.skip_masked = h->opt_skip_masked;
     a.uh = nullptr;
+    a.pmh = nullptr;
+    a.nonfinite_bf = h->pm_bf16_nonfinite;
+    // opt-in ("pm_bf16"): whenever the vectorised C = 4 kernels run, they read the user rows from the bf16 mirror -- whatever the
+    // batch size, so a call's scores depend on its inputs and options only.  The mirror wins over "user_high_table".
+    // (m2d_rank_candidates passes may_use_mirror = false: the evaluator's lists stay the f32 table's.)
+    if (may_use_mirror && h->opt_pm_bf16 && h->C == 4 && h->E % 4 == 0 && h->E <= 256 && h->opt_variant != 9) {
+        const int rc = m2d_ensure_pm_bf16(h, stream);
+        if (rc != M2D_OK) return rc;
+        a.pmh = h->pm_bf16;
+    }
     // opt-in ("user_high_table"): batches large enough to pay for a pass over U_high take the high-level sum from the derived
     // table (rebuilt when Personal_Memory / Category_Embedding changed); smaller ones never do, so a call's scores depend
     // on its inputs and its size only, not on what ran before
-    if (!use_ingredients && h->opt_user_high && h->C == 4 && h->E % 4 == 0 && h->E <= 256 && h->opt_variant != 9 &&
+    if (!a.pmh && !use_ingredients && h->opt_user_high && h->C == 4 && h->E % 4 == 0 && h->E <= 256 && h->opt_variant != 9 &&
         (h->opt_prefetch == 2 || h->opt_prefetch == 4) && h->opt_nt != 0 && B >= (1 << 18)) {
         int rc = m2d_ensure_user_high(h, stream);
         if (rc != M2D_OK) return rc;

@@ -122,7 +122,8 @@ int m2d_launch_rank_candidates(m2d_engine *h, const int32_t *users, const int32_
     M2D_HIP_TRY(h, hipGetLastError());
     // `head`: the segment scores are the 3-layer head's (m2d_rank_candidates_mlp; it writes neither this scratch nor the outputs)
     rc = head ? m2d_launch_score_pairs_mlp(h, users_x, items_x, total, scores, stream)
-              : m2d_launch_score_pairs(h, users_x, items_x, h->dish_cats, /*by_dish=*/true, total, scores, stream);
+              : m2d_launch_score_pairs(h, users_x, items_x, h->dish_cats, /*by_dish=*/true, total, scores, stream,
+                                       /*use_ingredients=*/false, /*may_use_mirror=*/false);
     if (rc != M2D_OK) return rc;
     const int64_t rb = (nseg + RANK_WAVES - 1) / RANK_WAVES;
     const size_t lds = (size_t)RANK_WAVES * 3 * L * 4;

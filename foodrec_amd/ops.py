@@ -306,6 +306,15 @@ class ScoringEngine:
         """Call after writing to self.pm / self.re / self.ce directly (they are borrowed by the engine)."""
         _native.raise_for(_native.lib().m2d_tables_updated(self._h), self._h)
 
+    def personal_memory_bf16(self) -> torch.Tensor:
+        """The serving mirror of Personal_Memory (option "pm_bf16"): its round-to-nearest-even bfloat16 image [U, C+1, E], made
+        current first -- built if a write made it stale -- whatever the option says.  For checkpointing a serving image."""
+        buf = torch.empty(tuple(self.pm.shape), dtype=torch.bfloat16, device=self.device)
+        with torch.cuda.device(self.device):
+            rc = _native.lib().m2d_pm_bf16(self._h, buf.data_ptr(), _stream_ptr())
+        _native.raise_for(rc, self._h)
+        return buf
+
     def train_steps(self, restore: Optional[int] = None) -> int:
         """Optimizer steps applied since train_begin; with `restore`, sets that count (checkpoint resume)."""
         v = ctypes.c_int64(0 if restore is None else int(restore))

@@ -232,6 +232,32 @@ int m2d_train_slot(m2d_engine *h, int32_t table, int32_t slot, float *buf, int32
  * m2d_write_memory do this themselves. */
 int m2d_tables_updated(m2d_engine *h);
 
+/* Serving mirror (option "pm_bf16", default 0; a serving option like "user_high_table").  pm_bf16 u16[U, C+1, E] is the bf16 image of
+ * Personal_Memory, every value rounded to nearest, ties to even, exactly as torch's float32 -> bfloat16 does it: subnormals are
+ * rounded, not flushed; -0 and +-inf are kept; a NaN becomes the quiet NaN 0x7fc0; finite values past the bf16 range become +-inf.
+ * The engine builds it on the first call that needs it and again after anything that writes Personal_Memory (m2d_write_memory,
+ * m2d_train_step, m2d_tables_updated): one whole pass over the table.  If its allocation fails the call returns M2D_ERR_HIP (text
+ * in m2d_last_error); nothing falls back to the f32 table.
+ * With the option on, m2d_score_pairs, m2d_score_pairs_bydish, m2d_score_pairs_host and m2d_score_pairs_ingredients read the user
+ * rows from the mirror whenever the vectorised C = 4 kernels run -- C = 4, E % 4 == 0, E <= 256, "variant" != 9 -- whatever the
+ * batch size.  The scores are the graph's on the rounded table, bit for bit what the f32 kernels return on an engine built from it,
+ * NaN and inf positions included; every kernel form ("prefetch", "nt_loads", "skip_masked", "blocks_per_cu", "variant" 11 / 12)
+ * returns the same bits.  Against the f32 table a score moves by at most 2^-8 (|a| sum|high-level terms| + |b| sum|low-level
+ * terms|) / n.  Because rounding can make an inf the f32 table does not hold, the mirror has a non-finite word of its own:
+ * "skip_masked" leaves weight-0 rows out only while that word and the engine's are both clear.  m2d_last_kernel names the f32
+ * kernel with "_bf16" behind: m2d_score_pairs_c4_bf16, m2d_score_pairs_c4_small_bf16, m2d_score_pairs_c4_hv_bf16,
+ * m2d_score_pairs_c4_small_hv_bf16.  Other shapes (m2d_score_pairs_cn, m2d_score_pairs_generic, "variant" = 9) keep reading the f32
+ * table, and m2d_last_kernel says so.  With "user_high_table" = 1 as well the mirror wins: the derived high table is not used, the
+ * bits are those of "pm_bf16" alone.
+ * NOT affected -- they read the f32 table as before: m2d_rank_candidates (and the evaluator built on it), m2d_topk_users,
+ * m2d_catalogue_rank, m2d_topk_users_excluding, the MLP head (m2d_score_pairs_mlp, m2d_topk_users_mlp, m2d_rank_candidates_mlp),
+ * m2d_train_step and m2d_write_memory, which read and write the f32 table and make the mirror stale.
+ *
+ * m2d_pm_bf16 makes the mirror current -- building it if it is stale, whatever the option says -- and copies it into the device
+ * buffer `buf` (U (C+1) E halves), on `stream`, without synchronising.  For checkpointing a serving image.  A null pointer is
+ * M2D_ERR_INVALID_ARG. */
+int m2d_pm_bf16(m2d_engine *h, uint16_t *buf, void *stream);
+
 /* Optimizer steps applied since m2d_train_begin: read (*steps receives it, set = 0) or restored (set = 1, for a
  * checkpoint resume; Adam's bias-correction powers are re-derived from it). */
 int m2d_train_steps(m2d_engine *h, int64_t *steps, int32_t set);
@@ -306,7 +332,8 @@ int m2d_rank_candidates_mlp(m2d_engine *h, const int32_t *users, const int32_t *
  * bad_value / bad_index (host pointers, may be NULL) receive the offending id and its position. */
 int m2d_check(m2d_engine *h, void *stream, int64_t *bad_value, int64_t *bad_index);
 
-/* Options.  m2d_score_pairs* -- the reference path (Model_Recommender.py:56-97) -- is exact float32 whatever is set here.
+/* Options.  m2d_score_pairs* -- the reference path (Model_Recommender.py:56-97) -- is exact float32 whatever is set here, "pm_bf16"
+ * excepted (exact float32 arithmetic on the bf16-rounded Personal_Memory).
  * Unknown names: M2D_ERR_INVALID_ARG.  "Results" = the scores / ids a call returns.
  *
  * ---- product switches -------------------------------------------------------------------------------------------------------------
@@ -321,6 +348,10 @@ int m2d_check(m2d_engine *h, void *stream, int64_t *bad_value, int64_t *bad_inde
  * user_high_table  0        0 / 1   scores within 1e-6 (another summation     Calls of >= 2^18 pairs read sum_c m_c <U_high[u], CE_c> / n from a derived
  *                                   order)                                    [U, 4] table (16 B per user; rebuilt after the engine's writers or
  *                                                                             m2d_tables_updated) instead of the U_high row.  A serving option.
+ * pm_bf16          0        0 / 1   yes: the graph on the bf16-rounded        The C = 4 pair kernels (C = 4, E a multiple of 4 up to 256, "variant" != 9) read a
+ *                                   Personal_Memory                           pair's Personal_Memory rows from a bf16 mirror of the table: (1 + active
+ *                                                                             categories) E 2 B of user rows per pair instead of E 4 B each.  Any batch
+ *                                                                             size; see "Serving mirror" below.
  * host_zero_copy   2        0 1 2   no                                        m2d_score_pairs_host up to 65 536 pairs: 2 = the kernel works on the pinned
  *                                                                             block and the call spins on a completion word, 1 = without the spin, 0 = staged copies.
  * topk_bf16x3      1        0 / 1   scores within ~1e-5 relative; dish ids    m2d_topk_users, 0/1 masks, E = 64 / 128: contraction on split-bf16 MFMA
