@@ -196,10 +196,10 @@ static inline int64_t m2d_table_floats(const m2d_engine *h, int table)
     return table == 0 ? h->U * (int64_t)(h->C + 1) * h->E : table == 1 ? h->I * (int64_t)h->E : (int64_t)h->C * h->E;
 }
 
-// grid of a grid-stride launch: one block per `per_block` items, at least one, at most eight per CU
-static inline unsigned m2d_blocks_for(const m2d_engine *h, int64_t items, int64_t per_block)
+// grid of a grid-stride launch: one block per `per_block` items, at least one, at most `per_cu` (eight) per CU
+static inline unsigned m2d_blocks_for(const m2d_engine *h, int64_t items, int64_t per_block, int per_cu = 8)
 {
-    const int64_t b = (items + per_block - 1) / per_block, cap = (int64_t)h->num_cu * 8;
+    const int64_t b = (items + per_block - 1) / per_block, cap = (int64_t)h->num_cu * per_cu;
     return (unsigned)(b > cap ? cap : b < 1 ? 1 : b);
 }
 

@@ -17,5 +17,5 @@ names = subprocess.run(["c++filt"] + [r["name"] for r in rows], capture_output=T
 for r, n in zip(rows, names):
     n = n.replace("(anonymous namespace)::", "").split("(")[0]
     if re.search(sys.argv[1], n):
-        print("%-62s VGPR %3s AGPR %3s spill v%s s%s occ %s LDS %s" % (n[:62], r.get("VGPRs"), r.get("AGPRs"), r.get("VGPRs Spill"), r.get("SGPRs Spill"), r.get("Occupancy"), r.get("LDS Size")))
+        print("%-78s VGPR %3s AGPR %3s spill v%s s%s occ %s LDS %s" % (n[:78], r.get("VGPRs"), r.get("AGPRs"), r.get("VGPRs Spill"), r.get("SGPRs Spill"), r.get("Occupancy"), r.get("LDS Size")))
 ' "$filt"
