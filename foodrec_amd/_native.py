@@ -59,6 +59,8 @@ SIGNATURES = {
     "m2d_score_pairs_mlp": (_c.c_int, [_vp, _vp, _vp, _i64, _vp, _vp]),
     "m2d_topk_users_mlp": (_c.c_int, [_vp, _vp, _i64, _i32, _i32, _vp, _vp, _vp]),
     "m2d_rank_candidates_mlp": (_c.c_int, [_vp, _vp, _vp, _vp, _i64, _i32, _i32, _vp, _vp, _vp, _vp]),
+    "m2d_score_slate": (_c.c_int, [_vp, _vp, _i64, _vp, _i64, _vp, _vp]),
+    "m2d_topk_slate": (_c.c_int, [_vp, _vp, _i64, _vp, _i64, _i32, _vp, _vp, _vp]),
     "m2d_write_memory": (_c.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _vp, _c.c_float, _c.c_float,
                                     _c.c_float, _i32, _vp, _vp]),
     "m2d_train_begin": (_c.c_int, [_vp, _i32, _c.c_float, _c.c_float, _vp]),

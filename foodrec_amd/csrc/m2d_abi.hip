@@ -148,6 +148,8 @@ void release(m2d_engine *h)
     if (h->topk_mlp_ids) (void)hipFree(h->topk_mlp_ids);
     if (h->topk_mlp_scores) (void)hipFree(h->topk_mlp_scores);
     if (h->topk_mlp_cand) (void)hipFree(h->topk_mlp_cand);
+    if (h->slate_dt) (void)hipFree(h->slate_dt);
+    if (h->slate_scores) (void)hipFree(h->slate_scores);
     if (h->err_dev) (void)hipFree(h->err_dev);
     if (h->err_host) (void)hipHostFree(h->err_host);
 }
@@ -542,6 +544,30 @@ int m2d_topk_users_excluding(m2d_engine *h, const int32_t *users, int64_t nU, in
     return m2d_launch_topk_users_excluding(h, users, nU, k, excl_off, excl_ids, out_scores, out_ids, (hipStream_t)stream);
 }
 
+int m2d_score_slate(m2d_engine *h, const int32_t *users, int64_t nU, const int32_t *slate, int64_t nD, float *out, void *stream)
+{
+    if (!h) return M2D_ERR_INVALID_ARG;
+    if (nU < 0 || nD < 1 || nD > h->I) return fail(h, M2D_ERR_INVALID_ARG, "m2d_score_slate: need nU >= 0 and 1 <= nD <= I");
+    if (nU == 0) return M2D_OK;
+    if (!users || !slate || !out) return fail(h, M2D_ERR_INVALID_ARG, "m2d_score_slate: null buffer");
+    if (!h->dish_cats) return fail(h, M2D_ERR_NOT_CONFIGURED, "call m2d_set_dish_categories first");
+    M2D_HIP_TRY(h, hipSetDevice(h->device));
+    return m2d_launch_slate(h, "m2d_score_slate", users, nU, slate, nD, 0, out, nullptr, nullptr, (hipStream_t)stream);
+}
+
+int m2d_topk_slate(m2d_engine *h, const int32_t *users, int64_t nU, const int32_t *slate, int64_t nD, int32_t k, float *out_scores,
+                   int32_t *out_ids, void *stream)
+{
+    if (!h) return M2D_ERR_INVALID_ARG;
+    if (nU < 0 || nD < 1 || nD > h->I || k < 1 || k > 64 || (int64_t)k > nD)
+        return fail(h, M2D_ERR_INVALID_ARG, "m2d_topk_slate: need nU >= 0, 1 <= nD <= I and 1 <= k <= min(64, nD)");
+    if (nU == 0) return M2D_OK;
+    if (!users || !slate || !out_scores || !out_ids) return fail(h, M2D_ERR_INVALID_ARG, "m2d_topk_slate: null buffer");
+    if (!h->dish_cats) return fail(h, M2D_ERR_NOT_CONFIGURED, "call m2d_set_dish_categories first");
+    M2D_HIP_TRY(h, hipSetDevice(h->device));
+    return m2d_launch_slate(h, "m2d_topk_slate", users, nU, slate, nD, k, nullptr, out_scores, out_ids, (hipStream_t)stream);
+}
+
 int m2d_clear_ingredients(m2d_engine *h)
 {
     if (!h) return M2D_ERR_INVALID_ARG;
@@ -818,9 +844,10 @@ int m2d_check(m2d_engine *h, void *stream, int64_t *bad_value, int64_t *bad_inde
                         "words (stage " + std::to_string(value) + "): that call's lists are invalid";
         return code;
     }
-    if (code == M2D_ERR_INVALID_ARG) {              // the exclusion lists of m2d_catalogue_rank / m2d_topk_users_excluding
-        h->last_error = "m2d_catalogue_rank / m2d_topk_users_excluding: exclusion list not ascending: value " + std::to_string(value) + " at position " +
-                        std::to_string(index) + " (an id below its predecessor in excl_ids, or an offset below its predecessor in excl_off)";
+    if (code == M2D_ERR_INVALID_ARG) {              // the exclusion lists of m2d_catalogue_rank / m2d_topk_users_excluding, the slate of m2d_*_slate
+        h->last_error = "m2d_catalogue_rank / m2d_topk_users_excluding / m2d_score_slate / m2d_topk_slate: id list not ascending: value " +
+                        std::to_string(value) + " at position " + std::to_string(index) +
+                        " (an id below its predecessor in excl_ids, an offset below its predecessor in excl_off, or a slate id not above its predecessor)";
         return code;
     }
     const char *what = code == M2D_ERR_BAD_USER_ID ? "user" : code == M2D_ERR_BAD_ITEM_ID ? "item" : "ingredient";
@@ -857,6 +884,10 @@ int m2d_set_option(m2d_engine *h, const char *name, int64_t value)
     else if (!strcmp(name, "topk_mlp_chunk_pairs")) {
         if (value < 256 || value > (1 << 24)) return fail(h, M2D_ERR_INVALID_ARG, "m2d_set_option: topk_mlp_chunk_pairs takes 256 ... 2^24");
         h->opt_topk_mlp_chunk_pairs = value;
+    }
+    else if (!strcmp(name, "slate_chunk_pairs")) {
+        if (value < 256 || value > (1 << 24)) return fail(h, M2D_ERR_INVALID_ARG, "m2d_set_option: slate_chunk_pairs takes 256 ... 2^24");
+        h->opt_slate_chunk_pairs = value;
     }
     else if (!strcmp(name, "mlp_bf16x3")) h->opt_mlp_bf16x3 = (int)value;
     else if (!strcmp(name, "mlp_form")) h->opt_mlp_form = (int)value;
@@ -939,6 +970,7 @@ int m2d_get_option(const m2d_engine *h, const char *name, int64_t *value)
     else if (!strcmp(name, "topk_grouped")) *value = h->opt_topk_grouped;
     else if (!strcmp(name, "topk_mlp_chunk_pairs")) *value = h->opt_topk_mlp_chunk_pairs;
     else if (!strcmp(name, "topk_mlp_launches")) *value = h->topk_mlp_launches;
+    else if (!strcmp(name, "slate_chunk_pairs")) *value = h->opt_slate_chunk_pairs;
     else if (!strcmp(name, "mlp_bf16x3")) *value = h->opt_mlp_bf16x3;
     else if (!strcmp(name, "mlp_form")) *value = h->opt_mlp_form;
     else if (!strcmp(name, "skip_masked")) *value = h->opt_skip_masked;

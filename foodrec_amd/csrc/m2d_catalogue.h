@@ -10,6 +10,8 @@
 //   m2d_catalogue_repair.hip      users whose k-th score is tied three ways or more: re-ranked over their patterns in id order
 //   m2d_catalogue_rank.hip        m2d_catalogue_rank: a held-out dish's rank over the catalogue, in the repair's arithmetic
 //   m2d_catalogue_excl.hip        m2d_topk_users_excluding: the top k without each user's excluded dishes, in the same arithmetic
+//   m2d_slate.hip                 m2d_score_slate / m2d_topk_slate: users x one shared dish list, dense exact f32 over gathered rows (shares
+//                            dish_vector_row, the dish-vector formula, with m2d_catalogue_dense.hip)
 //
 // Reference behaviour all of it reproduces: score = Model_Recommender.py:67-96 per (user, dish), ranking = heapq.nlargest
 // (evaluate.py:63: score descending, ties to the lower dish id, NaN last).
@@ -157,6 +159,24 @@ __device__ __forceinline__ bool ahead(float v, float w)
 {
     // does v rank strictly before w?  NaN ranks after everything.
     return (v > w) || (w != w && v == v);
+}
+
+// One row of the factored dish vectors (m2d_catalogue_dense.hip's header: Model_Recommender.py:67-96 per dish), by the 64 lanes of a wave:
+//   o[0 .. E) = a (sum_c m_c CE_c) / n  (hv: a H[d], the ingredient extension),  o[(c + 1) E + e] = b ((m_c / n) RE[d][e]),  n = sum_c m_c.
+// The one statement of these expressions: m2d_build_dish_vectors (the whole catalogue) and m2d_build_slate_vectors (a call's slate,
+// m2d_slate.hip) both write their rows through here, so a dish's vector is the same bits in both.
+__device__ __forceinline__ void dish_vector_row(const float *re, const float *ce, const float *dish_cats, const float *hv, const int64_t d,
+                                                const int C, const int E, const float a, const float b, const int lane, float *o)
+{
+    float n = 0.f;
+    for (int c = 0; c < C; ++c) n += dish_cats[d * C + c];                 // :77
+    for (int e = lane; e < E; e += 64) {
+        float s = 0.f;
+        for (int c = 0; c < C; ++c) s = fmaf(dish_cats[d * C + c], ce[(size_t)c * E + e], s);   // :67 summed over c
+        o[e] = hv ? a * hv[d * E + e] : a * (s / n);                       // :79, :95 (hv: ingredient extension)
+        const float r = re[d * E + e];
+        for (int c = 0; c < C; ++c) o[(size_t)(c + 1) * E + e] = b * ((dish_cats[d * C + c] / n) * r);   // :82-96
+    }
 }
 
 // Insert (x, id) into a descending register list of N slots and drop the last one -- for EVERY lane at once,

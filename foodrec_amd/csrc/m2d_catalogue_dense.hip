@@ -39,15 +39,7 @@ __global__ __launch_bounds__(256) void m2d_build_dish_vectors(const float *re, c
         for (int k = lane; k < K; k += 64) o[k] = 0.f;
         return;
     }
-    float n = 0.f;
-    for (int c = 0; c < C; ++c) n += dish_cats[d * C + c];                 // :77
-    for (int e = lane; e < E; e += 64) {
-        float s = 0.f;
-        for (int c = 0; c < C; ++c) s = fmaf(dish_cats[d * C + c], ce[(size_t)c * E + e], s);   // :67 summed over c
-        o[e] = hv ? a * hv[d * E + e] : a * (s / n);                       // :79, :95 (hv: ingredient extension)
-        const float r = re[d * E + e];
-        for (int c = 0; c < C; ++c) o[(size_t)(c + 1) * E + e] = b * ((dish_cats[d * C + c] / n) * r);   // :82-96
-    }
+    dish_vector_row(re, ce, dish_cats, hv, d, C, E, a, b, lane, o);
 }
 
 struct TopkArgs {

@@ -957,6 +957,9 @@ int m2d_grouped_tables(m2d_engine *h, hipStream_t st)
     return refresh_grouped_nonfinite(h, st);
 }
 
+// for m2d_score_slate / m2d_topk_slate (m2d_slate.hip): the word alone -- no sorted table is built
+int m2d_refresh_nonfinite(m2d_engine *h, hipStream_t st) { return refresh_grouped_nonfinite(h, st); }
+
 // the counting sort of plan records (stride 8) by word 5: `hist` holds PLAN_KEYS words, zeroed here unless the caller's kernels
 // have done so (`hist_zeroed`)
 int m2d_plan_sort_launch(m2d_engine *h, const float *plan, int64_t nU, int32_t *hist, int32_t *order, hipStream_t st, bool hist_zeroed)

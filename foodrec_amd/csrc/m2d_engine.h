@@ -76,6 +76,14 @@ struct m2d_engine {
     int64_t opt_topk_mlp_chunk_pairs = 1 << 22;   // pairs per head launch of that call (diagnostic: the lists do not depend on it)
     int64_t topk_mlp_launches = 0;                // head launches of the last call
 
+    // m2d_score_slate / m2d_topk_slate (m2d_slate.hip): the call's slate vectors Dt_s -- rows of K rounded up to the kernel's k chunk
+    // floats, zero beyond K: the slate's nD rows, zero rows up to the dish-tile multiple and one more zero row that pads the
+    // user operand -- rebuilt by every call (they hang on the call's slate and on every table); and a user block's scores of m2d_topk_slate
+    float *slate_dt = nullptr;
+    float *slate_scores = nullptr;
+    size_t slate_dt_cap = 0, slate_scores_cap = 0;   // floats
+    int64_t opt_slate_chunk_pairs = 1 << 22;         // pairs of score scratch per m2d_topk_slate pass (the lists do not depend on it)
+
     // derived table for pair scoring: <U_high[u], CE_c> per user and category (built lazily by large m2d_score_pairs calls;
     // stale after any write to Personal_Memory / Category_Embedding: the engine's own writers and m2d_tables_updated reset it)
     float *user_high = nullptr;  // [U, 4]
@@ -373,6 +381,15 @@ int m2d_launch_topk_users_mlp(m2d_engine *h, const int32_t *users, int64_t nU, i
                               int32_t *out_ids, hipStream_t stream);
 int m2d_launch_topk_users(m2d_engine *h, const int32_t *users, int64_t nU, int32_t k, float *out_scores,
                           int32_t *out_ids, hipStream_t stream);
+// m2d_topk_mlp.hip: m2d_topk_mlp_select over `rows` score rows of W columns (column e of row r at scores[r * rs + e * es]); ids: row r's
+// at ids + r * ids_stride (0: one id row shared by all), or d0 + e when null; first = 0 merges into the lists the outputs hold
+int m2d_launch_topk_select(m2d_engine *h, const float *scores, const int32_t *ids, int64_t ids_stride, int64_t rows, int64_t W, int32_t d0,
+                           int32_t k, int32_t first, float *out_scores, int32_t *out_ids, int64_t rs, int64_t es, hipStream_t stream);
+// m2d_slate.hip: out == null: the scores of user blocks go to scratch and the lists of k to out_scores / out_ids
+int m2d_launch_slate(m2d_engine *h, const char *entry, const int32_t *users, int64_t nU, const int32_t *slate, int64_t nD, int32_t k,
+                     float *out, float *out_scores, int32_t *out_ids, hipStream_t stream);
+// m2d_catalogue_plan.hip: the host's copy of the "a table value is not finite" word (grp_nonfinite), read again if a writer made it stale
+int m2d_refresh_nonfinite(m2d_engine *h, hipStream_t stream);
 int m2d_launch_catalogue_rank(m2d_engine *h, const int32_t *users, const int32_t *items, int64_t n, const int64_t *excl_off,
                               const int32_t *excl_ids, int32_t *out_rank, float *out_scores, hipStream_t stream);
 int m2d_launch_topk_users_excluding(m2d_engine *h, const int32_t *users, int64_t nU, int32_t k, const int64_t *excl_off,

@@ -50,7 +50,8 @@ __device__ __forceinline__ uint64_t tkm_key(const float s, const int32_t id)
 }
 
 // One workgroup per user row: the row's W scores -- column e at scores[row * rs + e * es]: rs = 1, es = rows behind the dish-major
-// generator, rs = W, es = 1 behind the candidate form; ids: ids[row * W + e], or d0 + e when null -- merged into the row's list of k
+// generator, rs = W, es = 1 behind the candidate form; ids: ids[row * ids_stride + e] (ids_stride = W: a row of ids per user, 0: one row
+// shared by all, the slate of m2d_topk_slate), or d0 + e when null -- merged into the row's list of k
 // (score, id) in out_scores / out_ids -- `first`: the list starts with this range, otherwise it takes part as k more candidates.
 // Every wave keeps the k best of the 64-wide slices it reads as a sorted list ACROSS its lanes (lane j: the j-th best, k <= 64
 // is why one wave holds a whole list): a slice is compared with lane k - 1's key in one ballot, and the few candidates that
@@ -59,13 +60,14 @@ __device__ __forceinline__ uint64_t tkm_key(const float s, const int32_t id)
 // running list meet in LDS ((waves + 1) k keys of 8 B and score words of 4 B), where every entry counts the entries in front of
 // it and the first k write themselves out.  No atomics; the score written is the word that was read (a NaN's payload, a -0).
 __global__ __launch_bounds__(1024) void m2d_topk_mlp_select(const float *scores, const int32_t *ids, int64_t W, int32_t d0, int32_t k,
-                                                            int32_t first, float *out_scores, int32_t *out_ids, int64_t rs, int64_t es)
+                                                            int32_t first, float *out_scores, int32_t *out_ids, int64_t rs, int64_t es,
+                                                            int64_t ids_stride)
 {
     extern __shared__ __align__(16) unsigned char smem[];
     const int nw = blockDim.x >> 6, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
     const int64_t row = blockIdx.x;
     const float *sc = scores + row * rs;
-    const int32_t *idr = ids ? ids + row * W : nullptr;
+    const int32_t *idr = ids ? ids + row * ids_stride : nullptr;
     uint64_t *mk = reinterpret_cast<uint64_t *>(smem);                          // [(nw + 1) k]
     uint32_t *ms = reinterpret_cast<uint32_t *>(mk + (size_t)(nw + 1) * k);     // [(nw + 1) k]
 
@@ -134,6 +136,18 @@ int select_threads(const int64_t W) { return W <= 256 ? 64 : W <= 16384 ? 256 : 
 
 }  // namespace
 
+int m2d_launch_topk_select(m2d_engine *h, const float *scores, const int32_t *ids, int64_t ids_stride, int64_t rows, int64_t W, int32_t d0,
+                           int32_t k, int32_t first, float *out_scores, int32_t *out_ids, int64_t rs, int64_t es, hipStream_t stream)
+{
+    const int threads = select_threads(W);
+    const size_t lds = (size_t)(threads / 64 + 1) * k * (sizeof(uint64_t) + sizeof(uint32_t));
+    M2D_HIP_TRY(h, m2d_lds_limit((const void *)m2d_topk_mlp_select, (int)lds));
+    hipLaunchKernelGGL(m2d_topk_mlp_select, dim3((unsigned)rows), dim3(threads), lds, stream, scores, ids, W, d0, k, first, out_scores, out_ids,
+                       rs, es, ids_stride);
+    M2D_HIP_TRY(h, hipGetLastError());
+    return M2D_OK;
+}
+
 int m2d_launch_topk_users_mlp(m2d_engine *h, const int32_t *users, int64_t nU, int32_t k, int32_t candidates, float *out_scores,
                               int32_t *out_ids, hipStream_t stream)
 {
@@ -150,9 +164,6 @@ int m2d_launch_topk_users_mlp(m2d_engine *h, const int32_t *users, int64_t nU, i
     if (two && (rc = m2d_grow(h, h->topk_mlp_cand, h->topk_mlp_cand_cap, n, sizeof(int32_t))) != M2D_OK) return rc;
     int32_t *users_x = h->topk_mlp_ids, *items_x = users_x + n;
     float *scores = h->topk_mlp_scores;
-    const int threads = select_threads(W);
-    const size_t lds = (size_t)(threads / 64 + 1) * k * (sizeof(uint64_t) + sizeof(uint32_t));
-    M2D_HIP_TRY(h, m2d_lds_limit((const void *)m2d_topk_mlp_select, (int)lds));
     for (int64_t u0 = 0; u0 < nU; u0 += R) {
         const int64_t rows = nU - u0 < R ? nU - u0 : R;
         // stage 1, as m2d_topk_users runs it: the K1 best by the reference / ingredient score (its scores are not kept: the
@@ -168,10 +179,9 @@ int m2d_launch_topk_users_mlp(m2d_engine *h, const int32_t *users, int64_t nU, i
             M2D_HIP_TRY(h, hipGetLastError());
             if ((rc = m2d_launch_score_pairs_mlp(h, users_x, items_x, rows * Wc, scores, stream)) != M2D_OK) return rc;
             ++h->topk_mlp_launches;
-            hipLaunchKernelGGL(m2d_topk_mlp_select, dim3((unsigned)rows), dim3(threads), lds, stream, scores,
-                               two ? (const int32_t *)items_x : nullptr, Wc, (int32_t)d0, k, d0 == 0 ? 1 : 0, out_scores + u0 * k, out_ids + u0 * k,
-                               two ? Wc : (int64_t)1, two ? (int64_t)1 : rows);
-            M2D_HIP_TRY(h, hipGetLastError());
+            if ((rc = m2d_launch_topk_select(h, scores, two ? (const int32_t *)items_x : nullptr, Wc, rows, Wc, (int32_t)d0, k, d0 == 0 ? 1 : 0,
+                                             out_scores + u0 * k, out_ids + u0 * k, two ? Wc : (int64_t)1, two ? (int64_t)1 : rows, stream)) != M2D_OK)
+                return rc;
         }
     }
     return M2D_OK;

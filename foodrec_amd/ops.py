@@ -459,6 +459,42 @@ class ScoringEngine:
         self._topk_mlp_keep = users                      # stays alive until the queued kernels have read it
         return out_s, out_i
 
+    def _slate_ids(self, users: torch.Tensor, slate: torch.Tensor, what: str):
+        for t, name in ((users, "users"), (slate, "slate")):
+            if not isinstance(t, torch.Tensor) or t.dtype != torch.int32 or t.device != self.device:
+                raise TypeError("%s: %s must be an int32 tensor on %s" % (what, name, self.device))
+        return users.contiguous().reshape(-1), slate.contiguous().reshape(-1)
+
+    def score_slate(self, users: torch.Tensor, slate: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """EXTENSION (``m2d_score_slate``, include/m2d.h): the score of every listed user for every dish of one shared slate --
+        users i32[nU] (global ids, repeats allowed), slate i32[nD] strictly ascending dish ids -> f32[nU, nD], row-major.  Masks are
+        the resident dish table.  Does not synchronise; bad ids and a slate that is not ascending surface from ``check()``."""
+        users, slate = self._slate_ids(users, slate, "score_slate")
+        nU, nD = users.numel(), slate.numel()
+        if out is None:
+            out = torch.empty((nU, nD), dtype=torch.float32, device=self.device)
+        elif (tuple(out.shape) != (nU, nD) or out.dtype != torch.float32 or not out.is_contiguous() or out.device != self.device):
+            raise ValueError("score_slate: out must be a contiguous f32[%d, %d] tensor on %s" % (nU, nD, self.device))
+        with torch.cuda.device(self.device):
+            rc = _native.lib().m2d_score_slate(self._h, users.data_ptr(), nU, slate.data_ptr(), nD, out.data_ptr(), _stream_ptr())
+        _native.raise_for(rc, self._h)
+        self._slate_keep = (users, slate)                # inputs stay alive until the queued kernels have read them
+        return out
+
+    def topk_slate(self, users: torch.Tensor, slate: torch.Tensor, k: int):
+        """EXTENSION (``m2d_topk_slate``): the first k of ``topk_users``' order over the slate's dishes only -> (scores f32[nU, k],
+        dish ids i32[nU, k]); a listed score is the word ``score_slate`` writes for that (user, dish).  Does not synchronise."""
+        users, slate = self._slate_ids(users, slate, "topk_slate")
+        nU, nD, k = users.numel(), slate.numel(), int(k)
+        out_s = torch.empty((nU, max(k, 0)), dtype=torch.float32, device=self.device)
+        out_i = torch.empty((nU, max(k, 0)), dtype=torch.int32, device=self.device)
+        with torch.cuda.device(self.device):
+            rc = _native.lib().m2d_topk_slate(self._h, users.data_ptr(), nU, slate.data_ptr(), nD, k, out_s.data_ptr(), out_i.data_ptr(),
+                                              _stream_ptr())
+        _native.raise_for(rc, self._h)
+        self._slate_keep = (users, slate)
+        return out_s, out_i
+
     def catalogue_rank(self, users, items, exclude=None):
         """Full-catalogue rank of held-out dishes (``m2d_catalogue_rank``, include/m2d.h): for each query (users[i], items[i]) the
         number of dishes ranked before items[i] in ``topk_users``' order, leaving out the query's excluded ids.
@@ -612,6 +648,27 @@ def topk_users_mlp_op(engine: int, users: torch.Tensor, k: int, candidates: int 
 
 @topk_users_mlp_op.register_fake
 def _(engine, users, k, candidates=0):
+    return (users.new_empty((users.numel(), k), dtype=torch.float32),
+            users.new_empty((users.numel(), k), dtype=torch.int32))
+
+
+@torch.library.custom_op("m2d::score_slate", mutates_args=(), device_types="cuda")
+def score_slate_op(engine: int, users: torch.Tensor, slate: torch.Tensor) -> torch.Tensor:
+    return _engine(engine).score_slate(users, slate)
+
+
+@score_slate_op.register_fake
+def _(engine, users, slate):
+    return users.new_empty((users.numel(), slate.numel()), dtype=torch.float32)
+
+
+@torch.library.custom_op("m2d::topk_slate", mutates_args=(), device_types="cuda")
+def topk_slate_op(engine: int, users: torch.Tensor, slate: torch.Tensor, k: int) -> tuple[torch.Tensor, torch.Tensor]:
+    return _engine(engine).topk_slate(users, slate, k)
+
+
+@topk_slate_op.register_fake
+def _(engine, users, slate, k):
     return (users.new_empty((users.numel(), k), dtype=torch.float32),
             users.new_empty((users.numel(), k), dtype=torch.int32))
 

@@ -333,7 +333,25 @@ class Model:
 
 
     # -- retrieval and build-defined extensions (no reference counterpart; DESIGN.md sections 4.3-4.4, 8) ---
-    def topk(self, users, k: int = 10, exclude=None, head: bool = False, candidates: int = 0):
+    def _slate(self, users, dishes):
+        """(users, sorted distinct dish ids) as int32 device tensors, and each given dish's column among the distinct ones"""
+        u, d = _ids(users, "user"), _ids(dishes, "item")
+        ut = u.to(self.device, torch.int32) if isinstance(u, torch.Tensor) else torch.from_numpy(u).to(self.device)
+        d = d.cpu().numpy() if isinstance(d, torch.Tensor) else d
+        distinct, col = np.unique(np.asarray(d, dtype=np.int32).reshape(-1), return_inverse=True)
+        return ut, torch.from_numpy(distinct).to(self.device), col.reshape(-1)
+
+    def score_slate(self, users, dishes) -> np.ndarray:
+        """EXTENSION (no reference counterpart): what each of `users` scores for each of `dishes` -- one shared list, the dishes
+        that can be cooked from today's market, a shared negative pool, an editorial list.  Ids as str or int, in any order, repeats
+        allowed; returns float32 [len(users), len(dishes)] with the columns in the order given.  Needs `set_dish_categories`.
+        (``ScoringEngine.score_slate``, which takes the sorted distinct ids.)"""
+        ut, slate, col = self._slate(users, dishes)
+        out = torch.ops.m2d.score_slate(self.engine.id, ut, slate)
+        self.engine.check()
+        return out.cpu().numpy()[:, col]
+
+    def topk(self, users, k: int = 10, exclude=None, head: bool = False, candidates: int = 0, among=None):
         """The k best dishes of every user in `users` over the whole catalogue -- the ranking rule of
         evaluate.py:63 applied to all dishes instead of 51 candidates.  Needs `set_dish_categories`.
         Returns (scores float32 [n, k], dish ids int32 [n, k]).
@@ -345,7 +363,18 @@ class Model:
 
         EXTENSION, `head=True`: the lists under the MLP head (`set_mlp_head`), the score `predict_extended(head=True)` returns --
         `candidates` = 0 scores every dish under the head, K1 = `candidates` >= k reranks the K1 best by the reference score
-        (``ScoringEngine.topk_users_mlp``).  Exclusions under the head are not served: `head=True` with `exclude` raises."""
+        (``ScoringEngine.topk_users_mlp``).  Exclusions under the head are not served: `head=True` with `exclude` raises.
+
+        EXTENSION, `among=dishes`: the k best among those dishes only (str or int ids, any order, repeats ignored;
+        ``ScoringEngine.topk_slate``) -- the same order, the scores `score_slate` returns.  `among` with `exclude` or `head=True`
+        raises."""
+        if among is not None:
+            if exclude is not None or head or candidates:
+                raise ValueError("topk: among together with exclude or head=True (or its candidates) is not supported")
+            ut, slate, _ = self._slate(users, among)
+            s, i = torch.ops.m2d.topk_slate(self.engine.id, ut, slate, int(k))
+            self.engine.check()
+            return s.cpu().numpy(), i.cpu().numpy()
         if head and exclude is not None:
             raise ValueError("topk: head=True together with exclude is not supported (exclusions under the MLP head)")
         if candidates and not head:

@@ -324,11 +324,48 @@ int m2d_rank_candidates_mlp(m2d_engine *h, const int32_t *users, const int32_t *
                             int64_t nseg, int32_t L, int32_t k, float *out_scores, int32_t *out_items,
                             int32_t *out_flags, void *stream);
 
+/* ---- build-defined generalisation, NO reference counterpart (like m2d_topk_users) ----
+ * Slate scoring: many users against ONE shared list of dishes -- the dishes that can be cooked from today's market, a shared negative
+ * pool, an editorial list.  m2d_score_slate writes the whole score matrix, m2d_topk_slate the k best dishes of the slate per user.
+ *
+ * Inputs.  users i32[nU], device memory, global ids: m2d_set_user_base is honoured, users may repeat.  slate i32[nD], device memory,
+ * 1 <= nD <= I, STRICTLY ASCENDING dish ids (the convention of the exclusion lists: "lower column" and "lower dish id" are the same).
+ * A slate id outside [0, I) is latched as M2D_ERR_BAD_ITEM_ID with its index, an entry not greater than its predecessor as
+ * M2D_ERR_INVALID_ARG with its index, a bad user id as M2D_ERR_BAD_USER_ID with its index in `users`; m2d_check reports them as
+ * elsewhere.  The rows of a call with a latched error are unspecified; no kernel reads out of bounds and the engine stays usable.
+ * nU == 0 returns M2D_OK and launches nothing.  nD < 1, nD > I, k < 1, k > min(64, nD) or a null pointer: M2D_ERR_INVALID_ARG.
+ *
+ * Score.  out[i, j] = <flatten(PM[users[i]]), Dt[slate[j]]>, out f32[nU, nD] row-major, Dt[d] computed by exactly the expressions of
+ * the full-catalogue dish vectors (Model_Recommender.py:67-96 in factored form: Dt[d] = concat(a (sum_c m_c CE_c) / n,
+ * (1 - a) (m_c / n) RE[d] for each c), n = sum_c m_c).  One f32 accumulator per (user, dish) starts at +0 and takes one fused
+ * multiply-add per k, in an order of k that depends on E alone: the bits of out[i, j] do not depend on nU, nD, the row's or the
+ * column's position, or how the launcher cuts the work.  Masks are the resident dish table (m2d_set_dish_categories; without it
+ * M2D_ERR_NOT_CONFIGURED), any float weights; a dish with an empty mask gives a NaN column (0 / 0, as everywhere).
+ *
+ * m2d_topk_slate returns the first k of m2d_topk_users' order over the slate only -- score descending, bit-equal scores and -0 / +0 to
+ * the lower dish id, NaN last in id order -- as out_ids i32[nU, k] (dish ids, not columns) / out_scores f32[nU, k]; a listed score is
+ * the word m2d_score_slate writes for that (user, dish), bit for bit.  Users are taken in blocks of max(1, P / nD) rows, P = option
+ * "slate_chunk_pairs": a block's scores go to engine scratch and m2d_topk_mlp_select lists them.  The lists do not depend on P.
+ *
+ * Refused with M2D_ERR_UNSUPPORTED, the condition named in m2d_last_error (m2d_catalogue_rank's precedent): a table value that is not
+ * finite (the engine's "a table value is not finite" word), the ingredient table set, an MLP head set.
+ *
+ * Kernels: m2d_build_slate_vectors writes the slate's dish vectors into engine scratch on every call (the full-catalogue table of
+ * m2d_topk_users is neither built nor read); m2d_score_slate_mfma -- C = 4, E a multiple of 4 up to 256 -- is an LDS-tiled contraction
+ * on the exact-f32 matrix instruction, m2d_score_slate_generic serves every other shape (and "variant" = 9).  m2d_last_kernel names the
+ * scoring kernel.  Neither call synchronises, beyond one read of the not-finite word after a write to the tables (as m2d_topk_users);
+ * after the first call of a size they allocate only on growth. */
+int m2d_score_slate(m2d_engine *h, const int32_t *users, int64_t nU, const int32_t *slate, int64_t nD,
+                    float *out /* f32[nU, nD], row-major */, void *stream);
+int m2d_topk_slate(m2d_engine *h, const int32_t *users, int64_t nU, const int32_t *slate, int64_t nD, int32_t k,
+                   float *out_scores /* [nU, k] */, int32_t *out_ids /* [nU, k] */, void *stream);
+
 /* Synchronise `stream` and report (then clear) the first id error latched by kernels since the
  * previous check: M2D_OK, M2D_ERR_BAD_USER_ID or M2D_ERR_BAD_ITEM_ID.  TF-CPU GatherV2 raises
  * InvalidArgument for such ids; the kernels never read out of bounds and write NaN for the pair.
  * M2D_ERR_INVALID_ARG: an exclusion list of m2d_catalogue_rank / m2d_topk_users_excluding is not ascending (bad_value: the id or offset, bad_index: its
- * position in excl_ids / excl_off).
+ * position in excl_ids / excl_off), or a slate entry of m2d_score_slate / m2d_topk_slate is not above its predecessor (bad_value: the id,
+ * bad_index: its position in the slate).
  * bad_value / bad_index (host pointers, may be NULL) receive the offending id and its position. */
 int m2d_check(m2d_engine *h, void *stream, int64_t *bad_value, int64_t *bad_index);
 
@@ -390,9 +427,11 @@ int m2d_check(m2d_engine *h, void *stream, int64_t *bad_value, int64_t *bad_inde
  *                                        for the users left short and for every other case; 2 = the exact scan for every user.  Same ids, same score bits.
  * topk_mlp_chunk_pairs  4194304  256 ... 2^24  m2d_topk_users_mlp: pairs per head launch (the --workload mlp batch by default); other values are
  *                                        M2D_ERR_INVALID_ARG.  Same ids, same score bits.
+ * slate_chunk_pairs  4194304  256 ... 2^24  m2d_topk_slate: pairs of score scratch one pass may hold (user blocks of max(1, P / nD) rows); other values
+ *                                        are M2D_ERR_INVALID_ARG.  Same ids, same score bits.
  * variant          0        7 9 11 12 13 14 15 16, 100 + n
- *                                        7 / 9: retrieval on the dense MFMA kernel / on the one-block-per-user kernel; 9 also forces the generic pair
- *                                        and head kernels; 11 / 12: the pair kernel's throughput / latency form whatever the batch size; 13: tie
+ *                                        7 / 9: retrieval on the dense MFMA kernel / on the one-block-per-user kernel; 9 also forces the generic pair,
+ *                                        head and slate kernels; 11 / 12: the pair kernel's throughput / latency form whatever the batch size; 13: tie
  *                                        repair's one-block-per-user tier from the third listed user on; 14: the nine-launch training step;
  *                                        15: the retrieval scan's progress-word wait gives up at once (M2D_ERR_KERNEL_TIMEOUT: test hook);
  *                                        16: the MLP head's row offsets in 16-byte units (the instantiation tables of 4 GiB and more take);
