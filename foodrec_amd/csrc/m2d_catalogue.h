@@ -153,6 +153,33 @@ M2D_INTERNAL int m2d_plan_sort_launch(m2d_engine *h, const float *plan, int64_t 
 // sorted dish table, the per-tile largest row norms of that table (h->rank_tnorm, built once per table)
 M2D_INTERNAL int m2d_rank_prepare(m2d_engine *h, const char *entry, hipStream_t st);
 
+// The scratch both calls keep per call of n records: records [n, 8] | bound sums [n, 16] | order [n4] | sort histogram [PLAN_KEYS] |
+// counters [8], carved from `base` (null: the float count alone, to grow the buffer by before it is carved)
+struct RankScratch {
+    float *plan, *bnd;
+    int32_t *order, *hist;
+    unsigned long long *counters;
+    size_t floats;                   // of the whole carve
+};
+inline RankScratch rank_scratch(float *base, const int64_t n)
+{
+    const size_t bnd = (size_t)n * 8, order = bnd + (size_t)n * 16, hist = order + (((size_t)n + 3) & ~(size_t)3), counters = hist + PLAN_KEYS;
+    if (!base) return RankScratch{nullptr, nullptr, nullptr, nullptr, nullptr, counters + 8};
+    return RankScratch{base, base + bnd, reinterpret_cast<int32_t *>(base + order), reinterpret_cast<int32_t *>(base + hist),
+                       reinterpret_cast<unsigned long long *>(base + counters), counters + 8};
+}
+
+// f(W) for the scan of E-float rows: W = std::integral_constant 8 / 16 / 32, the float4 columns a lane of the one-lane form holds
+// (E <= 32 / 64 / 128), or 0, the 16-lane form
+template <typename F>
+void with_rank_width(const int E, F &&f)
+{
+    if (E <= 32) f(std::integral_constant<int, 8>{});
+    else if (E <= 64) f(std::integral_constant<int, 16>{});
+    else if (E <= 128) f(std::integral_constant<int, 32>{});
+    else f(std::integral_constant<int, 0>{});
+}
+
 namespace {
 
 __device__ __forceinline__ bool ahead(float v, float w)
@@ -679,18 +706,141 @@ __device__ __forceinline__ int csr_check_id(const int64_t *off, const int32_t *i
     return r;
 }
 
-// does dish (s, d) precede the held-out (t, p)?  score descending, NaN last, equal scores (NaN included) to the lower id
-__device__ __forceinline__ bool rank_precedes(const float s, const int32_t d, const float t, const int32_t p)
+// is `d` among the ascending ids at(lo) ... at(hi - 1)?  The one lower-bound search of both calls; `at` says where the ids live (a user's
+// segment in HBM, a lane's column of LDS).
+template <typename Pos, typename At>
+__device__ __forceinline__ bool sorted_contains(Pos lo, Pos hi, const int32_t d, At &&at)
 {
-    if (d == p) return false;
+    const Pos end = hi;
+    while (lo < hi) {                                       // first position with an id >= d
+        const Pos mid = (lo + hi) >> 1;
+        if (at(mid) < d) lo = mid + 1; else hi = mid;
+    }
+    return lo < end && at(lo) == d;
+}
+
+// (s, d) before (t, p) in the ranking: score descending, NaN last, equal scores (NaN included) to the lower id
+__device__ __forceinline__ bool rank_before(const float s, const int32_t d, const float t, const int32_t p)
+{
     if (t != t) return s == s || d < p;
     return s > t || (s == t && d < p);
 }
+
+// does dish (s, d) precede the held-out (t, p)?  (p itself does not)
+__device__ __forceinline__ bool rank_precedes(const float s, const int32_t d, const float t, const int32_t p) { return d != p && rank_before(s, d, t, p); }
 
 __device__ __forceinline__ int dish_pattern(const float *cats, const int64_t d)
 {
     const v4f m = *reinterpret_cast<const v4f *>(cats + (size_t)d * 4);
     return (m.x != 0.f ? 1 : 0) | (m.y != 0.f ? 2 : 0) | (m.z != 0.f ? 4 : 0) | (m.w != 0.f ? 8 : 0);
+}
+
+// The tables both calls read: the fields their argument blocks share, filled in one place (after m2d_rank_prepare, which may move tnorm)
+struct RankTables {
+    const float *pm, *re, *ce, *cats;
+    const float *rs, *tnorm;         // the pattern-sorted f32 dish table (row stride ew floats), per-tile largest row norm
+    const int32_t *perm, *tile_info, *grp;
+    int64_t U, I, user_base;
+    int32_t E, ew;
+    float a, b;
+    int32_t *err;
+};
+inline RankTables rank_tables(const m2d_engine *h)
+{
+    RankTables t;
+    t.pm = h->pm; t.re = h->re; t.ce = h->ce; t.cats = h->dish_cats; t.rs = h->grp_rs; t.tnorm = h->rank_tnorm;
+    t.perm = h->grp_perm; t.tile_info = h->grp_tile_info; t.grp = grouped_grp(h);
+    t.U = h->U; t.I = h->I; t.user_base = h->user_base; t.E = h->E; t.ew = h->grp_ew; t.a = h->a; t.b = h->b; t.err = h->err_dev;
+    return t;
+}
+
+// User uid's Personal_Memory block; an id outside the table reads row 0 (the kernels that meet a user first latch the error themselves,
+// the ones behind them do not report it again).  A lane without a user passes user_base.
+__device__ __forceinline__ const v4f *user_block(const RankTables &t, const int64_t uid)
+{
+    int64_t ul = uid - t.user_base;
+    if (ul < 0 || ul >= t.U) ul = 0;
+    return reinterpret_cast<const v4f *>(t.pm) + (size_t)ul * (5 * (t.E >> 2));
+}
+
+// The record a plan kernel leaves per query (m2d_catalogue_rank) or per short user (m2d_topk_users_excluding) for the kernels behind
+// it, in two arrays:
+//   plan[i * 8 + 0]      s     s*, the held-out dish's score / the seed, the threshold a list starts from      [1..4]  hc  <U_high, CE_c>
+//   plan[i * 8 + 5]      mask  the patterns to visit, bits 1..15 -- the word m2d_plan_sort_launch sorts by (plan_key)
+//   plan[i * 8 + 6]      id    the held-out dish p / the user's position in the call (-1: a record without a user)
+//   plan[i * 8 + 7]      tag   p's own pattern / 0
+//   bnd[i * 16 + 0..3]   ha    sum |U_high CE_c|           bnd[i * 16 + 4..13]  G  the Gram matrix of the U_low rows
+// Everything that touches a word by its index is below.
+struct RankRecord {
+    float s, hc[4];
+    uint32_t mask;
+    int32_t id, tag;
+    float ha[4], G[10];
+};
+
+// by the 16 lanes that all hold the sums (j = lane & 15): lane 0 the plan words, lanes 0..3 ha, lanes 0..9 G
+__device__ __forceinline__ void record_store(float *plan, float *bnd, const int64_t i, const int j, const float s, const float (&hc)[4],
+                                             const uint32_t mask, const int32_t id, const int32_t tag, const float (&ha)[4], const float (&G)[10])
+{
+    if (j == 0) {
+        float *o = plan + (size_t)i * 8;
+        o[0] = s; o[1] = hc[0]; o[2] = hc[1]; o[3] = hc[2]; o[4] = hc[3]; o[5] = __uint_as_float(mask);
+        o[6] = __int_as_float(id); o[7] = __int_as_float(tag);
+    }
+    if (j < 4) bnd[(size_t)i * 16 + j] = ha[j];
+    if (j < 10) bnd[(size_t)i * 16 + 4 + j] = G[j];
+}
+
+// a record without a user, by lanes 0..7: an empty mask, id -1; its bound sums are never read
+__device__ __forceinline__ void record_store_none(float *plan, const int64_t i, const int j) { if (j < 8) plan[(size_t)i * 8 + j] = j == 6 ? __int_as_float(-1) : 0.f; }
+
+// (a reader that leaves ha and G alone pays nothing for them: the loads go with their uses)
+__device__ __forceinline__ RankRecord record_load(const float *plan, const float *bnd, const int64_t i)
+{
+    const float *rec = plan + (size_t)i * 8, *sums = bnd + (size_t)i * 16;
+    RankRecord r;
+    r.s = rec[0]; r.mask = __float_as_uint(rec[5]); r.id = __float_as_int(rec[6]); r.tag = __float_as_int(rec[7]);
+#pragma unroll
+    for (int c = 0; c < 4; ++c) { r.hc[c] = rec[1 + c]; r.ha[c] = sums[c]; }
+#pragma unroll
+    for (int c = 0; c < 10; ++c) r.G[c] = sums[4 + c];
+    return r;
+}
+__device__ __forceinline__ int32_t record_id(const float *plan, const int64_t i) { return __float_as_int(plan[(size_t)i * 8 + 6]); }
+
+// Shares: the T units of an item (the tiles of a wave's patterns, a query's rows) are cut into nsplit runs of equal length, share
+// `split` is [t0, t1) (empty past the end); share_count: as many shares as fill `want` waves or groups from `units` items, 1 ... 512.
+__device__ __forceinline__ void share_of(const int64_t T, const int nsplit, const int split, int64_t &t0, int64_t &t1)
+{
+    const int64_t per = (T + nsplit - 1) / nsplit;
+    t0 = (int64_t)split * per;
+    t1 = t0 + per < T ? t0 + per : T;
+}
+__host__ __device__ __forceinline__ int share_count(const int64_t want, const int64_t units)
+{
+    const int64_t ns = (want + units - 1) / units;
+    return (int)(ns < 1 ? 1 : (ns > 512 ? 512 : ns));
+}
+
+// 32-row tiles of the patterns in `set` (wave- or group-uniform)
+__device__ __forceinline__ int64_t pattern_set_tiles(const int32_t *grp, const uint32_t set)
+{
+    int64_t T = 0;
+    for (int q = 1; q < GRP_MAXPAT; ++q) T += ((set >> q) & 1u) ? (grp[40 + q] + 31) >> 5 : 0;
+    return T;
+}
+
+// Pattern q's tiles, taken after `cum` tiles of the patterns before it, clipped to the share [t0, t1): tiles [tile0, tile1) of the
+// sorted table, false if none; cum moves past the pattern either way.
+__device__ __forceinline__ bool pattern_span(const int32_t *grp, const int q, const int64_t t0, const int64_t t1, int64_t &cum, int64_t &tile0,
+                                             int64_t &tile1)
+{
+    const int64_t nt = (grp[40 + q] + 31) >> 5;
+    const int64_t lo_t = t0 > cum ? t0 : cum, hi_t = t1 < cum + nt ? t1 : cum + nt;
+    const int64_t tfirst = (grp[q] >> 5) - cum;
+    cum += nt;
+    tile0 = tfirst + lo_t; tile1 = tfirst + hi_t;
+    return lo_t < hi_t;
 }
 
 // A user's sums from 16 lanes (j = lane & 15), every lane returning the same bits: <U_high, CE_c> (hc) bit for bit as
@@ -786,6 +936,50 @@ __device__ __forceinline__ float rank_exact_score16(const v4f *pmu, const float 
     }
     lo = row16_sum(lo);
     return repair_score_planned(repair_alpha(a, hc, pt), b, lo / (float)__builtin_popcount(pt));
+}
+
+// The wave walk of the one-lane scans (m2d_rank_count, m2d_topk_excl_scan; E <= 128).  A wave holds 64 sorted records, one per lane
+// (rec; pmu: the lane's user block), and share [t0, t1) of the tiles of the patterns `um`, the union of its lanes' masks, counted in
+// the order the patterns are taken in: order(avail) names the next one of the wave-uniform set `avail`.  Per pattern the lane's bound
+// terms, alpha_P and w_P (in registers); per tile the lane's bound with the tile's largest row norm in the pattern's place, and
+// tile(q, blo, bhi, nrows): does this lane need the tile's rows scored?  A tile some lane needs is multiplied for all, a row at a
+// time -- the row and its id are wave-uniform (scalar loads) -- and every lane gets row(score, id, need).  What a lane decides about
+// a tile and does with a score is the caller's; both must inline (no indirect call, no scratch).  Returns the tiles multiplied.
+template <int E4MAX, typename Order, typename Tile, typename Row>
+__device__ __forceinline__ unsigned long long walk_tiles(const RankTables &p, const v4f *pmu, const RankRecord &rec, const uint32_t um,
+                                                         const int64_t t0, const int64_t t1, Order &&order, Tile &&tile_fn, Row &&row_fn)
+{
+    const int E4 = p.E >> 2, EW4 = p.ew >> 2;
+    const v4f *rows4 = reinterpret_cast<const v4f *>(p.rs);
+    unsigned long long multiplied = 0ull;
+    uint32_t avail = um;
+    int64_t cum = 0;
+    while (avail != 0u && cum < t1) {                       // wave-uniform
+        const int q = order(avail);
+        if (q < 0) break;
+        avail &= ~(1u << q);
+        int64_t tile, tile1;
+        if (!pattern_span(p.grp, q, t0, t1, cum, tile, tile1)) continue;
+        const PatternBoundTerms rb = pattern_bound_terms(rec.hc, rec.ha, rec.G, q, p.a, p.b, p.E);
+        const float alpha = repair_alpha(p.a, rec.hc, q);
+        const float npat = (float)__builtin_popcount(q);
+        v4f w[E4MAX];
+        rank_pattern_weights<E4MAX>(w, pmu, E4, q);
+        for (; tile < tile1; ++tile) {
+            const int nrows = p.tile_info[tile] >> 8;
+            float blo, bhi;
+            pattern_bound(rb, p.tnorm[tile], blo, bhi);
+            const bool need = tile_fn(q, blo, bhi, nrows);
+            if (__ballot(need) == 0ull) continue;
+            multiplied += 1ull;
+            for (int r = 0; r < nrows; ++r) {
+                const int64_t slot = tile * 32 + r;
+                const int32_t id = __builtin_amdgcn_readfirstlane(p.perm[slot]);
+                row_fn(rank_exact_score_lane<E4MAX>(w, rows4 + (size_t)slot * EW4, E4, alpha, p.b, npat), id, need);
+            }
+        }
+    }
+    return multiplied;
 }
 
 #ifndef M2D_TOPK_HALF_BLOCKS

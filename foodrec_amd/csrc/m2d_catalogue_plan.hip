@@ -374,6 +374,7 @@ __global__ __launch_bounds__(256) void m2d_topk_user_plan(const float *pm, const
 // pass; one per wave and distinct mask, found with ballots: 50 us).  Now a workgroup counts its users in a 128-KiB LDS table
 // of all 32 768 keys and adds only the table's non-zero entries to the global counts; the scatter reserves a range per
 // non-zero entry the same way and places its users inside the ranges with LDS atomics.
+// (word 5 of an 8-float record: the mask of m2d_topk_user_plan's records and of the ranking scans' RankRecord, m2d_catalogue.h, alike)
 __device__ __forceinline__ int plan_key(const float *plan, const int64_t u)
 {
     return (int)((__float_as_uint(plan[(size_t)u * 8 + 5]) >> 1) & (PLAN_KEYS - 1));
