@@ -138,6 +138,12 @@ void release(m2d_engine *h)
         if (h->ing_ids) (void)hipFree((void *)h->ing_ids);
         if (h->ing_w) (void)hipFree((void *)h->ing_w);
     }
+    if (h->own_rcp) {
+        if (h->rcp_off) (void)hipFree((void *)h->rcp_off);
+        if (h->rcp_ids) (void)hipFree((void *)h->rcp_ids);
+    }
+    if (h->market_buf) (void)hipFree(h->market_buf);
+    if (h->market_count_host) (void)hipHostFree(h->market_count_host);
     if (h->scratch) (void)hipFree(h->scratch);
     if (h->topk_flags) (void)hipFree(h->topk_flags);
     if (h->topk_plan) (void)hipFree(h->topk_plan);
@@ -636,6 +642,77 @@ int m2d_set_ingredients(m2d_engine *h, const float *ing, int64_t R, const int32_
     }
     m2d_mark_written(h, M2D_TAB_ING, M2D_BY_CALLER);       // H[d] is part of the scan
     return M2D_OK;
+}
+
+int m2d_clear_recipes(m2d_engine *h)
+{
+    if (!h) return M2D_ERR_INVALID_ARG;
+    (void)hipSetDevice(h->device);
+    (void)hipDeviceSynchronize();
+    if (h->own_rcp) {
+        if (h->rcp_off) (void)hipFree((void *)h->rcp_off);
+        if (h->rcp_ids) (void)hipFree((void *)h->rcp_ids);
+    }
+    h->rcp_off = nullptr; h->rcp_ids = nullptr;
+    h->rcp_set = h->own_rcp = false; h->rcp_rows = 0; h->rcp_nnz = 0;
+    return M2D_OK;
+}
+
+int m2d_set_recipes(m2d_engine *h, int64_t R, const int32_t *off, const int32_t *ids, int64_t nnz, int32_t flags)
+{
+    if (!h || !off || (!ids && nnz > 0) || R < 1 || R > INT32_MAX || nnz < 0 || nnz > INT32_MAX)
+        return fail(h, M2D_ERR_INVALID_ARG, "m2d_set_recipes: bad argument (need 1 <= R, 0 <= nnz, both within int32, offsets, and ids where nnz > 0)");
+    if (flags != M2D_TABLES_HOST && flags != M2D_TABLES_DEVICE) return fail(h, M2D_ERR_INVALID_ARG, "m2d_set_recipes: bad flags");
+    // an id error latched by an earlier launch is reported as what it is, before the checks below can mislabel it
+    int rc = m2d_check(h, nullptr, nullptr, nullptr);
+    if (rc != M2D_OK) return rc;
+    if ((rc = m2d_clear_recipes(h)) != M2D_OK) return rc;
+    M2D_HIP_TRY(h, hipSetDevice(h->device));
+    if (flags == M2D_TABLES_DEVICE) {
+        h->rcp_off = off; h->rcp_ids = ids;
+    } else {
+        bool own = false;
+        const float *t = nullptr;
+        h->own_rcp = true;
+        if ((rc = adopt_table(h, reinterpret_cast<const float *>(off), (size_t)h->I + 1, flags, &t, &own)) != M2D_OK) return rc;
+        h->rcp_off = reinterpret_cast<const int32_t *>(t);
+        if (nnz > 0) {
+            if ((rc = adopt_table(h, reinterpret_cast<const float *>(ids), (size_t)nnz, flags, &t, &own)) != M2D_OK) {
+                (void)m2d_clear_recipes(h);
+                return rc;
+            }
+            h->rcp_ids = reinterpret_cast<const int32_t *>(t);
+        }
+    }
+    // the row pointer first: the id pass reads ids[0, nnz) only, but nothing may call the lists valid before both have passed
+    // (every failure from here on leaves the recipes unset; one that is not the check's own finding -- a HIP error -- keeps its code)
+    auto unset = [&](int code, const std::string &msg) {
+        (void)m2d_clear_recipes(h);
+        h->last_error = "m2d_set_recipes: " + msg;
+        return code;
+    };
+    if ((rc = m2d_launch_check_csr(h, h->rcp_off, nnz, nullptr)) != M2D_OK) return unset(rc, h->last_error);
+    if ((rc = m2d_check(h, nullptr, nullptr, nullptr)) != M2D_OK)
+        return rc == M2D_ERR_BAD_INGREDIENT ? unset(rc, "offsets are not a CSR row pointer (off[0] = 0, non-decreasing, off[I] = nnz)")
+                                            : unset(rc, h->last_error);
+    if ((rc = m2d_launch_check_recipe_ids(h, h->rcp_ids, nnz, R, nullptr)) != M2D_OK) return unset(rc, h->last_error);
+    if ((rc = m2d_check(h, nullptr, nullptr, nullptr)) != M2D_OK) return unset(rc, h->last_error);
+    h->rcp_rows = R;
+    h->rcp_nnz = nnz;
+    h->rcp_set = true;
+    return M2D_OK;
+}
+
+int m2d_cookable_dishes(m2d_engine *h, const int32_t *market, int64_t nM, int32_t max_missing, int32_t *out_ids, int32_t *out_missing,
+                        int64_t *out_count, void *stream)
+{
+    if (!h) return M2D_ERR_INVALID_ARG;
+    if (nM < 0 || nM > INT32_MAX || max_missing < 0)
+        return fail(h, M2D_ERR_INVALID_ARG, "m2d_cookable_dishes: need 0 <= nM < 2^31 and max_missing >= 0");
+    if ((!market && nM > 0) || !out_ids || !out_count) return fail(h, M2D_ERR_INVALID_ARG, "m2d_cookable_dishes: null buffer");
+    if (!h->rcp_set) return fail(h, M2D_ERR_NOT_CONFIGURED, "call m2d_set_recipes first");
+    M2D_HIP_TRY(h, hipSetDevice(h->device));
+    return m2d_launch_cookable(h, market, nM, max_missing, out_ids, out_missing, out_count, (hipStream_t)stream);
 }
 
 int m2d_score_pairs_ingredients(m2d_engine *h, const int32_t *users, const int32_t *items, const float *cats,

@@ -84,6 +84,18 @@ struct m2d_engine {
     size_t slate_dt_cap = 0, slate_scores_cap = 0;   // floats
     int64_t opt_slate_chunk_pairs = 1 << 22;         // pairs of score scratch per m2d_topk_slate pass (the lists do not depend on it)
 
+    // m2d_set_recipes / m2d_cookable_dishes (m2d_market.hip): every dish's ingredient list, CSR, validated once by the setter (CSR
+    // shape, every id in [0, R)); lists only -- no table, no weights, nothing the scoring path reads, and no tie to `ing` above.
+    // market_buf: the call's scratch -- bitmap of R bits | missing[I] (unless the caller gives a buffer) | kept dishes per block |
+    // their exclusive scan | the total (8 bytes)
+    const int32_t *rcp_off = nullptr;  // [I+1]
+    const int32_t *rcp_ids = nullptr;  // [nnz]
+    bool rcp_set = false, own_rcp = false;
+    int64_t rcp_rows = 0, rcp_nnz = 0;
+    int32_t *market_buf = nullptr;
+    size_t market_cap = 0;             // ints
+    int64_t *market_count_host = nullptr;   // pinned: the count of the last call
+
     // derived table for pair scoring: <U_high[u], CE_c> per user and category (built lazily by large m2d_score_pairs calls;
     // stale after any write to Personal_Memory / Category_Embedding: the engine's own writers and m2d_tables_updated reset it)
     float *user_high = nullptr;  // [U, 4]
@@ -358,7 +370,12 @@ int m2d_launch_rows_finite_check(m2d_engine *h, const int32_t *users, int64_t B,
 int m2d_launch_build_dish_high(m2d_engine *h, hipStream_t stream);
 int m2d_ensure_user_high(m2d_engine *h, hipStream_t stream);
 int m2d_ensure_pm_bf16(m2d_engine *h, hipStream_t stream);
-int m2d_launch_check_csr(m2d_engine *h, hipStream_t stream);
+int m2d_launch_check_csr(m2d_engine *h, hipStream_t stream);                                          // the ingredient table's offsets
+int m2d_launch_check_csr(m2d_engine *h, const int32_t *off, int64_t nnz, hipStream_t stream);        // any row pointer of I + 1 entries
+// m2d_market.hip: latches the first recipe id outside [0, R); the filter behind m2d_cookable_dishes
+int m2d_launch_check_recipe_ids(m2d_engine *h, const int32_t *ids, int64_t nnz, int64_t R, hipStream_t stream);
+int m2d_launch_cookable(m2d_engine *h, const int32_t *market, int64_t nM, int32_t max_missing, int32_t *out_ids, int32_t *out_missing,
+                        int64_t *out_count, hipStream_t stream);
 int m2d_ensure_dish_vectors(m2d_engine *h, hipStream_t stream);
 int m2d_launch_write_memory(m2d_engine *h, const int32_t *users, const int32_t *items, const float *cats,
                             const float *sign, const float *labels, int64_t B, int32_t L, float *gm, float beta_1,

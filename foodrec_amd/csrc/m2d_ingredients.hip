@@ -134,13 +134,14 @@ __global__ void m2d_check_csr(const int32_t *off, int64_t I, int64_t nnz, int32_
 
 }  // namespace
 
-int m2d_launch_check_csr(m2d_engine *h, hipStream_t stream)
+int m2d_launch_check_csr(m2d_engine *h, const int32_t *off, int64_t nnz, hipStream_t stream)
 {
-    hipLaunchKernelGGL(m2d_check_csr, dim3((unsigned)((h->I + 256) / 256)), dim3(256), 0, stream, h->ing_off, h->I,
-                       h->ing_nnz, h->err_dev);
+    hipLaunchKernelGGL(m2d_check_csr, dim3((unsigned)((h->I + 256) / 256)), dim3(256), 0, stream, off, h->I, nnz, h->err_dev);
     M2D_HIP_TRY(h, hipGetLastError());
     return M2D_OK;
 }
+
+int m2d_launch_check_csr(m2d_engine *h, hipStream_t stream) { return m2d_launch_check_csr(h, h->ing_off, h->ing_nnz, stream); }
 
 int m2d_launch_build_dish_high(m2d_engine *h, hipStream_t stream)
 {

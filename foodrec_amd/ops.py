@@ -495,6 +495,78 @@ class ScoringEngine:
         self._slate_keep = (users, slate)
         return out_s, out_i
 
+    # -- market retrieval (include/m2d.h, "Market retrieval") -------------------------------------------
+    def set_recipes(self, offsets, ids, num_ingredients: int):
+        """EXTENSION (``m2d_set_recipes``): every dish's ingredient list, CSR -- offsets i32[I + 1], ids i32[nnz] in
+        [0, num_ingredients).  Lists only, independent of ``set_ingredients``.  Validated once, here (synchronises): a malformed row
+        pointer or an id out of range raises IndexError and leaves the recipes unset; a call refused before that -- a bad argument, an id
+        error still latched from an earlier launch -- leaves the previous lists set and served."""
+        off, idt = self._as_ids(offsets, "offset"), self._as_ids(ids, "ingredient")
+        if off.numel() != self.I + 1:
+            raise ValueError("offsets must have I + 1 = %d entries" % (self.I + 1))
+        with torch.cuda.device(self.device):
+            rc = _native.lib().m2d_set_recipes(self._h, int(num_ingredients), off.data_ptr(), idt.data_ptr() if idt.numel() else None,
+                                               idt.numel(), _native.M2D_TABLES_DEVICE)
+        # a call refused for its arguments, or for an id error latched earlier, leaves the previous lists in place -- and borrowed:
+        # their tensors are let go of only once the engine holds the new ones
+        _native.raise_for(rc, self._h)
+        self._recipes = (off, idt)                       # keep the borrowed device buffers alive
+
+    def clear_recipes(self):
+        _native.raise_for(_native.lib().m2d_clear_recipes(self._h), self._h)
+        self._recipes = None
+
+    def cookable_dishes(self, market, max_missing: int = 0, return_missing: bool = False, out_ids: Optional[torch.Tensor] = None,
+                        out_missing: Optional[torch.Tensor] = None):
+        """EXTENSION (``m2d_cookable_dishes``): the dishes that can be cooked from `market` -- ingredient ids, an int32 device tensor
+        or any id sequence, any order, repeats allowed, may be empty -- as an int32 device tensor [count] in strictly ascending order: a
+        legal slate.  A dish is cookable iff its list is non-empty and at most `max_missing` of its list entries (every occurrence
+        counted) are not in the market.  ``return_missing=True`` also returns int32 [I]: every dish's missing-entry count, -1 for an
+        empty list.  `out_ids` / `out_missing`: caller-owned contiguous int32 [I] buffers to write into (the result is then a view of
+        `out_ids`; words from `count` on are not written).
+
+        SYNCHRONISES the current stream once, for the count; a market id out of range raises IndexError (value and index named) from
+        this call.  No ``torch.library`` op is registered for it: the output length depends on the data, which a registered op's
+        fake kernel cannot state."""
+        market = self._as_ids(market, "ingredient")
+        for t, name in ((out_ids, "out_ids"), (out_missing, "out_missing")):
+            if t is not None and (t.dtype != torch.int32 or t.device != self.device or not t.is_contiguous() or t.numel() != self.I):
+                raise ValueError("cookable_dishes: %s must be a contiguous int32[%d] tensor on %s" % (name, self.I, self.device))
+        if out_ids is None:
+            out_ids = torch.empty(self.I, dtype=torch.int32, device=self.device)
+        if out_missing is None and return_missing:
+            out_missing = torch.empty(self.I, dtype=torch.int32, device=self.device)
+        count = ctypes.c_int64(0)
+        with torch.cuda.device(self.device):
+            rc = _native.lib().m2d_cookable_dishes(self._h, market.data_ptr() if market.numel() else None, market.numel(), int(max_missing),
+                                                   out_ids.data_ptr(), out_missing.data_ptr() if out_missing is not None else None,
+                                                   ctypes.byref(count), _stream_ptr())
+        _native.raise_for(rc, self._h)
+        ids = out_ids.reshape(-1)[:count.value]
+        return (ids, out_missing) if return_missing else ids
+
+    def topk_market(self, users, market, k: int, max_missing: int = 0):
+        """EXTENSION: the k best dishes per user among those that can be cooked from `market` -- ``cookable_dishes``, then
+        ``topk_slate`` over that list with min(k, count) -> (scores f32[nU, k], dish ids i32[nU, k], count).  Columns from `count` on
+        hold NaN / -1 (``topk_users_excluding``'s convention when fewer than k dishes remain); count = 0 returns all NaN / -1 without
+        calling the slate.  1 <= k <= 64.  The scoring step is ``topk_slate``'s, requirements and refusals unchanged: dish masks
+        set, finite tables, no ingredient table, no MLP head.  Synchronises once (the count)."""
+        if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or not 1 <= int(k) <= 64:
+            raise ValueError("topk_market: k must be an int in 1..64, got %r" % (k,))
+        users, k = self._as_ids(users, "user"), int(k)
+        slate = self.cookable_dishes(market, max_missing)
+        count, nU = slate.numel(), users.numel()
+        if count >= k and nU:
+            return self.topk_slate(users, slate, k) + (count,)
+        out_s = torch.full((nU, k), float("nan"), dtype=torch.float32, device=self.device)
+        out_i = torch.full((nU, k), -1, dtype=torch.int32, device=self.device)
+        if count and nU:
+            kk = min(k, count)
+            s, i = self.topk_slate(users, slate, kk)
+            out_s[:, :kk] = s
+            out_i[:, :kk] = i
+        return out_s, out_i, count
+
     def catalogue_rank(self, users, items, exclude=None):
         """Full-catalogue rank of held-out dishes (``m2d_catalogue_rank``, include/m2d.h): for each query (users[i], items[i]) the
         number of dishes ranked before items[i] in ``topk_users``' order, leaving out the query's excluded ids.

@@ -351,7 +351,37 @@ class Model:
         self.engine.check()
         return out.cpu().numpy()[:, col]
 
-    def topk(self, users, k: int = 10, exclude=None, head: bool = False, candidates: int = 0, among=None):
+    def set_recipes(self, dish_to_ingredients, num_ingredients: int):
+        """EXTENSION: every dish's ingredient list, for `cookable` and `topk(market=...)` -- a dict ``{str(dish): [ingredient ids]}``
+        (dishes missing from it get an empty list and are never cookable; a key outside the catalogue raises IndexError) or an ``(offsets, ids)`` CSR pair; ids in
+        [0, num_ingredients), repeats allowed.  Independent of `set_ingredients`.  (``ScoringEngine.set_recipes``.)"""
+        I = self.engine.I
+        if isinstance(dish_to_ingredients, dict):
+            lists = [()] * I
+            for key, val in dish_to_ingredients.items():
+                d = int(key)
+                if not 0 <= d < I:
+                    raise IndexError("set_recipes: dish id %d is outside the catalogue [0, %d)" % (d, I))
+                lists[d] = val
+            off = np.zeros(I + 1, dtype=np.int64)
+            np.cumsum([len(l) for l in lists], out=off[1:])
+            ids = _ids([v for l in lists for v in l], "ingredient")
+            if off[-1] >= 2 ** 31:
+                raise ValueError("set_recipes: more than 2^31 - 1 list entries")
+            off = off.astype(np.int32)
+        else:
+            off, ids = dish_to_ingredients
+        self.engine.set_recipes(off, ids, num_ingredients)
+
+    def cookable(self, market, max_missing: int = 0) -> np.ndarray:
+        """EXTENSION: the dishes that can be cooked from `market` (ingredient ids as str or int, any order, repeats allowed) with at
+        most `max_missing` list entries absent, as a sorted numpy int32 array.  Needs `set_recipes`."""
+        m = _ids(market, "ingredient")
+        mt = m.to(self.device, torch.int32) if isinstance(m, torch.Tensor) else torch.from_numpy(m).to(self.device)
+        return self.engine.cookable_dishes(mt, max_missing).cpu().numpy()
+
+    def topk(self, users, k: int = 10, exclude=None, head: bool = False, candidates: int = 0, among=None, market=None,
+             max_missing: int = 0):
         """The k best dishes of every user in `users` over the whole catalogue -- the ranking rule of
         evaluate.py:63 applied to all dishes instead of 51 candidates.  Needs `set_dish_categories`.
         Returns (scores float32 [n, k], dish ids int32 [n, k]).
@@ -367,7 +397,20 @@ class Model:
 
         EXTENSION, `among=dishes`: the k best among those dishes only (str or int ids, any order, repeats ignored;
         ``ScoringEngine.topk_slate``) -- the same order, the scores `score_slate` returns.  `among` with `exclude` or `head=True`
-        raises."""
+        raises.
+
+        EXTENSION, `market=ingredients`: the k best among the dishes that can be cooked from those ingredients (`set_recipes`;
+        `cookable(market, max_missing)` is the list), k <= 64 -- ``ScoringEngine.topk_market``: `among`'s order and scores; rows end in
+        id -1 / NaN when fewer than k dishes are cookable.  `market` with `exclude`, `head=True`, `candidates` or `among` raises."""
+        if market is not None:
+            for name, given in (("exclude", exclude is not None), ("head=True", head), ("candidates", bool(candidates)), ("among", among is not None)):
+                if given:
+                    raise ValueError("topk: market together with %s is not supported" % name)
+            u, m = _ids(users, "user"), _ids(market, "ingredient")
+            dev = lambda a: a.to(self.device, torch.int32) if isinstance(a, torch.Tensor) else torch.from_numpy(a).to(self.device)
+            s, i, _ = self.engine.topk_market(dev(u), dev(m), k, max_missing)
+            self.engine.check()
+            return s.cpu().numpy(), i.cpu().numpy()
         if among is not None:
             if exclude is not None or head or candidates:
                 raise ValueError("topk: among together with exclude or head=True (or its candidates) is not supported")

@@ -360,6 +360,50 @@ int m2d_score_slate(m2d_engine *h, const int32_t *users, int64_t nU, const int32
 int m2d_topk_slate(m2d_engine *h, const int32_t *users, int64_t nU, const int32_t *slate, int64_t nD, int32_t k,
                    float *out_scores /* [nU, k] */, int32_t *out_ids /* [nU, k] */, void *stream);
 
+/* ---- build-defined extension, NO reference counterpart ----
+ * Market retrieval: from the ingredients seen at the market to the dishes that can be cooked from them -- the slate the calls above
+ * were written for.  m2d_set_recipes makes every dish's ingredient list resident, m2d_cookable_dishes turns a market into the
+ * ascending list of cookable dishes, which m2d_score_slate / m2d_topk_slate take as it stands.
+ *
+ * Recipe lists.  off i32[I+1], ids i32[nnz]: dish d's list is ids[off[d] .. off[d+1]), ingredient ids in [0, R), repeats allowed,
+ * any order.  R >= 1; nnz = 0 is legal (nothing is ever cookable).  Lists only: no embedding table, no weights.  They are separate
+ * from m2d_set_ingredients -- setting or clearing one never touches the other, no scoring call reads the recipes, and the recipes
+ * do not make m2d_score_slate / m2d_topk_slate refuse.  `flags`: M2D_TABLES_DEVICE borrows both arrays (they must stay valid and
+ * unchanged), M2D_TABLES_HOST copies them.  The call validates once and synchronises, as m2d_set_ingredients does: offsets that are
+ * not a CSR row pointer (off[0] = 0, non-decreasing, off[I] = nnz) and an id outside [0, R) (value and position in m2d_last_error)
+ * return M2D_ERR_BAD_INGREDIENT and leave the recipes UNSET, and so does a HIP error met on the way (under M2D_ERR_HIP, its own
+ * text kept).  A call refused BEFORE anything is replaced leaves the previous recipes set and served, its borrowed arrays still
+ * borrowed: M2D_ERR_INVALID_ARG (below), and an id error still latched from an earlier launch, which is returned first, under its
+ * own code.  No later kernel range-checks a recipe id.  A second m2d_set_recipes replaces the first; m2d_clear_recipes
+ * returns the engine to "not configured"; m2d_destroy frees owned copies.  R > INT32_MAX, nnz > INT32_MAX, a null pointer or bad
+ * flags: M2D_ERR_INVALID_ARG.
+ *
+ * m2d_cookable_dishes.  Dish d is cookable iff its list is non-empty and the number of its list ENTRIES whose id is not in the
+ * market is <= max_missing -- every occurrence counts, an id listed twice and absent counts twice.
+ * market i32[nM], device memory: ingredient ids in any order, repeats allowed, nM = 0 allowed (market may then be null).  A market
+ * id outside [0, R) is latched as M2D_ERR_BAD_INGREDIENT with its value and index and contributes nothing.  max_missing < 0,
+ * nM < 0 or a null out_ids / out_count: M2D_ERR_INVALID_ARG.  No recipes set: M2D_ERR_NOT_CONFIGURED.
+ * out_ids i32, device memory, capacity I: out_ids[0 .. count) receives the cookable dishes in STRICTLY ASCENDING order;
+ * out_ids[count .. I) is not written.  out_missing i32[I], device memory, may be null: the missing-entry count of EVERY dish, -1 for
+ * an empty list.  *out_count (HOST memory) receives count.
+ * THE CALL SYNCHRONISES `stream` ONCE, for the count; everything else is stream-ordered.  Because it waits anyway it reads the
+ * id-error latch in the same wait and returns what m2d_check would (and clears the latch): a bad market id comes back from this
+ * call as M2D_ERR_BAD_INGREDIENT -- the outputs are then those of the market without the bad ids -- and an error latched by an
+ * earlier, unchecked launch comes back under its own code.
+ *
+ * Kernels, in engine scratch that grows on demand: the market as a bitmap of R bits (a memset, then m2d_market_bitmap: atomicOr on
+ * 32-bit words); m2d_market_flag, in which a wave owns 64 consecutive dishes -- one contiguous run of `ids`, read coalesced 64 entries
+ * a batch, the bitmap in LDS up to 65 536 bits (m2d_market_flag_lds) and read through L2 beyond (m2d_market_flag_l2) -- and writes
+ * missing[d] and one kept-count per block of 256 dishes; m2d_market_scan, the exclusive scan of those counts; m2d_market_write, in
+ * which every block ranks its kept dishes and stores their ids from its base on.  The order is fixed by construction: no atomic
+ * cursor, no sort, and no block waits for another -- four launches give the ordering.  m2d_last_kernel names the flag kernel. */
+int m2d_set_recipes(m2d_engine *h, int64_t R, const int32_t *off /* [I+1] */, const int32_t *ids /* [nnz] */, int64_t nnz,
+                    int32_t flags);
+int m2d_clear_recipes(m2d_engine *h);
+int m2d_cookable_dishes(m2d_engine *h, const int32_t *market /* device, [nM] */, int64_t nM, int32_t max_missing,
+                        int32_t *out_ids /* device, capacity I */, int32_t *out_missing /* device, [I], may be null */,
+                        int64_t *out_count /* HOST */, void *stream);
+
 /* Synchronise `stream` and report (then clear) the first id error latched by kernels since the
  * previous check: M2D_OK, M2D_ERR_BAD_USER_ID or M2D_ERR_BAD_ITEM_ID.  TF-CPU GatherV2 raises
  * InvalidArgument for such ids; the kernels never read out of bounds and write NaN for the pair.
