@@ -143,6 +143,7 @@ void release(m2d_engine *h)
         if (h->rcp_ids) (void)hipFree((void *)h->rcp_ids);
     }
     if (h->market_buf) (void)hipFree(h->market_buf);
+    if (h->markets_buf) (void)hipFree(h->markets_buf);
     if (h->market_count_host) (void)hipHostFree(h->market_count_host);
     if (h->scratch) (void)hipFree(h->scratch);
     if (h->topk_flags) (void)hipFree(h->topk_flags);
@@ -715,6 +716,24 @@ int m2d_cookable_dishes(m2d_engine *h, const int32_t *market, int64_t nM, int32_
     return m2d_launch_cookable(h, market, nM, max_missing, out_ids, out_missing, out_count, (hipStream_t)stream);
 }
 
+int m2d_topk_markets(m2d_engine *h, const int32_t *users, int64_t nQ, const int64_t *market_off, const int32_t *market_ids, int64_t nnzM,
+                     int32_t k, int32_t max_missing, float *out_scores, int32_t *out_ids, int32_t *out_counts, void *stream)
+{
+    if (!h) return M2D_ERR_INVALID_ARG;
+    if (nQ < 0 || nnzM < 0 || k < 1 || k > 64 || max_missing < 0)
+        return fail(h, M2D_ERR_INVALID_ARG, "m2d_topk_markets: need nQ >= 0, nnzM >= 0, 1 <= k <= 64 and max_missing >= 0");
+    if (nQ == 0) return M2D_OK;
+    if (!users || !market_off || (!market_ids && nnzM > 0) || !out_scores || !out_ids)
+        return fail(h, M2D_ERR_INVALID_ARG, "m2d_topk_markets: null buffer");
+    if (!h->rcp_set) return fail(h, M2D_ERR_NOT_CONFIGURED, "call m2d_set_recipes first");
+    if (!h->dish_cats) return fail(h, M2D_ERR_NOT_CONFIGURED, "call m2d_set_dish_categories first");
+    if (h->ing) return fail(h, M2D_ERR_UNSUPPORTED, "m2d_topk_markets: the ingredient table is set");
+    if (h->mlp_w1) return fail(h, M2D_ERR_UNSUPPORTED, "m2d_topk_markets: the MLP head is set");
+    M2D_HIP_TRY(h, hipSetDevice(h->device));
+    return m2d_launch_topk_markets(h, users, nQ, market_off, market_ids, nnzM, k, max_missing, out_scores, out_ids, out_counts,
+                                   (hipStream_t)stream);
+}
+
 int m2d_score_pairs_ingredients(m2d_engine *h, const int32_t *users, const int32_t *items, const float *cats,
                                 int64_t B, float *out, void *stream)
 {
@@ -924,7 +943,8 @@ int m2d_check(m2d_engine *h, void *stream, int64_t *bad_value, int64_t *bad_inde
     if (code == M2D_ERR_INVALID_ARG) {              // the exclusion lists of m2d_catalogue_rank / m2d_topk_users_excluding, the slate of m2d_*_slate
         h->last_error = "m2d_catalogue_rank / m2d_topk_users_excluding / m2d_score_slate / m2d_topk_slate: id list not ascending: value " +
                         std::to_string(value) + " at position " + std::to_string(index) +
-                        " (an id below its predecessor in excl_ids, an offset below its predecessor in excl_off, or a slate id not above its predecessor)";
+                        " (an id below its predecessor in excl_ids, an offset below its predecessor in excl_off, or a slate id not above its predecessor;"
+                        " m2d_topk_markets: the end offset of a market segment that decreases or reaches outside [0, nnzM], at its request)";
         return code;
     }
     const char *what = code == M2D_ERR_BAD_USER_ID ? "user" : code == M2D_ERR_BAD_ITEM_ID ? "item" : "ingredient";
@@ -958,6 +978,10 @@ int m2d_set_option(m2d_engine *h, const char *name, int64_t value)
     else if (!strcmp(name, "topk_refine")) h->opt_topk_refine = (int)value;
     else if (!strcmp(name, "topk_grouped")) h->opt_topk_grouped = (int)value;
     else if (!strcmp(name, "topk_excl_tier")) h->opt_topk_excl_tier = (int)value;
+    else if (!strcmp(name, "market_shares")) {
+        if (value < 0 || value > 64) return fail(h, M2D_ERR_INVALID_ARG, "m2d_set_option: market_shares takes 0 ... 64");
+        h->opt_market_shares = (int)value;
+    }
     else if (!strcmp(name, "topk_mlp_chunk_pairs")) {
         if (value < 256 || value > (1 << 24)) return fail(h, M2D_ERR_INVALID_ARG, "m2d_set_option: topk_mlp_chunk_pairs takes 256 ... 2^24");
         h->opt_topk_mlp_chunk_pairs = value;
@@ -1044,6 +1068,8 @@ int m2d_get_option(const m2d_engine *h, const char *name, int64_t *value)
             *value = tiles ? (int64_t)v : (int64_t)c;
         }
     }
+    else if (!strcmp(name, "market_shares")) *value = h->opt_market_shares;
+    else if (!strcmp(name, "market_shares_used")) *value = h->market_shares_used;
     else if (!strcmp(name, "topk_grouped")) *value = h->opt_topk_grouped;
     else if (!strcmp(name, "topk_mlp_chunk_pairs")) *value = h->opt_topk_mlp_chunk_pairs;
     else if (!strcmp(name, "topk_mlp_launches")) *value = h->topk_mlp_launches;

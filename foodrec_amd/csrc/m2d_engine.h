@@ -96,6 +96,13 @@ struct m2d_engine {
     size_t market_cap = 0;             // ints
     int64_t *market_count_host = nullptr;   // pinned: the count of the last call
 
+    // m2d_topk_markets (m2d_market_requests.hip): the shares' partial lists, ids [nQ, S k] | score words [nQ, S k], and in the
+    // through-L2 form (R > 65 536) one bitmap of ceil(R / 32) words per request behind them
+    int32_t *markets_buf = nullptr;
+    size_t markets_cap = 0;            // ints
+    int opt_market_shares = 0;         // shares of the catalogue per request: 0 = the launcher's rule, 1 ... 64 forced (A/B: same words)
+    int market_shares_used = 0;        // what the last call used
+
     // derived table for pair scoring: <U_high[u], CE_c> per user and category (built lazily by large m2d_score_pairs calls;
     // stale after any write to Personal_Memory / Category_Embedding: the engine's own writers and m2d_tables_updated reset it)
     float *user_high = nullptr;  // [U, 4]
@@ -331,6 +338,22 @@ __device__ __forceinline__ float m2d_pair_score_wave(const float *um, const floa
     return m2d_blend_unfused(a, hv ? hs : hs / n, b, ls / n);                   // :79, :92, :95-96
 }
 
+// m2d_topk_users' order as ONE unsigned comparison: a smaller key comes earlier in the list.  High word: NaN -> all ones (after
+// every -inf), otherwise the complement of the float's ascending-orderable image, -0 folded onto +0 (they tie); low word: the
+// dish id.  Ids of a row are distinct, so the order is strict: whatever way a row's candidates are cut into ranges, waves and
+// lanes, the first k of it are the same.  TKM_NONE (NaN, id -1) is "no entry": it loses against everything a launch can score.
+constexpr uint64_t TKM_NONE = ~0ull;
+
+__device__ __forceinline__ uint64_t tkm_key(const float s, const int32_t id)
+{
+    uint32_t hi = 0xFFFFFFFFu;
+    if (s == s) {
+        const uint32_t b = s == 0.f ? 0u : __float_as_uint(s);
+        hi = (b & 0x80000000u) ? b : ~(b | 0x80000000u);      // ~(negative ? ~b : b | sign)
+    }
+    return ((uint64_t)hi << 32) | (uint32_t)id;
+}
+
 // ---- device helpers shared by the LDS-DMA kernels (m2d_catalogue_*.hip, m2d_mlp.hip) ----
 // vmcnt(0) twice over: the builtin is an s_waitcnt the compiler's own counter model sees (so it stops assuming that
 // loads from a previous loop trip are still in flight), the asm one cannot be optimised away on the grounds that
@@ -376,6 +399,10 @@ int m2d_launch_check_csr(m2d_engine *h, const int32_t *off, int64_t nnz, hipStre
 int m2d_launch_check_recipe_ids(m2d_engine *h, const int32_t *ids, int64_t nnz, int64_t R, hipStream_t stream);
 int m2d_launch_cookable(m2d_engine *h, const int32_t *market, int64_t nM, int32_t max_missing, int32_t *out_ids, int32_t *out_missing,
                         int64_t *out_count, hipStream_t stream);
+// m2d_market_requests.hip: one (user, market) per request -- filter, score and list in one launch per batch
+int m2d_launch_topk_markets(m2d_engine *h, const int32_t *users, int64_t nQ, const int64_t *market_off, const int32_t *market_ids,
+                            int64_t nnzM, int32_t k, int32_t max_missing, float *out_scores, int32_t *out_ids, int32_t *out_counts,
+                            hipStream_t stream);
 int m2d_ensure_dish_vectors(m2d_engine *h, hipStream_t stream);
 int m2d_launch_write_memory(m2d_engine *h, const int32_t *users, const int32_t *items, const float *cats,
                             const float *sign, const float *labels, int64_t B, int32_t L, float *gm, float beta_1,

@@ -33,22 +33,7 @@ __global__ __launch_bounds__(256) void m2d_topk_mlp_pairs_cand(const int32_t *us
 }
 
 // ---- selection ------------------------------------------------------------------------------------------------------------
-// m2d_topk_users' order as ONE unsigned comparison: a smaller key comes earlier in the list.  High word: NaN -> all ones (after
-// every -inf), otherwise the complement of the float's ascending-orderable image, -0 folded onto +0 (they tie); low word: the
-// dish id.  Ids of a row are distinct, so the order is strict: whatever way a row's candidates are cut into ranges, waves and
-// lanes, the first k of it are the same.  TKM_NONE (NaN, id -1) is "no entry": it loses against everything a launch can score.
-constexpr uint64_t TKM_NONE = ~0ull;
-
-__device__ __forceinline__ uint64_t tkm_key(const float s, const int32_t id)
-{
-    uint32_t hi = 0xFFFFFFFFu;
-    if (s == s) {
-        const uint32_t b = s == 0.f ? 0u : __float_as_uint(s);
-        hi = (b & 0x80000000u) ? b : ~(b | 0x80000000u);      // ~(negative ? ~b : b | sign)
-    }
-    return ((uint64_t)hi << 32) | (uint32_t)id;
-}
-
+// (the order's key -- TKM_NONE, tkm_key -- is m2d_engine.h's: m2d_market_requests.hip lists by it as well)
 // One workgroup per user row: the row's W scores -- column e at scores[row * rs + e * es]: rs = 1, es = rows behind the dish-major
 // generator, rs = W, es = 1 behind the candidate form; ids: ids[row * ids_stride + e] (ids_stride = W: a row of ids per user, 0: one row
 // shared by all, the slate of m2d_topk_slate), or d0 + e when null -- merged into the row's list of k

@@ -567,6 +567,53 @@ class ScoringEngine:
             out_i[:, :kk] = i
         return out_s, out_i, count
 
+    def _markets_csr(self, markets, nQ: int):
+        """`markets` of ``topk_markets`` as device tensors (offsets int64[nQ + 1], ids int32[nnzM]): a CSR pair of tensors or arrays,
+        or a list of nQ id sequences"""
+        if isinstance(markets, tuple) and len(markets) == 2 and isinstance(markets[0], (torch.Tensor, np.ndarray)):
+            off, ids = markets                           # the CSR pair is a TUPLE of arrays; per-request sequences come in a list
+            if isinstance(off, torch.Tensor):
+                if off.dtype != torch.int64 or off.device != self.device:
+                    raise TypeError("topk_markets: market offsets must be an int64 tensor on %s" % self.device)
+                off = off.contiguous().reshape(-1)
+            else:
+                off = torch.from_numpy(np.ascontiguousarray(off, dtype=np.int64).reshape(-1)).to(self.device)
+            return off, self._as_ids(ids, "ingredient")
+        if len(markets) != nQ:
+            raise ValueError("topk_markets: %d markets for %d users" % (len(markets), nQ))
+        lists = [_int32_ids(m.cpu().numpy() if isinstance(m, torch.Tensor) else m, "ingredient") for m in markets]
+        off = np.zeros(nQ + 1, np.int64)
+        np.cumsum([len(l) for l in lists], out=off[1:])
+        ids = np.concatenate(lists).astype(np.int32) if lists and off[-1] else np.zeros(0, np.int32)
+        return torch.from_numpy(off).to(self.device), torch.from_numpy(ids).to(self.device)
+
+    def topk_markets(self, users, markets, k: int, max_missing: int = 0, return_counts: bool = False):
+        """EXTENSION (``m2d_topk_markets``, include/m2d.h): one user, one market PER REQUEST -- request q is
+        (users[q], markets[q]) -- filtered, scored and listed in one stream-ordered call.  `markets`: a CSR pair ``(offsets int64[nQ + 1],
+        ids int32)`` of device tensors or arrays, or a list of nQ ingredient-id sequences (any order, repeats allowed, may be empty).
+        Returns (scores f32[nQ, k], dish ids i32[nQ, k]) and, with ``return_counts``, counts i32[nQ]: row q holds the first
+        min(k, count_q) dishes cookable from market q (``cookable_dishes``' definition) in ``topk_users``' order, NaN / -1 from column
+        count_q on; count_q is the number of cookable dishes.  A listed score is the word ``score_pairs_bydish`` returns under
+        ``variant`` = 9.  1 <= k <= 64.
+
+        Does not synchronise: bad market ids (value and index in `ids`), bad user ids and malformed offsets surface from ``check()``."""
+        users = self._as_ids(users, "user")
+        nQ = users.numel()
+        off, ids = self._markets_csr(markets, nQ)
+        if off.numel() != nQ + 1:
+            raise ValueError("topk_markets: market offsets must have nQ + 1 = %d entries" % (nQ + 1))
+        k = int(k)
+        out_s = torch.empty((nQ, max(k, 0)), dtype=torch.float32, device=self.device)
+        out_i = torch.empty((nQ, max(k, 0)), dtype=torch.int32, device=self.device)
+        counts = torch.empty((nQ,), dtype=torch.int32, device=self.device) if return_counts else None
+        with torch.cuda.device(self.device):
+            rc = _native.lib().m2d_topk_markets(self._h, users.data_ptr(), nQ, off.data_ptr(), ids.data_ptr() if ids.numel() else None,
+                                                ids.numel(), k, int(max_missing), out_s.data_ptr(), out_i.data_ptr(),
+                                                counts.data_ptr() if counts is not None else None, _stream_ptr())
+        _native.raise_for(rc, self._h)
+        self._markets_keep = (users, off, ids)           # inputs stay alive until the queued kernels have read them
+        return (out_s, out_i, counts) if return_counts else (out_s, out_i)
+
     def catalogue_rank(self, users, items, exclude=None):
         """Full-catalogue rank of held-out dishes (``m2d_catalogue_rank``, include/m2d.h): for each query (users[i], items[i]) the
         number of dishes ranked before items[i] in ``topk_users``' order, leaving out the query's excluded ids.
@@ -771,3 +818,18 @@ def topk_users_excluding_op(engine: int, users: torch.Tensor, k: int, excl_off: 
 def _(engine, users, k, excl_off=None, excl_ids=None):
     return (users.new_empty((users.numel(), k), dtype=torch.float32),
             users.new_empty((users.numel(), k), dtype=torch.int32))
+
+
+@torch.library.custom_op("m2d::topk_markets", mutates_args=(), device_types="cuda")
+def topk_markets_op(engine: int, users: torch.Tensor, market_off: torch.Tensor, market_ids: torch.Tensor, k: int,
+                    max_missing: int = 0) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """``ScoringEngine.topk_markets`` with the counts: (scores f32[nQ, k], ids i32[nQ, k], counts i32[nQ]).  Unlike ``cookable_dishes``
+    this call can be a registered op: its output shapes are static, so the fake kernel below states them."""
+    return _engine(engine).topk_markets(users, (market_off, market_ids), k, max_missing, return_counts=True)
+
+
+@topk_markets_op.register_fake
+def _(engine, users, market_off, market_ids, k, max_missing=0):
+    return (users.new_empty((users.numel(), k), dtype=torch.float32),
+            users.new_empty((users.numel(), k), dtype=torch.int32),
+            users.new_empty((users.numel(),), dtype=torch.int32))

@@ -380,6 +380,26 @@ class Model:
         mt = m.to(self.device, torch.int32) if isinstance(m, torch.Tensor) else torch.from_numpy(m).to(self.device)
         return self.engine.cookable_dishes(mt, max_missing).cpu().numpy()
 
+    def topk_markets(self, users, markets, k: int = 10, max_missing: int = 0):
+        """EXTENSION: one user, one market per request -- `users` as str or int, `markets` a list of ingredient-id sequences (str or
+        int, any order, repeats allowed, may be empty) aligned with `users`.  Returns numpy (scores float32 [n, k], dish ids int32
+        [n, k], counts int32 [n]): row q lists the k best dishes that can be cooked from markets[q] for users[q]
+        (``ScoringEngine.topk_markets``: one call for the whole batch, `cookable`'s definition, `topk`'s order), id -1 / NaN from
+        column counts[q] on; counts[q] is the number of cookable dishes.  k <= 64.  Needs `set_dish_categories` and `set_recipes`."""
+        u = _ids(users, "user")
+        n = u.numel() if isinstance(u, torch.Tensor) else len(u)
+        if len(markets) != n:
+            raise ValueError("topk_markets: %d markets for %d users" % (len(markets), n))
+        lists = [_ids(m, "ingredient") for m in markets]
+        lists = [m.cpu().numpy().astype(np.int32) if isinstance(m, torch.Tensor) else m for m in lists]
+        off = np.zeros(n + 1, np.int64)
+        np.cumsum([len(m) for m in lists], out=off[1:])
+        ids = np.concatenate(lists).astype(np.int32) if off[-1] else np.zeros(0, np.int32)
+        dev = lambda a: a.to(self.device) if isinstance(a, torch.Tensor) else torch.from_numpy(a).to(self.device)
+        s, i, c = torch.ops.m2d.topk_markets(self.engine.id, dev(u).to(torch.int32), dev(off), dev(ids), int(k), int(max_missing))
+        self.engine.check()
+        return s.cpu().numpy(), i.cpu().numpy(), c.cpu().numpy()
+
     def topk(self, users, k: int = 10, exclude=None, head: bool = False, candidates: int = 0, among=None, market=None,
              max_missing: int = 0):
         """The k best dishes of every user in `users` over the whole catalogue -- the ranking rule of

@@ -404,12 +404,61 @@ int m2d_cookable_dishes(m2d_engine *h, const int32_t *market /* device, [nM] */,
                         int32_t *out_ids /* device, capacity I */, int32_t *out_missing /* device, [I], may be null */,
                         int64_t *out_count /* HOST */, void *stream);
 
+/* ---- build-defined extension, NO reference counterpart ----
+ * Market requests: one user, one market PER REQUEST -- the shape a server meets, many shoppers at once, each with the ingredients seen
+ * at their own stall.  m2d_topk_markets filters, scores and lists nQ such requests in one stream-ordered call.  Request q is
+ * (users[q], market_ids[market_off[q] .. market_off[q+1])).
+ *
+ * Cookable set.  Dish d is cookable for request q by m2d_cookable_dishes' definition: its list is non-empty and at most max_missing
+ * of its list ENTRIES, every occurrence counted, name an id that is not in the request's market.  Market ids in any order, repeats
+ * allowed, an empty market legal (market_ids may be null when nnzM == 0).
+ *
+ * Outputs.  Row q of out_ids i32[nQ, k] / out_scores f32[nQ, k]: the first min(k, count_q) cookable dishes of request q in
+ * m2d_topk_users' order -- score descending, bit-equal scores and -0 / +0 to the lower id, NaN last in id order --, NaN / -1 from
+ * column count_q on.  out_counts i32[nQ] (may be null): count_q, the number of COOKABLE dishes, not of listed ones.
+ *
+ * Score.  A listed score is the literal pair arithmetic's (Model_Recommender.py:67-96 as written, one wave per pair) for (user, dish,
+ * the dish's resident mask): bit for bit the word m2d_score_pairs_bydish returns under "variant" = 9, and the way m2d_topk_users'
+ * literal kernel defines its scores.  Rows of weight-0 categories are left out as the pair kernels decide it: option "skip_masked" and
+ * the engine's "a table value is not finite" word, after the queued table scan has run.  So on tables that hold inf / NaN the call
+ * returns the graph's answer (+inf first, -inf after every finite score, NaN last) instead of refusing, and on finite tables the bits do
+ * not depend on the option.
+ *
+ * THE CALL NEVER SYNCHRONISES: everything is stream-ordered, errors are latched for m2d_check, and after the first call of a size it
+ * allocates only on growth.  A row's words do not depend on nQ, on the request's position, or on how the launcher cuts the work.
+ *
+ * Errors.  nQ < 0, nnzM < 0, k < 1, k > 64, max_missing < 0 or a null required pointer: M2D_ERR_INVALID_ARG.  nQ == 0: M2D_OK, nothing
+ * launched.  No recipes or no dish masks set: M2D_ERR_NOT_CONFIGURED.  The ingredient table or an MLP head set: M2D_ERR_UNSUPPORTED, the
+ * condition named (the refusals of m2d_topk_slate).  Latched, first error wins: a market id outside [0, R) as M2D_ERR_BAD_INGREDIENT
+ * with its value and its index in market_ids -- the id contributes nothing; a user id outside the engine's range as
+ * M2D_ERR_BAD_USER_ID with its value and q -- that row is all NaN / -1, its count is still the market's, nothing is read for that
+ * user; a segment with market_off[q+1] < market_off[q] or one that reaches outside [0, nnzM] as M2D_ERR_INVALID_ARG with
+ * market_off[q+1] and q -- the segment is clamped into [0, nnzM] before anything is read.  No kernel reads out of bounds and the
+ * engine stays usable.
+ *
+ * Kernels.  m2d_markets_topk: a block of four waves serves one (request, share), a share being a contiguous range of 256-dish blocks
+ * of the catalogue.  The block sets its market's bits in a bitmap -- in LDS up to R = 65 536 (m2d_markets_topk_lds, 8 KiB a block; LDS
+ * atomicOr); beyond, a memset and m2d_markets_bitmap write one bitmap of ceil(R / 32) words PER REQUEST into engine scratch in front
+ * of it and the block reads its own through L2 (m2d_markets_topk_l2: nQ ceil(R / 32) words of scratch, grown on demand) --, its waves
+ * walk the share's 64-dish groups as m2d_market_flag does, score each kept dish with the whole wave and keep the k best as a sorted
+ * list across lanes; the four lists meet in LDS (3 KiB).  S = clamp(4 num_cu / nQ, 1, min(64, ceil(I / 256))) shares per request
+ * ("market_shares" forces it): with S = 1 the block writes the row, with S > 1 it writes its k (score, id) words into scratch
+ * [nQ, S k], adds its count into out_counts (zeroed in front; an integer sum) and m2d_topk_mlp_select merges the shares.  The order is
+ * strict, so the words do not depend on S.  m2d_last_kernel names the form. */
+int m2d_topk_markets(m2d_engine *h, const int32_t *users /* device, [nQ] */, int64_t nQ,
+                     const int64_t *market_off /* device, [nQ + 1] */,
+                     const int32_t *market_ids /* device, [nnzM], may be null when nnzM == 0 */, int64_t nnzM,
+                     int32_t k, int32_t max_missing, float *out_scores /* device, [nQ, k] */,
+                     int32_t *out_ids /* device, [nQ, k] */, int32_t *out_counts /* device, [nQ], may be null */,
+                     void *stream);
+
 /* Synchronise `stream` and report (then clear) the first id error latched by kernels since the
  * previous check: M2D_OK, M2D_ERR_BAD_USER_ID or M2D_ERR_BAD_ITEM_ID.  TF-CPU GatherV2 raises
  * InvalidArgument for such ids; the kernels never read out of bounds and write NaN for the pair.
  * M2D_ERR_INVALID_ARG: an exclusion list of m2d_catalogue_rank / m2d_topk_users_excluding is not ascending (bad_value: the id or offset, bad_index: its
  * position in excl_ids / excl_off), or a slate entry of m2d_score_slate / m2d_topk_slate is not above its predecessor (bad_value: the id,
- * bad_index: its position in the slate).
+ * bad_index: its position in the slate), or a market segment of m2d_topk_markets decreases or reaches outside [0, nnzM] (bad_value: its
+ * end offset, bad_index: the request).  M2D_ERR_BAD_INGREDIENT: a market id out of range (m2d_cookable_dishes, m2d_topk_markets).
  * bad_value / bad_index (host pointers, may be NULL) receive the offending id and its position. */
 int m2d_check(m2d_engine *h, void *stream, int64_t *bad_value, int64_t *bad_index);
 
@@ -469,6 +518,8 @@ int m2d_check(m2d_engine *h, void *stream, int64_t *bad_value, int64_t *bad_inde
  * topk_block       0        0 128 256    users per block of a pruned pipelined launch (0 = the launcher's choice)
  * topk_excl_tier   0        0 / 2        m2d_topk_users_excluding: 0 = m2d_topk_users' lists filtered where they are index-exact, the exact scan
  *                                        for the users left short and for every other case; 2 = the exact scan for every user.  Same ids, same score bits.
+ * market_shares    0        0 ... 64     m2d_topk_markets: shares of the catalogue per request: 0 = clamp(4 num_cu / nQ, 1, min(64, ceil(I / 256))),
+ *                                        1 ... 64 forced (clamped to the catalogue's 256-dish blocks).  Same ids, same score bits, same counts.
  * topk_mlp_chunk_pairs  4194304  256 ... 2^24  m2d_topk_users_mlp: pairs per head launch (the --workload mlp batch by default); other values are
  *                                        M2D_ERR_INVALID_ARG.  Same ids, same score bits.
  * slate_chunk_pairs  4194304  256 ... 2^24  m2d_topk_slate: pairs of score scratch one pass may hold (user blocks of max(1, P / nD) rows); other values
@@ -497,6 +548,9 @@ int m2d_check(m2d_engine *h, void *stream, int64_t *bad_value, int64_t *bad_inde
  * topk_excl_short          users sent to the exact scan: those the filter left with fewer than k dishes, or all of them
  * topk_excl_tiles_scanned  32-dish tiles the exact scan multiplied
  * (the "topk_*" diagnostics above then describe the call's internal m2d_topk_users retrieval, if its first tier ran)
+ *
+ * ---- read-only diagnostic of the last m2d_topk_markets call (host value, no synchronisation) -----------------------------------------------
+ * market_shares_used       shares per request the launcher used
  *
  * ---- read-only diagnostic of the last m2d_topk_users_mlp call (host counter, no synchronisation) --------------------------------------------
  * topk_mlp_launches        head launches: user blocks x dish ranges (two-stage: user blocks; the "topk_*" diagnostics then describe stage 1)
