@@ -65,6 +65,7 @@ SIGNATURES = {
     "m2d_clear_recipes": (_c.c_int, [_vp]),
     "m2d_cookable_dishes": (_c.c_int, [_vp, _vp, _i64, _i32, _vp, _vp, _c.POINTER(_i64), _vp]),
     "m2d_topk_markets": (_c.c_int, [_vp, _vp, _i64, _vp, _vp, _i64, _i32, _i32, _vp, _vp, _vp, _vp]),
+    "m2d_topk_markets_excluding": (_c.c_int, [_vp, _vp, _i64, _vp, _vp, _i64, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp]),
     "m2d_write_memory": (_c.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _vp, _c.c_float, _c.c_float,
                                     _c.c_float, _i32, _vp, _vp]),
     "m2d_train_begin": (_c.c_int, [_vp, _i32, _c.c_float, _c.c_float, _vp]),

@@ -734,6 +734,25 @@ int m2d_topk_markets(m2d_engine *h, const int32_t *users, int64_t nQ, const int6
                                    (hipStream_t)stream);
 }
 
+int m2d_topk_markets_excluding(m2d_engine *h, const int32_t *users, int64_t nQ, const int64_t *market_off, const int32_t *market_ids,
+                               int64_t nnzM, const int64_t *excl_off, const int32_t *excl_ids, int32_t k, int32_t max_missing,
+                               float *out_scores, int32_t *out_ids, int32_t *out_counts, int32_t *out_missing, void *stream)
+{
+    if (!h) return M2D_ERR_INVALID_ARG;
+    if (nQ < 0 || nnzM < 0 || k < 1 || k > 64 || max_missing < 0)
+        return fail(h, M2D_ERR_INVALID_ARG, "m2d_topk_markets_excluding: need nQ >= 0, nnzM >= 0, 1 <= k <= 64 and max_missing >= 0");
+    if (nQ == 0) return M2D_OK;
+    if (!users || !market_off || (!market_ids && nnzM > 0) || !out_scores || !out_ids)
+        return fail(h, M2D_ERR_INVALID_ARG, "m2d_topk_markets_excluding: null buffer");
+    if (!h->rcp_set) return fail(h, M2D_ERR_NOT_CONFIGURED, "call m2d_set_recipes first");
+    if (!h->dish_cats) return fail(h, M2D_ERR_NOT_CONFIGURED, "call m2d_set_dish_categories first");
+    if (h->ing) return fail(h, M2D_ERR_UNSUPPORTED, "m2d_topk_markets_excluding: the ingredient table is set");
+    if (h->mlp_w1) return fail(h, M2D_ERR_UNSUPPORTED, "m2d_topk_markets_excluding: the MLP head is set");
+    M2D_HIP_TRY(h, hipSetDevice(h->device));
+    return m2d_launch_topk_markets(h, users, nQ, market_off, market_ids, nnzM, k, max_missing, out_scores, out_ids, out_counts,
+                                   (hipStream_t)stream, excl_off, excl_ids, out_missing);
+}
+
 int m2d_score_pairs_ingredients(m2d_engine *h, const int32_t *users, const int32_t *items, const float *cats,
                                 int64_t B, float *out, void *stream)
 {
@@ -944,7 +963,9 @@ int m2d_check(m2d_engine *h, void *stream, int64_t *bad_value, int64_t *bad_inde
         h->last_error = "m2d_catalogue_rank / m2d_topk_users_excluding / m2d_score_slate / m2d_topk_slate: id list not ascending: value " +
                         std::to_string(value) + " at position " + std::to_string(index) +
                         " (an id below its predecessor in excl_ids, an offset below its predecessor in excl_off, or a slate id not above its predecessor;"
-                        " m2d_topk_markets: the end offset of a market segment that decreases or reaches outside [0, nnzM], at its request)";
+                        " m2d_topk_markets: the end offset of a market segment that decreases or reaches outside [0, nnzM], at its request;"
+                        " m2d_topk_markets_excluding: also an excluded id below its predecessor, at its index in excl_ids, or the end offset of an"
+                        " exclusion segment that decreases or reaches outside the array, at its index in excl_off)";
         return code;
     }
     const char *what = code == M2D_ERR_BAD_USER_ID ? "user" : code == M2D_ERR_BAD_ITEM_ID ? "item" : "ingredient";

@@ -399,10 +399,12 @@ int m2d_launch_check_csr(m2d_engine *h, const int32_t *off, int64_t nnz, hipStre
 int m2d_launch_check_recipe_ids(m2d_engine *h, const int32_t *ids, int64_t nnz, int64_t R, hipStream_t stream);
 int m2d_launch_cookable(m2d_engine *h, const int32_t *market, int64_t nM, int32_t max_missing, int32_t *out_ids, int32_t *out_missing,
                         int64_t *out_count, hipStream_t stream);
-// m2d_market_requests.hip: one (user, market) per request -- filter, score and list in one launch per batch
+// m2d_market_requests.hip: one (user, market) per request -- filter, score and list in one launch per batch; with `excl_off` the
+// exclusion form of the kernel, with `out_missing` (and max_missing > 0) m2d_markets_missing after the rows are final
 int m2d_launch_topk_markets(m2d_engine *h, const int32_t *users, int64_t nQ, const int64_t *market_off, const int32_t *market_ids,
                             int64_t nnzM, int32_t k, int32_t max_missing, float *out_scores, int32_t *out_ids, int32_t *out_counts,
-                            hipStream_t stream);
+                            hipStream_t stream, const int64_t *excl_off = nullptr, const int32_t *excl_ids = nullptr,
+                            int32_t *out_missing = nullptr);
 int m2d_ensure_dish_vectors(m2d_engine *h, hipStream_t stream);
 int m2d_launch_write_memory(m2d_engine *h, const int32_t *users, const int32_t *items, const float *cats,
                             const float *sign, const float *labels, int64_t B, int32_t L, float *gm, float beta_1,

@@ -14,6 +14,11 @@
 // TKM_NONE, so the words do not depend on S.  Nothing synchronises: no block waits for another, the stream orders the launches.
 // The setter has validated the recipe lists (m2d_set_recipes), so no kernel here range-checks a recipe id or a recipe offset; the
 // call's own inputs -- market ids, user ids, market offsets -- are checked where they are read.
+//
+// m2d_topk_markets_excluding is the same call with two additions.  m2d_markets_topk<LDS, true> takes an ascending
+// CSR of dish ids per request and drops them from the `kept` ballot of each 64-dish group before anything is scored or counted; the
+// instantiations without it are the code above, unchanged.  m2d_markets_missing<LDS> runs after the rows are final and writes, for every
+// listed dish, the ids of its list entries that are absent from the request's market, in list order.
 #include "m2d_engine.h"
 
 namespace {
@@ -45,6 +50,10 @@ struct MarketsArgs {
     uint32_t *part_scores;     // S > 1: [nQ, S k] score words
     int32_t *part_ids;
     int32_t *err;
+    // exclusion form (m2d_markets_topk<LDS, true>): request q leaves out xids[xoff[q] .. xoff[q + 1]), ascending dish ids
+    const int64_t *xoff;
+    const int32_t *xids;
+    int64_t nQ;
 };
 
 // Wave-uniform values are carried in SGPRs: every loop with a ballot or a shuffle in it is scalar control flow, no cross-lane
@@ -76,7 +85,17 @@ __global__ __launch_bounds__(256) void m2d_markets_bitmap(const int64_t *moff, c
     }
 }
 
-template <bool LDS>
+// first position in [lo, hi) of the ascending ids whose id is not below d
+__device__ __forceinline__ int64_t excl_lower_bound(const int32_t *ids, int64_t lo, int64_t hi, const int64_t d)
+{
+    while (lo < hi) {
+        const int64_t mid = (lo + hi) >> 1;
+        if (ids[mid] < d) lo = mid + 1; else hi = mid;
+    }
+    return lo;
+}
+
+template <bool LDS, bool EXCL = false>
 __global__ __launch_bounds__(256) void m2d_markets_topk(MarketsArgs p)
 {
     __shared__ uint32_t bm[LDS ? MQ_LDS_BITS / 32 : 1];
@@ -111,6 +130,27 @@ __global__ __launch_bounds__(256) void m2d_markets_topk(MarketsArgs p)
         __syncthreads();
     }
     const uint32_t *bits = LDS ? bm : p.bitmaps + q * (int64_t)words;
+
+    // exclusion form: the request's segment, clamped into the array (its length is the last offset, as m2d_catalogue_rank takes it)
+    // before anything is read; the share-0 block checks every id once -- a dish of the catalogue, not below the id in front of it
+    // xw: where the next group's window starts -- a wave's groups ascend, so it only moves forward --, xv: the id there, held in a
+    // register: a group that ends at or below xv has an empty window and pays one compare
+    int64_t x0 = 0, x1 = 0, xw = 0;
+    int32_t xv = INT32_MAX;
+    if (EXCL) {
+        bool bad_x;
+        market_segment(p.xoff, q, p.xids ? p.xoff[p.nQ] : 0, x0, x1, bad_x);     // (no array: its length is 0, a non-empty segment is bad)
+        if (s == 0) {
+            if (threadIdx.x == 0 && bad_x) m2d_latch_error(p.err, M2D_ERR_INVALID_ARG, (int32_t)p.xoff[q + 1], q + 1);
+            for (int64_t i = x0 + threadIdx.x; i < x1; i += MQ_WAVES * 64) {
+                const int32_t x = p.xids[i];
+                if (x < 0 || x >= p.I) m2d_latch_error(p.err, M2D_ERR_BAD_ITEM_ID, x, i);
+                else if (i > x0 && p.xids[i - 1] > x) m2d_latch_error(p.err, M2D_ERR_INVALID_ARG, x, i);
+            }
+        }
+        xw = x0;
+        if (x0 < x1) xv = uni(p.xids[x0]);
+    }
 
     // the share: catalogue blocks [s nb / S, (s + 1) nb / S), S <= nb
     const int64_t nb = (p.I + MQ_DB - 1) / MQ_DB;
@@ -156,6 +196,17 @@ __global__ __launch_bounds__(256) void m2d_markets_topk(MarketsArgs p)
             }
         }
         unsigned long long kept = __ballot(lane < dn && my_end != my_begin && miss <= p.max_missing);
+        if (EXCL && xv < d0 + MQ_DW) {                                      // scalar: xv is the smallest id the wave has not passed
+            // the segment's window for [d0, d0 + 64): two wave-uniform lower bounds; an empty window costs nothing more
+            const int64_t w0 = excl_lower_bound(p.xids, xw, x1, d0), w1 = excl_lower_bound(p.xids, w0, x1, d0 + MQ_DW);
+            xw = w1;
+            xv = w1 < x1 ? uni(p.xids[w1]) : INT32_MAX;
+            if (w1 > w0) {                                                  // scalar branch; the search below has no cross-lane operation
+                const int64_t at = excl_lower_bound(p.xids, w0, w1, d0 + lane);
+                const bool out = at < w1 && p.xids[at] == d0 + lane;
+                kept &= ~__ballot(out);
+            }
+        }
         cnt += __popcll(kept);
         if (bad_user) continue;
         while (kept) {                                                      // wave-uniform: one dish, the whole wave
@@ -213,11 +264,57 @@ __global__ __launch_bounds__(256) void m2d_markets_topk(MarketsArgs p)
     }
 }
 
+// m2d_markets_missing<LDS>: block q, after row q is final.  It has the request's bitmap as m2d_markets_topk has it (rebuilt in LDS, or the
+// one m2d_markets_bitmap left in scratch, still valid in stream order); wave w takes the listed dishes j = w, w + MQ_WAVES, ... and walks
+// the dish's list MQ_EB entries a batch.  An absent entry's place is the running total plus the absent entries below its lane in the
+// batch's ballot, so the words come out in list order without an atomic or a sort.  Every word of [nQ, k, max_missing] is written.
+template <bool LDS>
+__global__ __launch_bounds__(256) void m2d_markets_missing(MarketsArgs p, int32_t *out_missing)
+{
+    __shared__ uint32_t bm[LDS ? MQ_LDS_BITS / 32 : 1];
+    const int wave = uni(threadIdx.x >> 6), lane = threadIdx.x & 63;
+    const int64_t q = blockIdx.x;
+    const int k = p.k, mm = p.max_missing;
+    const int words = (p.R + 31) >> 5;
+    if (LDS) {                                               // (the ids have been reported by m2d_markets_topk: a bad one is skipped)
+        int64_t m0, m1;
+        bool bad_seg;
+        market_segment(p.moff, q, p.nnzM, m0, m1, bad_seg);
+        for (int i = threadIdx.x; i < words; i += MQ_WAVES * 64) bm[i] = 0u;
+        __syncthreads();
+        for (int64_t i = m0 + threadIdx.x; i < m1; i += MQ_WAVES * 64) {
+            const int32_t id = p.mids[i];
+            if (id >= 0 && id < p.R) atomicOr(&bm[id >> 5], 1u << (id & 31));
+        }
+        __syncthreads();
+    }
+    const uint32_t *bits = LDS ? bm : p.bitmaps + q * (int64_t)words;
+    for (int j = wave; j < k; j += MQ_WAVES) {                               // scalar bounds
+        const int32_t d = uni(p.out_ids[q * k + j]);
+        int32_t *row = out_missing + (q * k + j) * (int64_t)mm;
+        int total = 0;                                                       // absent entries so far (wave-uniform)
+        if (d >= 0 && d < p.I) {
+            const uint32_t e_begin = uni(p.rcp_off[d]), e_end = uni(p.rcp_off[d + 1]);
+            for (uint32_t pos = e_begin; pos < e_end; pos += MQ_EB) {        // scalar bounds
+                const uint32_t e = pos + lane;
+                const int32_t id = e < e_end ? p.rcp_ids[e] : -1;
+                const int32_t v = id < 0 ? 0 : id;
+                const bool absent = id >= 0 && ((bits[v >> 5] >> (v & 31)) & 1u) == 0;
+                const unsigned long long word = __ballot(absent);
+                const int at = total + __popcll(word & ((1ull << lane) - 1));
+                if (absent && at < mm) row[at] = id;                         // (more than max_missing only if the row is wrong: capped)
+                total += __popcll(word);
+            }
+        }
+        for (int i = (total < mm ? total : mm) + lane; i < mm; i += 64) row[i] = -1;
+    }
+}
+
 }  // namespace
 
 int m2d_launch_topk_markets(m2d_engine *h, const int32_t *users, int64_t nQ, const int64_t *market_off, const int32_t *market_ids,
                             int64_t nnzM, int32_t k, int32_t max_missing, float *out_scores, int32_t *out_ids, int32_t *out_counts,
-                            hipStream_t st)
+                            hipStream_t st, const int64_t *excl_off, const int32_t *excl_ids, int32_t *out_missing)
 {
     int rc;
     if ((rc = m2d_ensure_finite_scan(h, st)) != M2D_OK) return rc;
@@ -251,6 +348,7 @@ int m2d_launch_topk_markets(m2d_engine *h, const int32_t *users, int64_t nQ, con
     a.out_scores = out_scores; a.out_ids = out_ids; a.counts = out_counts;
     a.part_ids = h->markets_buf; a.part_scores = reinterpret_cast<uint32_t *>(h->markets_buf + part);
     a.err = h->err_dev;
+    a.xoff = excl_off; a.xids = excl_ids; a.nQ = nQ;
 
     if (S > 1 && out_counts) M2D_HIP_TRY(h, hipMemsetAsync(out_counts, 0, (size_t)nQ * sizeof(int32_t), st));
     if (!lds) {
@@ -259,11 +357,20 @@ int m2d_launch_topk_markets(m2d_engine *h, const int32_t *users, int64_t nQ, con
                            reinterpret_cast<uint32_t *>(h->markets_buf + o_bm), h->err_dev);
     }
     h->last_kernel = lds ? "m2d_markets_topk_lds" : "m2d_markets_topk_l2";
-    if (lds) hipLaunchKernelGGL(m2d_markets_topk<true>, dim3((unsigned)(nQ * S)), dim3(MQ_WAVES * 64), 0, st, a);
+    if (excl_off) {
+        h->last_kernel = lds ? "m2d_markets_topk_excl_lds" : "m2d_markets_topk_excl_l2";
+        if (lds) hipLaunchKernelGGL((m2d_markets_topk<true, true>), dim3((unsigned)(nQ * S)), dim3(MQ_WAVES * 64), 0, st, a);
+        else hipLaunchKernelGGL((m2d_markets_topk<false, true>), dim3((unsigned)(nQ * S)), dim3(MQ_WAVES * 64), 0, st, a);
+    } else if (lds) hipLaunchKernelGGL(m2d_markets_topk<true>, dim3((unsigned)(nQ * S)), dim3(MQ_WAVES * 64), 0, st, a);
     else hipLaunchKernelGGL(m2d_markets_topk<false>, dim3((unsigned)(nQ * S)), dim3(MQ_WAVES * 64), 0, st, a);
     M2D_HIP_TRY(h, hipGetLastError());
-    if (S > 1)
-        return m2d_launch_topk_select(h, reinterpret_cast<const float *>(a.part_scores), a.part_ids, S * k, nQ, S * k, 0, k, 1, out_scores,
-                                      out_ids, S * k, 1, st);
+    if (S > 1 && (rc = m2d_launch_topk_select(h, reinterpret_cast<const float *>(a.part_scores), a.part_ids, S * k, nQ, S * k, 0, k, 1,
+                                              out_scores, out_ids, S * k, 1, st)) != M2D_OK)
+        return rc;
+    if (out_missing && max_missing > 0) {                    // the rows are final; the bitmaps in markets_buf have not moved (one growth, above)
+        if (lds) hipLaunchKernelGGL(m2d_markets_missing<true>, dim3((unsigned)nQ), dim3(MQ_WAVES * 64), 0, st, a, out_missing);
+        else hipLaunchKernelGGL(m2d_markets_missing<false>, dim3((unsigned)nQ), dim3(MQ_WAVES * 64), 0, st, a, out_missing);
+        M2D_HIP_TRY(h, hipGetLastError());
+    }
     return M2D_OK;
 }

@@ -614,6 +614,49 @@ class ScoringEngine:
         self._markets_keep = (users, off, ids)           # inputs stay alive until the queued kernels have read them
         return (out_s, out_i, counts) if return_counts else (out_s, out_i)
 
+    def topk_markets_excluding(self, users, markets, exclude=None, k: int = 10, max_missing: int = 0, return_counts: bool = False,
+                               return_missing: bool = False):
+        """EXTENSION (``m2d_topk_markets_excluding``, include/m2d.h): ``topk_markets`` that leaves out, per
+        request, the dishes in `exclude` and can name what each listed dish lacks.  `exclude`: None, a list of nQ dish-id lists or an
+        ``(offsets, ids)`` pair of arrays -- sorted and de-duplicated per request here, as ``catalogue_rank`` does --, or a pair of
+        DEVICE tensors (offsets int64[nQ + 1], ids int32), taken as they are: ascending per segment, checked on the device.
+        Returns (scores f32[nQ, k], dish ids i32[nQ, k]), then with ``return_counts`` counts i32[nQ] -- the cookable dishes that are
+        not excluded --, then with ``return_missing`` missing i32[nQ, k, max_missing]: for listed dish [q, j] the ingredient ids of its
+        list entries absent from market q, in list order, every occurrence, -1 from the number missing on.
+
+        Does not synchronise: bad ids, lists that are not ascending and malformed offsets surface from ``check()``."""
+        users = self._as_ids(users, "user")
+        nQ = users.numel()
+        off, ids = self._markets_csr(markets, nQ)
+        if off.numel() != nQ + 1:
+            raise ValueError("topk_markets_excluding: market offsets must have nQ + 1 = %d entries" % (nQ + 1))
+        xoff = xids = None
+        if exclude is not None:
+            if isinstance(exclude, tuple) and len(exclude) == 2 and all(isinstance(t, torch.Tensor) and t.device == self.device for t in exclude):
+                xoff, xids = exclude
+                if xoff.dtype != torch.int64 or xids.dtype != torch.int32:
+                    raise TypeError("topk_markets_excluding: device exclusions are (int64 offsets, int32 ids)")
+                xoff, xids = xoff.contiguous().reshape(-1), xids.contiguous().reshape(-1)
+                if xoff.numel() != nQ + 1:
+                    raise ValueError("topk_markets_excluding: exclusion offsets must have nQ + 1 = %d entries" % (nQ + 1))
+            else:
+                off_np, ids_np = exclusion_csr(exclude, nQ)
+                xoff, xids = torch.from_numpy(off_np).to(self.device), torch.from_numpy(ids_np).to(self.device)
+        k, mm = int(k), int(max_missing)
+        out_s = torch.empty((nQ, max(k, 0)), dtype=torch.float32, device=self.device)
+        out_i = torch.empty((nQ, max(k, 0)), dtype=torch.int32, device=self.device)
+        counts = torch.empty((nQ,), dtype=torch.int32, device=self.device) if return_counts else None
+        missing = torch.empty((nQ, max(k, 0), max(mm, 0)), dtype=torch.int32, device=self.device) if return_missing else None
+        with torch.cuda.device(self.device):
+            rc = _native.lib().m2d_topk_markets_excluding(
+                self._h, users.data_ptr(), nQ, off.data_ptr(), ids.data_ptr() if ids.numel() else None, ids.numel(),
+                xoff.data_ptr() if xoff is not None else None, xids.data_ptr() if xids is not None and xids.numel() else None, k, mm,
+                out_s.data_ptr(), out_i.data_ptr(), counts.data_ptr() if counts is not None else None,
+                missing.data_ptr() if missing is not None and missing.numel() else None, _stream_ptr())
+        _native.raise_for(rc, self._h)
+        self._markets_keep = (users, off, ids, xoff, xids)   # inputs stay alive until the queued kernels have read them
+        return (out_s, out_i) + ((counts,) if return_counts else ()) + ((missing,) if return_missing else ())
+
     def catalogue_rank(self, users, items, exclude=None):
         """Full-catalogue rank of held-out dishes (``m2d_catalogue_rank``, include/m2d.h): for each query (users[i], items[i]) the
         number of dishes ranked before items[i] in ``topk_users``' order, leaving out the query's excluded ids.
@@ -833,3 +876,23 @@ def _(engine, users, market_off, market_ids, k, max_missing=0):
     return (users.new_empty((users.numel(), k), dtype=torch.float32),
             users.new_empty((users.numel(), k), dtype=torch.int32),
             users.new_empty((users.numel(),), dtype=torch.int32))
+
+
+@torch.library.custom_op("m2d::topk_markets_excluding", mutates_args=(), device_types="cuda")
+def topk_markets_excluding_op(engine: int, users: torch.Tensor, market_off: torch.Tensor, market_ids: torch.Tensor,
+                              excl_off: Optional[torch.Tensor] = None, excl_ids: Optional[torch.Tensor] = None, k: int = 10,
+                              max_missing: int = 0) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    """``ScoringEngine.topk_markets_excluding`` with the counts and the missing entries: (scores f32[nQ, k], ids i32[nQ, k],
+    counts i32[nQ], missing i32[nQ, k, max_missing]).  `excl_off` / `excl_ids`: device tensors, ascending per segment, taken as they
+    are."""
+    exclude = None if excl_off is None else (excl_off, excl_ids if excl_ids is not None else excl_off.new_empty((0,), dtype=torch.int32))
+    return _engine(engine).topk_markets_excluding(users, (market_off, market_ids), exclude, k, max_missing, return_counts=True,
+                                                  return_missing=True)
+
+
+@topk_markets_excluding_op.register_fake
+def _(engine, users, market_off, market_ids, excl_off=None, excl_ids=None, k=10, max_missing=0):
+    return (users.new_empty((users.numel(), k), dtype=torch.float32),
+            users.new_empty((users.numel(), k), dtype=torch.int32),
+            users.new_empty((users.numel(),), dtype=torch.int32),
+            users.new_empty((users.numel(), k, max_missing), dtype=torch.int32))

@@ -400,6 +400,40 @@ class Model:
         self.engine.check()
         return s.cpu().numpy(), i.cpu().numpy(), c.cpu().numpy()
 
+    def topk_markets_excluding(self, users, markets, exclude=None, k: int = 10, max_missing: int = 0, missing: bool = False):
+        """EXTENSION: `topk_markets` that leaves out what each shopper has already had and can say what to buy.  `exclude`: a dict
+        keyed by the user as given in `users` (a missing key excludes nothing) or a list aligned with `users`, of dish ids (str or
+        int, any order, repeats allowed), as in `topk`; None excludes nothing.  Returns numpy (scores [n, k], dish ids [n, k], counts
+        [n]) -- counts[q] is the number of cookable dishes that are not excluded -- and with `missing=True` a fourth array int32
+        [n, k, max_missing]: for listed dish [q, j] the ingredient ids of its list entries that markets[q] lacks, in list order, every
+        occurrence, -1 from the number missing on.  (``ScoringEngine.topk_markets_excluding``, one call for the whole batch.)"""
+        u = _ids(users, "user")
+        n = u.numel() if isinstance(u, torch.Tensor) else len(u)
+        if len(markets) != n:
+            raise ValueError("topk_markets_excluding: %d markets for %d users" % (len(markets), n))
+        lists = [_ids(m, "ingredient") for m in markets]
+        lists = [m.cpu().numpy().astype(np.int32) if isinstance(m, torch.Tensor) else m for m in lists]
+        off = np.zeros(n + 1, np.int64)
+        np.cumsum([len(m) for m in lists], out=off[1:])
+        ids = np.concatenate(lists).astype(np.int32) if off[-1] else np.zeros(0, np.int32)
+        dev = lambda a: a.to(self.device) if isinstance(a, torch.Tensor) else torch.from_numpy(a).to(self.device)
+        xoff = xids = None
+        if exclude is not None:
+            from .ops import exclusion_csr
+            if isinstance(exclude, dict):
+                exclude = [exclude.get(x, ()) for x in users]
+            elif len(exclude) != n:
+                raise ValueError("topk_markets_excluding: %d exclusion lists for %d users" % (len(exclude), n))
+            had = [_ids(x, "item") for x in exclude]
+            had = [x.cpu().numpy() if isinstance(x, torch.Tensor) else x for x in had]
+            xo, xi = exclusion_csr(had, n)                   # sorted and de-duplicated per request
+            xoff, xids = dev(xo), dev(xi)
+        s, i, c, m = torch.ops.m2d.topk_markets_excluding(self.engine.id, dev(u).to(torch.int32), dev(off), dev(ids), xoff, xids, int(k),
+                                                          int(max_missing))
+        self.engine.check()
+        out = (s.cpu().numpy(), i.cpu().numpy(), c.cpu().numpy())
+        return out + (m.cpu().numpy(),) if missing else out
+
     def topk(self, users, k: int = 10, exclude=None, head: bool = False, candidates: int = 0, among=None, market=None,
              max_missing: int = 0):
         """The k best dishes of every user in `users` over the whole catalogue -- the ranking rule of

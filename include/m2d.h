@@ -452,6 +452,45 @@ int m2d_topk_markets(m2d_engine *h, const int32_t *users /* device, [nQ] */, int
                      int32_t *out_ids /* device, [nQ, k] */, int32_t *out_counts /* device, [nQ], may be null */,
                      void *stream);
 
+/* ---- build-defined extension, NO reference counterpart ----
+ * m2d_topk_markets with two additions: dishes the shopper has already had are left out, and for every listed dish the call names the
+ * list entries its market lacks.  Everything not said here is m2d_topk_markets' rule: the cookable definition, the order, the literal pair
+ * score bit for bit, non-finite tables, the refusals, "never synchronises".
+ *
+ * Exclusions.  X_q = excl_ids[excl_off[q] .. excl_off[q+1]): dish ids, ascending within a segment, repeats count once
+ * (m2d_catalogue_rank's conventions; excl_off == NULL: no exclusions).  Row q is the first k of the order over {cookable for q} \ X_q,
+ * out_counts[q] the size of that set -- what could be listed, not what is cookable.  An excluded dish is never scored; one that is not
+ * cookable has no effect.  With excl_off == NULL and out_missing == NULL every output word equals m2d_topk_markets' (the same kernels
+ * are launched).
+ *
+ * Missing entries.  out_missing i32[nQ, k, max_missing] (may be null; ignored when max_missing == 0): for the listed dish
+ * out_ids[q, j] the ingredient ids of its list ENTRIES that are absent from market q, in list order, every occurrence (an id listed twice
+ * and absent appears twice), -1 from the number missing on, and all -1 where the id is -1.  Every word is written.  The number of
+ * non-negative words equals m2d_cookable_dishes' out_missing for that dish and market.
+ *
+ * Errors.  Arguments: those of m2d_topk_markets.  excl_ids carries no length: as in m2d_catalogue_rank it is excl_off[nQ], read on the
+ * device (0 when excl_ids is NULL).  Latched, first wins: an excluded id outside [0, I) as M2D_ERR_BAD_ITEM_ID with its value and its
+ * index in excl_ids; an excluded id below its predecessor in the segment as M2D_ERR_INVALID_ARG with its value and index in excl_ids; a
+ * segment with excl_off[q+1] < excl_off[q] or one that reaches outside [0, excl_off[nQ]] -- any non-empty segment when excl_ids is NULL
+ * -- as M2D_ERR_INVALID_ARG with excl_off[q+1] and q + 1, its index in excl_off.  Segments are clamped into the array before anything is
+ * read, no kernel reads out of bounds; rows of a call with a latched error are unspecified, every other request's row is right.
+ *
+ * Kernels.  m2d_markets_topk<LDS, true> (m2d_last_kernel: m2d_markets_topk_excl_lds / _l2): per 64-dish group two wave-uniform lower
+ * bounds give the segment's window for [d0, d0 + 64); an empty window costs nothing more, otherwise each lane searches the window for
+ * its own dish and the result leaves the kept ballot before the scoring loop.  The share-0 block of a request validates its segment
+ * once.  m2d_markets_missing, after the rows are final (after the share merge when S > 1): one block per request with the request's
+ * bitmap (rebuilt in LDS, or the one left in scratch by the through-L2 form), a wave per listed dish, 64 entries a batch, each absent
+ * entry placed by the ballot's popcount below its lane plus the running total -- list order by construction, writes capped at
+ * max_missing. */
+int m2d_topk_markets_excluding(m2d_engine *h, const int32_t *users /* device, [nQ] */, int64_t nQ,
+                               const int64_t *market_off /* device, [nQ + 1] */,
+                               const int32_t *market_ids /* device, [nnzM], may be null when nnzM == 0 */, int64_t nnzM,
+                               const int64_t *excl_off /* device, [nQ + 1], NULL = no exclusions */,
+                               const int32_t *excl_ids /* device, [excl_off[nQ]] */,
+                               int32_t k, int32_t max_missing, float *out_scores /* device, [nQ, k] */,
+                               int32_t *out_ids /* device, [nQ, k] */, int32_t *out_counts /* device, [nQ], may be null */,
+                               int32_t *out_missing /* device, [nQ, k, max_missing], may be null */, void *stream);
+
 /* Synchronise `stream` and report (then clear) the first id error latched by kernels since the
  * previous check: M2D_OK, M2D_ERR_BAD_USER_ID or M2D_ERR_BAD_ITEM_ID.  TF-CPU GatherV2 raises
  * InvalidArgument for such ids; the kernels never read out of bounds and write NaN for the pair.
@@ -459,7 +498,10 @@ int m2d_topk_markets(m2d_engine *h, const int32_t *users /* device, [nQ] */, int
  * position in excl_ids / excl_off), or a slate entry of m2d_score_slate / m2d_topk_slate is not above its predecessor (bad_value: the id,
  * bad_index: its position in the slate), or a market segment of m2d_topk_markets decreases or reaches outside [0, nnzM] (bad_value: its
  * end offset, bad_index: the request).  M2D_ERR_BAD_INGREDIENT: a market id out of range (m2d_cookable_dishes, m2d_topk_markets).
- * bad_value / bad_index (host pointers, may be NULL) receive the offending id and its position. */
+ * bad_value / bad_index (host pointers, may be NULL) receive the offending id and its position.
+ * m2d_topk_markets_excluding: its market and user errors are m2d_topk_markets'; an excluded id out of range is M2D_ERR_BAD_ITEM_ID
+ * (bad_index: its position in excl_ids), an excluded id below its predecessor M2D_ERR_INVALID_ARG (the id, its position in excl_ids), an
+ * exclusion segment that decreases or reaches outside the array M2D_ERR_INVALID_ARG (its end offset, that offset's index in excl_off). */
 int m2d_check(m2d_engine *h, void *stream, int64_t *bad_value, int64_t *bad_index);
 
 /* Options.  m2d_score_pairs* -- the reference path (Model_Recommender.py:56-97) -- is exact float32 whatever is set here, "pm_bf16"
