@@ -58,6 +58,8 @@ SIGNATURES = {
     "m2d_clear_mlp_head": (_c.c_int, [_vp]),
     "m2d_score_pairs_mlp": (_c.c_int, [_vp, _vp, _vp, _i64, _vp, _vp]),
     "m2d_topk_users_mlp": (_c.c_int, [_vp, _vp, _i64, _i32, _i32, _vp, _vp, _vp]),
+    "m2d_topk_users_mlp_excluding": (_c.c_int, [_vp, _vp, _i64, _i32, _i32, _vp, _vp, _vp, _vp, _vp]),
+    "m2d_catalogue_rank_mlp": (_c.c_int, [_vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp]),
     "m2d_rank_candidates_mlp": (_c.c_int, [_vp, _vp, _vp, _vp, _i64, _i32, _i32, _vp, _vp, _vp, _vp]),
     "m2d_score_slate": (_c.c_int, [_vp, _vp, _i64, _vp, _i64, _vp, _vp]),
     "m2d_topk_slate": (_c.c_int, [_vp, _vp, _i64, _vp, _i64, _i32, _vp, _vp, _vp]),

@@ -155,6 +155,7 @@ void release(m2d_engine *h)
     if (h->topk_mlp_ids) (void)hipFree(h->topk_mlp_ids);
     if (h->topk_mlp_scores) (void)hipFree(h->topk_mlp_scores);
     if (h->topk_mlp_cand) (void)hipFree(h->topk_mlp_cand);
+    if (h->topk_mlp_held) (void)hipFree(h->topk_mlp_held);
     if (h->slate_dt) (void)hipFree(h->slate_dt);
     if (h->slate_scores) (void)hipFree(h->slate_scores);
     if (h->err_dev) (void)hipFree(h->err_dev);
@@ -853,6 +854,38 @@ int m2d_topk_users_mlp(m2d_engine *h, const int32_t *users, int64_t nU, int32_t 
     return m2d_launch_topk_users_mlp(h, users, nU, k, candidates, out_scores, out_ids, (hipStream_t)stream);
 }
 
+int m2d_topk_users_mlp_excluding(m2d_engine *h, const int32_t *users, int64_t nU, int32_t k, int32_t candidates, const int64_t *excl_off,
+                                 const int32_t *excl_ids, float *out_scores, int32_t *out_ids, void *stream)
+{
+    if (!h) return M2D_ERR_INVALID_ARG;
+    if (!excl_off)                                  // no exclusions: m2d_topk_users_mlp's launches and words, its argument rules
+        return m2d_topk_users_mlp(h, users, nU, k, candidates, out_scores, out_ids, stream);
+    if (nU < 0 || k < 1 || k > 64 || (int64_t)k > h->I)
+        return fail(h, M2D_ERR_INVALID_ARG, "m2d_topk_users_mlp_excluding: need nU >= 0 and 1 <= k <= min(64, I)");
+    if (candidates != 0 && (candidates < k || candidates > 16 || (int64_t)candidates > h->I))
+        return fail(h, M2D_ERR_INVALID_ARG, "m2d_topk_users_mlp_excluding: with exclusions candidates must be 0 (exact) or k <= candidates <= min(16, I)");
+    if (nU == 0) return M2D_OK;
+    if (!users || !out_scores || !out_ids || !excl_ids) return fail(h, M2D_ERR_INVALID_ARG, "m2d_topk_users_mlp_excluding: null buffer");
+    if (!h->mlp_w1) return fail(h, M2D_ERR_NOT_CONFIGURED, "call m2d_set_mlp_head first");
+    if (!h->dish_cats) return fail(h, M2D_ERR_NOT_CONFIGURED, "call m2d_set_dish_categories first");
+    M2D_HIP_TRY(h, hipSetDevice(h->device));
+    return m2d_launch_topk_users_mlp(h, users, nU, k, candidates, out_scores, out_ids, (hipStream_t)stream, excl_off, excl_ids);
+}
+
+int m2d_catalogue_rank_mlp(m2d_engine *h, const int32_t *users, const int32_t *items, int64_t n, const int64_t *excl_off,
+                           const int32_t *excl_ids, int32_t *out_rank, float *out_scores, void *stream)
+{
+    if (!h) return M2D_ERR_INVALID_ARG;
+    if (n < 0) return fail(h, M2D_ERR_INVALID_ARG, "m2d_catalogue_rank_mlp: need n >= 0");
+    if (n == 0) return M2D_OK;
+    if (!users || !items || !out_rank || (excl_off && !excl_ids))
+        return fail(h, M2D_ERR_INVALID_ARG, "m2d_catalogue_rank_mlp: null buffer");
+    if (!h->mlp_w1) return fail(h, M2D_ERR_NOT_CONFIGURED, "call m2d_set_mlp_head first");
+    if (!h->dish_cats) return fail(h, M2D_ERR_NOT_CONFIGURED, "call m2d_set_dish_categories first");
+    M2D_HIP_TRY(h, hipSetDevice(h->device));
+    return m2d_launch_catalogue_rank_mlp(h, users, items, n, excl_off, excl_ids, out_rank, out_scores, (hipStream_t)stream);
+}
+
 int m2d_rank_candidates_mlp(m2d_engine *h, const int32_t *users, const int32_t *items, const int32_t *lens, int64_t nseg, int32_t L,
                             int32_t k, float *out_scores, int32_t *out_items, int32_t *out_flags, void *stream)
 {
@@ -965,7 +998,8 @@ int m2d_check(m2d_engine *h, void *stream, int64_t *bad_value, int64_t *bad_inde
                         " (an id below its predecessor in excl_ids, an offset below its predecessor in excl_off, or a slate id not above its predecessor;"
                         " m2d_topk_markets: the end offset of a market segment that decreases or reaches outside [0, nnzM], at its request;"
                         " m2d_topk_markets_excluding: also an excluded id below its predecessor, at its index in excl_ids, or the end offset of an"
-                        " exclusion segment that decreases or reaches outside the array, at its index in excl_off)";
+                        " exclusion segment that decreases or reaches outside the array, at its index in excl_off;"
+                        " m2d_topk_users_mlp_excluding / m2d_catalogue_rank_mlp: the exclusion lists as m2d_catalogue_rank reports them)";
         return code;
     }
     const char *what = code == M2D_ERR_BAD_USER_ID ? "user" : code == M2D_ERR_BAD_ITEM_ID ? "item" : "ingredient";

@@ -150,8 +150,9 @@ M2D_INTERNAL int m2d_topk_literal_launch(m2d_engine *h, const int32_t *users, in
 M2D_INTERNAL int m2d_plan_sort_launch(m2d_engine *h, const float *plan, int64_t nU, int32_t *hist, int32_t *order, hipStream_t st,
                                       bool hist_zeroed = false);
 // m2d_catalogue_rank.hip, also for m2d_topk_users_excluding (`entry`): the refusals of a model the ranking arithmetic does not cover, the
-// sorted dish table, the per-tile largest row norms of that table (h->rank_tnorm, built once per table)
-M2D_INTERNAL int m2d_rank_prepare(m2d_engine *h, const char *entry, hipStream_t st);
+// sorted dish table, the per-tile largest row norms of that table (h->rank_tnorm, built once per table).  under_head: an installed MLP
+// head is no refusal -- the caller scores the result under it (m2d_topk_users_mlp_excluding's stage 1)
+M2D_INTERNAL int m2d_rank_prepare(m2d_engine *h, const char *entry, hipStream_t st, bool under_head = false);
 
 // The scratch both calls keep per call of n records: records [n, 8] | bound sums [n, 16] | order [n4] | sort histogram [PLAN_KEYS] |
 // counters [8], carved from `base` (null: the float count alone, to grow the buffer by before it is carved)
@@ -697,7 +698,7 @@ __device__ __forceinline__ int csr_check_id(const int64_t *off, const int32_t *i
         r = 0;
     } else {
         q = csr_owner(off, n, i);
-        if (i > off[q]) {
+        if (i > off[q] && i > 0) {                          // (i > 0: a negative first offset must not reach in front of the array)
             const int32_t prev = ids[i - 1];
             if (prev > x && report) m2d_latch_error(err, M2D_ERR_INVALID_ARG, x, i);
             r = prev > x ? 0 : (prev == x ? 2 : 1);

@@ -390,10 +390,11 @@ __global__ __launch_bounds__(256) void m2d_topk_excl_merge(ExclArgs p)
 }  // namespace
 
 int m2d_launch_topk_users_excluding(m2d_engine *h, const int32_t *users, int64_t nU, int32_t k, const int64_t *excl_off,
-                                    const int32_t *excl_ids, float *out_scores, int32_t *out_ids, hipStream_t st)
+                                    const int32_t *excl_ids, float *out_scores, int32_t *out_ids, hipStream_t st, const char *entry,
+                                    bool under_head)
 {
     int rc;
-    if ((rc = m2d_rank_prepare(h, "m2d_topk_users_excluding", st)) != M2D_OK) return rc;
+    if ((rc = m2d_rank_prepare(h, entry, st, under_head)) != M2D_OK) return rc;
 
     // tier 1 where m2d_topk_users' lists are index-exact against the ranking arithmetic (include/m2d.h), under the default options
     const int K1 = h->E == 128 ? 10 : 16;

@@ -226,7 +226,7 @@ __global__ __launch_bounds__(256) void m2d_rank_tile_norms(const float *rs, int6
 // What m2d_catalogue_rank and m2d_topk_users_excluding (`entry`: the name their refusals carry) need before they launch: a model
 // the ranking arithmetic covers, the sorted dish table, and h->rank_tnorm for that table as it stands (rebuilt when the table
 // was: grp_gen)
-int m2d_rank_prepare(m2d_engine *h, const char *entry, hipStream_t st)
+int m2d_rank_prepare(m2d_engine *h, const char *entry, hipStream_t st, bool under_head)
 {
     auto refuse = [&](const char *why) {
         h->last_error = std::string(entry) + ": " + why;
@@ -235,7 +235,7 @@ int m2d_rank_prepare(m2d_engine *h, const char *entry, hipStream_t st)
     if (h->C != 4) return refuse("needs C = 4 categories");
     if (h->E % 4 != 0 || h->E > 256) return refuse("needs E a multiple of 4 up to 256");
     if (h->ing || h->dish_high) return refuse("the ingredient table is set (not supported)");
-    if (h->mlp_w1) return refuse("the MLP head is set (not supported)");
+    if (h->mlp_w1 && !under_head) return refuse("the MLP head is set (not supported)");
     int rc;
     if ((rc = m2d_ensure_finite_scan(h, st)) != M2D_OK) return rc;
     if ((rc = m2d_grouped_tables(h, st)) != M2D_OK) return rc;

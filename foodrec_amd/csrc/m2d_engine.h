@@ -68,11 +68,14 @@ struct m2d_engine {
     size_t mlp_pg_cap = 0;              // ints
 
     // m2d_topk_users_mlp (m2d_topk_mlp.hip): a chunk's pair ids (users | items), its head scores and, in the two-stage form, stage 1's
-    // candidate ids -- buffers of their own: stage 1 writes `scratch`, the head's pair grouping writes mlp_pg
+    // candidate ids (with exclusions: the whole call's, ids [nU, K1] | stage 1's scores [nU, K1]) -- buffers of their own: stage 1
+    // writes `scratch`, the head's pair grouping writes mlp_pg
     int32_t *topk_mlp_ids = nullptr;
     float *topk_mlp_scores = nullptr;
     int32_t *topk_mlp_cand = nullptr;
     size_t topk_mlp_ids_cap = 0, topk_mlp_scores_cap = 0, topk_mlp_cand_cap = 0;   // ints / floats / ints
+    float *topk_mlp_held = nullptr;               // m2d_catalogue_rank_mlp: the held-out pairs' scores when the caller takes none
+    size_t topk_mlp_held_cap = 0;                 // floats
     int64_t opt_topk_mlp_chunk_pairs = 1 << 22;   // pairs per head launch of that call (diagnostic: the lists do not depend on it)
     int64_t topk_mlp_launches = 0;                // head launches of the last call
 
@@ -354,6 +357,27 @@ __device__ __forceinline__ uint64_t tkm_key(const float s, const int32_t id)
     return ((uint64_t)hi << 32) | (uint32_t)id;
 }
 
+// A CSR segment per row, as m2d_topk_markets takes a request's market and the exclusion forms (m2d_markets_topk<LDS, true>,
+// m2d_topk_mlp_select<true, false>, m2d_topk_mlp_count) a row's excluded dishes.
+// request q's market segment, clamped into [0, nnzM] before anything is read; `bad`: it decreases or reaches outside
+__device__ __forceinline__ void market_segment(const int64_t *moff, int64_t q, int64_t nnzM, int64_t &m0, int64_t &m1, bool &bad)
+{
+    const int64_t lo = moff[q], hi = moff[q + 1];
+    bad = hi < lo || lo < 0 || hi > nnzM;
+    m0 = lo < 0 ? 0 : lo > nnzM ? nnzM : lo;
+    m1 = hi < m0 ? m0 : hi > nnzM ? nnzM : hi;
+}
+
+// first position in [lo, hi) of the ascending ids whose id is not below d
+__device__ __forceinline__ int64_t excl_lower_bound(const int32_t *ids, int64_t lo, int64_t hi, const int64_t d)
+{
+    while (lo < hi) {
+        const int64_t mid = (lo + hi) >> 1;
+        if (ids[mid] < d) lo = mid + 1; else hi = mid;
+    }
+    return lo;
+}
+
 // ---- device helpers shared by the LDS-DMA kernels (m2d_catalogue_*.hip, m2d_mlp.hip) ----
 // vmcnt(0) twice over: the builtin is an s_waitcnt the compiler's own counter model sees (so it stops assuming that
 // loads from a previous loop trip are still in flight), the asm one cannot be optimised away on the grounds that
@@ -423,14 +447,22 @@ void m2d_mlp_free_derived(m2d_engine *h, bool grouping);
 int m2d_launch_rank_candidates(m2d_engine *h, const int32_t *users, const int32_t *items,
                                const int32_t *lens, int64_t nseg, int32_t L, int32_t k, float *out_scores,
                                int32_t *out_items, int32_t *out_flags, hipStream_t stream, bool head = false);
+// excl_off: the exclusion forms (m2d_topk_users_mlp_excluding) -- the exact mode strikes each row's ids inside the selection, the
+// two-stage mode takes its candidates from m2d_topk_users_excluding
 int m2d_launch_topk_users_mlp(m2d_engine *h, const int32_t *users, int64_t nU, int32_t k, int32_t candidates, float *out_scores,
-                              int32_t *out_ids, hipStream_t stream);
+                              int32_t *out_ids, hipStream_t stream, const int64_t *excl_off = nullptr, const int32_t *excl_ids = nullptr);
+int m2d_launch_catalogue_rank_mlp(m2d_engine *h, const int32_t *users, const int32_t *items, int64_t n, const int64_t *excl_off,
+                                  const int32_t *excl_ids, int32_t *out_rank, float *out_scores, hipStream_t stream);
 int m2d_launch_topk_users(m2d_engine *h, const int32_t *users, int64_t nU, int32_t k, float *out_scores,
                           int32_t *out_ids, hipStream_t stream);
 // m2d_topk_mlp.hip: m2d_topk_mlp_select over `rows` score rows of W columns (column e of row r at scores[r * rs + e * es]); ids: row r's
-// at ids + r * ids_stride (0: one id row shared by all), or d0 + e when null; first = 0 merges into the lists the outputs hold
+// at ids + r * ids_stride (0: one id row shared by all), or d0 + e when null; first = 0 merges into the lists the outputs hold;
+// xoff (dish-major form, ids == null): row r leaves out the ascending dish ids xids[xoff[r] .. xoff[r + 1]), *xend = the array's length;
+// holes: an id below 0 in `ids` is no entry whatever its score (the candidates of the exclusion retrieval)
 int m2d_launch_topk_select(m2d_engine *h, const float *scores, const int32_t *ids, int64_t ids_stride, int64_t rows, int64_t W, int32_t d0,
-                           int32_t k, int32_t first, float *out_scores, int32_t *out_ids, int64_t rs, int64_t es, hipStream_t stream);
+                           int32_t k, int32_t first, float *out_scores, int32_t *out_ids, int64_t rs, int64_t es, hipStream_t stream,
+                           const int64_t *xoff = nullptr, const int32_t *xids = nullptr, const int64_t *xend = nullptr,
+                           bool holes = false);
 // m2d_slate.hip: out == null: the scores of user blocks go to scratch and the lists of k to out_scores / out_ids
 int m2d_launch_slate(m2d_engine *h, const char *entry, const int32_t *users, int64_t nU, const int32_t *slate, int64_t nD, int32_t k,
                      float *out, float *out_scores, int32_t *out_ids, hipStream_t stream);
@@ -438,5 +470,7 @@ int m2d_launch_slate(m2d_engine *h, const char *entry, const int32_t *users, int
 int m2d_refresh_nonfinite(m2d_engine *h, hipStream_t stream);
 int m2d_launch_catalogue_rank(m2d_engine *h, const int32_t *users, const int32_t *items, int64_t n, const int64_t *excl_off,
                               const int32_t *excl_ids, int32_t *out_rank, float *out_scores, hipStream_t stream);
+// entry: the name its refusals carry; under_head: the caller ranks the lists under the MLP head afterwards (m2d_topk_users_mlp_excluding)
 int m2d_launch_topk_users_excluding(m2d_engine *h, const int32_t *users, int64_t nU, int32_t k, const int64_t *excl_off,
-                                    const int32_t *excl_ids, float *out_scores, int32_t *out_ids, hipStream_t stream);
+                                    const int32_t *excl_ids, float *out_scores, int32_t *out_ids, hipStream_t stream,
+                                    const char *entry = "m2d_topk_users_excluding", bool under_head = false);

@@ -60,14 +60,7 @@ struct MarketsArgs {
 // operation executes under a partial EXEC mask.
 __device__ __forceinline__ int uni(int v) { return __builtin_amdgcn_readfirstlane(v); }
 
-// request q's market segment, clamped into [0, nnzM] before anything is read; `bad`: it decreases or reaches outside
-__device__ __forceinline__ void market_segment(const int64_t *moff, int64_t q, int64_t nnzM, int64_t &m0, int64_t &m1, bool &bad)
-{
-    const int64_t lo = moff[q], hi = moff[q + 1];
-    bad = hi < lo || lo < 0 || hi > nnzM;
-    m0 = lo < 0 ? 0 : lo > nnzM ? nnzM : lo;
-    m1 = hi < m0 ? m0 : hi > nnzM ? nnzM : hi;
-}
+// (market_segment and excl_lower_bound are m2d_engine.h's: m2d_topk_mlp.hip takes its exclusion windows with them as well)
 
 // through-L2 form: block q sets request q's bits in its own bitmap (zeroed by a memset in front)
 __global__ __launch_bounds__(256) void m2d_markets_bitmap(const int64_t *moff, const int32_t *mids, int64_t nnzM, int32_t R, int64_t words,
@@ -83,16 +76,6 @@ __global__ __launch_bounds__(256) void m2d_markets_bitmap(const int64_t *moff, c
         if (id < 0 || id >= R) m2d_latch_error(err, M2D_ERR_BAD_INGREDIENT, id, i);
         else atomicOr(&bm[id >> 5], 1u << (id & 31));
     }
-}
-
-// first position in [lo, hi) of the ascending ids whose id is not below d
-__device__ __forceinline__ int64_t excl_lower_bound(const int32_t *ids, int64_t lo, int64_t hi, const int64_t d)
-{
-    while (lo < hi) {
-        const int64_t mid = (lo + hi) >> 1;
-        if (ids[mid] < d) lo = mid + 1; else hi = mid;
-    }
-    return lo;
 }
 
 template <bool LDS, bool EXCL = false>

@@ -1,7 +1,10 @@
 // Retrieval under the 3-layer head (build-defined extension): full-catalogue top-k and the two-stage
 // retrieve-then-rerank form.  The head arithmetic is m2d_launch_score_pairs_mlp's (m2d_mlp.hip), whichever kernel family the
 // shape selects; this file is what stands around it: the pair generators, the selection kernel and the chunked launcher.
-#include "m2d_engine.h"
+// With exclusions: m2d_topk_mlp_select<true, false> strikes a row's excluded dishes from every step before its
+// ballots, m2d_topk_mlp_count counts the dishes in front of a held-out one (m2d_catalogue_rank_mlp), m2d_topk_mlp_check_excl looks
+// at the lists once per call.
+#include "m2d_catalogue.h"   // (csr_check_offset / csr_check_id: the list checks of m2d_catalogue_rank)
 
 namespace {
 
@@ -21,15 +24,73 @@ __global__ __launch_bounds__(256) void m2d_topk_mlp_pairs(const int32_t *users, 
 }
 
 // stage 2 of the two-stage form: pair r * W + j is (users[r], cand[r][j]), cand i32[rows, W] as stage 1 left it (user-major: every
-// user has candidates of its own)
+// user has candidates of its own).  FILL: a slot stage 1 left empty (id -1: fewer than W dishes remained) becomes a pair on dish 0, so
+// that the head launch stays in bounds; the selection reads the ids from `cand` and drops the slot whatever it scored.
+template <bool FILL = false>
 __global__ __launch_bounds__(256) void m2d_topk_mlp_pairs_cand(const int32_t *users, const int32_t *cand, int64_t rows, int64_t W,
                                                                int32_t *users_x, int32_t *items_x)
 {
     const int64_t total = rows * W, stride = (int64_t)gridDim.x * blockDim.x;
     for (int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += stride) {
         users_x[t] = users[t / W];
-        items_x[t] = cand[t];
+        items_x[t] = FILL && cand[t] < 0 ? 0 : cand[t];
     }
+}
+
+// ---- a row's exclusion window ---------------------------------------------------------------------------------------------
+// The row's segment of ascending dish ids, clamped into the array before anything is read, and a cursor into it that only moves
+// forward: a wave's 256-score steps cover consecutive ids [id0, id0 + 256) and ascend.  Everything here is wave-uniform and carried
+// in SGPRs (readfirstlane), so the branches around the window are scalar ones; the per-lane search inside has no cross-lane operation.
+// The ids are only ever compared: a bad one (reported by m2d_topk_mlp_check_excl) indexes nothing.
+__device__ __forceinline__ int64_t uni64(const int64_t v)
+{
+    return (int64_t)(((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)((uint64_t)v >> 32)) << 32) |
+                     (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)v));
+}
+
+struct ExclCursor {
+    int64_t xw = 0, x1 = 0;          // the next step's window starts at xw or behind it; the segment's end
+    int32_t xv = INT32_MAX;          // the id at xw: a step that ends at or below it has an empty window and pays one compare
+
+    __device__ __forceinline__ void open(const int64_t *xoff, const int32_t *xids, const int64_t *xend, const int64_t row)
+    {
+        if (!xoff) return;
+        int64_t x0;
+        bool bad;
+        market_segment(xoff, row, *xend, x0, x1, bad);       // (a bad segment is m2d_topk_mlp_check_excl's to report)
+        xw = uni64(x0);
+        x1 = uni64(x1);
+        if (xw < x1) xv = __builtin_amdgcn_readfirstlane(xids[xw]);
+    }
+
+    // keys of the step's four slices (slice q, lane l: id id0 + 64 q + l) whose id is in the segment become TKM_NONE
+    __device__ __forceinline__ void strike(const int32_t *xids, const int64_t id0, const int lane, uint64_t (&ck)[4])
+    {
+        if ((int64_t)xv >= id0 + 256) return;                // scalar: xv is the smallest id the wave has not passed
+        const int64_t w0 = uni64(excl_lower_bound(xids, xw, x1, id0)), w1 = uni64(excl_lower_bound(xids, w0, x1, id0 + 256));
+        xw = w1;
+        xv = w1 < x1 ? __builtin_amdgcn_readfirstlane(xids[w1]) : INT32_MAX;
+        if (w1 == w0) return;                                // scalar: nothing of the segment in this step
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const int64_t id = id0 + q * 64 + lane;
+            const int64_t at = excl_lower_bound(xids, w0, w1, id);
+            if (at < w1 && xids[at] == id) ck[q] = TKM_NONE;
+        }
+    }
+};
+
+// The lists of a call, looked at once: offsets non-decreasing from 0 (so none reaches past the array, whose length is the last of
+// them), every id a dish of the catalogue and not below the id in front of it in its segment -- m2d_catalogue_rank's checks and
+// latch values (m2d_catalogue.h).
+__global__ __launch_bounds__(256) void m2d_topk_mlp_check_excl(const int64_t *xoff, const int32_t *xids, int64_t n, int64_t I, int32_t *err)
+{
+    const int64_t t0 = (int64_t)blockIdx.x * 256 + threadIdx.x, nt = (int64_t)gridDim.x * 256;
+    for (int64_t q = t0; q <= n; q += nt) csr_check_offset(xoff, q, err);
+    const int64_t nnz = xoff[n];
+    int32_t x;
+    int64_t row;
+    for (int64_t i = t0; i < nnz; i += nt) csr_check_id(xoff, xids, n, I, i, true, err, x, row);
 }
 
 // ---- selection ------------------------------------------------------------------------------------------------------------
@@ -44,9 +105,14 @@ __global__ __launch_bounds__(256) void m2d_topk_mlp_pairs_cand(const int32_t *us
 // k ln(W / k) candidates pass per wave, the rest costs a load, a compare and a ballot per 64 scores.  The waves' lists and the
 // running list meet in LDS ((waves + 1) k keys of 8 B and score words of 4 B), where every entry counts the entries in front of
 // it and the first k write themselves out.  No atomics; the score written is the word that was read (a NaN's payload, a -0).
+// EXCL (dish-major form only: ids == null): row r leaves out xids[xoff[r] .. xoff[r + 1]), ascending dish ids, the array's length at
+// *xend -- struck by ExclCursor::strike between a step's loads and its ballots.  HOLES (candidate form behind the exclusion
+// retrieval): an id below 0 in `ids` is no entry (TKM_NONE), whatever its score.  <false, false> is the kernel as it stood.
+template <bool EXCL, bool HOLES>
 __global__ __launch_bounds__(1024) void m2d_topk_mlp_select(const float *scores, const int32_t *ids, int64_t W, int32_t d0, int32_t k,
                                                             int32_t first, float *out_scores, int32_t *out_ids, int64_t rs, int64_t es,
-                                                            int64_t ids_stride)
+                                                            int64_t ids_stride, const int64_t *xoff, const int32_t *xids,
+                                                            const int64_t *xend)
 {
     extern __shared__ __align__(16) unsigned char smem[];
     const int nw = blockDim.x >> 6, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
@@ -58,6 +124,8 @@ __global__ __launch_bounds__(1024) void m2d_topk_mlp_select(const float *scores,
 
     uint64_t lk = TKM_NONE, thr = TKM_NONE;      // this lane's list entry; lane k - 1's: what a candidate has to beat
     uint32_t ls = 0x7FC00000u;
+    ExclCursor xc;
+    if (EXCL) xc.open(xoff, xids, xend, row);
     for (int64_t base = (int64_t)wave * 256; base < W; base += (int64_t)nw * 256) {
         uint64_t ck[4];
         uint32_t cs[4];
@@ -69,9 +137,12 @@ __global__ __launch_bounds__(1024) void m2d_topk_mlp_select(const float *scores,
             if (e < W) {
                 const float s = sc[e * es];
                 cs[q] = __float_as_uint(s);
-                ck[q] = tkm_key(s, idr ? idr[e] : d0 + (int32_t)e);
+                const int32_t id = idr ? idr[e] : d0 + (int32_t)e;
+                ck[q] = tkm_key(s, id);
+                if (HOLES) ck[q] |= (uint64_t)(int64_t)(id >> 31);          // an id below 0: all ones, TKM_NONE (no branch)
             }
         }
+        if (EXCL) xc.strike(xids, (int64_t)d0 + base, lane, ck);
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
             unsigned long long m = __ballot(ck[q] < thr);
@@ -115,58 +186,183 @@ __global__ __launch_bounds__(1024) void m2d_topk_mlp_select(const float *scores,
     }
 }
 
-// threads of a selection block: a wave for the reranker's short rows, sixteen for a catalogue-wide range (few rows then share
+// ---- the rank of a held-out dish ---------------------------------------------------------------------------------------------
+// One workgroup per query row (user, held-out dish p): the row's W scores in the dish-major layout (column e at scores[row + e *
+// rows], dish d0 + e), read in the selection's steps.  A lane counts the dishes whose key is in front of p's -- held[row] is p's
+// score word, from the same launcher --, p itself and the row's excluded dishes (ExclCursor) left out; one full-wave reduction, the
+// waves' sums meet in LDS, and thread 0 stores the count (`first`: the first dish range) or adds it to out_rank[row].  No atomics:
+// a row has one block per range and the ranges are stream-ordered.
+__global__ __launch_bounds__(1024) void m2d_topk_mlp_count(const float *scores, int64_t rows, int64_t W, int32_t d0, int32_t first,
+                                                           const int32_t *items, const float *held, int32_t *out_rank,
+                                                           const int64_t *xoff, const int32_t *xids, const int64_t *xend)
+{
+    __shared__ int32_t wsum[16];
+    const int nw = blockDim.x >> 6, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
+    const int64_t row = blockIdx.x;
+    const float *sc = scores + row;
+    const int32_t p = items[row];
+    const uint64_t pk = tkm_key(held[row], p);
+    ExclCursor xc;
+    xc.open(xoff, xids, xend, row);
+    int32_t cnt = 0;
+    for (int64_t base = (int64_t)wave * 256; base < W; base += (int64_t)nw * 256) {
+        uint64_t ck[4];
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {            // four slices in flight
+            const int64_t e = base + q * 64 + lane;
+            ck[q] = TKM_NONE;
+            if (e < W) ck[q] = tkm_key(sc[e * rows], d0 + (int32_t)e);
+        }
+        if (xoff) xc.strike(xids, (int64_t)d0 + base, lane, ck);             // scalar: a kernel argument
+#pragma unroll
+        for (int q = 0; q < 4; ++q) cnt += (ck[q] < pk && (uint32_t)ck[q] != (uint32_t)p) ? 1 : 0;   // (TKM_NONE is in front of no key)
+    }
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) cnt += __shfl_xor(cnt, off, 64);
+    if (lane == 0) wsum[wave] = cnt;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        int32_t total = first ? 0 : out_rank[row];
+        for (int w = 0; w < nw; ++w) total += wsum[w];
+        out_rank[row] = total;
+    }
+}
+
+// threads of a selection / count block: a wave for the reranker's short rows, sixteen for a catalogue-wide range (few rows then share
 // the device: a block of P / W rows)
 int select_threads(const int64_t W) { return W <= 256 ? 64 : W <= 16384 ? 256 : 1024; }
 
 }  // namespace
 
 int m2d_launch_topk_select(m2d_engine *h, const float *scores, const int32_t *ids, int64_t ids_stride, int64_t rows, int64_t W, int32_t d0,
-                           int32_t k, int32_t first, float *out_scores, int32_t *out_ids, int64_t rs, int64_t es, hipStream_t stream)
+                           int32_t k, int32_t first, float *out_scores, int32_t *out_ids, int64_t rs, int64_t es, hipStream_t stream,
+                           const int64_t *xoff, const int32_t *xids, const int64_t *xend, bool holes)
 {
     const int threads = select_threads(W);
     const size_t lds = (size_t)(threads / 64 + 1) * k * (sizeof(uint64_t) + sizeof(uint32_t));
-    M2D_HIP_TRY(h, m2d_lds_limit((const void *)m2d_topk_mlp_select, (int)lds));
-    hipLaunchKernelGGL(m2d_topk_mlp_select, dim3((unsigned)rows), dim3(threads), lds, stream, scores, ids, W, d0, k, first, out_scores, out_ids,
-                       rs, es, ids_stride);
+    const auto launch = [&](auto kernel) -> int {
+        M2D_HIP_TRY(h, m2d_lds_limit((const void *)kernel, (int)lds));
+        hipLaunchKernelGGL(kernel, dim3((unsigned)rows), dim3(threads), lds, stream, scores, ids, W, d0, k, first, out_scores, out_ids, rs, es,
+                           ids_stride, xoff, xids, xend);
+        M2D_HIP_TRY(h, hipGetLastError());
+        return M2D_OK;
+    };
+    return xoff ? launch(m2d_topk_mlp_select<true, false>) : holes ? launch(m2d_topk_mlp_select<false, true>) : launch(m2d_topk_mlp_select<false, false>);
+}
+
+namespace {
+
+// the chunk geometry of both calls: dish ranges of W dishes, blocks of R rows, n pairs of scratch a chunk
+struct ChunkShape {
+    int64_t W, R;
+    size_t n;
+};
+
+ChunkShape chunk_shape(const m2d_engine *h, const int64_t rows, const int64_t width)
+{
+    const int64_t P = h->opt_topk_mlp_chunk_pairs;
+    ChunkShape c;
+    c.W = width < P ? width : P;
+    const int64_t R0 = P / c.W > 1 ? P / c.W : 1;
+    c.R = R0 < rows ? R0 : rows;
+    c.n = ((size_t)c.R * c.W + 3) & ~(size_t)3;                     // (the id halves stay 16-byte aligned)
+    return c;
+}
+
+int launch_check_excl(m2d_engine *h, const int64_t *excl_off, const int32_t *excl_ids, int64_t n, hipStream_t stream)
+{
+    hipLaunchKernelGGL(m2d_topk_mlp_check_excl, dim3(m2d_blocks_for(h, n + 1, 256, 4)), dim3(256), 0, stream, excl_off, excl_ids, n, h->I,
+                       h->err_dev);
     M2D_HIP_TRY(h, hipGetLastError());
     return M2D_OK;
 }
 
+}  // namespace
+
 int m2d_launch_topk_users_mlp(m2d_engine *h, const int32_t *users, int64_t nU, int32_t k, int32_t candidates, float *out_scores,
-                              int32_t *out_ids, hipStream_t stream)
+                              int32_t *out_ids, hipStream_t stream, const int64_t *excl_off, const int32_t *excl_ids)
 {
     h->topk_mlp_launches = 0;
     if (nU == 0) return M2D_OK;
     const bool two = candidates > 0;
-    const int64_t P = h->opt_topk_mlp_chunk_pairs;
-    const int64_t W = two ? candidates : (h->I < P ? h->I : P);     // dish range (two-stage: the K1 candidates)
-    const int64_t R0 = P / W > 1 ? P / W : 1, R = R0 < nU ? R0 : nU; // user rows of a block
-    const size_t n = ((size_t)R * W + 3) & ~(size_t)3;              // pairs of a chunk (the id halves stay 16-byte aligned)
+    const ChunkShape cs = chunk_shape(h, nU, two ? candidates : h->I);   // dish range (two-stage: the K1 candidates), user rows of a block
+    const int64_t W = cs.W, R = cs.R;
+    const size_t n = cs.n;                                          // pairs of a chunk
     int rc;
     if ((rc = m2d_grow(h, h->topk_mlp_ids, h->topk_mlp_ids_cap, 2 * n, sizeof(int32_t))) != M2D_OK) return rc;
     if ((rc = m2d_grow(h, h->topk_mlp_scores, h->topk_mlp_scores_cap, n, sizeof(float))) != M2D_OK) return rc;
-    if (two && (rc = m2d_grow(h, h->topk_mlp_cand, h->topk_mlp_cand_cap, n, sizeof(int32_t))) != M2D_OK) return rc;
+    // two-stage with exclusions: stage 1 runs once for the whole call (its offsets are the call's), ids [nU, K1] | scores [nU, K1]
+    const bool two_x = two && excl_off;
+    const size_t ncand = two_x ? 2 * (size_t)nU * candidates : n;
+    if (two && (rc = m2d_grow(h, h->topk_mlp_cand, h->topk_mlp_cand_cap, ncand, sizeof(int32_t))) != M2D_OK) return rc;
     int32_t *users_x = h->topk_mlp_ids, *items_x = users_x + n;
     float *scores = h->topk_mlp_scores;
+    if (two_x) {      // the K1 best by the reference score among the dishes left, -1 where fewer are (its checks are the lists' checks)
+        if ((rc = m2d_launch_topk_users_excluding(h, users, nU, candidates, excl_off, excl_ids,
+                                                  reinterpret_cast<float *>(h->topk_mlp_cand + (size_t)nU * candidates), h->topk_mlp_cand, stream,
+                                                  "m2d_topk_users_mlp_excluding", /*under_head=*/true)) != M2D_OK)
+            return rc;
+    } else if (excl_off && (rc = launch_check_excl(h, excl_off, excl_ids, nU, stream)) != M2D_OK)
+        return rc;
     for (int64_t u0 = 0; u0 < nU; u0 += R) {
         const int64_t rows = nU - u0 < R ? nU - u0 : R;
         // stage 1, as m2d_topk_users runs it: the K1 best by the reference / ingredient score (its scores are not kept: the
         // head's land on them)
-        if (two && (rc = m2d_launch_topk_users(h, users + u0, rows, candidates, scores, h->topk_mlp_cand, stream)) != M2D_OK) return rc;
+        if (two && !two_x && (rc = m2d_launch_topk_users(h, users + u0, rows, candidates, scores, h->topk_mlp_cand, stream)) != M2D_OK) return rc;
+        const int32_t *cand = two_x ? h->topk_mlp_cand + u0 * candidates : h->topk_mlp_cand;
         for (int64_t d0 = 0; d0 < (two ? W : h->I); d0 += W) {
             const int64_t Wc = two || h->I - d0 > W ? W : h->I - d0;
             const unsigned gb = m2d_blocks_for(h, rows * Wc, 1024);
-            if (two)
-                hipLaunchKernelGGL(m2d_topk_mlp_pairs_cand, dim3(gb), dim3(256), 0, stream, users + u0, h->topk_mlp_cand, rows, Wc, users_x, items_x);
+            if (two_x)
+                hipLaunchKernelGGL(m2d_topk_mlp_pairs_cand<true>, dim3(gb), dim3(256), 0, stream, users + u0, cand, rows, Wc, users_x, items_x);
+            else if (two)
+                hipLaunchKernelGGL(m2d_topk_mlp_pairs_cand<>, dim3(gb), dim3(256), 0, stream, users + u0, cand, rows, Wc, users_x, items_x);
             else
                 hipLaunchKernelGGL(m2d_topk_mlp_pairs, dim3(gb), dim3(256), 0, stream, users + u0, rows, Wc, (int32_t)d0, users_x, items_x);
             M2D_HIP_TRY(h, hipGetLastError());
             if ((rc = m2d_launch_score_pairs_mlp(h, users_x, items_x, rows * Wc, scores, stream)) != M2D_OK) return rc;
             ++h->topk_mlp_launches;
-            if ((rc = m2d_launch_topk_select(h, scores, two ? (const int32_t *)items_x : nullptr, Wc, rows, Wc, (int32_t)d0, k, d0 == 0 ? 1 : 0,
-                                             out_scores + u0 * k, out_ids + u0 * k, two ? Wc : (int64_t)1, two ? (int64_t)1 : rows, stream)) != M2D_OK)
+            const int32_t *ids = two_x ? cand : two ? (const int32_t *)items_x : nullptr;
+            const bool strike = excl_off && !two;
+            if ((rc = m2d_launch_topk_select(h, scores, ids, Wc, rows, Wc, (int32_t)d0, k, d0 == 0 ? 1 : 0, out_scores + u0 * k, out_ids + u0 * k,
+                                             two ? Wc : (int64_t)1, two ? (int64_t)1 : rows, stream, strike ? excl_off + u0 : nullptr, excl_ids,
+                                             strike ? excl_off + nU : nullptr, two_x)) != M2D_OK)
                 return rc;
+        }
+    }
+    return M2D_OK;
+}
+
+int m2d_launch_catalogue_rank_mlp(m2d_engine *h, const int32_t *users, const int32_t *items, int64_t n, const int64_t *excl_off,
+                                  const int32_t *excl_ids, int32_t *out_rank, float *out_scores, hipStream_t stream)
+{
+    h->topk_mlp_launches = 0;
+    if (n == 0) return M2D_OK;
+    const ChunkShape cs = chunk_shape(h, n, h->I);
+    const int64_t W = cs.W, R = cs.R;
+    int rc;
+    if ((rc = m2d_grow(h, h->topk_mlp_ids, h->topk_mlp_ids_cap, 2 * cs.n, sizeof(int32_t))) != M2D_OK) return rc;
+    if ((rc = m2d_grow(h, h->topk_mlp_scores, h->topk_mlp_scores_cap, cs.n, sizeof(float))) != M2D_OK) return rc;
+    if (!out_scores && (rc = m2d_grow(h, h->topk_mlp_held, h->topk_mlp_held_cap, (size_t)n, sizeof(float))) != M2D_OK) return rc;
+    int32_t *users_x = h->topk_mlp_ids, *items_x = users_x + cs.n;
+    float *scores = h->topk_mlp_scores, *held = out_scores ? out_scores : h->topk_mlp_held;
+    // the held-out pairs' words (and the call's id checks: a bad user or held-out id is latched at its query)
+    if ((rc = m2d_launch_score_pairs_mlp(h, users, items, n, held, stream)) != M2D_OK) return rc;
+    ++h->topk_mlp_launches;
+    if (excl_off && (rc = launch_check_excl(h, excl_off, excl_ids, n, stream)) != M2D_OK) return rc;
+    for (int64_t q0 = 0; q0 < n; q0 += R) {
+        const int64_t rows = n - q0 < R ? n - q0 : R;
+        for (int64_t d0 = 0; d0 < h->I; d0 += W) {
+            const int64_t Wc = h->I - d0 > W ? W : h->I - d0;
+            hipLaunchKernelGGL(m2d_topk_mlp_pairs, dim3(m2d_blocks_for(h, rows * Wc, 1024)), dim3(256), 0, stream, users + q0, rows, Wc, (int32_t)d0,
+                               users_x, items_x);
+            M2D_HIP_TRY(h, hipGetLastError());
+            if ((rc = m2d_launch_score_pairs_mlp(h, users_x, items_x, rows * Wc, scores, stream)) != M2D_OK) return rc;
+            ++h->topk_mlp_launches;
+            hipLaunchKernelGGL(m2d_topk_mlp_count, dim3((unsigned)rows), dim3(select_threads(Wc)), 0, stream, scores, rows, Wc, (int32_t)d0,
+                               d0 == 0 ? 1 : 0, items + q0, held + q0, out_rank + q0, excl_off ? excl_off + q0 : nullptr, excl_ids,
+                               excl_off ? excl_off + n : nullptr);
+            M2D_HIP_TRY(h, hipGetLastError());
         }
     }
     return M2D_OK;

@@ -70,11 +70,19 @@ def eval_one_rating(*args):
         model, user, testRatings, testNegatives, K, dish_to_category = args
     else:
         raise TypeError("eval_one_rating takes (user) or (model, user, testRatings, testNegatives, K, dish_to_category)")
+    return _eval_one(model, user, testRatings, testNegatives, K, dish_to_category, False)
+
+
+def _eval_one(model, user, testRatings, testNegatives, K, dish_to_category, head: bool):
+    # evaluate.py:35-66; `head`: the scores are predict_extended(head=True)'s (the resident dish masks: the caller has set them)
     if str(user) not in testRatings or len(testRatings[str(user)]) == 0:
         return None
     items = _candidates(user, testRatings, testNegatives)
-    cats = [dish_to_category[str(i)] for i in items]
-    scores = model.predict([user] * len(items), items, cats)
+    if head:
+        scores = model.predict_extended([user] * len(items), items, head=True)
+    else:
+        cats = [dish_to_category[str(i)] for i in items]
+        scores = model.predict([user] * len(items), items, cats)
     table = {}
     for it, sc in zip(items, scores):
         table[it] = sc
@@ -183,7 +191,7 @@ def _plan_for(model: Model, testRatings, testNegatives, dish_to_category) -> _Ev
 
 
 def evaluate_model(sess, model: Model, testRatings: Dict[str, List[int]], testNegatives: Dict[str, List[int]],
-                   K: int, dish_to_category: Dict[str, list]) -> Tuple[List[int], List[float]]:
+                   K: int, dish_to_category: Dict[str, list], head: bool = False) -> Tuple[List[int], List[float]]:
     """HR@K / NDCG@K for every user of ``testRatings``, in dict order (evaluate.py:13-32).
 
     ``sess`` is accepted for signature parity (a ``foodrec_amd.Session`` or ``None``); the launch goes
@@ -200,6 +208,9 @@ def evaluate_model(sess, model: Model, testRatings: Dict[str, List[int]], testNe
     Like the reference, which feeds ``categories`` from ``dish_to_category`` on every call (evaluate.py:43, :50), this
     makes ``dish_to_category`` the engine's resident dish mask table: a table set earlier with ``set_dish_categories`` is
     replaced.
+
+    EXTENSION ``head=True``: the candidates are scored under the MLP head (``rank_candidates(head=True)``; needs ``set_mlp_head``);
+    rows with a NaN score take the same host sequence with ``predict_extended(head=True)``'s scores.
     """
     global _model, _testRatings, _testNegatives, _K, _dish_to_category
     _model, _testRatings, _testNegatives, _K, _dish_to_category = model, testRatings, testNegatives, K, dish_to_category
@@ -211,7 +222,7 @@ def evaluate_model(sess, model: Model, testRatings: Dict[str, List[int]], testNe
     eng = model.engine
     if eng.dish_cats is None or eng.dish_cats.data_ptr() != plan.dish_table.data_ptr():
         eng.set_dish_categories(plan.dish_table)             # another mask table is resident: put ours back (a pointer, no copy)
-    s, ids, flags = eng.rank_candidates(plan.users_dev, plan.items_dev, int(K), lens=plan.lens_dev)
+    s, ids, flags = eng.rank_candidates(plan.users_dev, plan.items_dev, int(K), lens=plan.lens_dev, head=bool(head))
     eng.check()
     ids = ids.cpu().numpy()
     flags = flags.cpu().numpy()
@@ -225,12 +236,12 @@ def evaluate_model(sess, model: Model, testRatings: Dict[str, List[int]], testNe
     hits: List[int] = hit.astype(np.int64).tolist()
     ndcgs: List[float] = np.where(hit, gain[rank], 0.0).tolist()
     for r in np.flatnonzero(flags & 1).tolist():            # NaN among the scores: the reference's host sequence
-        hits[r], ndcgs[r] = eval_one_rating(model, plan.users[r], testRatings, testNegatives, K, dish_to_category)
+        hits[r], ndcgs[r] = _eval_one(model, plan.users[r], testRatings, testNegatives, K, dish_to_category, bool(head))
     return hits, ndcgs
 
 
 def evaluate_model_full(sess, model: Model, testRatings: Dict[str, List[int]], trainRatings, K: int,
-                        dish_to_category: Dict[str, list]) -> Tuple[List[int], List[float]]:
+                        dish_to_category: Dict[str, list], head: bool = False) -> Tuple[List[int], List[float]]:
     """HR@K / NDCG@K under the full-ranking protocol: each user's held-out dish ``testRatings[u][0]`` ranked against the whole
     catalogue, leaving out the dishes of ``trainRatings[u]`` (the split's training dict, ``Dataset.trainMatrix``; None = no
     exclusion).  ``evaluate_model``'s argument order with ``trainRatings`` in the place of ``testNegatives``.
@@ -238,7 +249,9 @@ def evaluate_model_full(sess, model: Model, testRatings: Dict[str, List[int]], t
     Per user, in ``testRatings`` order: ``hit = rank < K`` and ``ndcg = log 2 / log(rank + 2)`` if hit, else 0 -- getHitRatio /
     getNDCG (evaluate.py:69-81) applied to the first K dishes of the filtered full ranking.  The rank is
     ``ScoringEngine.catalogue_rank`` (one launch for all users, no limit on K).  ``dish_to_category`` becomes the engine's
-    resident mask table, as in ``evaluate_model``."""
+    resident mask table, as in ``evaluate_model``.
+
+    EXTENSION ``head=True``: the rank under the MLP head (``catalogue_rank(head=True)``: every dish scored under the head)."""
     if isinstance(K, bool) or not isinstance(K, (int, np.integer)) or K < 1:
         raise ValueError("evaluate_model_full: K must be a positive int, got %r" % (K,))
     if not testRatings:
@@ -253,7 +266,7 @@ def evaluate_model_full(sess, model: Model, testRatings: Dict[str, List[int]], t
     exclude = None
     if trainRatings is not None:
         exclude = [trainRatings.get(u, ()) for u in users]
-    ranks, _ = eng.catalogue_rank(users, held, exclude)
+    ranks, _ = eng.catalogue_rank(users, held, exclude, head=bool(head))
     eng.check()
     ranks = ranks.cpu().numpy()
     hit = ranks < K

@@ -442,21 +442,52 @@ class ScoringEngine:
         _native.raise_for(rc, self._h)
         return out_s, out_i
 
+    def _device_exclusions(self, exclude, n: int, what: str):
+        """``exclude`` -> device tensors (offsets i64[n + 1], ids i32) for the calls under the head: a pair of device tensors is taken as
+        it is (ascending within each segment: the kernels check it), a list of n id lists or a host ``(offsets, ids)`` pair goes
+        through ``exclusion_csr`` (sorted, de-duplicated, range-checked)."""
+        if isinstance(exclude, tuple) and len(exclude) == 2 and all(isinstance(t, torch.Tensor) and t.device == self.device for t in exclude):
+            off, ids = exclude[0].contiguous(), exclude[1].contiguous()
+            if off.dtype != torch.int64 or ids.dtype != torch.int32 or off.numel() != n + 1:
+                raise ValueError("%s: device exclusions are (int64 offsets[%d], int32 ids)" % (what, n + 1))
+        else:
+            off_np, ids_np = exclusion_csr(exclude, n)
+            off, ids = torch.from_numpy(off_np).to(self.device), torch.from_numpy(ids_np).to(self.device)
+        if ids.numel() == 0:
+            ids = torch.zeros(1, dtype=torch.int32, device=self.device)
+        return off, ids
+
     def topk_users_mlp(self, users: torch.Tensor, k: int, candidates: int = 0):
         """``topk_users`` under the MLP head (``m2d_topk_users_mlp``, include/m2d.h): users i32[nU] -> (scores f32[nU, k],
         dish ids i32[nU, k]).  ``candidates`` = 0: every dish is scored under the head (exact); K1 = ``candidates`` >= k: the K1
-        best by the reference score (``topk_users``) are reranked under the head.  Does not synchronise."""
+        best by the reference score (``topk_users``) are reranked under the head.  Does not synchronise.  (Without each user's
+        excluded dishes: ``topk_users_mlp_excluding``.)"""
+        return self.topk_users_mlp_excluding(users, k, None, candidates)
+
+    def topk_users_mlp_excluding(self, users: torch.Tensor, k: int, exclude=None, candidates: int = 0):
+        """EXTENSION (``m2d_topk_users_mlp_excluding``, include/m2d.h): ``topk_users_mlp`` whose lists leave
+        out users[i]'s excluded dishes -- ``exclude``: a list of nU id lists, a host ``(offsets, ids)`` pair (both through
+        ``exclusion_csr``), or a pair of device tensors as is (``topk_users_excluding``'s forms); None: ``topk_users_mlp`` itself.
+        Rows end in id -1 / NaN when fewer than k dishes remain; with exclusions K1 <= 16 and stage 1 is ``topk_users_excluding``.
+        ``catalogue_rank(users[i], ids[i][j], exclude[i], head=True) == j`` for the exact mode's lists.  Does not synchronise."""
         if users.dtype != torch.int32 or users.device != self.device:
             raise TypeError("topk_users_mlp: users must be an int32 tensor on %s" % self.device)
         users = users.contiguous()
         nU, k, candidates = users.numel(), int(k), int(candidates)
+        off = ids = None
+        if exclude is not None:
+            off, ids = self._device_exclusions(exclude, nU, "topk_users_mlp_excluding")
         out_s = torch.empty((nU, max(k, 0)), dtype=torch.float32, device=self.device)
         out_i = torch.empty((nU, max(k, 0)), dtype=torch.int32, device=self.device)
         with torch.cuda.device(self.device):
-            rc = _native.lib().m2d_topk_users_mlp(self._h, users.data_ptr(), nU, k, candidates, out_s.data_ptr(), out_i.data_ptr(),
-                                                  _stream_ptr())
+            if off is None:
+                rc = _native.lib().m2d_topk_users_mlp(self._h, users.data_ptr(), nU, k, candidates, out_s.data_ptr(), out_i.data_ptr(),
+                                                      _stream_ptr())
+            else:
+                rc = _native.lib().m2d_topk_users_mlp_excluding(self._h, users.data_ptr(), nU, k, candidates, off.data_ptr(),
+                                                                ids.data_ptr(), out_s.data_ptr(), out_i.data_ptr(), _stream_ptr())
         _native.raise_for(rc, self._h)
-        self._topk_mlp_keep = users                      # stays alive until the queued kernels have read it
+        self._topk_mlp_keep = (users, off, ids)          # stay alive until the queued kernels have read them
         return out_s, out_i
 
     def _slate_ids(self, users: torch.Tensor, slate: torch.Tensor, what: str):
@@ -657,20 +688,25 @@ class ScoringEngine:
         self._markets_keep = (users, off, ids, xoff, xids)   # inputs stay alive until the queued kernels have read them
         return (out_s, out_i) + ((counts,) if return_counts else ()) + ((missing,) if return_missing else ())
 
-    def catalogue_rank(self, users, items, exclude=None):
+    def catalogue_rank(self, users, items, exclude=None, head: bool = False):
         """Full-catalogue rank of held-out dishes (``m2d_catalogue_rank``, include/m2d.h): for each query (users[i], items[i]) the
         number of dishes ranked before items[i] in ``topk_users``' order, leaving out the query's excluded ids.
 
         ``exclude``: None, a tuple ``(offsets, ids)`` (CSR, offsets of length n + 1), or a list of n per-query id lists; either form
         is sorted and de-duplicated per query here.  Returns device tensors (ranks i32[n], held-out scores f32[n]) without
-        synchronising; out-of-range ids surface as IndexError from ``check()``."""
+        synchronising; out-of-range ids surface as IndexError from ``check()``.
+
+        EXTENSION ``head=True`` (``m2d_catalogue_rank_mlp``): scores and order are ``topk_users_mlp``'s -- every
+        dish is scored under the MLP head --, and a pair of device tensors is taken as ``exclude`` as it is."""
         users = self._as_ids(users, "user")
         items = self._as_ids(items, "item")
         n = users.numel()
         if items.numel() != n:
             raise ValueError("catalogue_rank: users[%d] and items[%d] disagree" % (n, items.numel()))
         off = ids = None
-        if exclude is not None:
+        if exclude is not None and head:
+            off, ids = self._device_exclusions(exclude, n, "catalogue_rank")
+        elif exclude is not None:
             off_np, ids_np = exclusion_csr(exclude, n)
             off = torch.from_numpy(off_np).to(self.device)
             ids = torch.from_numpy(ids_np).to(self.device) if ids_np.size else torch.zeros(1, dtype=torch.int32, device=self.device)
@@ -679,10 +715,9 @@ class ScoringEngine:
         if n == 0:
             return ranks, scores
         with torch.cuda.device(self.device):
-            rc = _native.lib().m2d_catalogue_rank(self._h, users.data_ptr(), items.data_ptr(), n,
-                                                  off.data_ptr() if off is not None else None,
-                                                  ids.data_ptr() if ids is not None else None,
-                                                  ranks.data_ptr(), scores.data_ptr(), _stream_ptr())
+            call = _native.lib().m2d_catalogue_rank_mlp if head else _native.lib().m2d_catalogue_rank
+            rc = call(self._h, users.data_ptr(), items.data_ptr(), n, off.data_ptr() if off is not None else None,
+                      ids.data_ptr() if ids is not None else None, ranks.data_ptr(), scores.data_ptr(), _stream_ptr())
         _native.raise_for(rc, self._h)
         self._rank_keep = (users, items, off, ids)       # inputs stay alive until the queued kernels have read them
         return ranks, scores
@@ -812,6 +847,36 @@ def topk_users_mlp_op(engine: int, users: torch.Tensor, k: int, candidates: int 
 def _(engine, users, k, candidates=0):
     return (users.new_empty((users.numel(), k), dtype=torch.float32),
             users.new_empty((users.numel(), k), dtype=torch.int32))
+
+
+@torch.library.custom_op("m2d::topk_users_mlp_excluding", mutates_args=(), device_types="cuda")
+def topk_users_mlp_excluding_op(engine: int, users: torch.Tensor, k: int, candidates: int = 0, excl_off: Optional[torch.Tensor] = None,
+                                excl_ids: Optional[torch.Tensor] = None) -> tuple[torch.Tensor, torch.Tensor]:
+    """``ScoringEngine.topk_users_mlp_excluding``; `excl_off` / `excl_ids`: device tensors, ascending per segment, taken as they are."""
+    exclude = None if excl_off is None else (excl_off, excl_ids if excl_ids is not None else excl_off.new_empty((0,), dtype=torch.int32))
+    s, i = _engine(engine).topk_users_mlp_excluding(users, k, exclude, candidates)
+    return s, i
+
+
+@topk_users_mlp_excluding_op.register_fake
+def _(engine, users, k, candidates=0, excl_off=None, excl_ids=None):
+    return (users.new_empty((users.numel(), k), dtype=torch.float32),
+            users.new_empty((users.numel(), k), dtype=torch.int32))
+
+
+@torch.library.custom_op("m2d::catalogue_rank_mlp", mutates_args=(), device_types="cuda")
+def catalogue_rank_mlp_op(engine: int, users: torch.Tensor, items: torch.Tensor, excl_off: Optional[torch.Tensor] = None,
+                          excl_ids: Optional[torch.Tensor] = None) -> tuple[torch.Tensor, torch.Tensor]:
+    """``ScoringEngine.catalogue_rank(head=True)``: (ranks i32[n], held-out scores f32[n]); the exclusions as above."""
+    exclude = None if excl_off is None else (excl_off, excl_ids if excl_ids is not None else excl_off.new_empty((0,), dtype=torch.int32))
+    r, s = _engine(engine).catalogue_rank(users, items, exclude, head=True)
+    return r, s
+
+
+@catalogue_rank_mlp_op.register_fake
+def _(engine, users, items, excl_off=None, excl_ids=None):
+    return (users.new_empty((users.numel(),), dtype=torch.int32),
+            users.new_empty((users.numel(),), dtype=torch.float32))
 
 
 @torch.library.custom_op("m2d::score_slate", mutates_args=(), device_types="cuda")

@@ -447,7 +447,8 @@ class Model:
 
         EXTENSION, `head=True`: the lists under the MLP head (`set_mlp_head`), the score `predict_extended(head=True)` returns --
         `candidates` = 0 scores every dish under the head, K1 = `candidates` >= k reranks the K1 best by the reference score
-        (``ScoringEngine.topk_users_mlp``).  Exclusions under the head are not served: `head=True` with `exclude` raises.
+        (``ScoringEngine.topk_users_mlp``).  `head=True` with `exclude` raises here: the lists under the head without the dishes
+        already had are `topk_head`'s.
 
         EXTENSION, `among=dishes`: the k best among those dishes only (str or int ids, any order, repeats ignored;
         ``ScoringEngine.topk_slate``) -- the same order, the scores `score_slate` returns.  `among` with `exclude` or `head=True`
@@ -473,7 +474,8 @@ class Model:
             self.engine.check()
             return s.cpu().numpy(), i.cpu().numpy()
         if head and exclude is not None:
-            raise ValueError("topk: head=True together with exclude is not supported (exclusions under the MLP head)")
+            raise ValueError("topk: head=True together with exclude is not supported (exclusions under the MLP head): "
+                             "topk_head(users, k, exclude) serves them")
         if candidates and not head:
             raise ValueError("topk: candidates is the head's rerank width; it needs head=True")
         if exclude is not None:
@@ -491,6 +493,24 @@ class Model:
             s, i = torch.ops.m2d.topk_users_mlp(self.engine.id, ut, int(k), int(candidates))
         else:
             s, i = torch.ops.m2d.topk_users(self.engine.id, ut, int(k))
+        self.engine.check()
+        return s.cpu().numpy(), i.cpu().numpy()
+
+    def topk_head(self, users, k: int = 10, exclude=None, candidates: int = 0):
+        """EXTENSION: the k best dishes of every user under the MLP head (`set_mlp_head`), leaving out `exclude`'s dishes per user -- a
+        dict keyed by the user as given in `users` (a missing key excludes nothing) or a list aligned with `users`, as in `topk`; None
+        excludes nothing.  k <= 64; rows end in id -1 / NaN when fewer than k dishes remain.  `candidates` = 0 scores every dish under
+        the head; K1 = `candidates` >= k (K1 <= 16 with exclusions) reranks the K1 best by the reference score among the dishes left
+        (``ScoringEngine.topk_users_mlp_excluding``).  Returns (scores float32 [n, k], dish ids int32 [n, k])."""
+        if exclude is not None:
+            if isinstance(exclude, dict):
+                exclude = [exclude.get(u, ()) for u in users]
+            elif len(exclude) != len(users):
+                raise ValueError("topk_head: %d exclusion lists for %d users" % (len(exclude), len(users)))
+            exclude = list(exclude)
+        u = _ids(users, "user")
+        ut = u.to(self.device, torch.int32) if isinstance(u, torch.Tensor) else torch.from_numpy(u).to(self.device)
+        s, i = self.engine.topk_users_mlp_excluding(ut, int(k), exclude, int(candidates))
         self.engine.check()
         return s.cpu().numpy(), i.cpu().numpy()
 

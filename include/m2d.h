@@ -324,6 +324,39 @@ int m2d_rank_candidates_mlp(m2d_engine *h, const int32_t *users, const int32_t *
                             int64_t nseg, int32_t L, int32_t k, float *out_scores, int32_t *out_items,
                             int32_t *out_flags, void *stream);
 
+/* Seen-dish filtering under the head (build-defined, like the head).  Score and order are those above: the pair's
+ * m2d_score_pairs_mlp word, score descending, equal bits and -0 / +0 to the lower id, NaN after every -inf in id order.  The
+ * exclusion lists follow m2d_catalogue_rank: device CSR, excl_off i64[n + 1], excl_ids i32 of excl_off[n] entries (read on the
+ * device), ascending within a segment, equal neighbours allowed and counted once; excl_off == NULL: no exclusions.
+ *
+ * m2d_topk_users_mlp_excluding, candidates == 0: row i holds the first k of the order over [0, I) less user i's segment, id -1 /
+ * NaN from the number of dishes left on (m2d_topk_users_excluding's convention); 1 <= k <= min(64, I).  Chunk geometry, engine
+ * buffers and "topk_mlp_launches" are m2d_topk_users_mlp's; the lists do not depend on "topk_mlp_chunk_pairs".
+ * k <= candidates <= min(16, I): stage 1 is m2d_topk_users_excluding (K1 = candidates dishes by the reference score, the segment
+ * already left out) with that call's conditions -- C = 4, 0/1 masks, finite tables, E a multiple of 4 up to 256, no ingredient
+ * table: otherwise M2D_ERR_UNSUPPORTED naming the condition --, stage 2 scores the nU x K1 candidates under the head and lists the
+ * first k; a slot stage 1 left empty is dropped.  Any other `candidates` with exclusions: M2D_ERR_INVALID_ARG.
+ * excl_off == NULL: the call IS m2d_topk_users_mlp -- its launches, its words, its `candidates` range.
+ *
+ * m2d_catalogue_rank_mlp: for query i = (u, p) with segment X,
+ *     out_rank[i] = #{ d in [0, I), d not in X, d != p : (score(u, d), d) precedes (score(u, p), p) in the order },
+ * out_scores[i] (may be NULL) the held-out pair's word; an id of X equal to p is ignored.  For the same u and X,
+ * m2d_catalogue_rank_mlp(u, out_ids[u][j], X) == j for every dish the exact mode lists, at every chunk size.
+ * "topk_mlp_launches" counts the held-out launch too.
+ *
+ * Both: no head or no dish masks: M2D_ERR_NOT_CONFIGURED; null buffers, excl_off without excl_ids: M2D_ERR_INVALID_ARG.  Latched
+ * (m2d_check): a bad user id (M2D_ERR_BAD_USER_ID), a bad held-out id (M2D_ERR_BAD_ITEM_ID), a bad excluded id (M2D_ERR_BAD_ITEM_ID,
+ * its index into excl_ids), an id below its predecessor or an offset below its predecessor / a first offset other than 0
+ * (M2D_ERR_INVALID_ARG, its index) -- looked at once per call; a bad excluded id indexes nothing.  A call with a latched error leaves
+ * its rows unspecified and the engine usable.  Neither call synchronises; after the first call of a size they allocate only on
+ * growth.  m2d_set_user_base is honoured. */
+int m2d_topk_users_mlp_excluding(m2d_engine *h, const int32_t *users, int64_t nU, int32_t k, int32_t candidates,
+                                 const int64_t *excl_off, const int32_t *excl_ids,
+                                 float *out_scores, int32_t *out_ids, void *stream);
+int m2d_catalogue_rank_mlp(m2d_engine *h, const int32_t *users, const int32_t *items, int64_t n,
+                           const int64_t *excl_off, const int32_t *excl_ids,
+                           int32_t *out_rank, float *out_scores, void *stream);
+
 /* ---- build-defined generalisation, NO reference counterpart (like m2d_topk_users) ----
  * Slate scoring: many users against ONE shared list of dishes -- the dishes that can be cooked from today's market, a shared negative
  * pool, an editorial list.  m2d_score_slate writes the whole score matrix, m2d_topk_slate the k best dishes of the slate per user.
