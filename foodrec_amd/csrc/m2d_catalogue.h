@@ -667,59 +667,7 @@ __device__ __forceinline__ void grouped_publish(float *ls, int32_t *li, const fl
 // The ranking arithmetic and its bounds: what m2d_catalogue_rank (m2d_catalogue_rank.hip) and m2d_topk_users_excluding
 // (m2d_catalogue_excl.hip) share, so that a rank and a list position are the same integer.
 // =====================================================================================================
-// A CSR exclusion list -- offsets off[0 .. n], ascending dish ids per segment -- as both calls check it.  Offset q: non-decreasing from 0.
-__device__ __forceinline__ void csr_check_offset(const int64_t *off, const int64_t q, int32_t *err)
-{
-    const int64_t o = off[q];
-    if ((q == 0 && o != 0) || (q > 0 && o < off[q - 1])) m2d_latch_error(err, M2D_ERR_INVALID_ARG, (int32_t)o, q);
-}
-
-// the segment position i lies in: the last q with off[q] <= i
-__device__ __forceinline__ int64_t csr_owner(const int64_t *off, const int64_t n, const int64_t i)
-{
-    int64_t lo = 0, hi = n;
-    while (hi - lo > 1) {
-        const int64_t mid = (lo + hi) >> 1;
-        if (off[mid] <= i) lo = mid; else hi = mid;
-    }
-    return lo;
-}
-
-// The id x at position i: a dish of the catalogue, and not below the id before it in its segment q (set once x is in range).  Returns 0
-// for an id that is neither, 2 for one that repeats the id before it, else 1; `report`: whether this thread latches the violation -- the
-// callers' threads per id differ.
-__device__ __forceinline__ int csr_check_id(const int64_t *off, const int32_t *ids, const int64_t n, const int64_t I, const int64_t i,
-                                            const bool report, int32_t *err, int32_t &x, int64_t &q)
-{
-    x = ids[i];
-    int r = 1;
-    if (x < 0 || (int64_t)x >= I) {
-        if (report) m2d_latch_error(err, M2D_ERR_BAD_ITEM_ID, x, i);
-        r = 0;
-    } else {
-        q = csr_owner(off, n, i);
-        if (i > off[q] && i > 0) {                          // (i > 0: a negative first offset must not reach in front of the array)
-            const int32_t prev = ids[i - 1];
-            if (prev > x && report) m2d_latch_error(err, M2D_ERR_INVALID_ARG, x, i);
-            r = prev > x ? 0 : (prev == x ? 2 : 1);
-        }
-    }
-    return r;
-}
-
-// is `d` among the ascending ids at(lo) ... at(hi - 1)?  The one lower-bound search of both calls; `at` says where the ids live (a user's
-// segment in HBM, a lane's column of LDS).
-template <typename Pos, typename At>
-__device__ __forceinline__ bool sorted_contains(Pos lo, Pos hi, const int32_t d, At &&at)
-{
-    const Pos end = hi;
-    while (lo < hi) {                                       // first position with an id >= d
-        const Pos mid = (lo + hi) >> 1;
-        if (at(mid) < d) lo = mid + 1; else hi = mid;
-    }
-    return lo < end && at(lo) == d;
-}
-
+// (the exclusion lists' own operations -- segment clamp, lower bound, checks -- are m2d_exclusions.h's)
 // (s, d) before (t, p) in the ranking: score descending, NaN last, equal scores (NaN included) to the lower id
 __device__ __forceinline__ bool rank_before(const float s, const int32_t d, const float t, const int32_t p)
 {

@@ -21,8 +21,10 @@
 //   m2d_topk_excl_scan16    E > 128: 16 lanes per (record, share), the list held by all 16; of the walk, the shares and the clipping
 //   m2d_topk_excl_merge     the shares' partial lists merged with the same comparison; a list still not full takes the empty-mask
 //                           dishes (NaN scores, ranked last) that are not excluded in id order, then id -1 / NaN
-//   m2d_topk_excl_check     the offsets and ids themselves: out-of-range ids, segments not ascending, offsets not non-decreasing
+//   m2d_check_exclusions    the offsets and ids themselves: out-of-range ids, segments not ascending, offsets not non-decreasing --
+//                           the one whole-list check, also of the calls under the MLP head (m2d_launch_check_exclusions)
 #include "m2d_catalogue.h"
+#include "m2d_exclusions.h"
 
 #pragma clang fp contract(off)
 
@@ -60,21 +62,15 @@ __device__ __forceinline__ int excl_shape(const ExclArgs &p, const int64_t live,
     return units <= 0 ? 0 : share_count(p.want, units);
 }
 
-// user i's segment of excl_ids, kept inside [0, excl_off[nU]] whatever the offsets hold (m2d_topk_excl_check reports them)
+// user i's segment of excl_ids, kept inside [0, excl_off[nU]] whatever the offsets hold (m2d_check_exclusions reports them); no
+// lists, or a negative total: an empty window
 __device__ __forceinline__ void excl_segment(const ExclArgs &p, const int64_t i, int64_t &x0, int64_t &x1)
 {
     x0 = x1 = 0;
     if (!p.excl_off) return;
-    int64_t nnz = p.excl_off[p.nU];
-    nnz = nnz < 0 ? 0 : nnz;
-    const int64_t a = p.excl_off[i], b = p.excl_off[i + 1];
-    x0 = a < 0 ? 0 : (a > nnz ? nnz : a);
-    x1 = b < x0 ? x0 : (b > nnz ? nnz : b);
-}
-
-__device__ __forceinline__ bool excl_contains(const int32_t *ids, const int64_t lo, const int64_t hi, const int32_t d)
-{
-    return sorted_contains(lo, hi, d, [ids](const int64_t i) { return ids[i]; });
+    const int64_t nnz = p.excl_off[p.nU];
+    bool bad;
+    csr_segment(p.excl_off, i, nnz < 0 ? 0 : nnz, x0, x1, bad);
 }
 
 // (x, id) into a list sorted by rank_before, in place from the last slot up (slot i - 1 still holds its old entry when slot i is
@@ -113,14 +109,18 @@ __device__ __forceinline__ void excl_list_store(const float (&ls)[EXCL_KR], cons
 }
 
 // ---- the lists themselves ------------------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void m2d_topk_excl_check(ExclArgs p)
+// The lists of a call, looked at once: offsets non-decreasing from 0 (so none reaches past the array, whose length is the last of
+// them), every id a dish of the catalogue and not below the id in front of it in its segment -- m2d_catalogue_rank's checks and
+// latch values (m2d_exclusions.h).  A grid-stride walk: with a single malformed entry the latch is the same whatever the grid (with
+// several, the first thread to reach the latch wins, as in every kernel that writes it).
+__global__ __launch_bounds__(256) void m2d_check_exclusions(const int64_t *off, const int32_t *ids, int64_t n, int64_t I, int32_t *err)
 {
     const int64_t t0 = (int64_t)blockIdx.x * 256 + threadIdx.x, nt = (int64_t)gridDim.x * 256;
-    for (int64_t q = t0; q <= p.nU; q += nt) csr_check_offset(p.excl_off, q, p.t.err);
-    const int64_t nnz = p.excl_off[p.nU];
+    for (int64_t q = t0; q <= n; q += nt) csr_check_offset(off, q, err);
+    const int64_t nnz = off[n];
     int32_t x;
-    int64_t user;
-    for (int64_t i = t0; i < nnz; i += nt) csr_check_id(p.excl_off, p.excl_ids, p.nU, p.t.I, i, true, p.t.err, x, user);      // (a thread per id)
+    int64_t row;
+    for (int64_t i = t0; i < nnz; i += nt) csr_check_id(off, ids, n, I, i, true, err, x, row);      // (a thread per id)
 }
 
 // ---- tier 1: the unfiltered top K1 without the listed ids ----------------------------------------------------------------------------
@@ -141,7 +141,7 @@ __global__ __launch_bounds__(256) void m2d_topk_excl_filter(ExclArgs p)
     excl_segment(p, u, x0, x1);
     int32_t id = j < p.K1 ? p.list_i[(size_t)u * p.K1 + j] : -1;
     if ((int64_t)id >= t.I) id = -1;
-    const bool keep = id >= 0 && !excl_contains(p.excl_ids, x0, x1, id);
+    const bool keep = id >= 0 && !sorted_contains(p.excl_ids, x0, x1, id);
     const uint32_t bal = (uint32_t)((__ballot(keep) >> (lane & 48)) & 0xffffull);
     if (__builtin_popcount(bal) < k) {
         if (j == 0) p.short_list[4 + atomicAdd(&p.short_list[0], 1)] = (int32_t)u;
@@ -273,7 +273,7 @@ __global__ __launch_bounds__(256) void m2d_topk_excl_scan(ExclArgs p)
             if (__ballot(cand) != 0ull) {                   // rare once the lists are full
                 if (cand) {
                     const bool found = xn >= 0 ? sorted_contains(0, xn, id, [&](const int i) { return xs[wv][i][lane]; })
-                                               : excl_contains(p.excl_ids, x0, x1, id);
+                                               : sorted_contains(p.excl_ids, x0, x1, id);
                     if (!found) excl_insert(ls, li, sc, id);
                 }
             }
@@ -324,7 +324,7 @@ __global__ __launch_bounds__(256) void m2d_topk_excl_scan16(ExclArgs p)
             for (int r = 0; r < nrows; ++r) {
                 const int32_t id = t.perm[tile * 32 + r];
                 const float sc = rank_exact_score16(pmu, t.re, E4, j, id, q, t.a, t.b, rec.hc);
-                if (!(sc < seed) && rank_before(sc, id, ls[EXCL_KR - 1], li[EXCL_KR - 1]) && !excl_contains(p.excl_ids, x0, x1, id))
+                if (!(sc < seed) && rank_before(sc, id, ls[EXCL_KR - 1], li[EXCL_KR - 1]) && !sorted_contains(p.excl_ids, x0, x1, id))
                     excl_insert(ls, li, sc, id);
             }
         }
@@ -374,7 +374,7 @@ __global__ __launch_bounds__(256) void m2d_topk_excl_merge(ExclArgs p)
         int64_t x0, x1;
         excl_segment(p, u, x0, x1);
         for (int64_t d = 0; d < p.t.I && cnt < k; ++d) {
-            if (dish_pattern(p.t.cats, d) == 0 && !excl_contains(p.excl_ids, x0, x1, (int32_t)d)) {
+            if (dish_pattern(p.t.cats, d) == 0 && !sorted_contains(p.excl_ids, x0, x1, (int32_t)d)) {
                 ms[cnt][tx] = __builtin_nanf("");
                 mi[cnt][tx] = (int32_t)d;
                 ++cnt;
@@ -388,6 +388,13 @@ __global__ __launch_bounds__(256) void m2d_topk_excl_merge(ExclArgs p)
 }
 
 }  // namespace
+
+int m2d_launch_check_exclusions(m2d_engine *h, const int64_t *off, const int32_t *ids, int64_t n, hipStream_t st)
+{
+    hipLaunchKernelGGL(m2d_check_exclusions, dim3((unsigned)(h->num_cu * 4)), dim3(256), 0, st, off, ids, n, h->I, h->err_dev);
+    M2D_HIP_TRY(h, hipGetLastError());
+    return M2D_OK;
+}
 
 int m2d_launch_topk_users_excluding(m2d_engine *h, const int32_t *users, int64_t nU, int32_t k, const int64_t *excl_off,
                                     const int32_t *excl_ids, float *out_scores, int32_t *out_ids, hipStream_t st, const char *entry,
@@ -431,10 +438,7 @@ int m2d_launch_topk_users_excluding(m2d_engine *h, const int32_t *users, int64_t
     h->excl_all_short = tier1 ? -1 : nU;
     M2D_HIP_TRY(h, hipMemsetAsync(a.counters, 0, 8 * sizeof(int32_t), st));
     M2D_HIP_TRY(h, hipMemsetAsync(a.short_list, 0, 4 * sizeof(int32_t), st));
-    if (excl_off) {
-        hipLaunchKernelGGL(m2d_topk_excl_check, dim3((unsigned)(h->num_cu * 4)), dim3(256), 0, st, a);
-        M2D_HIP_TRY(h, hipGetLastError());
-    }
+    if (excl_off && (rc = m2d_launch_check_exclusions(h, excl_off, excl_ids, nU, st)) != M2D_OK) return rc;
     const dim3 g16((unsigned)((nU * 16 + 255) / 256));
     if (tier1) {
         if ((rc = m2d_launch_topk_users(h, users, nU, K1, list_s, list_i, st)) != M2D_OK) return rc;

@@ -15,6 +15,7 @@
 //   m2d_rank_count16   E > 128: 16 lanes per (query, share of its straddling ROWS), every row decided -- no tile bound, so no walk
 //   m2d_rank_exclude   16 lanes per (query, excluded id): the id's exact score against (s*, p); one less if it precedes
 #include "m2d_catalogue.h"
+#include "m2d_exclusions.h"   // (m2d_rank_exclude's fused check-and-count: csr_check_offset / csr_check_id)
 
 #pragma clang fp contract(off)
 

@@ -357,27 +357,6 @@ __device__ __forceinline__ uint64_t tkm_key(const float s, const int32_t id)
     return ((uint64_t)hi << 32) | (uint32_t)id;
 }
 
-// A CSR segment per row, as m2d_topk_markets takes a request's market and the exclusion forms (m2d_markets_topk<LDS, true>,
-// m2d_topk_mlp_select<true, false>, m2d_topk_mlp_count) a row's excluded dishes.
-// request q's market segment, clamped into [0, nnzM] before anything is read; `bad`: it decreases or reaches outside
-__device__ __forceinline__ void market_segment(const int64_t *moff, int64_t q, int64_t nnzM, int64_t &m0, int64_t &m1, bool &bad)
-{
-    const int64_t lo = moff[q], hi = moff[q + 1];
-    bad = hi < lo || lo < 0 || hi > nnzM;
-    m0 = lo < 0 ? 0 : lo > nnzM ? nnzM : lo;
-    m1 = hi < m0 ? m0 : hi > nnzM ? nnzM : hi;
-}
-
-// first position in [lo, hi) of the ascending ids whose id is not below d
-__device__ __forceinline__ int64_t excl_lower_bound(const int32_t *ids, int64_t lo, int64_t hi, const int64_t d)
-{
-    while (lo < hi) {
-        const int64_t mid = (lo + hi) >> 1;
-        if (ids[mid] < d) lo = mid + 1; else hi = mid;
-    }
-    return lo;
-}
-
 // ---- device helpers shared by the LDS-DMA kernels (m2d_catalogue_*.hip, m2d_mlp.hip) ----
 // vmcnt(0) twice over: the builtin is an s_waitcnt the compiler's own counter model sees (so it stops assuming that
 // loads from a previous loop trip are still in flight), the asm one cannot be optimised away on the grounds that
@@ -474,3 +453,6 @@ int m2d_launch_catalogue_rank(m2d_engine *h, const int32_t *users, const int32_t
 int m2d_launch_topk_users_excluding(m2d_engine *h, const int32_t *users, int64_t nU, int32_t k, const int64_t *excl_off,
                                     const int32_t *excl_ids, float *out_scores, int32_t *out_ids, hipStream_t stream,
                                     const char *entry = "m2d_topk_users_excluding", bool under_head = false);
+// m2d_catalogue_excl.hip: the one whole-list check of a call's exclusion lists (n rows: offsets off[0 .. n], ids[off[n]]) -- what it
+// finds goes to the id-error latch
+int m2d_launch_check_exclusions(m2d_engine *h, const int64_t *off, const int32_t *ids, int64_t n, hipStream_t stream);

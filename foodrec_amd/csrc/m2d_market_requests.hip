@@ -19,7 +19,7 @@
 // CSR of dish ids per request and drops them from the `kept` ballot of each 64-dish group before anything is scored or counted; the
 // instantiations without it are the code above, unchanged.  m2d_markets_missing<LDS> runs after the rows are final and writes, for every
 // listed dish, the ids of its list entries that are absent from the request's market, in list order.
-#include "m2d_engine.h"
+#include "m2d_exclusions.h"   // (csr_segment: a request's market; ExclCursor: its excluded dishes)
 
 namespace {
 
@@ -60,8 +60,6 @@ struct MarketsArgs {
 // operation executes under a partial EXEC mask.
 __device__ __forceinline__ int uni(int v) { return __builtin_amdgcn_readfirstlane(v); }
 
-// (market_segment and excl_lower_bound are m2d_engine.h's: m2d_topk_mlp.hip takes its exclusion windows with them as well)
-
 // through-L2 form: block q sets request q's bits in its own bitmap (zeroed by a memset in front)
 __global__ __launch_bounds__(256) void m2d_markets_bitmap(const int64_t *moff, const int32_t *mids, int64_t nnzM, int32_t R, int64_t words,
                                                           uint32_t *bitmaps, int32_t *err)
@@ -69,7 +67,7 @@ __global__ __launch_bounds__(256) void m2d_markets_bitmap(const int64_t *moff, c
     const int64_t q = blockIdx.x;
     int64_t m0, m1;
     bool bad;
-    market_segment(moff, q, nnzM, m0, m1, bad);
+    csr_segment(moff, q, nnzM, m0, m1, bad);
     uint32_t *bm = bitmaps + q * words;
     for (int64_t i = m0 + threadIdx.x; i < m1; i += 256) {
         const int32_t id = mids[i];
@@ -92,7 +90,7 @@ __global__ __launch_bounds__(256) void m2d_markets_topk(MarketsArgs p)
 
     int64_t m0, m1;
     bool bad_seg;
-    market_segment(p.moff, q, p.nnzM, m0, m1, bad_seg);
+    csr_segment(p.moff, q, p.nnzM, m0, m1, bad_seg);
     const int32_t uid = p.users[q];
     const int64_t ul = (int64_t)uid - p.user_base;
     const bool bad_user = ul < 0 || ul >= p.U;               // block-uniform: nothing is read for that user
@@ -116,13 +114,11 @@ __global__ __launch_bounds__(256) void m2d_markets_topk(MarketsArgs p)
 
     // exclusion form: the request's segment, clamped into the array (its length is the last offset, as m2d_catalogue_rank takes it)
     // before anything is read; the share-0 block checks every id once -- a dish of the catalogue, not below the id in front of it
-    // xw: where the next group's window starts -- a wave's groups ascend, so it only moves forward --, xv: the id there, held in a
-    // register: a group that ends at or below xv has an empty window and pays one compare
-    int64_t x0 = 0, x1 = 0, xw = 0;
-    int32_t xv = INT32_MAX;
+    // (these latch values are this call's own, not csr_check_offset's); the cursor then walks the window group by group
+    ExclCursor xc;
     if (EXCL) {
-        bool bad_x;
-        market_segment(p.xoff, q, p.xids ? p.xoff[p.nQ] : 0, x0, x1, bad_x);     // (no array: its length is 0, a non-empty segment is bad)
+        const bool bad_x = xc.open(p.xoff, p.xids, p.xids ? p.xoff[p.nQ] : 0, q);     // (no array: its length is 0, a non-empty segment is bad)
+        const int64_t x0 = xc.xw, x1 = xc.x1;
         if (s == 0) {
             if (threadIdx.x == 0 && bad_x) m2d_latch_error(p.err, M2D_ERR_INVALID_ARG, (int32_t)p.xoff[q + 1], q + 1);
             for (int64_t i = x0 + threadIdx.x; i < x1; i += MQ_WAVES * 64) {
@@ -131,8 +127,6 @@ __global__ __launch_bounds__(256) void m2d_markets_topk(MarketsArgs p)
                 else if (i > x0 && p.xids[i - 1] > x) m2d_latch_error(p.err, M2D_ERR_INVALID_ARG, x, i);
             }
         }
-        xw = x0;
-        if (x0 < x1) xv = uni(p.xids[x0]);
     }
 
     // the share: catalogue blocks [s nb / S, (s + 1) nb / S), S <= nb
@@ -179,16 +173,10 @@ __global__ __launch_bounds__(256) void m2d_markets_topk(MarketsArgs p)
             }
         }
         unsigned long long kept = __ballot(lane < dn && my_end != my_begin && miss <= p.max_missing);
-        if (EXCL && xv < d0 + MQ_DW) {                                      // scalar: xv is the smallest id the wave has not passed
-            // the segment's window for [d0, d0 + 64): two wave-uniform lower bounds; an empty window costs nothing more
-            const int64_t w0 = excl_lower_bound(p.xids, xw, x1, d0), w1 = excl_lower_bound(p.xids, w0, x1, d0 + MQ_DW);
-            xw = w1;
-            xv = w1 < x1 ? uni(p.xids[w1]) : INT32_MAX;
-            if (w1 > w0) {                                                  // scalar branch; the search below has no cross-lane operation
-                const int64_t at = excl_lower_bound(p.xids, w0, w1, d0 + lane);
-                const bool out = at < w1 && p.xids[at] == d0 + lane;
-                kept &= ~__ballot(out);
-            }
+        if (EXCL) {                                                         // the segment's window for [d0, d0 + 64): an empty one costs a compare
+            bool in[1] = {true};
+            xc.strike(p.xids, d0, lane, in, false);
+            kept &= __ballot(in[0]);
         }
         cnt += __popcll(kept);
         if (bad_user) continue;
@@ -262,7 +250,7 @@ __global__ __launch_bounds__(256) void m2d_markets_missing(MarketsArgs p, int32_
     if (LDS) {                                               // (the ids have been reported by m2d_markets_topk: a bad one is skipped)
         int64_t m0, m1;
         bool bad_seg;
-        market_segment(p.moff, q, p.nnzM, m0, m1, bad_seg);
+        csr_segment(p.moff, q, p.nnzM, m0, m1, bad_seg);
         for (int i = threadIdx.x; i < words; i += MQ_WAVES * 64) bm[i] = 0u;
         __syncthreads();
         for (int64_t i = m0 + threadIdx.x; i < m1; i += MQ_WAVES * 64) {

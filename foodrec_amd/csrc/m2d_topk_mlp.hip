@@ -2,9 +2,9 @@
 // retrieve-then-rerank form.  The head arithmetic is m2d_launch_score_pairs_mlp's (m2d_mlp.hip), whichever kernel family the
 // shape selects; this file is what stands around it: the pair generators, the selection kernel and the chunked launcher.
 // With exclusions: m2d_topk_mlp_select<true, false> strikes a row's excluded dishes from every step before its
-// ballots, m2d_topk_mlp_count counts the dishes in front of a held-out one (m2d_catalogue_rank_mlp), m2d_topk_mlp_check_excl looks
-// at the lists once per call.
-#include "m2d_catalogue.h"   // (csr_check_offset / csr_check_id: the list checks of m2d_catalogue_rank)
+// ballots, m2d_topk_mlp_count counts the dishes in front of a held-out one (m2d_catalogue_rank_mlp), m2d_launch_check_exclusions
+// (m2d_catalogue_excl.hip) looks at the lists once per call.
+#include "m2d_exclusions.h"   // (ExclCursor: a row's exclusion window)
 
 namespace {
 
@@ -35,62 +35,6 @@ __global__ __launch_bounds__(256) void m2d_topk_mlp_pairs_cand(const int32_t *us
         users_x[t] = users[t / W];
         items_x[t] = FILL && cand[t] < 0 ? 0 : cand[t];
     }
-}
-
-// ---- a row's exclusion window ---------------------------------------------------------------------------------------------
-// The row's segment of ascending dish ids, clamped into the array before anything is read, and a cursor into it that only moves
-// forward: a wave's 256-score steps cover consecutive ids [id0, id0 + 256) and ascend.  Everything here is wave-uniform and carried
-// in SGPRs (readfirstlane), so the branches around the window are scalar ones; the per-lane search inside has no cross-lane operation.
-// The ids are only ever compared: a bad one (reported by m2d_topk_mlp_check_excl) indexes nothing.
-__device__ __forceinline__ int64_t uni64(const int64_t v)
-{
-    return (int64_t)(((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)((uint64_t)v >> 32)) << 32) |
-                     (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)v));
-}
-
-struct ExclCursor {
-    int64_t xw = 0, x1 = 0;          // the next step's window starts at xw or behind it; the segment's end
-    int32_t xv = INT32_MAX;          // the id at xw: a step that ends at or below it has an empty window and pays one compare
-
-    __device__ __forceinline__ void open(const int64_t *xoff, const int32_t *xids, const int64_t *xend, const int64_t row)
-    {
-        if (!xoff) return;
-        int64_t x0;
-        bool bad;
-        market_segment(xoff, row, *xend, x0, x1, bad);       // (a bad segment is m2d_topk_mlp_check_excl's to report)
-        xw = uni64(x0);
-        x1 = uni64(x1);
-        if (xw < x1) xv = __builtin_amdgcn_readfirstlane(xids[xw]);
-    }
-
-    // keys of the step's four slices (slice q, lane l: id id0 + 64 q + l) whose id is in the segment become TKM_NONE
-    __device__ __forceinline__ void strike(const int32_t *xids, const int64_t id0, const int lane, uint64_t (&ck)[4])
-    {
-        if ((int64_t)xv >= id0 + 256) return;                // scalar: xv is the smallest id the wave has not passed
-        const int64_t w0 = uni64(excl_lower_bound(xids, xw, x1, id0)), w1 = uni64(excl_lower_bound(xids, w0, x1, id0 + 256));
-        xw = w1;
-        xv = w1 < x1 ? __builtin_amdgcn_readfirstlane(xids[w1]) : INT32_MAX;
-        if (w1 == w0) return;                                // scalar: nothing of the segment in this step
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            const int64_t id = id0 + q * 64 + lane;
-            const int64_t at = excl_lower_bound(xids, w0, w1, id);
-            if (at < w1 && xids[at] == id) ck[q] = TKM_NONE;
-        }
-    }
-};
-
-// The lists of a call, looked at once: offsets non-decreasing from 0 (so none reaches past the array, whose length is the last of
-// them), every id a dish of the catalogue and not below the id in front of it in its segment -- m2d_catalogue_rank's checks and
-// latch values (m2d_catalogue.h).
-__global__ __launch_bounds__(256) void m2d_topk_mlp_check_excl(const int64_t *xoff, const int32_t *xids, int64_t n, int64_t I, int32_t *err)
-{
-    const int64_t t0 = (int64_t)blockIdx.x * 256 + threadIdx.x, nt = (int64_t)gridDim.x * 256;
-    for (int64_t q = t0; q <= n; q += nt) csr_check_offset(xoff, q, err);
-    const int64_t nnz = xoff[n];
-    int32_t x;
-    int64_t row;
-    for (int64_t i = t0; i < nnz; i += nt) csr_check_id(xoff, xids, n, I, i, true, err, x, row);
 }
 
 // ---- selection ------------------------------------------------------------------------------------------------------------
@@ -125,7 +69,7 @@ __global__ __launch_bounds__(1024) void m2d_topk_mlp_select(const float *scores,
     uint64_t lk = TKM_NONE, thr = TKM_NONE;      // this lane's list entry; lane k - 1's: what a candidate has to beat
     uint32_t ls = 0x7FC00000u;
     ExclCursor xc;
-    if (EXCL) xc.open(xoff, xids, xend, row);
+    if (EXCL) xc.open(xoff, xids, xend, row);    // (a bad segment is the call's check to report)
     for (int64_t base = (int64_t)wave * 256; base < W; base += (int64_t)nw * 256) {
         uint64_t ck[4];
         uint32_t cs[4];
@@ -142,7 +86,7 @@ __global__ __launch_bounds__(1024) void m2d_topk_mlp_select(const float *scores,
                 if (HOLES) ck[q] |= (uint64_t)(int64_t)(id >> 31);          // an id below 0: all ones, TKM_NONE (no branch)
             }
         }
-        if (EXCL) xc.strike(xids, (int64_t)d0 + base, lane, ck);
+        if (EXCL) xc.strike(xids, (int64_t)d0 + base, lane, ck, TKM_NONE);
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
             unsigned long long m = __ballot(ck[q] < thr);
@@ -213,7 +157,7 @@ __global__ __launch_bounds__(1024) void m2d_topk_mlp_count(const float *scores, 
             ck[q] = TKM_NONE;
             if (e < W) ck[q] = tkm_key(sc[e * rows], d0 + (int32_t)e);
         }
-        if (xoff) xc.strike(xids, (int64_t)d0 + base, lane, ck);             // scalar: a kernel argument
+        if (xoff) xc.strike(xids, (int64_t)d0 + base, lane, ck, TKM_NONE);   // scalar: a kernel argument
 #pragma unroll
         for (int q = 0; q < 4; ++q) cnt += (ck[q] < pk && (uint32_t)ck[q] != (uint32_t)p) ? 1 : 0;   // (TKM_NONE is in front of no key)
     }
@@ -269,14 +213,6 @@ ChunkShape chunk_shape(const m2d_engine *h, const int64_t rows, const int64_t wi
     return c;
 }
 
-int launch_check_excl(m2d_engine *h, const int64_t *excl_off, const int32_t *excl_ids, int64_t n, hipStream_t stream)
-{
-    hipLaunchKernelGGL(m2d_topk_mlp_check_excl, dim3(m2d_blocks_for(h, n + 1, 256, 4)), dim3(256), 0, stream, excl_off, excl_ids, n, h->I,
-                       h->err_dev);
-    M2D_HIP_TRY(h, hipGetLastError());
-    return M2D_OK;
-}
-
 }  // namespace
 
 int m2d_launch_topk_users_mlp(m2d_engine *h, const int32_t *users, int64_t nU, int32_t k, int32_t candidates, float *out_scores,
@@ -302,7 +238,7 @@ int m2d_launch_topk_users_mlp(m2d_engine *h, const int32_t *users, int64_t nU, i
                                                   reinterpret_cast<float *>(h->topk_mlp_cand + (size_t)nU * candidates), h->topk_mlp_cand, stream,
                                                   "m2d_topk_users_mlp_excluding", /*under_head=*/true)) != M2D_OK)
             return rc;
-    } else if (excl_off && (rc = launch_check_excl(h, excl_off, excl_ids, nU, stream)) != M2D_OK)
+    } else if (excl_off && (rc = m2d_launch_check_exclusions(h, excl_off, excl_ids, nU, stream)) != M2D_OK)
         return rc;
     for (int64_t u0 = 0; u0 < nU; u0 += R) {
         const int64_t rows = nU - u0 < R ? nU - u0 : R;
@@ -349,7 +285,7 @@ int m2d_launch_catalogue_rank_mlp(m2d_engine *h, const int32_t *users, const int
     // the held-out pairs' words (and the call's id checks: a bad user or held-out id is latched at its query)
     if ((rc = m2d_launch_score_pairs_mlp(h, users, items, n, held, stream)) != M2D_OK) return rc;
     ++h->topk_mlp_launches;
-    if (excl_off && (rc = launch_check_excl(h, excl_off, excl_ids, n, stream)) != M2D_OK) return rc;
+    if (excl_off && (rc = m2d_launch_check_exclusions(h, excl_off, excl_ids, n, stream)) != M2D_OK) return rc;
     for (int64_t q0 = 0; q0 < n; q0 += R) {
         const int64_t rows = n - q0 < R ? n - q0 : R;
         for (int64_t d0 = 0; d0 < h->I; d0 += W) {

@@ -23,7 +23,7 @@ from typing import Dict, List, Sequence, Tuple
 import numpy as np
 import torch
 
-from .recommender import Model
+from .recommender import Model, _exclusion_lists
 
 
 def getHitRatio(ranklist: Sequence, gtItem) -> int:
@@ -263,9 +263,7 @@ def evaluate_model_full(sess, model: Model, testRatings: Dict[str, List[int]], t
     held = [testRatings[u][0] for u in users]
     eng = model.engine
     model.set_dish_categories(dish_to_category)
-    exclude = None
-    if trainRatings is not None:
-        exclude = [trainRatings.get(u, ()) for u in users]
+    exclude = None if trainRatings is None else _exclusion_lists(trainRatings, users, "evaluate_model_full")
     ranks, _ = eng.catalogue_rank(users, held, exclude, head=bool(head))
     eng.check()
     ranks = ranks.cpu().numpy()

@@ -74,6 +74,33 @@ def exclusion_csr(exclude, n: int):
     return off, np.ascontiguousarray(ids, dtype=np.int32)
 
 
+def exclusions_on_device(exclude, n: int, device, what: str, as_is: bool = True, dtype_error=ValueError):
+    """``exclude`` of the calls that leave out dishes per row -> device tensors (offsets int64[n + 1], ids int32), the one path of
+    ``topk_users_excluding``, ``topk_users_mlp_excluding``, ``catalogue_rank`` and ``topk_markets_excluding``.
+
+    ``as_is``: a pair of tensors already on ``device`` is taken as it is after the dtype and length checks (ascending within each
+    segment: the kernels check it, ``check()`` reports); a wrong dtype raises ``dtype_error`` and a wrong number of offsets ValueError,
+    both naming ``what``.  Anything else -- a list of n id lists, a host ``(offsets, ids)`` pair, and with ``as_is=False`` a device
+    pair as well -- goes through ``exclusion_csr`` (sorted, de-duplicated, range-checked; a device pair is copied to the host, which
+    synchronises).  ``catalogue_rank(head=False)`` is the one caller with ``as_is=False``: it has always sorted what it was given.
+
+    No ids at all: a one-element dummy under all-zero totals, so that the ABI's "ids non-null when offsets are given" always holds."""
+    device = torch.device(device)
+    if as_is and isinstance(exclude, tuple) and len(exclude) == 2 and all(isinstance(t, torch.Tensor) and t.device == device for t in exclude):
+        off, ids = exclude[0].contiguous().reshape(-1), exclude[1].contiguous().reshape(-1)
+        if off.dtype != torch.int64 or ids.dtype != torch.int32:
+            raise dtype_error("%s: device exclusions are (int64 offsets[%d], int32 ids)" % (what, n + 1))
+        if off.numel() != n + 1:
+            raise ValueError("%s: device exclusions are (int64 offsets[%d], int32 ids): exclusion offsets must have n + 1 = %d entries, "
+                             "got %d" % (what, n + 1, n + 1, off.numel()))
+    else:
+        off_np, ids_np = exclusion_csr(exclude, n)
+        off, ids = torch.from_numpy(off_np).to(device), torch.from_numpy(ids_np).to(device)
+    if ids.numel() == 0:
+        ids = torch.zeros(1, dtype=torch.int32, device=device)
+    return off, ids
+
+
 def topk_excluding_args(n_users: int, k, exclude):
     """Host-side argument checks of ``topk_users_excluding``: k in 1..16; ``exclude`` None, or a list of ``n_users`` id lists /
     an ``(offsets, ids)`` pair, which goes through ``exclusion_csr`` (sorted, de-duplicated, int32 range checked).
@@ -442,21 +469,6 @@ class ScoringEngine:
         _native.raise_for(rc, self._h)
         return out_s, out_i
 
-    def _device_exclusions(self, exclude, n: int, what: str):
-        """``exclude`` -> device tensors (offsets i64[n + 1], ids i32) for the calls under the head: a pair of device tensors is taken as
-        it is (ascending within each segment: the kernels check it), a list of n id lists or a host ``(offsets, ids)`` pair goes
-        through ``exclusion_csr`` (sorted, de-duplicated, range-checked)."""
-        if isinstance(exclude, tuple) and len(exclude) == 2 and all(isinstance(t, torch.Tensor) and t.device == self.device for t in exclude):
-            off, ids = exclude[0].contiguous(), exclude[1].contiguous()
-            if off.dtype != torch.int64 or ids.dtype != torch.int32 or off.numel() != n + 1:
-                raise ValueError("%s: device exclusions are (int64 offsets[%d], int32 ids)" % (what, n + 1))
-        else:
-            off_np, ids_np = exclusion_csr(exclude, n)
-            off, ids = torch.from_numpy(off_np).to(self.device), torch.from_numpy(ids_np).to(self.device)
-        if ids.numel() == 0:
-            ids = torch.zeros(1, dtype=torch.int32, device=self.device)
-        return off, ids
-
     def topk_users_mlp(self, users: torch.Tensor, k: int, candidates: int = 0):
         """``topk_users`` under the MLP head (``m2d_topk_users_mlp``, include/m2d.h): users i32[nU] -> (scores f32[nU, k],
         dish ids i32[nU, k]).  ``candidates`` = 0: every dish is scored under the head (exact); K1 = ``candidates`` >= k: the K1
@@ -476,7 +488,7 @@ class ScoringEngine:
         nU, k, candidates = users.numel(), int(k), int(candidates)
         off = ids = None
         if exclude is not None:
-            off, ids = self._device_exclusions(exclude, nU, "topk_users_mlp_excluding")
+            off, ids = exclusions_on_device(exclude, nU, self.device, "topk_users_mlp_excluding")
         out_s = torch.empty((nU, max(k, 0)), dtype=torch.float32, device=self.device)
         out_i = torch.empty((nU, max(k, 0)), dtype=torch.int32, device=self.device)
         with torch.cuda.device(self.device):
@@ -663,16 +675,7 @@ class ScoringEngine:
             raise ValueError("topk_markets_excluding: market offsets must have nQ + 1 = %d entries" % (nQ + 1))
         xoff = xids = None
         if exclude is not None:
-            if isinstance(exclude, tuple) and len(exclude) == 2 and all(isinstance(t, torch.Tensor) and t.device == self.device for t in exclude):
-                xoff, xids = exclude
-                if xoff.dtype != torch.int64 or xids.dtype != torch.int32:
-                    raise TypeError("topk_markets_excluding: device exclusions are (int64 offsets, int32 ids)")
-                xoff, xids = xoff.contiguous().reshape(-1), xids.contiguous().reshape(-1)
-                if xoff.numel() != nQ + 1:
-                    raise ValueError("topk_markets_excluding: exclusion offsets must have nQ + 1 = %d entries" % (nQ + 1))
-            else:
-                off_np, ids_np = exclusion_csr(exclude, nQ)
-                xoff, xids = torch.from_numpy(off_np).to(self.device), torch.from_numpy(ids_np).to(self.device)
+            xoff, xids = exclusions_on_device(exclude, nQ, self.device, "topk_markets_excluding", dtype_error=TypeError)
         k, mm = int(k), int(max_missing)
         out_s = torch.empty((nQ, max(k, 0)), dtype=torch.float32, device=self.device)
         out_i = torch.empty((nQ, max(k, 0)), dtype=torch.int32, device=self.device)
@@ -681,7 +684,7 @@ class ScoringEngine:
         with torch.cuda.device(self.device):
             rc = _native.lib().m2d_topk_markets_excluding(
                 self._h, users.data_ptr(), nQ, off.data_ptr(), ids.data_ptr() if ids.numel() else None, ids.numel(),
-                xoff.data_ptr() if xoff is not None else None, xids.data_ptr() if xids is not None and xids.numel() else None, k, mm,
+                xoff.data_ptr() if xoff is not None else None, xids.data_ptr() if xids is not None else None, k, mm,
                 out_s.data_ptr(), out_i.data_ptr(), counts.data_ptr() if counts is not None else None,
                 missing.data_ptr() if missing is not None and missing.numel() else None, _stream_ptr())
         _native.raise_for(rc, self._h)
@@ -693,23 +696,21 @@ class ScoringEngine:
         number of dishes ranked before items[i] in ``topk_users``' order, leaving out the query's excluded ids.
 
         ``exclude``: None, a tuple ``(offsets, ids)`` (CSR, offsets of length n + 1), or a list of n per-query id lists; either form
-        is sorted and de-duplicated per query here.  Returns device tensors (ranks i32[n], held-out scores f32[n]) without
+        is sorted and de-duplicated per query here -- a pair of DEVICE tensors too (``exclusions_on_device(as_is=False)``): it is
+        copied to the host, which synchronises.  Returns device tensors (ranks i32[n], held-out scores f32[n]), otherwise without
         synchronising; out-of-range ids surface as IndexError from ``check()``.
 
         EXTENSION ``head=True`` (``m2d_catalogue_rank_mlp``): scores and order are ``topk_users_mlp``'s -- every
-        dish is scored under the MLP head --, and a pair of device tensors is taken as ``exclude`` as it is."""
+        dish is scored under the MLP head --, and a pair of device tensors is taken as ``exclude`` as it is (``as_is=True``: not
+        sorted, not copied, checked on the device).  The two forms differ in this on purpose: ``head=False`` keeps what it always did."""
         users = self._as_ids(users, "user")
         items = self._as_ids(items, "item")
         n = users.numel()
         if items.numel() != n:
             raise ValueError("catalogue_rank: users[%d] and items[%d] disagree" % (n, items.numel()))
         off = ids = None
-        if exclude is not None and head:
-            off, ids = self._device_exclusions(exclude, n, "catalogue_rank")
-        elif exclude is not None:
-            off_np, ids_np = exclusion_csr(exclude, n)
-            off = torch.from_numpy(off_np).to(self.device)
-            ids = torch.from_numpy(ids_np).to(self.device) if ids_np.size else torch.zeros(1, dtype=torch.int32, device=self.device)
+        if exclude is not None:
+            off, ids = exclusions_on_device(exclude, n, self.device, "catalogue_rank", as_is=head)
         ranks = torch.empty(n, dtype=torch.int32, device=self.device)
         scores = torch.empty(n, dtype=torch.float32, device=self.device)
         if n == 0:
@@ -733,20 +734,10 @@ class ScoringEngine:
         and unsorted device segments surface from ``check()``."""
         users = self._as_ids(users, "user")
         n = users.numel()
-        raw = (isinstance(exclude, tuple) and len(exclude) == 2 and all(isinstance(t, torch.Tensor) and t.device == self.device for t in exclude))
-        if raw:
-            topk_excluding_args(n, k, None)
-            off, ids = exclude[0].contiguous(), exclude[1].contiguous()
-            if off.dtype != torch.int64 or ids.dtype != torch.int32 or off.numel() != n + 1:
-                raise ValueError("topk_users_excluding: device exclusions are (int64 offsets[%d], int32 ids)" % (n + 1))
-            if ids.numel() == 0:
-                ids = torch.zeros(1, dtype=torch.int32, device=self.device)
-        else:
-            off_np, ids_np = topk_excluding_args(n, k, exclude)
-            off = ids = None
-            if off_np is not None:
-                off = torch.from_numpy(off_np).to(self.device)
-                ids = torch.from_numpy(ids_np).to(self.device) if ids_np.size else torch.zeros(1, dtype=torch.int32, device=self.device)
+        topk_excluding_args(n, k, None)                  # (k: checked before the lists, as ever)
+        off = ids = None
+        if exclude is not None:
+            off, ids = exclusions_on_device(exclude, n, self.device, "topk_users_excluding")
         k = int(k)
         out_s = torch.empty((n, k), dtype=torch.float32, device=self.device)
         out_i = torch.empty((n, k), dtype=torch.int32, device=self.device)

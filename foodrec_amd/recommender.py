@@ -61,6 +61,16 @@ def _ids(x, what: str) -> np.ndarray:
     return a.astype(np.int32)
 
 
+def _exclusion_lists(exclude, users, what: str) -> list:
+    """`exclude` of `topk`, `topk_head`, `topk_markets_excluding` and the full evaluation -> one id list per user: a dict is read
+    by the user as given in `users` (a missing key excludes nothing), a list has to be aligned with `users`."""
+    if isinstance(exclude, dict):
+        return [exclude.get(u, ()) for u in users]
+    if len(exclude) != len(users):
+        raise ValueError("%s: %d exclusion lists for %d users" % (what, len(exclude), len(users)))
+    return list(exclude)
+
+
 def _mask(categories, C: int, B: int):
     """[B, C, 1] nested lists (dish_to_category.json values, evaluate.py:43) or [B, C] -> f32 [B, C]."""
     if isinstance(categories, torch.Tensor):
@@ -420,11 +430,7 @@ class Model:
         xoff = xids = None
         if exclude is not None:
             from .ops import exclusion_csr
-            if isinstance(exclude, dict):
-                exclude = [exclude.get(x, ()) for x in users]
-            elif len(exclude) != n:
-                raise ValueError("topk_markets_excluding: %d exclusion lists for %d users" % (len(exclude), n))
-            had = [_ids(x, "item") for x in exclude]
+            had = [_ids(x, "item") for x in _exclusion_lists(exclude, users, "topk_markets_excluding")]
             had = [x.cpu().numpy() if isinstance(x, torch.Tensor) else x for x in had]
             xo, xi = exclusion_csr(had, n)                   # sorted and de-duplicated per request
             xoff, xids = dev(xo), dev(xi)
@@ -480,11 +486,7 @@ class Model:
             raise ValueError("topk: candidates is the head's rerank width; it needs head=True")
         if exclude is not None:
             from .ops import topk_excluding_args
-            if isinstance(exclude, dict):
-                exclude = [exclude.get(u, ()) for u in users]
-            elif len(exclude) != len(users):
-                raise ValueError("topk: %d exclusion lists for %d users" % (len(exclude), len(users)))
-            off, ids = topk_excluding_args(len(users), k, list(exclude))
+            off, ids = topk_excluding_args(len(users), k, _exclusion_lists(exclude, users, "topk"))
         u = _ids(users, "user")
         ut = u.to(self.device, torch.int32) if isinstance(u, torch.Tensor) else torch.from_numpy(u).to(self.device)
         if exclude is not None:
@@ -503,11 +505,7 @@ class Model:
         the head; K1 = `candidates` >= k (K1 <= 16 with exclusions) reranks the K1 best by the reference score among the dishes left
         (``ScoringEngine.topk_users_mlp_excluding``).  Returns (scores float32 [n, k], dish ids int32 [n, k])."""
         if exclude is not None:
-            if isinstance(exclude, dict):
-                exclude = [exclude.get(u, ()) for u in users]
-            elif len(exclude) != len(users):
-                raise ValueError("topk_head: %d exclusion lists for %d users" % (len(exclude), len(users)))
-            exclude = list(exclude)
+            exclude = _exclusion_lists(exclude, users, "topk_head")
         u = _ids(users, "user")
         ut = u.to(self.device, torch.int32) if isinstance(u, torch.Tensor) else torch.from_numpy(u).to(self.device)
         s, i = self.engine.topk_users_mlp_excluding(ut, int(k), exclude, int(candidates))

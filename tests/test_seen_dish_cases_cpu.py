@@ -78,7 +78,7 @@ def test_share_count_cases_reach_their_share_count(num_cu):
             assert sd.excl_nsplit(E, n, num_cu) == ns, (E, ns, n)
     assert sd.share_counts(132, 256)[512] == 50               # clamped: ceil(128 * 256 / 50) = 656
     assert sd.share_counts(8, num_cu)[1] > 2048 * num_cu - 1  # m2d_rank_exclude's offsets: n + 1 of them, 2048 num_cu threads
-    assert 4 * sd.share_counts(8, num_cu)[1] > 1024 * num_cu  # m2d_topk_excl_check's ids at |X_u| = 4
+    assert 4 * sd.share_counts(8, num_cu)[1] > 1024 * num_cu  # m2d_check_exclusions' ids at |X_u| = 4
     r = sd.launch_recipe(8)
     _, tiles = sd.pattern_tiles(r.cats)
     assert int(tiles[1:].sum()) % 3 != 0, tiles               # nsplit 3: the last share is shorter than the others
