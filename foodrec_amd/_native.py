@@ -68,6 +68,10 @@ SIGNATURES = {
     "m2d_cookable_dishes": (_c.c_int, [_vp, _vp, _i64, _i32, _vp, _vp, _c.POINTER(_i64), _vp]),
     "m2d_topk_markets": (_c.c_int, [_vp, _vp, _i64, _vp, _vp, _i64, _i32, _i32, _vp, _vp, _vp, _vp]),
     "m2d_topk_markets_excluding": (_c.c_int, [_vp, _vp, _i64, _vp, _vp, _i64, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp]),
+    "m2d_compose_profiles": (_c.c_int, [_vp, _vp, _vp, _vp]),
+    "m2d_topk_profiles": (_c.c_int, [_vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp]),
+    "m2d_score_profiles": (_c.c_int, [_vp, _vp, _vp, _vp, _i64, _vp, _vp]),
+    "m2d_topk_markets_profiles": (_c.c_int, [_vp, _vp, _vp, _vp, _i64, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp]),
     "m2d_write_memory": (_c.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _vp, _c.c_float, _c.c_float,
                                     _c.c_float, _i32, _vp, _vp]),
     "m2d_train_begin": (_c.c_int, [_vp, _i32, _c.c_float, _c.c_float, _vp]),
@@ -82,6 +86,13 @@ SIGNATURES = {
     "m2d_set_option": (_c.c_int, [_vp, _c.c_char_p, _i64]),
     "m2d_get_option": (_c.c_int, [_vp, _c.c_char_p, _c.POINTER(_i64)]),
 }
+
+
+
+class ProfileBatch(_c.Structure):
+    """``m2d_profile_batch`` (include/m2d.h): the profile calls take a pointer to one -- ``ctypes.byref(batch)``."""
+    _fields_ = [("users", _vp), ("labels", _vp), ("general_memory", _vp), ("n", _i64), ("L", _i32), ("alpha", _c.c_float)]
+
 
 _lib = None
 

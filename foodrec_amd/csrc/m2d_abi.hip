@@ -144,6 +144,7 @@ void release(m2d_engine *h)
     }
     if (h->market_buf) (void)hipFree(h->market_buf);
     if (h->markets_buf) (void)hipFree(h->markets_buf);
+    if (h->profile_buf) (void)hipFree(h->profile_buf);
     if (h->market_count_host) (void)hipHostFree(h->market_count_host);
     if (h->scratch) (void)hipFree(h->scratch);
     if (h->topk_flags) (void)hipFree(h->topk_flags);

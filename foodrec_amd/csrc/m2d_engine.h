@@ -106,6 +106,11 @@ struct m2d_engine {
     int opt_market_shares = 0;         // shares of the catalogue per request: 0 = the launcher's rule, 1 ... 64 forced (A/B: same words)
     int market_shares_used = 0;        // what the last call used
 
+    // m2d_*_profiles (m2d_profiles.hip): the call's composed rows [n, C+1, E] and, behind them, the ids 0 .. n-1 its launchers are
+    // handed as users (m2d_rows_view below)
+    float *profile_buf = nullptr;
+    size_t profile_cap = 0;            // floats
+
     // derived table for pair scoring: <U_high[u], CE_c> per user and category (built lazily by large m2d_score_pairs calls;
     // stale after any write to Personal_Memory / Category_Embedding: the engine's own writers and m2d_tables_updated reset it)
     float *user_high = nullptr;  // [U, 4]
@@ -255,6 +260,30 @@ static inline void m2d_mark_written(m2d_engine *h, unsigned tables, m2d_written_
     if (who == M2D_BY_ENGINE) h->grp_nonfinite_known = false;
     if (who == M2D_BY_CALLER) h->finite_scan_pending = true;
 }
+
+// Scoped view (m2d_profiles.hip): while it lives, every launcher serves `rows` [n, C+1, E] in place of Personal_Memory -- users are
+// 0 .. n-1, no shard base, neither the <U_high, CE_c> table nor the bf16 mirror (both belong to the real table).  The destructor
+// puts the engine's own values back on every exit path; kernels and launcher signatures are what they were.  Rules:
+//   m2d_ensure_finite_scan runs BEFORE the view is entered (inside, a queued scan would walk `rows` instead of the table);
+//   user_high, pm_bf16, their validity flags and m2d_mark_written are neither read, rebuilt nor touched inside it -- with both
+//   options at 0 no launcher asks for them; the rows are finite while the engine's non-finite word is 0 (the composer sees to it).
+struct m2d_rows_view {
+    m2d_engine *const h;
+    const float *const pm;
+    const int64_t U, user_base;
+    const int opt_user_high, opt_pm_bf16;
+    m2d_rows_view(m2d_engine *e, const float *rows, int64_t n)
+        : h(e), pm(e->pm), U(e->U), user_base(e->user_base), opt_user_high(e->opt_user_high), opt_pm_bf16(e->opt_pm_bf16)
+    {
+        e->pm = rows; e->U = n; e->user_base = 0; e->opt_user_high = 0; e->opt_pm_bf16 = 0;
+    }
+    ~m2d_rows_view()
+    {
+        h->pm = pm; h->U = U; h->user_base = user_base; h->opt_user_high = opt_user_high; h->opt_pm_bf16 = opt_pm_bf16;
+    }
+    m2d_rows_view(const m2d_rows_view &) = delete;
+    m2d_rows_view &operator=(const m2d_rows_view &) = delete;
+};
 
 #define M2D_HIP_TRY(h, expr)                                                                   \
     do {                                                                                       \

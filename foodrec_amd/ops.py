@@ -691,6 +691,112 @@ class ScoringEngine:
         self._markets_keep = (users, off, ids, xoff, xids)   # inputs stay alive until the queued kernels have read them
         return (out_s, out_i) + ((counts,) if return_counts else ()) + ((missing,) if return_missing else ())
 
+    # -- EXTENSION (no reference counterpart): serving from health labels ---------------------------------------
+    def _profile_batch(self, labels, general_memory, users, alpha, what: str):
+        """The ``m2d_profile_batch`` of a profile call and the tensors it points into: (batch, n, keep).  `labels`: a device or host
+        [n, L] float array (``user_one_hot_label`` rows, any non-negative weights) or a LIST of n label-id lists, turned into one-hot
+        rows here with L = general_memory.shape[0] (an id outside [0, L) raises IndexError); `users`: None (all guests) or n ids,
+        -1 = guest."""
+        gm = general_memory if isinstance(general_memory, torch.Tensor) else torch.as_tensor(np.asarray(general_memory, dtype=np.float32))
+        gm = gm.to(device=self.device, dtype=torch.float32).contiguous()
+        if gm.dim() != 3 or tuple(gm.shape[1:]) != (self.C + 1, self.E):
+            raise ValueError("%s: general_memory must be [L, C+1=%d, E=%d], got %r" % (what, self.C + 1, self.E, tuple(gm.shape)))
+        L = gm.shape[0]
+        if isinstance(labels, list):
+            rows = np.zeros((len(labels), L), dtype=np.float32)
+            for q, ids in enumerate(labels):
+                ids = np.asarray(ids, dtype=np.int64).reshape(-1)
+                if ids.size and (ids.min() < 0 or ids.max() >= L):
+                    raise IndexError("%s: label id outside [0, %d) in request %d" % (what, L, q))
+                rows[q, ids] = 1.0
+            labels = rows
+        y = _dev_f32(labels, self.device)
+        if y.dim() != 2 or y.shape[1] != L:
+            raise ValueError("%s: labels must be [n, L=%d], got %r" % (what, L, tuple(y.shape)))
+        n = y.shape[0]
+        u = None
+        if users is not None:
+            u = self._as_ids(users, "user")
+            if u.numel() != n:
+                raise ValueError("%s: %d users for %d label rows" % (what, u.numel(), n))
+        batch = _native.ProfileBatch(u.data_ptr() if u is not None and n else None, y.data_ptr() if n else gm.data_ptr(), gm.data_ptr(),
+                                     n, L, float(alpha))
+        return batch, n, (u, y, gm)
+
+    def compose_profiles(self, labels, general_memory, users=None, alpha: float = 1.0) -> torch.Tensor:
+        """EXTENSION (``m2d_compose_profiles``, include/m2d.h): the memory block of each profile (users[q], labels[q]) BY VALUE --
+        f32[n, C+1, E], row q = base + alpha * (sum_l y_l GM[l]) / (sum_l y_l) with base = Personal_Memory[users[q]] or zeros for a
+        guest (-1, or ``users=None``): what ``write_memory`` would add to the user's block, without writing it.  Does not synchronise;
+        a request without labels (or with a non-finite row) gets zeros and surfaces from ``check()``."""
+        batch, n, keep = self._profile_batch(labels, general_memory, users, alpha, "compose_profiles")
+        out = torch.empty((n, self.C + 1, self.E), dtype=torch.float32, device=self.device)
+        with torch.cuda.device(self.device):
+            rc = _native.lib().m2d_compose_profiles(self._h, ctypes.byref(batch), out.data_ptr(), _stream_ptr())
+        _native.raise_for(rc, self._h)
+        self._profiles_keep = keep                       # inputs stay alive until the queued kernels have read them
+        return out
+
+    def topk_profiles(self, labels, general_memory, k: int, users=None, alpha: float = 1.0, exclude=None):
+        """EXTENSION (``m2d_topk_profiles``): ``topk_users`` -- with `exclude` ``topk_users_excluding``, k <= 16 -- for the composed
+        rows of ``compose_profiles``: (scores f32[n, k], dish ids i32[n, k]), the words that call returns on an engine whose
+        Personal_Memory is those rows.  `exclude` as in ``topk_users_excluding`` (``exclusions_on_device``).  Does not synchronise."""
+        batch, n, keep = self._profile_batch(labels, general_memory, users, alpha, "topk_profiles")
+        off = ids = None
+        if exclude is not None:
+            off, ids = exclusions_on_device(exclude, n, self.device, "topk_profiles")
+        k = int(k)
+        out_s = torch.empty((n, max(k, 0)), dtype=torch.float32, device=self.device)
+        out_i = torch.empty((n, max(k, 0)), dtype=torch.int32, device=self.device)
+        with torch.cuda.device(self.device):
+            rc = _native.lib().m2d_topk_profiles(self._h, ctypes.byref(batch), k, off.data_ptr() if off is not None else None,
+                                                 ids.data_ptr() if ids is not None else None, out_s.data_ptr(), out_i.data_ptr(),
+                                                 _stream_ptr())
+        _native.raise_for(rc, self._h)
+        self._profiles_keep = keep + (off, ids)
+        return out_s, out_i
+
+    def score_profiles(self, labels, general_memory, rows, items, users=None, alpha: float = 1.0) -> torch.Tensor:
+        """EXTENSION (``m2d_score_profiles``): ``score_pairs_bydish`` over pairs (profile rows[b], dish items[b]) -> f32[B]; `rows`
+        index the profiles of this call, one outside [0, n) surfaces as IndexError from ``check()``.  Does not synchronise."""
+        batch, n, keep = self._profile_batch(labels, general_memory, users, alpha, "score_profiles")
+        rows, items = self._as_ids(rows, "profile row"), self._as_ids(items, "item")
+        B = rows.numel()
+        if items.numel() != B:
+            raise ValueError("score_profiles: rows and items differ in length")
+        out = torch.empty(B, dtype=torch.float32, device=self.device)
+        with torch.cuda.device(self.device):
+            rc = _native.lib().m2d_score_profiles(self._h, ctypes.byref(batch), rows.data_ptr() if B else None,
+                                                  items.data_ptr() if B else None, B, out.data_ptr() if B else None, _stream_ptr())
+        _native.raise_for(rc, self._h)
+        self._profiles_keep = keep + (rows, items)
+        return out
+
+    def topk_markets_profiles(self, labels, general_memory, markets, k: int = 10, users=None, alpha: float = 1.0, exclude=None,
+                              max_missing: int = 0, return_counts: bool = False, return_missing: bool = False):
+        """EXTENSION (``m2d_topk_markets_profiles``): ``topk_markets_excluding`` with request q = (profile q, markets[q]); `markets`,
+        `exclude` and the returned tuple as there.  Does not synchronise."""
+        batch, n, keep = self._profile_batch(labels, general_memory, users, alpha, "topk_markets_profiles")
+        off, ids = self._markets_csr(markets, n)
+        if off.numel() != n + 1:
+            raise ValueError("topk_markets_profiles: market offsets must have n + 1 = %d entries" % (n + 1))
+        xoff = xids = None
+        if exclude is not None:
+            xoff, xids = exclusions_on_device(exclude, n, self.device, "topk_markets_profiles", dtype_error=TypeError)
+        k, mm = int(k), int(max_missing)
+        out_s = torch.empty((n, max(k, 0)), dtype=torch.float32, device=self.device)
+        out_i = torch.empty((n, max(k, 0)), dtype=torch.int32, device=self.device)
+        counts = torch.empty((n,), dtype=torch.int32, device=self.device) if return_counts else None
+        missing = torch.empty((n, max(k, 0), max(mm, 0)), dtype=torch.int32, device=self.device) if return_missing else None
+        with torch.cuda.device(self.device):
+            rc = _native.lib().m2d_topk_markets_profiles(
+                self._h, ctypes.byref(batch), off.data_ptr(), ids.data_ptr() if ids.numel() else None, ids.numel(),
+                xoff.data_ptr() if xoff is not None else None, xids.data_ptr() if xids is not None else None, k, mm,
+                out_s.data_ptr(), out_i.data_ptr(), counts.data_ptr() if counts is not None else None,
+                missing.data_ptr() if missing is not None and missing.numel() else None, _stream_ptr())
+        _native.raise_for(rc, self._h)
+        self._profiles_keep = keep + (off, ids, xoff, xids)
+        return (out_s, out_i) + ((counts,) if return_counts else ()) + ((missing,) if return_missing else ())
+
     def catalogue_rank(self, users, items, exclude=None, head: bool = False):
         """Full-catalogue rank of held-out dishes (``m2d_catalogue_rank``, include/m2d.h): for each query (users[i], items[i]) the
         number of dishes ranked before items[i] in ``topk_users``' order, leaving out the query's excluded ids.
@@ -952,3 +1058,31 @@ def _(engine, users, market_off, market_ids, excl_off=None, excl_ids=None, k=10,
             users.new_empty((users.numel(), k), dtype=torch.int32),
             users.new_empty((users.numel(),), dtype=torch.int32),
             users.new_empty((users.numel(), k, max_missing), dtype=torch.int32))
+
+
+@torch.library.custom_op("m2d::compose_profiles", mutates_args=(), device_types="cuda")
+def compose_profiles_op(engine: int, labels: torch.Tensor, general_memory: torch.Tensor, users: Optional[torch.Tensor] = None,
+                        alpha: float = 1.0) -> torch.Tensor:
+    """``ScoringEngine.compose_profiles``: labels f32[n, L], general_memory f32[L, C+1, E] -> rows f32[n, C+1, E]."""
+    return _engine(engine).compose_profiles(labels, general_memory, users, alpha)
+
+
+@compose_profiles_op.register_fake
+def _(engine, labels, general_memory, users=None, alpha=1.0):
+    return labels.new_empty((labels.shape[0],) + tuple(general_memory.shape[1:]), dtype=torch.float32)
+
+
+@torch.library.custom_op("m2d::topk_profiles", mutates_args=(), device_types="cuda")
+def topk_profiles_op(engine: int, labels: torch.Tensor, general_memory: torch.Tensor, k: int, users: Optional[torch.Tensor] = None,
+                     alpha: float = 1.0, excl_off: Optional[torch.Tensor] = None,
+                     excl_ids: Optional[torch.Tensor] = None) -> tuple[torch.Tensor, torch.Tensor]:
+    """``ScoringEngine.topk_profiles``; `excl_off` / `excl_ids`: device tensors, ascending per segment, taken as they are."""
+    exclude = None if excl_off is None else (excl_off, excl_ids if excl_ids is not None else excl_off.new_empty((0,), dtype=torch.int32))
+    s, i = _engine(engine).topk_profiles(labels, general_memory, k, users, alpha, exclude)
+    return s, i
+
+
+@topk_profiles_op.register_fake
+def _(engine, labels, general_memory, k, users=None, alpha=1.0, excl_off=None, excl_ids=None):
+    return (labels.new_empty((labels.shape[0], k), dtype=torch.float32),
+            labels.new_empty((labels.shape[0], k), dtype=torch.int32))

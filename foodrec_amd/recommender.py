@@ -116,7 +116,8 @@ class Model:
     ``num_categories, num_users, embed_size, high_level_score_coefficient`` are used; ``learner,
     num_labels, lr, decay_steps, decay_rate, beta_1, beta_2, alpha`` are recorded when present.
     Tables are numpy (or torch) arrays and are copied to HBM once; the caller keeps its host copies.
-    ``General_Memory`` is accepted for signature parity; the forward never reads it.
+    ``General_Memory`` is accepted for signature parity; the forward never reads it (``write_memory`` does, and the build-defined
+    ``topk_for_labels`` serves from it).
     """
 
     def __init__(self, args, Personal_Memory, Recipe_Embedding, Category_Embedding, General_Memory=None,
@@ -495,6 +496,46 @@ class Model:
             s, i = torch.ops.m2d.topk_users_mlp(self.engine.id, ut, int(k), int(candidates))
         else:
             s, i = torch.ops.m2d.topk_users(self.engine.id, ut, int(k))
+        self.engine.check()
+        return s.cpu().numpy(), i.cpu().numpy()
+
+    def topk_for_labels(self, labels, k: int = 10, users=None, exclude=None, market=None, max_missing: int = 0, alpha=None):
+        """EXTENSION (no reference counterpart): the k best dishes for people described by their HEALTH LABELS --
+        `labels` a list of label-id lists (one per request) or an [n, num_labels] array of ``user_one_hot_label`` rows.  Each request's
+        memory block is alpha * (the label-weighted mean of General_Memory's rows), on top of Personal_Memory[users[q]] when `users`
+        names a known user (str or int; -1 or ``users=None``: a guest): what ``write_memory`` would add to that user's block,
+        served without writing it.  General_Memory is read as it stands: a ``write_memory`` is visible to the next call.
+        `alpha`: 1 for guests, ``args.alpha`` when `users` is given.  `exclude`: a list of dish-id lists aligned with the requests, or a
+        dict keyed by the user as given in `users` (then k <= 16, as in `topk`).  `market`: a list of ingredient-id sequences, one per
+        request -- the lists are then those of `topk_markets_excluding` (k <= 64, `max_missing` as there), rows ending in -1 / NaN.
+        Returns (scores float32 [n, k], dish ids int32 [n, k]).  (``ScoringEngine.topk_profiles`` / ``topk_markets_profiles``.)"""
+        if self._gm_dev is None:
+            if self.General_Memory is None:
+                raise ValueError("Model was built without General_Memory")
+            self._gm_dev = torch.as_tensor(np.asarray(self.General_Memory, dtype=np.float32)).to(self.device).contiguous()
+        if not isinstance(labels, list):
+            labels = labels if isinstance(labels, torch.Tensor) else np.asarray(labels, dtype=np.float32)
+        n = len(labels)
+        if alpha is None:
+            alpha = 1.0 if users is None else float(self.alpha)
+        ut = None
+        if users is not None:
+            u = _ids(users, "user")
+            ut = u.to(self.device, torch.int32) if isinstance(u, torch.Tensor) else torch.from_numpy(u).to(self.device)
+        had = None
+        if exclude is not None:
+            if isinstance(exclude, dict) and users is None:
+                raise ValueError("topk_for_labels: a dict of exclusions is keyed by user; guests take a list aligned with the requests")
+            had = [_ids(x, "item") for x in _exclusion_lists(exclude, users if users is not None else range(n), "topk_for_labels")]
+            had = [x.cpu().numpy() if isinstance(x, torch.Tensor) else x for x in had]
+        if market is not None:
+            if len(market) != n:
+                raise ValueError("topk_for_labels: %d markets for %d requests" % (len(market), n))
+            lists = [_ids(m, "ingredient") for m in market]
+            lists = [m.cpu().numpy().astype(np.int32) if isinstance(m, torch.Tensor) else m for m in lists]
+            s, i = self.engine.topk_markets_profiles(labels, self._gm_dev, lists, int(k), ut, alpha, had, int(max_missing))
+        else:
+            s, i = self.engine.topk_profiles(labels, self._gm_dev, int(k), ut, alpha, had)
         self.engine.check()
         return s.cpu().numpy(), i.cpu().numpy()
 

@@ -524,6 +524,60 @@ int m2d_topk_markets_excluding(m2d_engine *h, const int32_t *users /* device, [n
                                int32_t *out_ids /* device, [nQ, k] */, int32_t *out_counts /* device, [nQ], may be null */,
                                int32_t *out_missing /* device, [nQ, k, max_missing], may be null */, void *stream);
 
+/* ---- build-defined extension, NO reference counterpart: serving from health labels ----
+ * The reference reads General_Memory only while it writes (Write_Memory, Model_Recommender.py:170-198: PM[u] += alpha * g, g the
+ * label-weighted mean of General_Memory's rows).  A profile is that row BY VALUE, nothing is written: q = (u_q, y_q), y_q the f32[L]
+ * user_one_hot_label row (any non-negative weights), u_q a user id or -1 for a guest (users == NULL: every request is a guest).
+ * In float32, in this order (label order, labels of weight 0 are not read):
+ *     ysum = sum_l y_l                     plain adds
+ *     g_k  = fmaf(y_l, GM[l][k], g_k)      from 0
+ *     M_k  = base_k + alpha * (g_k / ysum) true division, one rounded product, one rounded sum (not fused)
+ *     base = PM[u_q - user_base] for u_q >= 0, zeros for a guest
+ * -- m2d_write_memory's own g, ysum and alpha * (g / ysum) followed by the add its atomic performs: for distinct known users the row
+ * equals Personal_Memory[u] after m2d_write_memory(which = PERSONAL, beta_1 = beta_2 = 0) bit for bit.
+ *
+ * Containment.  While the engine's tables are finite, a request whose row would hold an inf / NaN (ysum == 0, an inf / NaN in an
+ * ADDRESSED General_Memory row, overflow) gets a row of zeros and latches M2D_ERR_INVALID_ARG with bad_value = its number of non-zero
+ * labels and bad_index = q; once a table value is not finite the rows are written as computed and retrieval takes the literal
+ * kernels, as it does for users.  u_q outside the table and not -1: a row of zeros, M2D_ERR_BAD_USER_ID with (u_q, q).  Rows of a
+ * request with a latched error are otherwise unspecified; the call always completes, m2d_check reports.
+ *
+ * m2d_compose_profiles writes the rows.  The three serving calls compose into engine-owned scratch and run an existing call against
+ * those rows, request q standing where user q stood -- same kernels, same order, same score words as that call on an engine whose
+ * Personal_Memory is the composed rows (with user_base 0 and the options "user_high_table" / "pm_bf16" off):
+ *   m2d_topk_profiles          excl_off == NULL: m2d_topk_users (1 <= k <= min(64, I)); otherwise m2d_topk_users_excluding
+ *                              (1 <= k <= min(16, I)), each with its own requirements, refusals and diagnostics;
+ *   m2d_score_profiles         m2d_score_pairs_bydish over pairs (rows[b], items[b]), rows[b] a profile index: one outside [0, n) is
+ *                              latched as M2D_ERR_BAD_USER_ID with its value and b;
+ *   m2d_topk_markets_profiles  m2d_topk_markets_excluding, request q = (profile q, market q).
+ * The engine's own Personal_Memory, shard base, derived tables and options are what they were when the call returns, on every path.
+ * Returned directly as M2D_ERR_INVALID_ARG: a null batch, labels, general_memory or output, L < 1, n < 0 or n >= 2^31, an alpha that is
+ * not finite.  n == 0: M2D_OK, nothing launched.  No call synchronises (beyond what the call it stands for does) or allocates after
+ * its first launch of a size.  general_memory is read as it stands when the kernel runs on `stream`. */
+typedef struct {
+    const int32_t *users;            /* device i32[n] or NULL (all guests); -1 = guest */
+    const float *labels;             /* device f32[n, L] */
+    const float *general_memory;     /* device f32[L, C+1, E] */
+    int64_t n;
+    int32_t L;
+    float alpha;
+} m2d_profile_batch;
+
+int m2d_compose_profiles(m2d_engine *h, const m2d_profile_batch *p, float *out_rows /* device, [n, C+1, E] */, void *stream);
+int m2d_topk_profiles(m2d_engine *h, const m2d_profile_batch *p, int32_t k,
+                      const int64_t *excl_off /* device, [n + 1], NULL = no exclusions */,
+                      const int32_t *excl_ids /* device, [excl_off[n]] */, float *out_scores /* device, [n, k] */,
+                      int32_t *out_ids /* device, [n, k] */, void *stream);
+int m2d_score_profiles(m2d_engine *h, const m2d_profile_batch *p, const int32_t *rows /* device, [B]: profile index */,
+                       const int32_t *items /* device, [B] */, int64_t B, float *out /* device, [B] */, void *stream);
+int m2d_topk_markets_profiles(m2d_engine *h, const m2d_profile_batch *p, const int64_t *market_off /* device, [n + 1] */,
+                              const int32_t *market_ids /* device, [nnzM], may be null when nnzM == 0 */, int64_t nnzM,
+                              const int64_t *excl_off /* device, [n + 1], NULL = no exclusions */,
+                              const int32_t *excl_ids /* device, [excl_off[n]] */, int32_t k, int32_t max_missing,
+                              float *out_scores /* device, [n, k] */, int32_t *out_ids /* device, [n, k] */,
+                              int32_t *out_counts /* device, [n], may be null */,
+                              int32_t *out_missing /* device, [n, k, max_missing], may be null */, void *stream);
+
 /* Synchronise `stream` and report (then clear) the first id error latched by kernels since the
  * previous check: M2D_OK, M2D_ERR_BAD_USER_ID or M2D_ERR_BAD_ITEM_ID.  TF-CPU GatherV2 raises
  * InvalidArgument for such ids; the kernels never read out of bounds and write NaN for the pair.
