@@ -873,6 +873,47 @@ int m2d_topk_users_mlp_excluding(m2d_engine *h, const int32_t *users, int64_t nU
     return m2d_launch_topk_users_mlp(h, users, nU, k, candidates, out_scores, out_ids, (hipStream_t)stream, excl_off, excl_ids);
 }
 
+int m2d_topk_users_deep(m2d_engine *h, const int32_t *users, int64_t nU, int32_t k, const int64_t *excl_off, const int32_t *excl_ids,
+                        float *out_scores, int32_t *out_ids, void *stream)
+{
+    if (!h) return M2D_ERR_INVALID_ARG;
+    if (nU < 0 || k < 1 || k > 1024 || (int64_t)k > h->I)
+        return fail(h, M2D_ERR_INVALID_ARG, "m2d_topk_users_deep: need nU >= 0 and 1 <= k <= min(1024, I)");
+    if (nU == 0) return M2D_OK;
+    if (!users || !out_scores || !out_ids || (excl_off && !excl_ids)) return fail(h, M2D_ERR_INVALID_ARG, "m2d_topk_users_deep: null buffer");
+    if (!h->dish_cats) return fail(h, M2D_ERR_NOT_CONFIGURED, "call m2d_set_dish_categories first");
+    M2D_HIP_TRY(h, hipSetDevice(h->device));
+    return m2d_launch_topk_users_deep(h, users, nU, k, excl_off, excl_ids, out_scores, out_ids, (hipStream_t)stream);
+}
+
+int m2d_topk_users_mlp_deep(m2d_engine *h, const int32_t *users, int64_t nU, int32_t k, int32_t candidates, const int64_t *excl_off,
+                            const int32_t *excl_ids, float *out_scores, int32_t *out_ids, void *stream)
+{
+    if (!h) return M2D_ERR_INVALID_ARG;
+    if (nU < 0 || k < 1 || k > 1024 || (int64_t)k > h->I)
+        return fail(h, M2D_ERR_INVALID_ARG, "m2d_topk_users_mlp_deep: need nU >= 0 and 1 <= k <= min(1024, I)");
+    if (candidates != 0 && (candidates < k || candidates > 1024 || (int64_t)candidates > h->I))
+        return fail(h, M2D_ERR_INVALID_ARG, "m2d_topk_users_mlp_deep: candidates must be 0 (exact) or k <= candidates <= min(1024, I)");
+    if (nU == 0) return M2D_OK;
+    if (!users || !out_scores || !out_ids || (excl_off && !excl_ids)) return fail(h, M2D_ERR_INVALID_ARG, "m2d_topk_users_mlp_deep: null buffer");
+    if (!h->mlp_w1) return fail(h, M2D_ERR_NOT_CONFIGURED, "call m2d_set_mlp_head first");
+    if (!h->dish_cats) return fail(h, M2D_ERR_NOT_CONFIGURED, "call m2d_set_dish_categories first");
+    M2D_HIP_TRY(h, hipSetDevice(h->device));
+    return m2d_launch_topk_users_mlp_deep(h, users, nU, k, candidates, excl_off, excl_ids, out_scores, out_ids, (hipStream_t)stream);
+}
+
+int m2d_select_probe(m2d_engine *h, const float *scores, int64_t rows, int64_t W, int32_t k, int32_t form, float *out_scores,
+                     int32_t *out_ids, void *stream)
+{
+    if (!h) return M2D_ERR_INVALID_ARG;
+    if (rows < 1 || rows > 0x7fffffff || W < 1 || W > 0x7fffffff || k < 1 || (int64_t)k > W || k > (form ? 64 : 1024) || form < 0 || form > 1)
+        return fail(h, M2D_ERR_INVALID_ARG, "m2d_select_probe: need rows >= 1, 1 <= k <= min(W, 1024) (form 1: 64), form 0 / 1");
+    if (!scores || !out_scores || !out_ids) return fail(h, M2D_ERR_INVALID_ARG, "m2d_select_probe: null buffer");
+    M2D_HIP_TRY(h, hipSetDevice(h->device));
+    return (form ? m2d_launch_topk_select : m2d_launch_select_deep)(h, scores, nullptr, 0, rows, W, 0, k, 1, out_scores, out_ids, W, 1,
+                                                                    (hipStream_t)stream, nullptr, nullptr, nullptr, false);
+}
+
 int m2d_catalogue_rank_mlp(m2d_engine *h, const int32_t *users, const int32_t *items, int64_t n, const int64_t *excl_off,
                            const int32_t *excl_ids, int32_t *out_rank, float *out_scores, void *stream)
 {
@@ -1046,6 +1087,10 @@ int m2d_set_option(m2d_engine *h, const char *name, int64_t value)
         if (value < 256 || value > (1 << 24)) return fail(h, M2D_ERR_INVALID_ARG, "m2d_set_option: slate_chunk_pairs takes 256 ... 2^24");
         h->opt_slate_chunk_pairs = value;
     }
+    else if (!strcmp(name, "deep_chunk_pairs")) {
+        if (value < 256 || value > (1 << 24)) return fail(h, M2D_ERR_INVALID_ARG, "m2d_set_option: deep_chunk_pairs takes 256 ... 2^24");
+        h->opt_deep_chunk_pairs = value;
+    }
     else if (!strcmp(name, "mlp_bf16x3")) h->opt_mlp_bf16x3 = (int)value;
     else if (!strcmp(name, "mlp_form")) h->opt_mlp_form = (int)value;
     else if (!strcmp(name, "skip_masked")) h->opt_skip_masked = (int)value;
@@ -1130,6 +1175,7 @@ int m2d_get_option(const m2d_engine *h, const char *name, int64_t *value)
     else if (!strcmp(name, "topk_mlp_chunk_pairs")) *value = h->opt_topk_mlp_chunk_pairs;
     else if (!strcmp(name, "topk_mlp_launches")) *value = h->topk_mlp_launches;
     else if (!strcmp(name, "slate_chunk_pairs")) *value = h->opt_slate_chunk_pairs;
+    else if (!strcmp(name, "deep_chunk_pairs")) *value = h->opt_deep_chunk_pairs;
     else if (!strcmp(name, "mlp_bf16x3")) *value = h->opt_mlp_bf16x3;
     else if (!strcmp(name, "mlp_form")) *value = h->opt_mlp_form;
     else if (!strcmp(name, "skip_masked")) *value = h->opt_skip_masked;

@@ -86,6 +86,7 @@ struct m2d_engine {
     float *slate_scores = nullptr;
     size_t slate_dt_cap = 0, slate_scores_cap = 0;   // floats
     int64_t opt_slate_chunk_pairs = 1 << 22;         // pairs of score scratch per m2d_topk_slate pass (the lists do not depend on it)
+    int64_t opt_deep_chunk_pairs = 1 << 22;          // the same for m2d_topk_users_deep: ranges of min(I, P, 65536) dishes, blocks of P / W users
 
     // m2d_set_recipes / m2d_cookable_dishes (m2d_market.hip): every dish's ingredient list, CSR, validated once by the setter (CSR
     // shape, every id in [0, R)); lists only -- no table, no weights, nothing the scoring path reads, and no tie to `ing` above.
@@ -471,6 +472,26 @@ int m2d_launch_topk_select(m2d_engine *h, const float *scores, const int32_t *id
                            int32_t k, int32_t first, float *out_scores, int32_t *out_ids, int64_t rs, int64_t es, hipStream_t stream,
                            const int64_t *xoff = nullptr, const int32_t *xids = nullptr, const int64_t *xend = nullptr,
                            bool holes = false);
+// threads of a selection / count block: a wave for the reranker's short rows, sixteen for a catalogue-wide range (few rows then share
+// the device: a block of P / W rows)
+static inline int select_threads(const int64_t W) { return W <= 256 ? 64 : W <= 16384 ? 256 : 1024; }
+// m2d_select_deep.hip: the same contract for 1 <= k <= 1024 -- m2d_select_deep, a radix select on the key
+int m2d_launch_select_deep(m2d_engine *h, const float *scores, const int32_t *ids, int64_t ids_stride, int64_t rows, int64_t W, int32_t d0,
+                           int32_t k, int32_t first, float *out_scores, int32_t *out_ids, int64_t rs, int64_t es, hipStream_t stream,
+                           const int64_t *xoff = nullptr, const int32_t *xids = nullptr, const int64_t *xend = nullptr,
+                           bool holes = false);
+// m2d_slate.hip, the deep catalogue lists (m2d_topk_users_deep).  m2d_deep_conditions: the slate launcher's table conditions without its
+// head refusal, under the name `entry`.  m2d_launch_deep_lists: the blocks and ranges of `nU` users whose conditions and exclusion
+// lists the caller has checked -- excl_off: these users' offsets (null: none), excl_end: where the array's length stands,
+// index_base: the position of users[0] in the call's array, for the error latch
+int m2d_deep_conditions(m2d_engine *h, const char *entry, hipStream_t stream);
+int m2d_launch_deep_lists(m2d_engine *h, const int32_t *users, int64_t nU, int32_t k, const int64_t *excl_off, const int32_t *excl_ids,
+                          const int64_t *excl_end, int64_t index_base, float *out_scores, int32_t *out_ids, hipStream_t stream);
+int m2d_launch_topk_users_deep(m2d_engine *h, const int32_t *users, int64_t nU, int32_t k, const int64_t *excl_off, const int32_t *excl_ids,
+                               float *out_scores, int32_t *out_ids, hipStream_t stream);
+// m2d_topk_mlp.hip: m2d_launch_topk_users_mlp's loop with m2d_select_deep; candidates > 0: stage 1 is m2d_launch_deep_lists per user block
+int m2d_launch_topk_users_mlp_deep(m2d_engine *h, const int32_t *users, int64_t nU, int32_t k, int32_t candidates, const int64_t *excl_off,
+                                   const int32_t *excl_ids, float *out_scores, int32_t *out_ids, hipStream_t stream);
 // m2d_slate.hip: out == null: the scores of user blocks go to scratch and the lists of k to out_scores / out_ids
 int m2d_launch_slate(m2d_engine *h, const char *entry, const int32_t *users, int64_t nU, const int32_t *slate, int64_t nD, int32_t k,
                      float *out, float *out_scores, int32_t *out_ids, hipStream_t stream);

@@ -36,10 +36,10 @@ constexpr int SL_DPAD = 128;                     // Dt_s holds zero rows up to t
 // One wave per row of Dt_s: rows [0, nD) are the slate's dish vectors -- dish_vector_row, the expressions of m2d_build_dish_vectors --
 // zero behind K; rows [nD, rows) are zero.  The wave of entry j checks it: an id outside [0, I) is latched as M2D_ERR_BAD_ITEM_ID (its
 // row stays zero: nothing is read for it), an id not above its predecessor as M2D_ERR_INVALID_ARG (a predecessor that is itself out
-// of range is reported by its own wave).
+// of range is reported by its own wave).  The d0 form (slate == null: a dish range of m2d_topk_users_deep): entry j is dish d0 + j.
 __global__ __launch_bounds__(256) void m2d_build_slate_vectors(const float *re, const float *ce, const float *dish_cats, const int32_t *slate,
-                                                               int64_t nD, int64_t rows, int64_t I, int C, int E, float a, float b, float *dt,
-                                                               int Kp, int32_t *err)
+                                                               int32_t d0, int64_t nD, int64_t rows, int64_t I, int C, int E, float a, float b,
+                                                               float *dt, int Kp, int32_t *err)
 {
     const int lane = threadIdx.x & 63;
     const int64_t j = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
@@ -48,11 +48,11 @@ __global__ __launch_bounds__(256) void m2d_build_slate_vectors(const float *re, 
     float *o = dt + (size_t)j * Kp;
     bool ok = false;
     if (j < nD) {
-        const int32_t d = slate[j];
+        const int32_t d = slate ? slate[j] : d0 + (int32_t)j;
         ok = d >= 0 && (int64_t)d < I;
         if (!ok) {
             if (lane == 0) m2d_latch_error(err, M2D_ERR_BAD_ITEM_ID, d, j);
-        } else if (j > 0) {
+        } else if (slate && j > 0) {
             const int32_t prev = slate[j - 1];
             if (prev >= 0 && (int64_t)prev < I && prev >= d && lane == 0) m2d_latch_error(err, M2D_ERR_INVALID_ARG, d, j);
         }
@@ -229,34 +229,53 @@ int launch_scores(m2d_engine *h, SlateArgs &a, const bool mfma, hipStream_t st)
     return M2D_OK;
 }
 
+// the call's slate vectors in slate_dt (`slate` null: the dishes d0 .. d0 + nD - 1) and what the score kernels take but users, rows and out
+int slate_prepare(m2d_engine *h, const int32_t *slate, int32_t d0, int64_t nD, SlateArgs &a, bool &mfma, hipStream_t st)
+{
+    const int K = (h->C + 1) * h->E, Kp = (K + SL_KC - 1) / SL_KC * SL_KC;
+    const int64_t rows = (nD + SL_DPAD - 1) / SL_DPAD * SL_DPAD + 1;          // the slate, zero rows up to the tile multiple, the zero row
+    int rc;
+    if ((rc = m2d_grow(h, h->slate_dt, h->slate_dt_cap, (size_t)rows * Kp, sizeof(float))) != M2D_OK) return rc;
+    hipLaunchKernelGGL(m2d_build_slate_vectors, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, st, h->re, h->ce, h->dish_cats, slate, d0, nD,
+                       rows, h->I, h->C, h->E, h->a, h->b, h->slate_dt, Kp, h->err_dev);
+    M2D_HIP_TRY(h, hipGetLastError());
+    mfma = h->C == 4 && h->E % 4 == 0 && h->E <= 256 && h->opt_variant != 9;
+    a.pm = h->pm; a.dt = h->slate_dt; a.zero = h->slate_dt + (size_t)(rows - 1) * Kp;
+    a.U = h->U; a.user_base = h->user_base; a.nD = nD; a.utiles = a.dtiles = 0; a.K = K; a.Kp = Kp; a.err = h->err_dev;
+    h->last_kernel = mfma ? "m2d_score_slate_mfma" : "m2d_score_slate_generic";
+    return M2D_OK;
+}
+
 }  // namespace
 
-int m2d_launch_slate(m2d_engine *h, const char *entry, const int32_t *users, int64_t nU, const int32_t *slate, int64_t nD, int32_t k,
-                     float *out, float *out_scores, int32_t *out_ids, hipStream_t st)
+// what every call on the slate kernels needs of the tables (the head refusal is the public slate entries' own)
+int m2d_deep_conditions(m2d_engine *h, const char *entry, hipStream_t st)
 {
     auto refuse = [&](const char *why) {
         h->last_error = std::string(entry) + ": " + why;
         return M2D_ERR_UNSUPPORTED;
     };
     if (h->ing || h->dish_high) return refuse("the ingredient table is set (not supported)");
-    if (h->mlp_w1) return refuse("the MLP head is set (not supported)");
     int rc;
     if ((rc = m2d_ensure_finite_scan(h, st)) != M2D_OK) return rc;
     if ((rc = m2d_refresh_nonfinite(h, st)) != M2D_OK) return rc;
     if (h->grp_nonfinite) return refuse("needs finite tables (a table value is not finite)");
+    return M2D_OK;
+}
 
-    const int K = (h->C + 1) * h->E, Kp = (K + SL_KC - 1) / SL_KC * SL_KC;
-    const int64_t rows = (nD + SL_DPAD - 1) / SL_DPAD * SL_DPAD + 1;          // the slate, zero rows up to the tile multiple, the zero row
-    if ((rc = m2d_grow(h, h->slate_dt, h->slate_dt_cap, (size_t)rows * Kp, sizeof(float))) != M2D_OK) return rc;
-    hipLaunchKernelGGL(m2d_build_slate_vectors, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, st, h->re, h->ce, h->dish_cats, slate, nD, rows,
-                       h->I, h->C, h->E, h->a, h->b, h->slate_dt, Kp, h->err_dev);
-    M2D_HIP_TRY(h, hipGetLastError());
+int m2d_launch_slate(m2d_engine *h, const char *entry, const int32_t *users, int64_t nU, const int32_t *slate, int64_t nD, int32_t k,
+                     float *out, float *out_scores, int32_t *out_ids, hipStream_t st)
+{
+    if (h->mlp_w1 && !(h->ing || h->dish_high)) {
+        h->last_error = std::string(entry) + ": the MLP head is set (not supported)";
+        return M2D_ERR_UNSUPPORTED;
+    }
+    int rc;
+    if ((rc = m2d_deep_conditions(h, entry, st)) != M2D_OK) return rc;
 
-    const bool mfma = h->C == 4 && h->E % 4 == 0 && h->E <= 256 && h->opt_variant != 9;
     SlateArgs a;
-    a.pm = h->pm; a.dt = h->slate_dt; a.zero = h->slate_dt + (size_t)(rows - 1) * Kp;
-    a.U = h->U; a.user_base = h->user_base; a.nD = nD; a.utiles = a.dtiles = 0; a.K = K; a.Kp = Kp; a.err = h->err_dev;
-    h->last_kernel = mfma ? "m2d_score_slate_mfma" : "m2d_score_slate_generic";
+    bool mfma;
+    if ((rc = slate_prepare(h, slate, 0, nD, a, mfma, st)) != M2D_OK) return rc;
     if (out) {
         a.users = users; a.nU = nU; a.index_base = 0; a.out = out;
         return launch_scores(h, a, mfma, st);
@@ -273,4 +292,41 @@ int m2d_launch_slate(m2d_engine *h, const char *entry, const int32_t *users, int
             return rc;
     }
     return M2D_OK;
+}
+
+// m2d_topk_users_deep: dish ranges of W = min(I, P, 65536) dishes, user blocks of max(1, P / W) rows; per block
+// and range the range's vectors (the builder's d0 form), the score kernel into scratch, m2d_select_deep over the block's rows -- the
+// first range starts a row's list, the others merge into it where it stands in the outputs.
+int m2d_launch_deep_lists(m2d_engine *h, const int32_t *users, int64_t nU, int32_t k, const int64_t *excl_off, const int32_t *excl_ids,
+                          const int64_t *excl_end, int64_t index_base, float *out_scores, int32_t *out_ids, hipStream_t st)
+{
+    const int64_t P = h->opt_deep_chunk_pairs;
+    const int64_t W0 = h->I < P ? h->I : P, W = W0 < 65536 ? W0 : 65536;
+    const int64_t R0 = P / W > 1 ? P / W : 1, R = R0 < nU ? R0 : nU;
+    int rc;
+    if ((rc = m2d_grow(h, h->slate_scores, h->slate_scores_cap, (size_t)R * W, sizeof(float))) != M2D_OK) return rc;
+    for (int64_t u0 = 0; u0 < nU; u0 += R) {
+        const int64_t n = nU - u0 < R ? nU - u0 : R;
+        for (int64_t d0 = 0; d0 < h->I; d0 += W) {
+            const int64_t Wc = h->I - d0 > W ? W : h->I - d0;
+            SlateArgs a;
+            bool mfma;
+            if ((rc = slate_prepare(h, nullptr, (int32_t)d0, Wc, a, mfma, st)) != M2D_OK) return rc;
+            a.users = users + u0; a.nU = n; a.index_base = index_base + u0; a.out = h->slate_scores;
+            if ((rc = launch_scores(h, a, mfma, st)) != M2D_OK) return rc;
+            if ((rc = m2d_launch_select_deep(h, h->slate_scores, nullptr, 0, n, Wc, (int32_t)d0, k, d0 == 0 ? 1 : 0, out_scores + u0 * k,
+                                             out_ids + u0 * k, Wc, 1, st, excl_off ? excl_off + u0 : nullptr, excl_ids, excl_end)) != M2D_OK)
+                return rc;
+        }
+    }
+    return M2D_OK;
+}
+
+int m2d_launch_topk_users_deep(m2d_engine *h, const int32_t *users, int64_t nU, int32_t k, const int64_t *excl_off, const int32_t *excl_ids,
+                               float *out_scores, int32_t *out_ids, hipStream_t st)
+{
+    int rc;
+    if ((rc = m2d_deep_conditions(h, "m2d_topk_users_deep", st)) != M2D_OK) return rc;
+    if (excl_off && (rc = m2d_launch_check_exclusions(h, excl_off, excl_ids, nU, st)) != M2D_OK) return rc;
+    return m2d_launch_deep_lists(h, users, nU, k, excl_off, excl_ids, excl_off ? excl_off + nU : nullptr, 0, out_scores, out_ids, st);
 }

@@ -172,10 +172,6 @@ __global__ __launch_bounds__(1024) void m2d_topk_mlp_count(const float *scores, 
     }
 }
 
-// threads of a selection / count block: a wave for the reranker's short rows, sixteen for a catalogue-wide range (few rows then share
-// the device: a block of P / W rows)
-int select_threads(const int64_t W) { return W <= 256 ? 64 : W <= 16384 ? 256 : 1024; }
-
 }  // namespace
 
 int m2d_launch_topk_select(m2d_engine *h, const float *scores, const int32_t *ids, int64_t ids_stride, int64_t rows, int64_t W, int32_t d0,
@@ -263,6 +259,65 @@ int m2d_launch_topk_users_mlp(m2d_engine *h, const int32_t *users, int64_t nU, i
             if ((rc = m2d_launch_topk_select(h, scores, ids, Wc, rows, Wc, (int32_t)d0, k, d0 == 0 ? 1 : 0, out_scores + u0 * k, out_ids + u0 * k,
                                              two ? Wc : (int64_t)1, two ? (int64_t)1 : rows, stream, strike ? excl_off + u0 : nullptr, excl_ids,
                                              strike ? excl_off + nU : nullptr, two_x)) != M2D_OK)
+                return rc;
+        }
+    }
+    return M2D_OK;
+}
+
+// m2d_topk_users_mlp_deep: the loop above with m2d_select_deep for every k up to 1024.  Exact form: the same
+// chunk geometry, dish-major, a row's excluded dishes struck inside the selection.  Two-stage form: blocks of max(1, P / K1) users;
+// per block stage 1 is m2d_launch_deep_lists' K1 dishes (exclusions already left out; its conditions and the lists' check are
+// looked at once, in front of the loop), then the candidate generator, the head and the selection with HOLES.
+int m2d_launch_topk_users_mlp_deep(m2d_engine *h, const int32_t *users, int64_t nU, int32_t k, int32_t candidates, const int64_t *excl_off,
+                                   const int32_t *excl_ids, float *out_scores, int32_t *out_ids, hipStream_t stream)
+{
+    h->topk_mlp_launches = 0;
+    if (nU == 0) return M2D_OK;
+    const bool two = candidates > 0;
+    ChunkShape cs = chunk_shape(h, nU, h->I);
+    if (two) {                                                      // (K1 may exceed the smallest P: a block is whole candidate rows)
+        const int64_t R0 = h->opt_topk_mlp_chunk_pairs / candidates > 1 ? h->opt_topk_mlp_chunk_pairs / candidates : 1;
+        cs.W = candidates;
+        cs.R = R0 < nU ? R0 : nU;
+        cs.n = ((size_t)cs.R * cs.W + 3) & ~(size_t)3;
+    }
+    const int64_t W = cs.W, R = cs.R;
+    const size_t n = cs.n;
+    int rc;
+    if (two && (rc = m2d_deep_conditions(h, "m2d_topk_users_mlp_deep", stream)) != M2D_OK) return rc;
+    if ((rc = m2d_grow(h, h->topk_mlp_ids, h->topk_mlp_ids_cap, 2 * n, sizeof(int32_t))) != M2D_OK) return rc;
+    if ((rc = m2d_grow(h, h->topk_mlp_scores, h->topk_mlp_scores_cap, n, sizeof(float))) != M2D_OK) return rc;
+    if (two && (rc = m2d_grow(h, h->topk_mlp_cand, h->topk_mlp_cand_cap, n, sizeof(int32_t))) != M2D_OK) return rc;
+    int32_t *users_x = h->topk_mlp_ids, *items_x = users_x + n;
+    float *scores = h->topk_mlp_scores;
+    if (excl_off && (rc = m2d_launch_check_exclusions(h, excl_off, excl_ids, nU, stream)) != M2D_OK) return rc;
+    const int64_t *xend = excl_off ? excl_off + nU : nullptr;
+    for (int64_t u0 = 0; u0 < nU; u0 += R) {
+        const int64_t rows = nU - u0 < R ? nU - u0 : R;
+        const int64_t *xoff = excl_off ? excl_off + u0 : nullptr;
+        if (two) {
+            if ((rc = m2d_launch_deep_lists(h, users + u0, rows, candidates, xoff, excl_ids, xend, u0, scores, h->topk_mlp_cand, stream)) != M2D_OK)
+                return rc;
+            hipLaunchKernelGGL(m2d_topk_mlp_pairs_cand<true>, dim3(m2d_blocks_for(h, rows * W, 1024)), dim3(256), 0, stream, users + u0,
+                               h->topk_mlp_cand, rows, W, users_x, items_x);
+            M2D_HIP_TRY(h, hipGetLastError());
+            if ((rc = m2d_launch_score_pairs_mlp(h, users_x, items_x, rows * W, scores, stream)) != M2D_OK) return rc;
+            ++h->topk_mlp_launches;
+            if ((rc = m2d_launch_select_deep(h, scores, h->topk_mlp_cand, W, rows, W, 0, k, 1, out_scores + u0 * k, out_ids + u0 * k, W, 1, stream,
+                                             nullptr, nullptr, nullptr, true)) != M2D_OK)
+                return rc;
+            continue;
+        }
+        for (int64_t d0 = 0; d0 < h->I; d0 += W) {
+            const int64_t Wc = h->I - d0 > W ? W : h->I - d0;
+            hipLaunchKernelGGL(m2d_topk_mlp_pairs, dim3(m2d_blocks_for(h, rows * Wc, 1024)), dim3(256), 0, stream, users + u0, rows, Wc, (int32_t)d0,
+                               users_x, items_x);
+            M2D_HIP_TRY(h, hipGetLastError());
+            if ((rc = m2d_launch_score_pairs_mlp(h, users_x, items_x, rows * Wc, scores, stream)) != M2D_OK) return rc;
+            ++h->topk_mlp_launches;
+            if ((rc = m2d_launch_select_deep(h, scores, nullptr, 0, rows, Wc, (int32_t)d0, k, d0 == 0 ? 1 : 0, out_scores + u0 * k, out_ids + u0 * k, 1,
+                                             rows, stream, xoff, excl_ids, xend)) != M2D_OK)
                 return rc;
         }
     }

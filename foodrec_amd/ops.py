@@ -502,6 +502,42 @@ class ScoringEngine:
         self._topk_mlp_keep = (users, off, ids)          # stay alive until the queued kernels have read them
         return out_s, out_i
 
+    def _topk_deep(self, what: str, users: torch.Tensor, k: int, exclude, candidates: Optional[int]):
+        if users.dtype != torch.int32 or users.device != self.device:
+            raise TypeError("%s: users must be an int32 tensor on %s" % (what, self.device))
+        if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or not 1 <= int(k) <= 1024:
+            raise ValueError("%s: 1 <= k <= 1024, got %r" % (what, k))
+        users = users.contiguous().reshape(-1)
+        nU, k = users.numel(), int(k)
+        off = ids = None
+        if exclude is not None:
+            off, ids = exclusions_on_device(exclude, nU, self.device, what)
+        out_s = torch.empty((nU, k), dtype=torch.float32, device=self.device)
+        out_i = torch.empty((nU, k), dtype=torch.int32, device=self.device)
+        xo, xi = (off.data_ptr(), ids.data_ptr()) if off is not None else (None, None)
+        with torch.cuda.device(self.device):
+            if candidates is None:
+                rc = _native.lib().m2d_topk_users_deep(self._h, users.data_ptr(), nU, k, xo, xi, out_s.data_ptr(), out_i.data_ptr(), _stream_ptr())
+            else:
+                rc = _native.lib().m2d_topk_users_mlp_deep(self._h, users.data_ptr(), nU, k, int(candidates), xo, xi, out_s.data_ptr(),
+                                                           out_i.data_ptr(), _stream_ptr())
+        _native.raise_for(rc, self._h)
+        self._deep_keep = (users, off, ids)              # stay alive until the queued kernels have read them
+        return out_s, out_i
+
+    def topk_users_deep(self, users: torch.Tensor, k: int, exclude=None):
+        """EXTENSION (``m2d_topk_users_deep``, include/m2d.h): the first k of ``topk_users``' order over the
+        whole catalogue for 1 <= k <= min(1024, I), leaving out users[i]'s excluded dishes -- ``exclude`` in ``topk_users_excluding``'s
+        forms, None for none -> (scores f32[nU, k], dish ids i32[nU, k]).  A listed score is the word ``score_slate`` writes for that
+        (user, dish); rows end in id -1 / NaN when fewer than k dishes remain.  Does not synchronise."""
+        return self._topk_deep("topk_users_deep", users, k, exclude, None)
+
+    def topk_users_mlp_deep(self, users: torch.Tensor, k: int, exclude=None, candidates: int = 0):
+        """EXTENSION (``m2d_topk_users_mlp_deep``): ``topk_users_mlp_excluding`` for 1 <= k <= min(1024, I).
+        ``candidates`` = 0 scores every dish under the head; k <= K1 = ``candidates`` <= min(1024, I) reranks ``topk_users_deep``'s K1
+        dishes of each user and segment.  Does not synchronise."""
+        return self._topk_deep("topk_users_mlp_deep", users, k, exclude, candidates)
+
     def _slate_ids(self, users: torch.Tensor, slate: torch.Tensor, what: str):
         for t, name in ((users, "users"), (slate, "slate")):
             if not isinstance(t, torch.Tensor) or t.dtype != torch.int32 or t.device != self.device:
@@ -959,6 +995,41 @@ def topk_users_mlp_excluding_op(engine: int, users: torch.Tensor, k: int, candid
 def _(engine, users, k, candidates=0, excl_off=None, excl_ids=None):
     return (users.new_empty((users.numel(), k), dtype=torch.float32),
             users.new_empty((users.numel(), k), dtype=torch.int32))
+
+
+def _excl_pair(excl_off, excl_ids):
+    return None if excl_off is None else (excl_off, excl_ids if excl_ids is not None else excl_off.new_empty((0,), dtype=torch.int32))
+
+
+def _deep_fake(users, k):
+    return (users.new_empty((users.numel(), k), dtype=torch.float32),
+            users.new_empty((users.numel(), k), dtype=torch.int32))
+
+
+@torch.library.custom_op("m2d::topk_users_deep", mutates_args=(), device_types="cuda")
+def topk_users_deep_op(engine: int, users: torch.Tensor, k: int, excl_off: Optional[torch.Tensor] = None,
+                       excl_ids: Optional[torch.Tensor] = None) -> tuple[torch.Tensor, torch.Tensor]:
+    """``ScoringEngine.topk_users_deep``; `excl_off` / `excl_ids`: device tensors, ascending per segment, taken as they are."""
+    s, i = _engine(engine).topk_users_deep(users, k, _excl_pair(excl_off, excl_ids))
+    return s, i
+
+
+@topk_users_deep_op.register_fake
+def _(engine, users, k, excl_off=None, excl_ids=None):
+    return _deep_fake(users, k)
+
+
+@torch.library.custom_op("m2d::topk_users_mlp_deep", mutates_args=(), device_types="cuda")
+def topk_users_mlp_deep_op(engine: int, users: torch.Tensor, k: int, candidates: int = 0, excl_off: Optional[torch.Tensor] = None,
+                           excl_ids: Optional[torch.Tensor] = None) -> tuple[torch.Tensor, torch.Tensor]:
+    """``ScoringEngine.topk_users_mlp_deep``; the exclusions as above."""
+    s, i = _engine(engine).topk_users_mlp_deep(users, k, _excl_pair(excl_off, excl_ids), candidates)
+    return s, i
+
+
+@topk_users_mlp_deep_op.register_fake
+def _(engine, users, k, candidates=0, excl_off=None, excl_ids=None):
+    return _deep_fake(users, k)
 
 
 @torch.library.custom_op("m2d::catalogue_rank_mlp", mutates_args=(), device_types="cuda")

@@ -553,6 +553,29 @@ class Model:
         self.engine.check()
         return s.cpu().numpy(), i.cpu().numpy()
 
+    def topk_deep(self, users, k: int = 100, exclude=None, head: bool = False, candidates: int = 0):
+        """EXTENSION (DESIGN.md sections 4.11, 8.8): deep lists -- the k best dishes of every user over the whole catalogue for
+        1 <= k <= 1024, leaving out `exclude`'s dishes per user (a dict keyed by the user as given in `users`, or a list aligned
+        with `users`, as in `topk`; None excludes nothing).  The order is `topk`'s; a listed score is the word `score_slate` returns
+        for that (user, dish); rows end in id -1 / NaN when fewer than k dishes remain (``ScoringEngine.topk_users_deep``).
+        `head=True`: the lists under the MLP head -- `candidates` = 0 scores every dish under the head, k <= K1 = `candidates` <= 1024
+        reranks the K1 best of the lists above (``ScoringEngine.topk_users_mlp_deep``).  Returns (scores float32 [n, k], dish ids
+        int32 [n, k])."""
+        if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or not 1 <= int(k) <= 1024:
+            raise ValueError("topk_deep: 1 <= k <= 1024, got %r" % (k,))
+        if candidates and not head:
+            raise ValueError("topk_deep: candidates is the head's rerank width; it needs head=True")
+        if exclude is not None:
+            exclude = _exclusion_lists(exclude, users, "topk_deep")
+        u = _ids(users, "user")
+        ut = u.to(self.device, torch.int32) if isinstance(u, torch.Tensor) else torch.from_numpy(u).to(self.device)
+        if head:
+            s, i = self.engine.topk_users_mlp_deep(ut, int(k), exclude, int(candidates))
+        else:
+            s, i = self.engine.topk_users_deep(ut, int(k), exclude)
+        self.engine.check()
+        return s.cpu().numpy(), i.cpu().numpy()
+
     def set_ingredients(self, ingredient_table, offsets, ids, weights=None):
         """EXTENSION: multi-hot ingredient lists per dish (CSR) replacing the category sum of the high-level path."""
         self.engine.set_ingredients(ingredient_table, offsets, ids, weights)

@@ -393,6 +393,48 @@ int m2d_score_slate(m2d_engine *h, const int32_t *users, int64_t nU, const int32
 int m2d_topk_slate(m2d_engine *h, const int32_t *users, int64_t nU, const int32_t *slate, int64_t nD, int32_t k,
                    float *out_scores /* [nU, k] */, int32_t *out_ids /* [nU, k] */, void *stream);
 
+/* ---- build-defined extension, NO reference counterpart ----
+ * Deep retrieval lists: full-catalogue top-k for 1 <= k <= min(1024, I), with optional per-user exclusion lists, and the same under the
+ * MLP head with up to 1024 first-stage candidates.  Every other retrieval call stops at 64 entries; these two take the same order
+ * further (candidate generation for a reranker, HR@100 / recall@500, pagination).
+ *
+ * m2d_topk_users_deep.  users i32[nU], device memory, global ids (m2d_set_user_base is honoured, users may repeat).  excl_off i64[nU + 1]
+ * / excl_ids i32[excl_off[nU]], device memory, or excl_off NULL for none: user i's list leaves out excl_ids[excl_off[i] .. excl_off[i+1]),
+ * the conventions of m2d_catalogue_rank (offsets from 0 and non-decreasing, ids of a segment ascending, repeats allowed).  out_ids
+ * i32[nU, k] / out_scores f32[nU, k]: the first k of m2d_topk_users' order -- score descending, bit-equal scores and -0 / +0 to the lower
+ * dish id, NaN last in id order -- over the dishes not excluded; rows end in id -1 / NaN where fewer than k remain.  A listed score is
+ * the word m2d_score_slate writes for that (user, dish), bit for bit; an MLP head, if set, is ignored (as by m2d_topk_users).
+ * nU == 0 returns M2D_OK and launches nothing.  k < 1, k > min(1024, I), a null pointer, excl_off without excl_ids:
+ * M2D_ERR_INVALID_ARG.  No dish masks: M2D_ERR_NOT_CONFIGURED.  Refused with M2D_ERR_UNSUPPORTED, the condition named in
+ * m2d_last_error: the ingredient table set, a table value that is not finite (m2d_topk_slate's rule).
+ * Diagnostics.  A bad user id is latched as M2D_ERR_BAD_USER_ID with its index in `users`; an excluded id outside [0, I) as
+ * M2D_ERR_BAD_ITEM_ID, an id below its predecessor or an offset that is not 0 at [0] / below its predecessor as M2D_ERR_INVALID_ARG,
+ * each with the position m2d_topk_users_excluding reports; m2d_check reports them.  The rows of a call with a latched error are
+ * unspecified; no kernel reads out of bounds and the engine stays usable.
+ * How.  Dish ranges of W = min(I, P, 65536) dishes, user blocks of max(1, P / W) rows, P = option "deep_chunk_pairs": per block and
+ * range m2d_build_slate_vectors (its dish-range form), the slate score kernel into engine scratch, and m2d_select_deep -- a radix
+ * select on the order's 64-bit key, one workgroup per row, O(W) for any k -- which starts the row's list on the first range and merges
+ * into it on the others.  The lists do not depend on P.  Does not synchronise beyond what m2d_topk_slate does; allocates only on growth.
+ *
+ * m2d_topk_users_mlp_deep.  m2d_topk_users_mlp_excluding's scores (the pair's m2d_score_pairs_mlp word) and order, 1 <= k <= min(1024, I).
+ * candidates == 0: every dish not excluded is scored under the head (m2d_topk_users_mlp's loop and "topk_mlp_chunk_pairs" geometry,
+ * m2d_select_deep in place of its selection); works with the ingredient table set.  k <= candidates <= min(1024, I): per block of
+ * max(1, P / candidates) users, stage 1 is m2d_topk_users_deep's list of `candidates` dishes for the user and segment -- with its
+ * refusals, under this call's name --, stage 2 scores them under the head and lists the first k; a slot stage 1 left empty is dropped.
+ * Any other `candidates`: M2D_ERR_INVALID_ARG.  No head or no dish masks: M2D_ERR_NOT_CONFIGURED.  Diagnostics as above. */
+int m2d_topk_users_deep(m2d_engine *h, const int32_t *users, int64_t nU, int32_t k,
+                        const int64_t *excl_off /* [nU + 1] or NULL */, const int32_t *excl_ids,
+                        float *out_scores /* [nU, k] */, int32_t *out_ids /* [nU, k] */, void *stream);
+int m2d_topk_users_mlp_deep(m2d_engine *h, const int32_t *users, int64_t nU, int32_t k, int32_t candidates,
+                            const int64_t *excl_off /* [nU + 1] or NULL */, const int32_t *excl_ids,
+                            float *out_scores /* [nU, k] */, int32_t *out_ids /* [nU, k] */, void *stream);
+
+/* Diagnostic (scripts/deep_time.py): one selection launch over a resident row-major score block f32[rows, W], ids 0 .. W - 1, no
+ * exclusions, into out_scores / out_ids [rows, k] -- form 0: m2d_select_deep (k <= 1024), form 1: m2d_topk_mlp_select (k <= 64).
+ * Reads no table.  Bad arguments: M2D_ERR_INVALID_ARG. */
+int m2d_select_probe(m2d_engine *h, const float *scores /* device */, int64_t rows, int64_t W, int32_t k, int32_t form,
+                     float *out_scores, int32_t *out_ids, void *stream);
+
 /* ---- build-defined extension, NO reference counterpart ----
  * Market retrieval: from the ingredients seen at the market to the dishes that can be cooked from them -- the slate the calls above
  * were written for.  m2d_set_recipes makes every dish's ingredient list resident, m2d_cookable_dishes turns a market into the
@@ -653,7 +695,9 @@ int m2d_check(m2d_engine *h, void *stream, int64_t *bad_value, int64_t *bad_inde
  *                                        M2D_ERR_INVALID_ARG.  Same ids, same score bits.
  * slate_chunk_pairs  4194304  256 ... 2^24  m2d_topk_slate: pairs of score scratch one pass may hold (user blocks of max(1, P / nD) rows); other values
  *                                        are M2D_ERR_INVALID_ARG.  Same ids, same score bits.
- * variant          0        7 9 11 12 13 14 15 16, 100 + n
+ * deep_chunk_pairs   4194304  256 ... 2^24  m2d_topk_users_deep (and stage 1 of m2d_topk_users_mlp_deep): dish ranges of W = min(I, P, 65536) dishes, user
+ *                                        blocks of max(1, P / W) rows; other values are M2D_ERR_INVALID_ARG.  Same ids, same score bits.
+ * variant         0        7 9 11 12 13 14 15 16, 100 + n
  *                                        7 / 9: retrieval on the dense MFMA kernel / on the one-block-per-user kernel; 9 also forces the generic pair,
  *                                        head and slate kernels; 11 / 12: the pair kernel's throughput / latency form whatever the batch size; 13: tie
  *                                        repair's one-block-per-user tier from the third listed user on; 14: the nine-launch training step;
