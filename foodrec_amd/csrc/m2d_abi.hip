@@ -852,7 +852,7 @@ int m2d_topk_users_mlp(m2d_engine *h, const int32_t *users, int64_t nU, int32_t 
     if (!h->mlp_w1) return fail(h, M2D_ERR_NOT_CONFIGURED, "call m2d_set_mlp_head first");
     if (!h->dish_cats) return fail(h, M2D_ERR_NOT_CONFIGURED, "call m2d_set_dish_categories first");
     M2D_HIP_TRY(h, hipSetDevice(h->device));
-    return m2d_launch_topk_users_mlp(h, users, nU, k, candidates, out_scores, out_ids, (hipStream_t)stream);
+    return m2d_launch_topk_users_mlp(h, users, nU, k, candidates, nullptr, nullptr, out_scores, out_ids, /*deep=*/false, (hipStream_t)stream);
 }
 
 int m2d_topk_users_mlp_excluding(m2d_engine *h, const int32_t *users, int64_t nU, int32_t k, int32_t candidates, const int64_t *excl_off,
@@ -870,7 +870,7 @@ int m2d_topk_users_mlp_excluding(m2d_engine *h, const int32_t *users, int64_t nU
     if (!h->mlp_w1) return fail(h, M2D_ERR_NOT_CONFIGURED, "call m2d_set_mlp_head first");
     if (!h->dish_cats) return fail(h, M2D_ERR_NOT_CONFIGURED, "call m2d_set_dish_categories first");
     M2D_HIP_TRY(h, hipSetDevice(h->device));
-    return m2d_launch_topk_users_mlp(h, users, nU, k, candidates, out_scores, out_ids, (hipStream_t)stream, excl_off, excl_ids);
+    return m2d_launch_topk_users_mlp(h, users, nU, k, candidates, excl_off, excl_ids, out_scores, out_ids, /*deep=*/false, (hipStream_t)stream);
 }
 
 int m2d_topk_users_deep(m2d_engine *h, const int32_t *users, int64_t nU, int32_t k, const int64_t *excl_off, const int32_t *excl_ids,
@@ -899,7 +899,7 @@ int m2d_topk_users_mlp_deep(m2d_engine *h, const int32_t *users, int64_t nU, int
     if (!h->mlp_w1) return fail(h, M2D_ERR_NOT_CONFIGURED, "call m2d_set_mlp_head first");
     if (!h->dish_cats) return fail(h, M2D_ERR_NOT_CONFIGURED, "call m2d_set_dish_categories first");
     M2D_HIP_TRY(h, hipSetDevice(h->device));
-    return m2d_launch_topk_users_mlp_deep(h, users, nU, k, candidates, excl_off, excl_ids, out_scores, out_ids, (hipStream_t)stream);
+    return m2d_launch_topk_users_mlp(h, users, nU, k, candidates, excl_off, excl_ids, out_scores, out_ids, /*deep=*/true, (hipStream_t)stream);
 }
 
 int m2d_select_probe(m2d_engine *h, const float *scores, int64_t rows, int64_t W, int32_t k, int32_t form, float *out_scores,
@@ -910,8 +910,9 @@ int m2d_select_probe(m2d_engine *h, const float *scores, int64_t rows, int64_t W
         return fail(h, M2D_ERR_INVALID_ARG, "m2d_select_probe: need rows >= 1, 1 <= k <= min(W, 1024) (form 1: 64), form 0 / 1");
     if (!scores || !out_scores || !out_ids) return fail(h, M2D_ERR_INVALID_ARG, "m2d_select_probe: null buffer");
     M2D_HIP_TRY(h, hipSetDevice(h->device));
-    return (form ? m2d_launch_topk_select : m2d_launch_select_deep)(h, scores, nullptr, 0, rows, W, 0, k, 1, out_scores, out_ids, W, 1,
-                                                                    (hipStream_t)stream, nullptr, nullptr, nullptr, false);
+    SelectJob job = SelectJob::row_major(scores, rows, W, nullptr, 0);
+    job.k = k; job.out_scores = out_scores; job.out_ids = out_ids;
+    return m2d_launch_select(h, job, /*deep=*/form == 0, (hipStream_t)stream);
 }
 
 int m2d_catalogue_rank_mlp(m2d_engine *h, const int32_t *users, const int32_t *items, int64_t n, const int64_t *excl_off,

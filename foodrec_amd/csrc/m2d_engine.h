@@ -456,30 +456,66 @@ void m2d_mlp_free_derived(m2d_engine *h, bool grouping);
 int m2d_launch_rank_candidates(m2d_engine *h, const int32_t *users, const int32_t *items,
                                const int32_t *lens, int64_t nseg, int32_t L, int32_t k, float *out_scores,
                                int32_t *out_items, int32_t *out_flags, hipStream_t stream, bool head = false);
-// excl_off: the exclusion forms (m2d_topk_users_mlp_excluding) -- the exact mode strikes each row's ids inside the selection, the
-// two-stage mode takes its candidates from m2d_topk_users_excluding
-int m2d_launch_topk_users_mlp(m2d_engine *h, const int32_t *users, int64_t nU, int32_t k, int32_t candidates, float *out_scores,
-                              int32_t *out_ids, hipStream_t stream, const int64_t *excl_off = nullptr, const int32_t *excl_ids = nullptr);
+// m2d_topk_mlp.hip, the chunked head loop of m2d_topk_users_mlp (deep = false: m2d_topk_mlp_select, k <= 64) and m2d_topk_users_mlp_deep
+// (deep = true: m2d_select_deep, k <= 1024).  excl_off: the exclusion forms -- the exact mode strikes each row's ids inside the selection;
+// the two-stage mode takes its candidates from m2d_topk_users_excluding, once per call, or under `deep` from m2d_launch_deep_lists per
+// user block
+int m2d_launch_topk_users_mlp(m2d_engine *h, const int32_t *users, int64_t nU, int32_t k, int32_t candidates, const int64_t *excl_off,
+                              const int32_t *excl_ids, float *out_scores, int32_t *out_ids, bool deep, hipStream_t stream);
 int m2d_launch_catalogue_rank_mlp(m2d_engine *h, const int32_t *users, const int32_t *items, int64_t n, const int64_t *excl_off,
                                   const int32_t *excl_ids, int32_t *out_rank, float *out_scores, hipStream_t stream);
 int m2d_launch_topk_users(m2d_engine *h, const int32_t *users, int64_t nU, int32_t k, float *out_scores,
                           int32_t *out_ids, hipStream_t stream);
-// m2d_topk_mlp.hip: m2d_topk_mlp_select over `rows` score rows of W columns (column e of row r at scores[r * rs + e * es]); ids: row r's
-// at ids + r * ids_stride (0: one id row shared by all), or d0 + e when null; first = 0 merges into the lists the outputs hold;
-// xoff (dish-major form, ids == null): row r leaves out the ascending dish ids xids[xoff[r] .. xoff[r + 1]), *xend = the array's length;
-// holes: an id below 0 in `ids` is no entry whatever its score (the candidates of the exclusion retrieval)
-int m2d_launch_topk_select(m2d_engine *h, const float *scores, const int32_t *ids, int64_t ids_stride, int64_t rows, int64_t W, int32_t d0,
-                           int32_t k, int32_t first, float *out_scores, int32_t *out_ids, int64_t rs, int64_t es, hipStream_t stream,
-                           const int64_t *xoff = nullptr, const int32_t *xids = nullptr, const int64_t *xend = nullptr,
-                           bool holes = false);
+// One selection request (m2d_select.hip): the k best of each of `rows` score rows of W columns, in tkm_key's order, as (score, id) lists
+// in out_scores / out_ids [rows, k].  It is the kernels' one argument, by value.
+struct SelectJob {
+    const float *scores;                // column e of row r at scores[r * rs + e * es]
+    int64_t rs, es;
+    const int32_t *ids;                 // row r's ids at ids + r * ids_stride (0: one id row shared by all); null: column e is dish d0 + e
+    int64_t ids_stride;
+    int64_t rows, W;
+    int32_t d0, k;
+    int32_t first;                      // 1: the lists start with this block; 0: the k entries the outputs hold take part as k more candidates
+    float *out_scores;
+    int32_t *out_ids;
+    // row r leaves out the ascending dish ids xids[xoff[r] .. xoff[r + 1]), *xend = the array's length (ids == null only; null: none)
+    const int64_t *xoff;
+    const int32_t *xids;
+    const int64_t *xend;
+    bool holes;                         // an id below 0 in `ids` is no entry whatever its score (candidates of a retrieval with exclusions)
+
+    // the two layouts in use; k, the outputs and the exclusions are the caller's to name
+    // dish-major range, as the head's pair generator leaves it: the `rows` scores of dish d0 + e are neighbours
+    static SelectJob dish_major(const float *scores, const int64_t rows, const int64_t W, const int32_t d0)
+    {
+        SelectJob j{};
+        j.scores = scores; j.rs = 1; j.es = rows;
+        j.rows = rows; j.W = W; j.d0 = d0; j.first = d0 == 0 ? 1 : 0;
+        return j;
+    }
+    // row-major [rows, W] with an id table (ids_stride W or 0), or without one: the dish range d0 + e
+    static SelectJob row_major(const float *scores, const int64_t rows, const int64_t W, const int32_t *ids, const int64_t ids_stride,
+                               const int32_t d0 = 0)
+    {
+        SelectJob j{};
+        j.scores = scores; j.rs = W; j.es = 1;
+        j.ids = ids; j.ids_stride = ids_stride;
+        j.rows = rows; j.W = W; j.d0 = d0; j.first = d0 == 0 ? 1 : 0;
+        return j;
+    }
+};
+// m2d_select.hip: the one selection launcher.  deep = false: m2d_topk_mlp_select, a sorted list across a wave's lanes (k <= 64);
+// deep = true: m2d_select_deep, a radix select on the key (1 <= k <= 1024).  Which one is the caller's choice.
+int m2d_launch_select(m2d_engine *h, const SelectJob &job, bool deep, hipStream_t stream);
 // threads of a selection / count block: a wave for the reranker's short rows, sixteen for a catalogue-wide range (few rows then share
 // the device: a block of P / W rows)
 static inline int select_threads(const int64_t W) { return W <= 256 ? 64 : W <= 16384 ? 256 : 1024; }
-// m2d_select_deep.hip: the same contract for 1 <= k <= 1024 -- m2d_select_deep, a radix select on the key
-int m2d_launch_select_deep(m2d_engine *h, const float *scores, const int32_t *ids, int64_t ids_stride, int64_t rows, int64_t W, int32_t d0,
-                           int32_t k, int32_t first, float *out_scores, int32_t *out_ids, int64_t rs, int64_t es, hipStream_t stream,
-                           const int64_t *xoff = nullptr, const int32_t *xids = nullptr, const int64_t *xend = nullptr,
-                           bool holes = false);
+// the block rule of every call that scores blocks of rows into P pairs of scratch, W columns a row: max(1, P / W) rows, no more than n
+static inline int64_t m2d_block_rows(const int64_t P, const int64_t W, const int64_t n)
+{
+    const int64_t R0 = P / W > 1 ? P / W : 1;
+    return R0 < n ? R0 : n;
+}
 // m2d_slate.hip, the deep catalogue lists (m2d_topk_users_deep).  m2d_deep_conditions: the slate launcher's table conditions without its
 // head refusal, under the name `entry`.  m2d_launch_deep_lists: the blocks and ranges of `nU` users whose conditions and exclusion
 // lists the caller has checked -- excl_off: these users' offsets (null: none), excl_end: where the array's length stands,
@@ -489,9 +525,6 @@ int m2d_launch_deep_lists(m2d_engine *h, const int32_t *users, int64_t nU, int32
                           const int64_t *excl_end, int64_t index_base, float *out_scores, int32_t *out_ids, hipStream_t stream);
 int m2d_launch_topk_users_deep(m2d_engine *h, const int32_t *users, int64_t nU, int32_t k, const int64_t *excl_off, const int32_t *excl_ids,
                                float *out_scores, int32_t *out_ids, hipStream_t stream);
-// m2d_topk_mlp.hip: m2d_launch_topk_users_mlp's loop with m2d_select_deep; candidates > 0: stage 1 is m2d_launch_deep_lists per user block
-int m2d_launch_topk_users_mlp_deep(m2d_engine *h, const int32_t *users, int64_t nU, int32_t k, int32_t candidates, const int64_t *excl_off,
-                                   const int32_t *excl_ids, float *out_scores, int32_t *out_ids, hipStream_t stream);
 // m2d_slate.hip: out == null: the scores of user blocks go to scratch and the lists of k to out_scores / out_ids
 int m2d_launch_slate(m2d_engine *h, const char *entry, const int32_t *users, int64_t nU, const int32_t *slate, int64_t nD, int32_t k,
                      float *out, float *out_scores, int32_t *out_ids, hipStream_t stream);

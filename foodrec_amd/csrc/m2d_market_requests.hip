@@ -335,9 +335,11 @@ int m2d_launch_topk_markets(m2d_engine *h, const int32_t *users, int64_t nQ, con
     } else if (lds) hipLaunchKernelGGL(m2d_markets_topk<true>, dim3((unsigned)(nQ * S)), dim3(MQ_WAVES * 64), 0, st, a);
     else hipLaunchKernelGGL(m2d_markets_topk<false>, dim3((unsigned)(nQ * S)), dim3(MQ_WAVES * 64), 0, st, a);
     M2D_HIP_TRY(h, hipGetLastError());
-    if (S > 1 && (rc = m2d_launch_topk_select(h, reinterpret_cast<const float *>(a.part_scores), a.part_ids, S * k, nQ, S * k, 0, k, 1,
-                                              out_scores, out_ids, S * k, 1, st)) != M2D_OK)
-        return rc;
+    if (S > 1) {                                             // the shares' partial lists, [nQ, S k] words and ids, become the rows
+        SelectJob job = SelectJob::row_major(reinterpret_cast<const float *>(a.part_scores), nQ, S * k, a.part_ids, S * k);
+        job.k = k; job.out_scores = out_scores; job.out_ids = out_ids;
+        if ((rc = m2d_launch_select(h, job, /*deep=*/false, st)) != M2D_OK) return rc;
+    }
     if (out_missing && max_missing > 0) {                    // the rows are final; the bitmaps in markets_buf have not moved (one growth, above)
         if (lds) hipLaunchKernelGGL(m2d_markets_missing<true>, dim3((unsigned)nQ), dim3(MQ_WAVES * 64), 0, st, a, out_missing);
         else hipLaunchKernelGGL(m2d_markets_missing<false>, dim3((unsigned)nQ), dim3(MQ_WAVES * 64), 0, st, a, out_missing);

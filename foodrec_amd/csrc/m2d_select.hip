@@ -1,29 +1,96 @@
-// Deep selection: m2d_topk_mlp_select's contract for 1 <= k <= 1024, O(W) work per row for any k.
-// One workgroup per score row -- column e at scores[row * rs + e * es], its id ids[row * ids_stride + e] or d0 + e when `ids` is null --
-// merged into the row's list of k (score, id) in out_scores / out_ids (`first`: the list starts with this range, otherwise its k
-// entries take part as k more candidates).  The order is tkm_key's (m2d_engine.h); EXCL / HOLES as in m2d_topk_mlp_select: both make
-// a candidate TKM_NONE, which takes part in nothing below.
-//
-// A radix select on the 64-bit key.  The list L (np2(k) keys of 8 B and score words of 4 B in LDS) starts as the running list, or as
-// TKM_NONE throughout.  A digit pass histograms the next 11 bits (the last pass: 9) of every key that matches the prefix found so
-// far -- the row, read again from L2, and L -- into 2 048 LDS bins; a wave adds once per distinct digit for the first four digits
-// of a slice (ballot, one add of the popcount), so a row of equal scores costs one add per wave and slice.  A block-wide scan of
-// the bins finds the digit of the k-th key, the count in front of it (`less`) and the keys that share it (`m`).  The passes end
-// when less + m == k (everything that shares the prefix is listed: the usual exit is m == 1), when all 64 bits are fixed (only equal
-// keys are left), or after the first pass when the row holds no more than k real keys (all are listed).  The gather then works on L
-// IN PLACE: entries of L that stay keep their slot, the slots of the others go to a free list (in the bins' space), the row's
-// listed keys take free slots in arrival order from an LDS counter, what is left of the free list becomes TKM_NONE.  A bitonic sort
-// of L on the key, and the row is written once: the result is a function of the key set alone.
-// LDS: 8 KiB of bins + 12 B x np2(k) + 128 B: 20.1 KiB at k = 1 024.  No global atomics, no block waits for another.
-#include "m2d_exclusions.h"
+// Selection: the k best of every row of a score block, as (score, id) lists in tkm_key's order (m2d_engine.h).  One request record
+// (SelectJob, m2d_engine.h), one row walk (select_walk, m2d_select.h), two kernels and the one launcher in front of them:
+//   m2d_topk_mlp_select   k <= 64: a sorted list across a wave's lanes, an insertion per candidate that passes
+//   m2d_select_deep       1 <= k <= 1024: a radix select on the key, O(W) work per row for any k
+// Both: one workgroup per score row -- column e at scores[row * rs + e * es], its id ids[row * ids_stride + e] or d0 + e when `ids` is
+// null -- merged into the row's list of k (score, id) in out_scores / out_ids (`first`: the list starts with this block, otherwise its k
+// entries take part as k more candidates).  EXCL (ids == null only): row r leaves out xids[xoff[r] .. xoff[r + 1]), ascending dish ids,
+// the array's length at *xend.  HOLES (the candidate form behind a retrieval with exclusions): an id below 0 in `ids` is no entry,
+// whatever its score.  Both make a candidate TKM_NONE, which takes part in nothing.  No global atomics, no block waits for another; the
+// score written is the word that was read (a NaN's payload, a -0).
+#include "m2d_select.h"
 
 namespace {
 
+// ---- the list across lanes ------------------------------------------------------------------------------------------------------
+// Every wave keeps the k best of the 64-wide slices it reads as a sorted list ACROSS its lanes (lane j: the j-th best, k <= 64
+// is why one wave holds a whole list): a slice is compared with lane k - 1's key in one ballot, and the few candidates that
+// pass are inserted one by one -- a ballot for the position, a one-lane shift for the tail.  After the first slices about
+// k ln(W / k) candidates pass per wave, the rest costs a load, a compare and a ballot per 64 scores.  The waves' lists and the
+// running list meet in LDS ((waves + 1) k keys of 8 B and score words of 4 B), where every entry counts the entries in front of
+// it and the first k write themselves out.  <false, false> is the kernel as it stood before exclusions.
+template <bool EXCL, bool HOLES>
+__global__ __launch_bounds__(1024) void m2d_topk_mlp_select(const SelectJob job)
+{
+    extern __shared__ __align__(16) unsigned char smem[];
+    const int nw = blockDim.x >> 6, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
+    const int64_t row = blockIdx.x;
+    const int k = job.k;
+    float *out_scores = job.out_scores;
+    int32_t *out_ids = job.out_ids;
+    uint64_t *mk = reinterpret_cast<uint64_t *>(smem);                          // [(nw + 1) k]
+    uint32_t *ms = reinterpret_cast<uint32_t *>(mk + (size_t)(nw + 1) * k);     // [(nw + 1) k]
+
+    uint64_t lk = TKM_NONE, thr = TKM_NONE;      // this lane's list entry; lane k - 1's: what a candidate has to beat
+    uint32_t ls = 0x7FC00000u;
+    select_walk<EXCL, HOLES>(job, row, wave, nw, lane, [&](const uint64_t key, const uint32_t word) {
+        unsigned long long m = __ballot(key < thr);
+        while (m) {                              // wave-uniform: m, c and thr are the same in every lane
+            const int src = __ffsll(m) - 1;
+            m &= m - 1;
+            const uint64_t c = __shfl(key, src, 64);
+            if (c >= thr) continue;              // the list moved on since the ballot
+            const uint32_t cb = __shfl(word, src, 64);
+            const int pos = __popcll(__ballot(lk < c));                        // sorted: the lanes in front of c
+            const uint64_t upk = __shfl_up(lk, 1, 64);
+            const uint32_t ups = __shfl_up(ls, 1, 64);
+            lk = lane == pos ? c : lane > pos ? upk : lk;                       // (selects: as if / else if the compiler branches here,
+            ls = lane == pos ? cb : lane > pos ? ups : ls;                      //  now that the list is reached through the walk's body)
+            thr = __shfl(lk, k - 1, 64);
+        }
+    });
+    if (lane < k) {
+        mk[wave * k + lane] = lk;
+        ms[wave * k + lane] = ls;
+    }
+    if (!job.first && (int)threadIdx.x < k) {
+        const float s = out_scores[row * k + threadIdx.x];
+        mk[nw * k + threadIdx.x] = tkm_key(s, out_ids[row * k + threadIdx.x]);
+        ms[nw * k + threadIdx.x] = __float_as_uint(s);
+    }
+    __syncthreads();                             // the running list has been read: from here on it is written
+    const int M = (nw + (job.first ? 0 : 1)) * k;
+    for (int i = threadIdx.x; i < M; i += blockDim.x) {
+        const uint64_t ki = mk[i];
+        int rank = 0;
+        for (int j = 0; j < M; ++j) {            // every lane reads the same word: a broadcast
+            const uint64_t kj = mk[j];
+            rank += (kj < ki || (kj == ki && j < i)) ? 1 : 0;
+        }
+        if (rank < k) {
+            out_scores[row * k + rank] = __uint_as_float(ki == TKM_NONE ? 0x7FC00000u : ms[i]);
+            out_ids[row * k + rank] = ki == TKM_NONE ? -1 : (int32_t)(uint32_t)(ki & 0xFFFFFFFFu);
+        }
+    }
+}
+
+// ---- the radix select -----------------------------------------------------------------------------------------------------------
+// The list L (np2(k) keys of 8 B and score words of 4 B in LDS) starts as the running list, or as TKM_NONE throughout.  A digit pass
+// histograms the next 11 bits (the last pass: 9) of every key that matches the prefix found so far -- the row, read again from L2,
+// and L -- into 2 048 LDS bins; a wave adds once per distinct digit for the first four digits of a slice (ballot, one add of the
+// popcount), so a row of equal scores costs one add per wave and slice.  A block-wide scan of the bins finds the digit of the k-th
+// key, the count in front of it (`less`) and the keys that share it (`m`).  The passes end when less + m == k (everything that
+// shares the prefix is listed: the usual exit is m == 1), when all 64 bits are fixed (only equal keys are left), or after the first
+// pass when the row holds no more than k real keys (all are listed).  The gather then works on L IN PLACE: entries of L that stay
+// keep their slot, the slots of the others go to a free list (in the bins' space), the row's listed keys take free slots in arrival
+// order from an LDS counter, what is left of the free list becomes TKM_NONE.  A bitonic sort of L on the key, and the row is written
+// once: the result is a function of the key set alone.
+// LDS: 8 KiB of bins + 12 B x np2(k) + 128 B: 20.1 KiB at k = 1 024.
 constexpr int SD_BITS = 11, SD_BINS = 1 << SD_BITS;
 constexpr int SD_PEEL = 4;                       // distinct digits of a slice a wave adds once each; the lanes left add for themselves
 enum { SD_WSUM = 0, SD_BIN = 16, SD_BEFORE, SD_COUNT, SD_TAKEN, SD_FREE, SD_EQ, SD_MISC = 32 };
 
-__device__ __forceinline__ int sd_np2(const int k)
+__host__ __device__ __forceinline__ int sd_np2(const int k)
 {
     int n = 1;
     while (n < k) n <<= 1;
@@ -61,16 +128,16 @@ struct SdCut {
 };
 
 template <bool EXCL, bool HOLES>
-__global__ __launch_bounds__(1024) void m2d_select_deep(const float *scores, const int32_t *ids, int64_t W, int32_t d0, int32_t k,
-                                                        int32_t first, float *out_scores, int32_t *out_ids, int64_t rs, int64_t es,
-                                                        int64_t ids_stride, const int64_t *xoff, const int32_t *xids, const int64_t *xend)
+__global__ __launch_bounds__(1024) void m2d_select_deep(const SelectJob job)
 {
     extern __shared__ __align__(16) unsigned char smem[];
     const int T = blockDim.x, nw = T >> 6, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
     const int tid = threadIdx.x;
     const int64_t row = blockIdx.x;
-    const float *sc = scores + row * rs;
-    const int32_t *idr = ids ? ids + row * ids_stride : nullptr;
+    const int k = job.k;
+    const int32_t first = job.first;
+    float *out_scores = job.out_scores;
+    int32_t *out_ids = job.out_ids;
     const int n2 = sd_np2(k);
     uint64_t *lk = reinterpret_cast<uint64_t *>(smem);                  // [n2]
     uint32_t *ls = reinterpret_cast<uint32_t *>(lk + n2);               // [n2]
@@ -90,32 +157,6 @@ __global__ __launch_bounds__(1024) void m2d_select_deep(const float *scores, con
         ls[i] = w;
     }
 
-    // one walk over the row in the selection's steps: body(key, score word) for every column, TKM_NONE where there is no entry
-    auto walk = [&](auto &&body) {
-        ExclCursor xc;
-        if (EXCL) xc.open(xoff, xids, xend, row);    // (a bad segment is the call's check to report)
-        for (int64_t base = (int64_t)wave * 256; base < W; base += (int64_t)nw * 256) {
-            uint64_t ck[4];
-            uint32_t cs[4];
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {            // four slices in flight
-                const int64_t e = base + q * 64 + lane;
-                ck[q] = TKM_NONE;
-                cs[q] = 0u;
-                if (e < W) {
-                    const float s = sc[e * es];
-                    cs[q] = __float_as_uint(s);
-                    const int32_t id = idr ? idr[e] : d0 + (int32_t)e;
-                    ck[q] = tkm_key(s, id);
-                    if (HOLES) ck[q] |= (uint64_t)(int64_t)(id >> 31);          // an id below 0: all ones, TKM_NONE (no branch)
-                }
-            }
-            if (EXCL) xc.strike(xids, (int64_t)d0 + base, lane, ck, TKM_NONE);
-#pragma unroll
-            for (int q = 0; q < 4; ++q) body(ck[q], cs[q]);
-        }
-    };
-
     // ---- the digit passes ----
     SdCut cut;
     cut.prefix = 0; cut.bits = 0; cut.need_eq = 0;
@@ -130,7 +171,7 @@ __global__ __launch_bounds__(1024) void m2d_select_deep(const float *scores, con
             const bool on = key != TKM_NONE && (cut.bits == 0 || (key >> (64 - cut.bits)) == cut.prefix);
             sd_hist_add(hist, on, (uint32_t)(key >> sh) & dmask, lane);
         };
-        walk(add);
+        select_walk<EXCL, HOLES>(job, row, wave, nw, lane, add);
         if (!first)
             for (int i0 = wave * 64; i0 < n2; i0 += T) add(i0 + lane < n2 ? lk[i0 + lane] : TKM_NONE, 0u);
         __syncthreads();
@@ -185,7 +226,7 @@ __global__ __launch_bounds__(1024) void m2d_select_deep(const float *scores, con
         if (!listed(lk[i])) freel[atomicAdd(&misc[SD_FREE], 1u)] = (uint32_t)i;
     __syncthreads();
     const uint32_t nfree = misc[SD_FREE];
-    walk([&](const uint64_t key, const uint32_t word) {
+    select_walk<EXCL, HOLES>(job, row, wave, nw, lane, [&](const uint64_t key, const uint32_t word) {
         const bool take = listed(key);
         const unsigned long long mk = __ballot(take);
         if (mk) {                                    // wave-uniform: one add per slice
@@ -232,20 +273,20 @@ __global__ __launch_bounds__(1024) void m2d_select_deep(const float *scores, con
 
 }  // namespace
 
-int m2d_launch_select_deep(m2d_engine *h, const float *scores, const int32_t *ids, int64_t ids_stride, int64_t rows, int64_t W, int32_t d0,
-                           int32_t k, int32_t first, float *out_scores, int32_t *out_ids, int64_t rs, int64_t es, hipStream_t stream,
-                           const int64_t *xoff, const int32_t *xids, const int64_t *xend, bool holes)
+int m2d_launch_select(m2d_engine *h, const SelectJob &job, const bool deep, hipStream_t stream)
 {
-    const int threads = select_threads(W);
-    int n2 = 1;
-    while (n2 < k) n2 <<= 1;
-    const size_t lds = (size_t)n2 * (sizeof(uint64_t) + sizeof(uint32_t)) + (size_t)(SD_BINS + SD_MISC) * sizeof(uint32_t);
+    const int threads = select_threads(job.W);
+    const size_t entry = sizeof(uint64_t) + sizeof(uint32_t);        // a list entry in LDS: key, score word
+    const size_t lds = deep ? (size_t)sd_np2(job.k) * entry + (size_t)(SD_BINS + SD_MISC) * sizeof(uint32_t)
+                            : (size_t)(threads / 64 + 1) * job.k * entry;
     const auto launch = [&](auto kernel) -> int {
         M2D_HIP_TRY(h, m2d_lds_limit((const void *)kernel, (int)lds));
-        hipLaunchKernelGGL(kernel, dim3((unsigned)rows), dim3(threads), lds, stream, scores, ids, W, d0, k, first, out_scores, out_ids, rs, es,
-                           ids_stride, xoff, xids, xend);
+        hipLaunchKernelGGL(kernel, dim3((unsigned)job.rows), dim3(threads), lds, stream, job);
         M2D_HIP_TRY(h, hipGetLastError());
         return M2D_OK;
     };
-    return xoff ? launch(m2d_select_deep<true, false>) : holes ? launch(m2d_select_deep<false, true>) : launch(m2d_select_deep<false, false>);
+    const auto form = [&](auto list, auto radix) { return deep ? launch(radix) : launch(list); };
+    return job.xoff  ? form(m2d_topk_mlp_select<true, false>, m2d_select_deep<true, false>)
+         : job.holes ? form(m2d_topk_mlp_select<false, true>, m2d_select_deep<false, true>)
+                     : form(m2d_topk_mlp_select<false, false>, m2d_select_deep<false, false>);
 }

@@ -281,15 +281,15 @@ int m2d_launch_slate(m2d_engine *h, const char *entry, const int32_t *users, int
         return launch_scores(h, a, mfma, st);
     }
     // m2d_topk_slate: user blocks of max(1, P / nD) rows are scored into scratch and selected from there
-    const int64_t P = h->opt_slate_chunk_pairs;
-    const int64_t R0 = P / nD > 1 ? P / nD : 1, R = R0 < nU ? R0 : nU;
+    const int64_t R = m2d_block_rows(h->opt_slate_chunk_pairs, nD, nU);
     if ((rc = m2d_grow(h, h->slate_scores, h->slate_scores_cap, (size_t)R * nD, sizeof(float))) != M2D_OK) return rc;
     for (int64_t u0 = 0; u0 < nU; u0 += R) {
         const int64_t n = nU - u0 < R ? nU - u0 : R;
         a.users = users + u0; a.nU = n; a.index_base = u0; a.out = h->slate_scores;
         if ((rc = launch_scores(h, a, mfma, st)) != M2D_OK) return rc;
-        if ((rc = m2d_launch_topk_select(h, h->slate_scores, slate, 0, n, nD, 0, k, 1, out_scores + u0 * k, out_ids + u0 * k, nD, 1, st)) != M2D_OK)
-            return rc;
+        SelectJob job = SelectJob::row_major(h->slate_scores, n, nD, slate, 0);      // one id row for all: the slate
+        job.k = k; job.out_scores = out_scores + u0 * k; job.out_ids = out_ids + u0 * k;
+        if ((rc = m2d_launch_select(h, job, /*deep=*/false, st)) != M2D_OK) return rc;
     }
     return M2D_OK;
 }
@@ -302,7 +302,7 @@ int m2d_launch_deep_lists(m2d_engine *h, const int32_t *users, int64_t nU, int32
 {
     const int64_t P = h->opt_deep_chunk_pairs;
     const int64_t W0 = h->I < P ? h->I : P, W = W0 < 65536 ? W0 : 65536;
-    const int64_t R0 = P / W > 1 ? P / W : 1, R = R0 < nU ? R0 : nU;
+    const int64_t R = m2d_block_rows(P, W, nU);
     int rc;
     if ((rc = m2d_grow(h, h->slate_scores, h->slate_scores_cap, (size_t)R * W, sizeof(float))) != M2D_OK) return rc;
     for (int64_t u0 = 0; u0 < nU; u0 += R) {
@@ -314,9 +314,10 @@ int m2d_launch_deep_lists(m2d_engine *h, const int32_t *users, int64_t nU, int32
             if ((rc = slate_prepare(h, nullptr, (int32_t)d0, Wc, a, mfma, st)) != M2D_OK) return rc;
             a.users = users + u0; a.nU = n; a.index_base = index_base + u0; a.out = h->slate_scores;
             if ((rc = launch_scores(h, a, mfma, st)) != M2D_OK) return rc;
-            if ((rc = m2d_launch_select_deep(h, h->slate_scores, nullptr, 0, n, Wc, (int32_t)d0, k, d0 == 0 ? 1 : 0, out_scores + u0 * k,
-                                             out_ids + u0 * k, Wc, 1, st, excl_off ? excl_off + u0 : nullptr, excl_ids, excl_end)) != M2D_OK)
-                return rc;
+            SelectJob job = SelectJob::row_major(h->slate_scores, n, Wc, nullptr, 0, (int32_t)d0);
+            job.k = k; job.out_scores = out_scores + u0 * k; job.out_ids = out_ids + u0 * k;
+            job.xoff = excl_off ? excl_off + u0 : nullptr; job.xids = excl_ids; job.xend = excl_end;
+            if ((rc = m2d_launch_select(h, job, /*deep=*/true, st)) != M2D_OK) return rc;
         }
     }
     return M2D_OK;

@@ -2,7 +2,7 @@
 sections 4.11 and 8.8).
 
 Every comparison of the two files is ids as integers and scores as 32-bit words: the order is restated here as the 64-bit key of
-m2d_engine.h (tkm_key), the selection as the radix select of m2d_select_deep.hip (digit passes, early exit, gather, fill) and the
+m2d_engine.h (tkm_key), the selection as the radix select of m2d_select.hip (digit passes, early exit, gather, fill) and the
 launcher as its walk over dish ranges with a running list.  Nothing here imports the engine.  Recipes are computed once and shared
 (lru_cache); callers do not write into them."""
 import functools
@@ -15,7 +15,7 @@ from helpers import mlp_head
 
 NONE = np.uint64(0xFFFFFFFFFFFFFFFF)        # m2d_engine.h: TKM_NONE
 NAN_WORD = 0x7FC00000                        # the score word of an empty slot
-BITS, BINS = 11, 2048                        # m2d_select_deep.hip: SD_BITS, SD_BINS
+BITS, BINS = 11, 2048                        # m2d_select.hip: SD_BITS, SD_BINS
 K_MAX = 1024
 DEFAULT_P = 1 << 22
 KS = (1, 63, 64, 65, 255, 256, 257, 1023, 1024)

@@ -32,10 +32,10 @@ def test_symbols_are_declared_in_the_header_and_the_ctypes_table():
     assert _native.SIGNATURES["m2d_topk_users_deep"][1] == [vp, vp, i64, i32, vp, vp, vp, vp, vp]
     assert _native.SIGNATURES["m2d_topk_users_mlp_deep"][1] == [vp, vp, i64, i32, i32, vp, vp, vp, vp, vp]
     assert _native.ABI_VERSION == 2
-    assert "m2d_select_deep.hip" in _read("foodrec_amd", "csrc", "Makefile")
-    src = _read("foodrec_amd", "csrc", "m2d_select_deep.hip")
+    assert "m2d_select.hip" in _read("foodrec_amd", "csrc", "Makefile")
+    src = _read("foodrec_amd", "csrc", "m2d_select.hip")
     assert "SD_BITS = %d" % dc.BITS in src and dc.BINS == 1 << dc.BITS
-    assert "int m2d_launch_select_deep(" in _read("foodrec_amd", "csrc", "m2d_engine.h")
+    assert "int m2d_launch_select(" in _read("foodrec_amd", "csrc", "m2d_engine.h") and "int m2d_launch_select(" in src
 
 
 def test_option_bounds_as_the_source_states_them():
@@ -48,7 +48,8 @@ def test_option_bounds_as_the_source_states_them():
     assert "int64_t opt_deep_chunk_pairs = 1 << 22;" in eng and dc.DEFAULT_P == 1 << 22
     assert "deep_chunk_pairs" in _read("include", "m2d.h") and "deep_chunk_pairs" in _read("README.md")
     slate = _read("foodrec_amd", "csrc", "m2d_slate.hip")
-    assert "W = W0 < 65536 ? W0 : 65536" in slate and "R0 = P / W > 1 ? P / W : 1" in slate
+    assert "W = W0 < 65536 ? W0 : 65536" in slate and "R = m2d_block_rows(P, W, nU)" in slate
+    assert "R0 = P / W > 1 ? P / W : 1" in eng and "return R0 < n ? R0 : n" in eng          # the block rule: m2d_block_rows
     assert dc.ranges(1300, 256) == (256, 1) and dc.ranges(1300, 2048) == (1300, 1) and dc.ranges(100000, 1 << 22) == (65536, 64)
 
 

@@ -70,9 +70,10 @@ def test_restated_constants_match_their_source_lines():
         assert line in src, line
     assert (mq.DW, mq.WAVES, mq.DB, mq.EB, mq.LB) == (mc.DW, mc.WAVES, mc.DB, mc.EB, mc.LB)      # the walk is m2d_market_flag's
     engine = _squeeze(open(os.path.join(ROOT, "foodrec_amd", "csrc", "m2d_engine.h")).read())
-    select = _squeeze(open(os.path.join(ROOT, "foodrec_amd", "csrc", "m2d_topk_mlp.hip")).read())
     assert "constexpr uint64_t TKM_NONE = ~0ull;" in engine and "uint64_t tkm_key(const float s, const int32_t id)" in engine
-    assert "constexpr uint64_t TKM_NONE" not in select and "uint64_t tkm_key(" not in select        # one definition
+    for name in ("m2d_topk_mlp.hip", "m2d_select.hip", "m2d_select.h"):                              # one definition
+        select = _squeeze(open(os.path.join(ROOT, "foodrec_amd", "csrc", name)).read())
+        assert "constexpr uint64_t TKM_NONE" not in select and "uint64_t tkm_key(" not in select, name
 
 
 def test_share_rule():
