@@ -159,6 +159,7 @@ void release(m2d_engine *h)
     if (h->topk_mlp_held) (void)hipFree(h->topk_mlp_held);
     if (h->slate_dt) (void)hipFree(h->slate_dt);
     if (h->slate_scores) (void)hipFree(h->slate_scores);
+    if (h->group_ids) (void)hipFree(h->group_ids);
     if (h->err_dev) (void)hipFree(h->err_dev);
     if (h->err_host) (void)hipHostFree(h->err_host);
 }
@@ -884,6 +885,58 @@ int m2d_topk_users_deep(m2d_engine *h, const int32_t *users, int64_t nU, int32_t
     if (!h->dish_cats) return fail(h, M2D_ERR_NOT_CONFIGURED, "call m2d_set_dish_categories first");
     M2D_HIP_TRY(h, hipSetDevice(h->device));
     return m2d_launch_topk_users_deep(h, users, nU, k, excl_off, excl_ids, out_scores, out_ids, (hipStream_t)stream);
+}
+
+// ---- household retrieval (m2d_groups.hip): the three calls share their group arguments' rules
+static const char *group_args_wrong(const int64_t nG, const int32_t M, const int32_t mode)
+{
+    if (nG < 0) return "need nG >= 0";
+    if (M < 1 || M > M2D_GROUP_MAX_MEMBERS) return "need 1 <= M <= 64";
+    if (mode != M2D_GROUP_LEAST && mode != M2D_GROUP_MEAN && mode != M2D_GROUP_MOST) return "mode must be M2D_GROUP_LEAST, _MEAN or _MOST";
+    return nullptr;
+}
+
+int m2d_topk_groups(m2d_engine *h, const int32_t *members, int64_t nG, int32_t M, int32_t mode, int32_t k, const int64_t *excl_off,
+                    const int32_t *excl_ids, float *out_scores, int32_t *out_ids, void *stream)
+{
+    if (!h) return M2D_ERR_INVALID_ARG;
+    if (const char *why = group_args_wrong(nG, M, mode)) return fail(h, M2D_ERR_INVALID_ARG, (std::string("m2d_topk_groups: ") + why).c_str());
+    if (k < 1 || k > 1024 || (int64_t)k > h->I) return fail(h, M2D_ERR_INVALID_ARG, "m2d_topk_groups: need 1 <= k <= min(1024, I)");
+    if (nG == 0) return M2D_OK;
+    if (!members || !out_scores || !out_ids || (excl_off && !excl_ids)) return fail(h, M2D_ERR_INVALID_ARG, "m2d_topk_groups: null buffer");
+    if (!h->dish_cats) return fail(h, M2D_ERR_NOT_CONFIGURED, "call m2d_set_dish_categories first");
+    M2D_HIP_TRY(h, hipSetDevice(h->device));
+    return m2d_launch_groups(h, "m2d_topk_groups", members, nG, M, mode, nullptr, 0, k, excl_off, excl_ids, nullptr, out_scores, out_ids,
+                             (hipStream_t)stream);
+}
+
+int m2d_score_groups_slate(m2d_engine *h, const int32_t *members, int64_t nG, int32_t M, int32_t mode, const int32_t *slate, int64_t nD,
+                           float *out, void *stream)
+{
+    if (!h) return M2D_ERR_INVALID_ARG;
+    if (const char *why = group_args_wrong(nG, M, mode)) return fail(h, M2D_ERR_INVALID_ARG, (std::string("m2d_score_groups_slate: ") + why).c_str());
+    if (nD < 1 || nD > h->I) return fail(h, M2D_ERR_INVALID_ARG, "m2d_score_groups_slate: need 1 <= nD <= I");
+    if (nG == 0) return M2D_OK;
+    if (!members || !slate || !out) return fail(h, M2D_ERR_INVALID_ARG, "m2d_score_groups_slate: null buffer");
+    if (!h->dish_cats) return fail(h, M2D_ERR_NOT_CONFIGURED, "call m2d_set_dish_categories first");
+    M2D_HIP_TRY(h, hipSetDevice(h->device));
+    return m2d_launch_groups(h, "m2d_score_groups_slate", members, nG, M, mode, slate, nD, 0, nullptr, nullptr, out, nullptr, nullptr,
+                             (hipStream_t)stream);
+}
+
+int m2d_topk_groups_slate(m2d_engine *h, const int32_t *members, int64_t nG, int32_t M, int32_t mode, const int32_t *slate, int64_t nD,
+                          int32_t k, float *out_scores, int32_t *out_ids, void *stream)
+{
+    if (!h) return M2D_ERR_INVALID_ARG;
+    if (const char *why = group_args_wrong(nG, M, mode)) return fail(h, M2D_ERR_INVALID_ARG, (std::string("m2d_topk_groups_slate: ") + why).c_str());
+    if (nD < 1 || nD > h->I || k < 1 || k > 1024 || (int64_t)k > nD)
+        return fail(h, M2D_ERR_INVALID_ARG, "m2d_topk_groups_slate: need 1 <= nD <= I and 1 <= k <= min(1024, nD)");
+    if (nG == 0) return M2D_OK;
+    if (!members || !slate || !out_scores || !out_ids) return fail(h, M2D_ERR_INVALID_ARG, "m2d_topk_groups_slate: null buffer");
+    if (!h->dish_cats) return fail(h, M2D_ERR_NOT_CONFIGURED, "call m2d_set_dish_categories first");
+    M2D_HIP_TRY(h, hipSetDevice(h->device));
+    return m2d_launch_groups(h, "m2d_topk_groups_slate", members, nG, M, mode, slate, nD, k, nullptr, nullptr, nullptr, out_scores, out_ids,
+                             (hipStream_t)stream);
 }
 
 int m2d_topk_users_mlp_deep(m2d_engine *h, const int32_t *users, int64_t nU, int32_t k, int32_t candidates, const int64_t *excl_off,

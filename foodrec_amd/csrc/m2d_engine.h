@@ -88,6 +88,11 @@ struct m2d_engine {
     int64_t opt_slate_chunk_pairs = 1 << 22;         // pairs of score scratch per m2d_topk_slate pass (the lists do not depend on it)
     int64_t opt_deep_chunk_pairs = 1 << 22;          // the same for m2d_topk_users_deep: ranges of min(I, P, 65536) dishes, blocks of P / W users
 
+    // m2d_topk_groups / m2d_*_groups_slate (m2d_groups.hip): the call's dense member array i32[nG * M] (valid ids only) | cnt i32[nG];
+    // the members' score rows go to slate_scores above
+    int32_t *group_ids = nullptr;
+    size_t group_cap = 0;                            // ints
+
     // m2d_set_recipes / m2d_cookable_dishes (m2d_market.hip): every dish's ingredient list, CSR, validated once by the setter (CSR
     // shape, every id in [0, R)); lists only -- no table, no weights, nothing the scoring path reads, and no tie to `ing` above.
     // market_buf: the call's scratch -- bitmap of R bits | missing[I] (unless the caller gives a buffer) | kept dishes per block |
@@ -525,6 +530,29 @@ int m2d_launch_deep_lists(m2d_engine *h, const int32_t *users, int64_t nU, int32
                           const int64_t *excl_end, int64_t index_base, float *out_scores, int32_t *out_ids, hipStream_t stream);
 int m2d_launch_topk_users_deep(m2d_engine *h, const int32_t *users, int64_t nU, int32_t k, const int64_t *excl_off, const int32_t *excl_ids,
                                float *out_scores, int32_t *out_ids, hipStream_t stream);
+// m2d_slate.hip: what the slate score kernels take, by value
+struct SlateArgs {
+    const float *pm;        // [U, K]
+    const float *dt;        // Dt_s [rows, Kp]
+    const float *zero;      // Dt_s's last row: Kp zeros
+    const int32_t *users;   // [nU] global ids
+    int64_t nU, U, user_base;
+    int64_t index_base;     // position of users[0] in the caller's array (m2d_topk_slate's user blocks), for the error latch
+    int64_t nD;
+    int64_t utiles, dtiles;
+    int32_t K, Kp;
+    float *out;             // [nU, nD]
+    int32_t *err;
+};
+// m2d_slate.hip's slate_prepare / launch_scores for other launchers: the call's slate vectors in slate_dt (`slate` null: the dishes
+// d0 .. d0 + nD - 1) and everything of `a` but users, nU, index_base and out; then one score launch of a.nU rows into a.out [nU, nD]
+int m2d_slate_prepare(m2d_engine *h, const int32_t *slate, int32_t d0, int64_t nD, SlateArgs &a, bool &mfma, hipStream_t stream);
+int m2d_launch_slate_scores(m2d_engine *h, SlateArgs &a, bool mfma, hipStream_t stream);
+// m2d_groups.hip: one launcher behind m2d_topk_groups (slate == null), m2d_topk_groups_slate (out == null) and m2d_score_groups_slate
+// (out: f32[nG, nD]); the arguments are checked by the ABI layer
+int m2d_launch_groups(m2d_engine *h, const char *entry, const int32_t *members, int64_t nG, int32_t M, int32_t mode, const int32_t *slate,
+                      int64_t nD, int32_t k, const int64_t *excl_off, const int32_t *excl_ids, float *out, float *out_scores,
+                      int32_t *out_ids, hipStream_t stream);
 // m2d_slate.hip: out == null: the scores of user blocks go to scratch and the lists of k to out_scores / out_ids
 int m2d_launch_slate(m2d_engine *h, const char *entry, const int32_t *users, int64_t nU, const int32_t *slate, int64_t nD, int32_t k,
                      float *out, float *out_scores, int32_t *out_ids, hipStream_t stream);

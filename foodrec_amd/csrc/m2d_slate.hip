@@ -61,19 +61,7 @@ __global__ __launch_bounds__(256) void m2d_build_slate_vectors(const float *re, 
     for (int k = (ok ? K : 0) + lane; k < Kp; k += 64) o[k] = 0.f;
 }
 
-struct SlateArgs {
-    const float *pm;        // [U, K]
-    const float *dt;        // Dt_s [rows, Kp]
-    const float *zero;      // Dt_s's last row: Kp zeros
-    const int32_t *users;   // [nU] global ids
-    int64_t nU, U, user_base;
-    int64_t index_base;     // position of users[0] in the caller's array (m2d_topk_slate's user blocks), for the error latch
-    int64_t nD;
-    int64_t utiles, dtiles;
-    int32_t K, Kp;
-    float *out;             // [nU, nD]
-    int32_t *err;
-};
+// (SlateArgs: m2d_engine.h)
 
 // a user's row in Personal_Memory, or -1 (past nU, or a bad id -- latched by `report`)
 __device__ __forceinline__ int64_t slate_user_row(const SlateArgs &p, const int64_t ui, const bool report)
@@ -331,3 +319,11 @@ int m2d_launch_topk_users_deep(m2d_engine *h, const int32_t *users, int64_t nU, 
     if (excl_off && (rc = m2d_launch_check_exclusions(h, excl_off, excl_ids, nU, st)) != M2D_OK) return rc;
     return m2d_launch_deep_lists(h, users, nU, k, excl_off, excl_ids, excl_off ? excl_off + nU : nullptr, 0, out_scores, out_ids, st);
 }
+
+// the two steps above for launchers outside this file (m2d_groups.hip): the same kernels, the same words
+int m2d_slate_prepare(m2d_engine *h, const int32_t *slate, int32_t d0, int64_t nD, SlateArgs &a, bool &mfma, hipStream_t st)
+{
+    return slate_prepare(h, slate, d0, nD, a, mfma, st);
+}
+
+int m2d_launch_slate_scores(m2d_engine *h, SlateArgs &a, bool mfma, hipStream_t st) { return launch_scores(h, a, mfma, st); }

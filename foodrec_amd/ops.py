@@ -20,6 +20,10 @@ _ENGINES: "weakref.WeakValueDictionary[int, ScoringEngine]" = weakref.WeakValueD
 _ENGINE_SERIAL = itertools.count(1)         # engine keys are never reused (id() of a collected engine can be)
 
 
+GROUP_MODES = {"least": 0, "mean": 1, "most": 2}      # include/m2d.h: M2D_GROUP_LEAST / _MEAN / _MOST
+GROUP_MAX_MEMBERS = 64                                 # include/m2d.h: M2D_GROUP_MAX_MEMBERS
+
+
 def _stream_ptr() -> int:
     return torch.cuda.current_stream().cuda_stream
 
@@ -574,6 +578,76 @@ class ScoringEngine:
         self._slate_keep = (users, slate)
         return out_s, out_i
 
+    # -- household retrieval (include/m2d.h, "Household retrieval") --------------------------------------
+    def _group_members(self, members, what: str) -> torch.Tensor:
+        """``members`` of the group calls -> a contiguous int32 device tensor [nG, M]: a device tensor with -1 padding as it is, a list
+        of id lists padded with -1 on the host (no list longer than 64)."""
+        if isinstance(members, torch.Tensor):
+            if members.dtype != torch.int32 or members.device != self.device or members.dim() != 2:
+                raise TypeError("%s: members must be an int32 tensor [nG, M] on %s" % (what, self.device))
+            return members.contiguous()
+        lists = [list(g) for g in members]
+        if any(len(g) > GROUP_MAX_MEMBERS for g in lists):
+            raise ValueError("%s: a group has at most %d members" % (what, GROUP_MAX_MEMBERS))
+        padded = np.full((len(lists), max([len(g) for g in lists] + [1])), -1, dtype=np.int32)
+        for g, ids in enumerate(lists):
+            padded[g, :len(ids)] = _int32_ids(ids, "user")
+        return torch.from_numpy(padded).to(self.device)
+
+    def topk_groups(self, members, k: int, mode: str = "least", exclude=None, among: Optional[torch.Tensor] = None):
+        """EXTENSION, build-defined (``m2d_topk_groups`` / ``m2d_topk_groups_slate``, include/m2d.h): one list
+        of k dishes per GROUP of users -> (scores f32[nG, k], dish ids i32[nG, k]).  ``members``: int32 device tensor [nG, M] with -1
+        padding, or a list of id lists (at most 64 each).  ``mode``: "least" (least misery: a dish scores what its unhappiest member
+        scores), "mean" or "most".  ``exclude``: per-group lists in ``topk_users_deep``'s forms; ``among``: an ascending int32 slate
+        (device tensor) instead of the whole catalogue -- not both.  1 <= k <= 1024.  Does not synchronise."""
+        if mode not in GROUP_MODES:
+            raise ValueError("topk_groups: mode must be one of %s, got %r" % (sorted(GROUP_MODES), mode))
+        if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or not 1 <= int(k) <= 1024:
+            raise ValueError("topk_groups: 1 <= k <= 1024, got %r" % (k,))
+        if exclude is not None and among is not None:
+            raise ValueError("topk_groups: `among` and `exclude` cannot be combined (take the ids out of the slate)")
+        members = self._group_members(members, "topk_groups")
+        nG, M = members.shape
+        k = int(k)
+        off = ids = slate = None
+        if exclude is not None:
+            off, ids = exclusions_on_device(exclude, nG, self.device, "topk_groups")
+        if among is not None:
+            if not isinstance(among, torch.Tensor) or among.dtype != torch.int32 or among.device != self.device:
+                raise TypeError("topk_groups: among must be an int32 tensor on %s" % self.device)
+            slate = among.contiguous().reshape(-1)
+        out_s = torch.empty((nG, k), dtype=torch.float32, device=self.device)
+        out_i = torch.empty((nG, k), dtype=torch.int32, device=self.device)
+        with torch.cuda.device(self.device):
+            if slate is None:
+                xo, xi = (off.data_ptr(), ids.data_ptr()) if off is not None else (None, None)
+                rc = _native.lib().m2d_topk_groups(self._h, members.data_ptr(), nG, M, GROUP_MODES[mode], k, xo, xi, out_s.data_ptr(),
+                                                   out_i.data_ptr(), _stream_ptr())
+            else:
+                rc = _native.lib().m2d_topk_groups_slate(self._h, members.data_ptr(), nG, M, GROUP_MODES[mode], slate.data_ptr(),
+                                                         slate.numel(), k, out_s.data_ptr(), out_i.data_ptr(), _stream_ptr())
+        _native.raise_for(rc, self._h)
+        self._group_keep = (members, off, ids, slate)    # stay alive until the queued kernels have read them
+        return out_s, out_i
+
+    def score_groups(self, members, slate: torch.Tensor, mode: str = "least") -> torch.Tensor:
+        """EXTENSION, build-defined (``m2d_score_groups_slate``): every group's word for every dish of one ascending slate ->
+        f32[nG, nD]; ``members`` and ``mode`` as in ``topk_groups``.  Does not synchronise."""
+        if mode not in GROUP_MODES:
+            raise ValueError("score_groups: mode must be one of %s, got %r" % (sorted(GROUP_MODES), mode))
+        members = self._group_members(members, "score_groups")
+        if not isinstance(slate, torch.Tensor) or slate.dtype != torch.int32 or slate.device != self.device:
+            raise TypeError("score_groups: slate must be an int32 tensor on %s" % self.device)
+        slate = slate.contiguous().reshape(-1)
+        nG, M = members.shape
+        out = torch.empty((nG, slate.numel()), dtype=torch.float32, device=self.device)
+        with torch.cuda.device(self.device):
+            rc = _native.lib().m2d_score_groups_slate(self._h, members.data_ptr(), nG, M, GROUP_MODES[mode], slate.data_ptr(), slate.numel(),
+                                                      out.data_ptr(), _stream_ptr())
+        _native.raise_for(rc, self._h)
+        self._group_keep = (members, None, None, slate)
+        return out
+
     # -- market retrieval (include/m2d.h, "Market retrieval"; DESIGN.md section 4.8) -------------------------------------------
     def set_recipes(self, offsets, ids, num_ingredients: int):
         """EXTENSION (``m2d_set_recipes``): every dish's ingredient list, CSR -- offsets i32[I + 1], ids i32[nnz] in
@@ -1066,6 +1140,30 @@ def topk_slate_op(engine: int, users: torch.Tensor, slate: torch.Tensor, k: int)
 def _(engine, users, slate, k):
     return (users.new_empty((users.numel(), k), dtype=torch.float32),
             users.new_empty((users.numel(), k), dtype=torch.int32))
+
+
+@torch.library.custom_op("m2d::topk_groups", mutates_args=(), device_types="cuda")
+def topk_groups_op(engine: int, members: torch.Tensor, k: int, mode: str = "least", excl_off: Optional[torch.Tensor] = None,
+                   excl_ids: Optional[torch.Tensor] = None, among: Optional[torch.Tensor] = None) -> tuple[torch.Tensor, torch.Tensor]:
+    """``ScoringEngine.topk_groups``; members i32[nG, M] with -1 padding; the exclusions as in ``topk_users_deep``."""
+    s, i = _engine(engine).topk_groups(members, k, mode, _excl_pair(excl_off, excl_ids), among)
+    return s, i
+
+
+@topk_groups_op.register_fake
+def _(engine, members, k, mode="least", excl_off=None, excl_ids=None, among=None):
+    return (members.new_empty((members.shape[0], k), dtype=torch.float32),
+            members.new_empty((members.shape[0], k), dtype=torch.int32))
+
+
+@torch.library.custom_op("m2d::score_groups", mutates_args=(), device_types="cuda")
+def score_groups_op(engine: int, members: torch.Tensor, slate: torch.Tensor, mode: str = "least") -> torch.Tensor:
+    return _engine(engine).score_groups(members, slate, mode)
+
+
+@score_groups_op.register_fake
+def _(engine, members, slate, mode="least"):
+    return members.new_empty((members.shape[0], slate.numel()), dtype=torch.float32)
 
 
 @torch.library.custom_op("m2d::catalogue_rank", mutates_args=(), device_types="cuda")

@@ -576,6 +576,55 @@ class Model:
         self.engine.check()
         return s.cpu().numpy(), i.cpu().numpy()
 
+    def topk_group(self, groups, k: int = 10, mode: str = "least", exclude=None, among=None, market=None, max_missing: int = 0):
+        """EXTENSION, build-defined (no reference counterpart): ONE list of k dishes per household -- `groups` a
+        list of lists of user ids (str or int, at most 64 each, repeats count twice in the mean).  `mode`: "least" (least misery: a
+        dish is worth what its unhappiest member scores), "mean" or "most".  `exclude`: a list of dish-id lists aligned with `groups`,
+        or a dict keyed by user (str or int, whichever form `groups` uses) -- a group then leaves out the sorted union of its members' lists.  `among`: the dishes to choose from,
+        as in `topk`.  `market=ingredients`: `cookable(market, max_missing)` is the slate; rows end in id -1 / NaN when fewer than k
+        dishes are cookable.  `market` with `among` or `exclude`, and `among` with `exclude`, raise.  1 <= k <= 1024.  Returns numpy
+        (scores float32 [nG, k], dish ids int32 [nG, k]).  (``ScoringEngine.topk_groups``.)"""
+        if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or not 1 <= int(k) <= 1024:
+            raise ValueError("topk_group: 1 <= k <= 1024, got %r" % (k,))
+        k = int(k)
+        if market is not None and (among is not None or exclude is not None):
+            raise ValueError("topk_group: market together with among or exclude is not supported")
+        if among is not None and exclude is not None:
+            raise ValueError("topk_group: among together with exclude is not supported (take the dishes out of `among`)")
+        groups = [list(g) for g in groups]
+        members = []
+        for g in groups:
+            m = _ids(g, "user")
+            members.append((m.cpu().numpy() if isinstance(m, torch.Tensor) else m).tolist())
+        if exclude is not None:
+            if isinstance(exclude, dict):                    # keys and members are compared as ints: "7" and 7 are the same user
+                by_user = {int(u): x for u, x in exclude.items()}
+                exclude = [sorted({int(d) for u in m for d in by_user.get(u, ())}) for m in members]
+            elif len(exclude) != len(groups):
+                raise ValueError("topk_group: %d exclusion lists for %d groups" % (len(exclude), len(groups)))
+            else:
+                exclude = [(lambda x: x.cpu().numpy() if isinstance(x, torch.Tensor) else x)(_ids(x, "item")) for x in exclude]
+        slate = None
+        if market is not None:
+            slate = np.asarray(self.cookable(market, max_missing), dtype=np.int32)
+        elif among is not None:
+            d = _ids(among, "item")
+            slate = np.unique(np.asarray(d.cpu().numpy() if isinstance(d, torch.Tensor) else d, dtype=np.int32).reshape(-1))
+        if slate is None:
+            s, i = self.engine.topk_groups(members, k, mode, exclude)
+            self.engine.check()
+            return s.cpu().numpy(), i.cpu().numpy()
+        out_s = np.full((len(groups), k), np.nan, dtype=np.float32)
+        out_i = np.full((len(groups), k), -1, dtype=np.int32)
+        kk = min(k, int(slate.size))
+        if market is None and kk < k:
+            raise ValueError("topk_group: k = %d exceeds the %d distinct dishes of `among`" % (k, slate.size))
+        if kk:
+            s, i = self.engine.topk_groups(members, kk, mode, None, torch.from_numpy(slate).to(self.device))
+            self.engine.check()
+            out_s[:, :kk], out_i[:, :kk] = s.cpu().numpy(), i.cpu().numpy()
+        return out_s, out_i
+
     def set_ingredients(self, ingredient_table, offsets, ids, weights=None):
         """EXTENSION: multi-hot ingredient lists per dish (CSR) replacing the category sum of the high-level path."""
         self.engine.set_ingredients(ingredient_table, offsets, ids, weights)

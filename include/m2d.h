@@ -429,6 +429,59 @@ int m2d_topk_users_mlp_deep(m2d_engine *h, const int32_t *users, int64_t nU, int
                             const int64_t *excl_off /* [nU + 1] or NULL */, const int32_t *excl_ids,
                             float *out_scores /* [nU, k] */, int32_t *out_ids /* [nU, k] */, void *stream);
 
+/* ---- build-defined extension, NO reference counterpart ----
+ * Household retrieval: ONE list of dishes for a GROUP of users -- the people at one table.
+ *
+ * Groups.  members i32[nG, M], device memory, row-major, 1 <= M <= M2D_GROUP_MAX_MEMBERS: group g's members are the leading entries
+ * >= 0 of row g, -1 fills the rest of the row; a group has at least one member.  Ids are global (m2d_set_user_base is honoured: EVERY
+ * member must lie in this engine's range -- a household spread over several shards is not served, sharding is out of scope) and may
+ * repeat; a repeated member counts twice in the mean.
+ *
+ * Group word.  With s_j the word m2d_score_slate writes for (member j, dish d), `mode` chooses the group's word for d:
+ *   M2D_GROUP_LEAST  least misery: the word of the member that ranks worst under m2d_topk_users' order -- the lowest score, -0 and +0
+ *                    equal, NaN worst; among equals the first in member order;
+ *   M2D_GROUP_MOST   the word of the member that ranks best (first member among equals); NaN only if every member's word is NaN;
+ *   M2D_GROUP_MEAN   acc = s_0; acc = acc + s_j for j = 1 .. cnt - 1 in member order, float32, round to nearest; then one correctly
+ *                    rounded float32 division by (float)cnt (cnt >= 2).  No fma, no reciprocal, no pairwise tree.
+ * With one member every mode returns that member's word: a group of one reproduces m2d_topk_users_deep bit for bit.  A group word
+ * does not depend on nG, the group's position in the call, M (the padding) or how the launcher cuts the work.
+ *
+ * m2d_topk_groups: the first k of m2d_topk_users' order on the group words over the whole catalogue, 1 <= k <= min(1024, I), as
+ * out_ids i32[nG, k] / out_scores f32[nG, k]; optional per-group exclusion lists excl_off i64[nG + 1] / excl_ids in m2d_catalogue_rank's
+ * conventions (excl_off NULL: none); rows end in id -1 / NaN where fewer than k dishes remain.
+ * m2d_score_groups_slate / m2d_topk_groups_slate: the group words of a slate -- m2d_topk_slate's slate: strictly ascending, 1 <= nD <= I,
+ * the same latched errors -- as out f32[nG, nD], or their first k, 1 <= k <= min(1024, nD), as dish ids (not columns).  The slate forms
+ * take no exclusion lists: the caller takes the ids out of the slate.
+ *
+ * nG == 0 returns M2D_OK and launches nothing.  M, mode or k out of range, a null required pointer, excl_off without excl_ids:
+ * M2D_ERR_INVALID_ARG.  No dish masks: M2D_ERR_NOT_CONFIGURED.  Refused with M2D_ERR_UNSUPPORTED under the call's own name, the condition
+ * in m2d_last_error: the ingredient table set, a table value that is not finite (m2d_topk_users_deep's conditions; an MLP head is ignored).
+ * Diagnostics (latched, first error wins; the member check runs first in stream order).  A member id that is neither -1 nor in the
+ * engine's range -- an entry below -1 included -- M2D_ERR_BAD_USER_ID with the id and its position g M + j in `members`; an empty group
+ * M2D_ERR_INVALID_ARG with value -1 and position g M; an id >= 0 behind a -1 M2D_ERR_INVALID_ARG with the id and its position;
+ * exclusion errors as m2d_topk_users_deep reports them.  A row with several defects (-1, id: an empty group AND an id behind a -1) has
+ * ONE of them reported, whichever thread latches first.  The rows of a call with a latched error are unspecified; no kernel reads out
+ * of bounds and the engine stays usable.
+ * How.  m2d_group_members checks the slots and writes a dense array of valid user ids and each group's count; per block of
+ * Gb = max(1, P / (M W)) whole groups (P = option "deep_chunk_pairs") and dish range of W = min(I, P, 65536) dishes (slate forms:
+ * W = nD, one range) the slate score kernel fills engine scratch [Gb M, W], m2d_group_reduce folds each group's first cnt rows into its
+ * row 0 (m2d_score_groups_slate: into `out`), and m2d_select_deep lists row 0 of every group, merging across ranges as m2d_topk_users_deep
+ * does.  The slate forms do not cut the slate into ranges: their scratch is at least M nD floats whatever the option says (M = 64 and
+ * nD = 10^6: 256 MB).  KNOWN COST: filler rows are scored too, so the scoring cost grows with the padding M - cnt; compaction is not done here.
+ * Does not synchronise beyond what m2d_topk_slate does; buffers grow only. */
+#define M2D_GROUP_LEAST 0
+#define M2D_GROUP_MEAN 1
+#define M2D_GROUP_MOST 2
+#define M2D_GROUP_MAX_MEMBERS 64
+int m2d_topk_groups(m2d_engine *h, const int32_t *members /* [nG, M] */, int64_t nG, int32_t M, int32_t mode, int32_t k,
+                    const int64_t *excl_off /* [nG + 1] or NULL */, const int32_t *excl_ids,
+                    float *out_scores /* [nG, k] */, int32_t *out_ids /* [nG, k] */, void *stream);
+int m2d_score_groups_slate(m2d_engine *h, const int32_t *members /* [nG, M] */, int64_t nG, int32_t M, int32_t mode,
+                           const int32_t *slate, int64_t nD, float *out /* f32[nG, nD], row-major */, void *stream);
+int m2d_topk_groups_slate(m2d_engine *h, const int32_t *members /* [nG, M] */, int64_t nG, int32_t M, int32_t mode,
+                          const int32_t *slate, int64_t nD, int32_t k,
+                          float *out_scores /* [nG, k] */, int32_t *out_ids /* [nG, k] */, void *stream);
+
 /* Diagnostic (scripts/deep_time.py): one selection launch over a resident row-major score block f32[rows, W], ids 0 .. W - 1, no
  * exclusions, into out_scores / out_ids [rows, k] -- form 0: m2d_select_deep (k <= 1024), form 1: m2d_topk_mlp_select (k <= 64).
  * Reads no table.  Bad arguments: M2D_ERR_INVALID_ARG. */
