@@ -83,85 +83,68 @@ int fail(m2d_engine *h, int code, const char *msg)
     if (h) h->last_error = msg; else g_create_error = msg;
     return code;
 }
+int fail(m2d_engine *h, int code, const std::string &msg) { return fail(h, code, msg.c_str()); }
 
 bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
+bool table_flags_ok(const int flags) { return flags == M2D_TABLES_HOST || flags == M2D_TABLES_DEVICE; }
+// what a setter can judge before it replaces anything: a BORROWED array that the kernels read 16 bytes at a time must be aligned
+// (the engine's own copies are hipMalloc's, checked after they are made)
+bool borrowed_misaligned(const void *p, const int flags) { return flags == M2D_TABLES_DEVICE && !aligned16(p); }
 
-// copy a host table to HBM (engine-owned) or borrow a device pointer
-int adopt_table(m2d_engine *h, const float *src, size_t count, int flags, const float **dst, bool *own)
+// copy a host table to HBM (engine-owned) or borrow a device pointer; a null `src` or no entries: no copy
+template <typename T> int adopt(m2d_engine *h, const T *src, const size_t count, const int flags, m2d_table<T> &t)
 {
-    if (flags == M2D_TABLES_DEVICE) {
-        *dst = src;
-        *own = false;
+    t.reset();
+    if (flags == M2D_TABLES_DEVICE || !src) {
+        t.p = src;
         return M2D_OK;
     }
-    float *d = nullptr;
-    M2D_HIP_TRY(h, hipMalloc((void **)&d, count * sizeof(float)));
-    hipError_t e = hipMemcpy(d, src, count * sizeof(float), hipMemcpyHostToDevice);
+    if (int rc = t.own.grow(h, count)) return rc;
+    const hipError_t e = hipMemcpy(t.own, src, count * sizeof(T), hipMemcpyHostToDevice);
     if (e != hipSuccess) {
-        (void)hipFree(d);
-        h->last_error = std::string("hipMemcpy(table): ") + hipGetErrorString(e);
-        return M2D_ERR_HIP;
+        t.reset();
+        return fail(h, M2D_ERR_HIP, std::string("hipMemcpy(table): ") + hipGetErrorString(e));
     }
-    *dst = d;
-    *own = true;
+    t.p = t.own;
     return M2D_OK;
 }
 
-void release(m2d_engine *h)
+// ---- what the entry points ask for before they launch, each check named once.  enter() runs them in the one order every entry
+// point uses -- recipes, head, dish masks, "plain scores only", then the engine's device -- and returns the refusal, if any.
+#define M2D_REQUIRE(expr)                                                                      \
+    do {                                                                                       \
+        if (const int rc_ = (expr)) return rc_;                                                \
+    } while (0)
+
+enum : unsigned { NEEDS_MASKS = 1, NEEDS_HEAD = 2, NEEDS_RECIPES = 4, PLAIN_SCORES_ONLY = 8 };
+
+int enter(m2d_engine *h, const unsigned needs = 0, const char *entry = "")
 {
-    for (hipEvent_t e : h->stage_ev)
-        if (e) (void)hipEventDestroy(e);
-    if (h->stage_host) (void)hipHostFree(h->stage_host);
-    if (h->stage_dev) (void)hipFree(h->stage_dev);
-    m2d_train_release(h);
-    if (h->own_pm && h->pm) (void)hipFree((void *)h->pm);
-    if (h->own_re && h->re) (void)hipFree((void *)h->re);
-    if (h->own_ce && h->ce) (void)hipFree((void *)h->ce);
-    if (h->own_dish_cats && h->dish_cats) (void)hipFree((void *)h->dish_cats);
-    if (h->dish_vec) (void)hipFree(h->dish_vec);
-    if (h->grp_rs) (void)hipFree(h->grp_rs);
-    if (h->grp_rs16) (void)hipFree(h->grp_rs16);
-    if (h->grp_perm) (void)hipFree(h->grp_perm);
-    if (h->grp_tile_info) (void)hipFree(h->grp_tile_info);
-    if (h->grp_work) (void)hipFree(h->grp_work);
-    if (h->own_mlp) {
-        for (const float *q : {h->mlp_w1, h->mlp_b1, h->mlp_w2, h->mlp_b2, h->mlp_w3})
-            if (q) (void)hipFree((void *)q);
-    }
-    m2d_mlp_free_derived(h, true);
-    if (h->user_high) (void)hipFree(h->user_high);
-    if (h->pm_bf16) (void)hipFree(h->pm_bf16);
-    if (h->dish_high) (void)hipFree(h->dish_high);
-    if (h->own_ing) {
-        if (h->ing) (void)hipFree((void *)h->ing);
-        if (h->ing_off) (void)hipFree((void *)h->ing_off);
-        if (h->ing_ids) (void)hipFree((void *)h->ing_ids);
-        if (h->ing_w) (void)hipFree((void *)h->ing_w);
-    }
-    if (h->own_rcp) {
-        if (h->rcp_off) (void)hipFree((void *)h->rcp_off);
-        if (h->rcp_ids) (void)hipFree((void *)h->rcp_ids);
-    }
-    if (h->market_buf) (void)hipFree(h->market_buf);
-    if (h->markets_buf) (void)hipFree(h->markets_buf);
-    if (h->profile_buf) (void)hipFree(h->profile_buf);
-    if (h->market_count_host) (void)hipHostFree(h->market_count_host);
-    if (h->scratch) (void)hipFree(h->scratch);
-    if (h->topk_flags) (void)hipFree(h->topk_flags);
-    if (h->topk_plan) (void)hipFree(h->topk_plan);
-    if (h->topk_ex) (void)hipFree(h->topk_ex);
-    if (h->rank_buf) (void)hipFree(h->rank_buf);
-    if (h->rank_tnorm) (void)hipFree(h->rank_tnorm);
-    if (h->excl_buf) (void)hipFree(h->excl_buf);
-    if (h->topk_mlp_ids) (void)hipFree(h->topk_mlp_ids);
-    if (h->topk_mlp_scores) (void)hipFree(h->topk_mlp_scores);
-    if (h->topk_mlp_cand) (void)hipFree(h->topk_mlp_cand);
-    if (h->topk_mlp_held) (void)hipFree(h->topk_mlp_held);
-    if (h->slate_dt) (void)hipFree(h->slate_dt);
-    if (h->slate_scores) (void)hipFree(h->slate_scores);
-    if (h->group_ids) (void)hipFree(h->group_ids);
-    if (h->err_dev) (void)hipFree(h->err_dev);
-    if (h->err_host) (void)hipHostFree(h->err_host);
+    if ((needs & NEEDS_RECIPES) && !h->rcp_set) return fail(h, M2D_ERR_NOT_CONFIGURED, "call m2d_set_recipes first");
+    if ((needs & NEEDS_HEAD) && !h->mlp_w1) return fail(h, M2D_ERR_NOT_CONFIGURED, "call m2d_set_mlp_head first");
+    if ((needs & NEEDS_MASKS) && !h->dish_cats) return fail(h, M2D_ERR_NOT_CONFIGURED, "call m2d_set_dish_categories first");
+    if ((needs & PLAIN_SCORES_ONLY) && h->ing) return fail(h, M2D_ERR_UNSUPPORTED, std::string(entry) + ": the ingredient table is set");
+    if ((needs & PLAIN_SCORES_ONLY) && h->mlp_w1) return fail(h, M2D_ERR_UNSUPPORTED, std::string(entry) + ": the MLP head is set");
+    M2D_HIP_TRY(h, hipSetDevice(h->device));
+    return M2D_OK;
+}
+
+int null_buffer(m2d_engine *h, const char *entry) { return fail(h, M2D_ERR_INVALID_ARG, std::string(entry) + ": null buffer"); }
+int negative_batch(m2d_engine *h, const char *entry) { return fail(h, M2D_ERR_INVALID_ARG, std::string(entry) + ": negative batch"); }
+
+// "need nU >= 0 and 1 <= k <= min(limit, I)" of the catalogue top-k calls
+int topk_range(m2d_engine *h, const char *entry, const int64_t nU, const int32_t k, const int limit)
+{
+    if (nU >= 0 && k >= 1 && k <= limit && (int64_t)k <= h->I) return M2D_OK;
+    return fail(h, M2D_ERR_INVALID_ARG, std::string(entry) + ": need nU >= 0 and 1 <= k <= min(" + std::to_string(limit) + ", I)");
+}
+
+// "candidates must be 0 (exact) or k <= candidates <= min(limit, I)" of the calls under the head
+int candidates_range(m2d_engine *h, const char *entry, const int32_t k, const int32_t candidates, const int limit, const char *when = "")
+{
+    if (candidates == 0 || (candidates >= k && candidates <= limit && (int64_t)candidates <= h->I)) return M2D_OK;
+    return fail(h, M2D_ERR_INVALID_ARG, std::string(entry) + ": " + when + "candidates must be 0 (exact) or k <= candidates <= min(" +
+                                            std::to_string(limit) + ", I)");
 }
 
 }  // namespace
@@ -211,8 +194,7 @@ int m2d_create(const float *pm, const float *re, const float *ce, int64_t U, int
         return fail(nullptr, M2D_ERR_INVALID_ARG, "m2d_create: U, I, C, E must be positive");
     if (I > INT32_MAX || U > (int64_t)INT32_MAX)
         return fail(nullptr, M2D_ERR_UNSUPPORTED, "m2d_create: ids are int32 (Model_Recommender.py:26-29)");
-    if (table_flags != M2D_TABLES_HOST && table_flags != M2D_TABLES_DEVICE)
-        return fail(nullptr, M2D_ERR_INVALID_ARG, "m2d_create: bad table_flags");
+    if (!table_flags_ok(table_flags)) return fail(nullptr, M2D_ERR_INVALID_ARG, "m2d_create: bad table_flags");
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
         return fail(nullptr, M2D_ERR_NO_DEVICE,
@@ -224,9 +206,8 @@ int m2d_create(const float *pm, const float *re, const float *ce, int64_t U, int
     h->a = coef;            // float32(coef)               Model_Recommender.py:17
     h->b = 1.0f - h->a;     // evaluated in float32        Model_Recommender.py:96
     int rc = M2D_OK;
-    auto bail = [&](int code) {
+    auto bail = [&](int code) {         // (the engine's device is current, or no device call has succeeded)
         g_create_error = h->last_error;
-        release(h);
         delete h;
         return code;
     };
@@ -234,16 +215,15 @@ int m2d_create(const float *pm, const float *re, const float *ce, int64_t U, int
     hipDeviceProp_t prop;
     if (hipGetDeviceProperties(&prop, device) == hipSuccess && prop.multiProcessorCount > 0)
         h->num_cu = prop.multiProcessorCount;
-    if ((rc = adopt_table(h, pm, (size_t)U * (C + 1) * E, table_flags, &h->pm, &h->own_pm)) != M2D_OK) return bail(rc);
-    if ((rc = adopt_table(h, re, (size_t)I * E, table_flags, &h->re, &h->own_re)) != M2D_OK) return bail(rc);
-    if ((rc = adopt_table(h, ce, (size_t)C * E, table_flags, &h->ce, &h->own_ce)) != M2D_OK) return bail(rc);
+    if ((rc = adopt(h, pm, (size_t)U * (C + 1) * E, table_flags, h->pm)) != M2D_OK) return bail(rc);
+    if ((rc = adopt(h, re, (size_t)I * E, table_flags, h->re)) != M2D_OK) return bail(rc);
+    if ((rc = adopt(h, ce, (size_t)C * E, table_flags, h->ce)) != M2D_OK) return bail(rc);
     if (!aligned16(h->pm) || !aligned16(h->re) || !aligned16(h->ce)) {
         h->last_error = "m2d_create: device tables must be 16-byte aligned";
         return bail(M2D_ERR_INVALID_ARG);
     }
-    if (hipMalloc((void **)&h->err_dev, 8 * sizeof(int32_t)) != hipSuccess ||       // id-error latch [4] | non-finite word | the bf16 mirror's | pad
-        hipMemset(h->err_dev, 0, 8 * sizeof(int32_t)) != hipSuccess ||
-        hipHostMalloc((void **)&h->err_host, 4 * sizeof(int32_t)) != hipSuccess) {
+    if (h->err_dev.grow(h, 8) != M2D_OK ||                                          // id-error latch [4] | non-finite word | the bf16 mirror's | pad
+        hipMemset(h->err_dev, 0, 8 * sizeof(int32_t)) != hipSuccess || h->err_host.alloc(h, 4) != M2D_OK) {
         h->last_error = "m2d_create: could not allocate the error latch";
         return bail(M2D_ERR_HIP);
     }
@@ -258,7 +238,6 @@ int m2d_destroy(m2d_engine *h)
 {
     if (!h) return M2D_OK;
     (void)hipSetDevice(h->device);
-    release(h);
     delete h;
     return M2D_OK;
 }
@@ -276,19 +255,19 @@ int m2d_set_user_base(m2d_engine *h, int64_t user_base)
     return M2D_OK;
 }
 
+// (failure contract: m2d.h, "Setters")
 int m2d_set_dish_categories(m2d_engine *h, const float *cats, int table_flags)
 {
     if (!h || !cats) return fail(h, M2D_ERR_INVALID_ARG, "m2d_set_dish_categories: null argument");
-    if (table_flags != M2D_TABLES_HOST && table_flags != M2D_TABLES_DEVICE)
-        return fail(h, M2D_ERR_INVALID_ARG, "m2d_set_dish_categories: bad table_flags");
-    M2D_HIP_TRY(h, hipSetDevice(h->device));
-    if (h->own_dish_cats && h->dish_cats) (void)hipFree((void *)h->dish_cats);
-    h->dish_cats = nullptr;
-    h->own_dish_cats = false;
+    if (!table_flags_ok(table_flags)) return fail(h, M2D_ERR_INVALID_ARG, "m2d_set_dish_categories: bad table_flags");
+    if (borrowed_misaligned(cats, table_flags)) return fail(h, M2D_ERR_INVALID_ARG, "dish categories must be 16-byte aligned");
+    M2D_REQUIRE(enter(h));
+    h->dish_cats.reset();               // replacement begins: from here on a failure leaves no table
     m2d_mark_written(h, M2D_TAB_MASKS, M2D_NO_VALUES);
-    int rc = adopt_table(h, cats, (size_t)h->I * h->C, table_flags, &h->dish_cats, &h->own_dish_cats);
-    if (rc != M2D_OK) return rc;
-    if (!aligned16(h->dish_cats)) return fail(h, M2D_ERR_INVALID_ARG, "dish categories must be 16-byte aligned");
+    m2d_table<float> t;
+    M2D_REQUIRE(adopt(h, cats, (size_t)h->I * h->C, table_flags, t));
+    if (!aligned16(t)) return fail(h, M2D_ERR_INVALID_ARG, "dish categories must be 16-byte aligned");
+    h->dish_cats = std::move(t);
     return M2D_OK;
 }
 
@@ -296,11 +275,11 @@ int m2d_score_pairs(m2d_engine *h, const int32_t *users, const int32_t *items, c
                     float *out, void *stream)
 {
     if (!h) return M2D_ERR_INVALID_ARG;
-    if (B < 0) return fail(h, M2D_ERR_INVALID_ARG, "m2d_score_pairs: negative batch");
+    if (B < 0) return negative_batch(h, "m2d_score_pairs");
     if (B == 0) return M2D_OK;
-    if (!users || !items || !cats || !out) return fail(h, M2D_ERR_INVALID_ARG, "m2d_score_pairs: null buffer");
+    if (!users || !items || !cats || !out) return null_buffer(h, "m2d_score_pairs");
     if (h->C == 4 && !aligned16(cats)) return fail(h, M2D_ERR_INVALID_ARG, "m2d_score_pairs: cats must be 16-byte aligned");
-    M2D_HIP_TRY(h, hipSetDevice(h->device));
+    M2D_REQUIRE(enter(h));
     return m2d_launch_score_pairs(h, users, items, cats, false, B, out, (hipStream_t)stream);
 }
 
@@ -323,18 +302,14 @@ constexpr int64_t HOST_CHUNK = 1 << 18;
 
 int ensure_stage(m2d_engine *h, size_t total, hipStream_t st)
 {
-    if (total <= h->stage_bytes) return M2D_OK;
+    if (total <= h->stage_dev.cap) return M2D_OK;
     M2D_HIP_TRY(h, hipStreamSynchronize(st));
-    if (h->stage_host) (void)hipHostFree(h->stage_host);
-    if (h->stage_dev) (void)hipFree(h->stage_dev);
-    h->stage_host = h->stage_dev = nullptr; h->stage_bytes = 0;
-    const size_t cap = total * 2;
+    h->stage_host.reset();
+    h->stage_dev.reset();
     // the kernel writes scores, the id-error latch and the completion word into this block and the host polls the word:
     // host-coherent (fine-grained) and mapped, stated rather than left to the runtime's default / HIP_HOST_COHERENT
-    M2D_HIP_TRY(h, hipHostMalloc((void **)&h->stage_host, cap, hipHostMallocCoherent | hipHostMallocMapped));
-    M2D_HIP_TRY(h, hipMalloc((void **)&h->stage_dev, cap));
-    h->stage_bytes = cap;
-    return M2D_OK;
+    M2D_REQUIRE(h->stage_host.alloc(h, total * 2, hipHostMallocCoherent | hipHostMallocMapped));
+    return h->stage_dev.grow(h, total * 2);
 }
 
 // Feeds of more than HOST_CHUNK pairs: chunks through two pinned blocks, so that the host's copy of chunk k + 1 into its
@@ -363,8 +338,8 @@ int score_pairs_host_chunked(m2d_engine *h, const int32_t *users, const int32_t 
             return M2D_ERR_HIP;                                                                \
         }                                                                                      \
     } while (0)
-    for (hipEvent_t &e : h->stage_ev)
-        if (!e) M2D_HIP_TRY(h, hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    for (m2d_event &ev : h->stage_ev)
+        if (!ev.e) M2D_HIP_TRY(h, hipEventCreateWithFlags(&ev.e, hipEventDisableTiming));
     const int64_t nch = (B + HOST_CHUNK - 1) / HOST_CHUNK;
     auto retire = [&](int64_t k) -> int {
         unsigned char *hs = h->stage_host + (size_t)(k & 1) * blk;
@@ -423,20 +398,17 @@ int m2d_score_pairs_host(m2d_engine *h, const int32_t *users, const int32_t *ite
                          float *out, void *stream)
 {
     if (!h) return M2D_ERR_INVALID_ARG;
-    if (B < 0) return fail(h, M2D_ERR_INVALID_ARG, "m2d_score_pairs_host: negative batch");
+    if (B < 0) return negative_batch(h, "m2d_score_pairs_host");
     if (B == 0) return M2D_OK;
-    if (!users || !items || !cats || !out) return fail(h, M2D_ERR_INVALID_ARG, "m2d_score_pairs_host: null buffer");
+    if (!users || !items || !cats || !out) return null_buffer(h, "m2d_score_pairs_host");
     hipStream_t st = (hipStream_t)stream;
-    M2D_HIP_TRY(h, hipSetDevice(h->device));
+    M2D_REQUIRE(enter(h));
     if (B > HOST_CHUNK && h->opt_host_zero_copy != 0) return score_pairs_host_chunked(h, users, items, cats, B, out, st);
     const int C = h->C;
     // layout (16-byte aligned sections): cats [B, C] | users [B] | items [B] || out [B] | err [4] | completion word
     const size_t nb = ((size_t)B + 3) & ~(size_t)3;
     const size_t in_bytes = nb * C * 4 + 2 * nb * 4, out_bytes = nb * 4 + 16, total = in_bytes + out_bytes + 16;
-    {
-        const int rc_stage = ensure_stage(h, total, st);
-        if (rc_stage != M2D_OK) return rc_stage;
-    }
+    M2D_REQUIRE(ensure_stage(h, total, st));
     unsigned char *hs = h->stage_host, *ds = h->stage_dev;
     memcpy(hs, cats, (size_t)B * C * 4);
     memcpy(hs + nb * C * 4, users, (size_t)B * 4);
@@ -490,40 +462,41 @@ int m2d_score_pairs_bydish(m2d_engine *h, const int32_t *users, const int32_t *i
                            void *stream)
 {
     if (!h) return M2D_ERR_INVALID_ARG;
-    if (B < 0) return fail(h, M2D_ERR_INVALID_ARG, "m2d_score_pairs_bydish: negative batch");
+    if (B < 0) return negative_batch(h, "m2d_score_pairs_bydish");
     if (B == 0) return M2D_OK;
-    if (!users || !items || !out) return fail(h, M2D_ERR_INVALID_ARG, "m2d_score_pairs_bydish: null buffer");
-    if (!h->dish_cats) return fail(h, M2D_ERR_NOT_CONFIGURED, "call m2d_set_dish_categories first");
-    M2D_HIP_TRY(h, hipSetDevice(h->device));
+    if (!users || !items || !out) return null_buffer(h, "m2d_score_pairs_bydish");
+    M2D_REQUIRE(enter(h, NEEDS_MASKS));
     return m2d_launch_score_pairs(h, users, items, h->dish_cats, true, B, out, (hipStream_t)stream);
+}
+
+// m2d_rank_candidates and m2d_rank_candidates_mlp
+static int rank_candidates(m2d_engine *h, const char *entry, const bool head, const int32_t *users, const int32_t *items, const int32_t *lens,
+                           int64_t nseg, int32_t L, int32_t k, float *out_scores, int32_t *out_items, int32_t *out_flags, void *stream)
+{
+    if (!h) return M2D_ERR_INVALID_ARG;
+    if (nseg < 0 || L < 1 || L > 1024 || k < 1 || k > 64)
+        return fail(h, M2D_ERR_INVALID_ARG, std::string(entry) + ": need nseg >= 0, 1 <= L <= 1024, 1 <= k <= 64");
+    if (nseg == 0) return M2D_OK;
+    if (!users || !items || !out_scores || !out_items || !out_flags) return null_buffer(h, entry);
+    M2D_REQUIRE(enter(h, head ? NEEDS_HEAD | NEEDS_MASKS : NEEDS_MASKS));
+    return m2d_launch_rank_candidates(h, users, items, lens, nseg, L, k, out_scores, out_items, out_flags, (hipStream_t)stream, head);
 }
 
 int m2d_rank_candidates(m2d_engine *h, const int32_t *users, const int32_t *items, const int32_t *lens,
                         int64_t nseg, int32_t L, int32_t k, float *out_scores, int32_t *out_items,
                         int32_t *out_flags, void *stream)
 {
-    if (!h) return M2D_ERR_INVALID_ARG;
-    if (nseg < 0 || L < 1 || L > 1024 || k < 1 || k > 64)
-        return fail(h, M2D_ERR_INVALID_ARG, "m2d_rank_candidates: need nseg >= 0, 1 <= L <= 1024, 1 <= k <= 64");
-    if (nseg == 0) return M2D_OK;
-    if (!users || !items || !out_scores || !out_items || !out_flags)
-        return fail(h, M2D_ERR_INVALID_ARG, "m2d_rank_candidates: null buffer");
-    if (!h->dish_cats) return fail(h, M2D_ERR_NOT_CONFIGURED, "call m2d_set_dish_categories first");
-    M2D_HIP_TRY(h, hipSetDevice(h->device));
-    return m2d_launch_rank_candidates(h, users, items, lens, nseg, L, k, out_scores, out_items, out_flags,
-                                      (hipStream_t)stream);
+    return rank_candidates(h, "m2d_rank_candidates", false, users, items, lens, nseg, L, k, out_scores, out_items, out_flags, stream);
 }
 
 int m2d_topk_users(m2d_engine *h, const int32_t *users, int64_t nU, int32_t k, float *out_scores,
                    int32_t *out_ids, void *stream)
 {
     if (!h) return M2D_ERR_INVALID_ARG;
-    if (nU < 0 || k < 1 || k > 64 || (int64_t)k > h->I)
-        return fail(h, M2D_ERR_INVALID_ARG, "m2d_topk_users: need nU >= 0 and 1 <= k <= min(64, I)");
+    M2D_REQUIRE(topk_range(h, "m2d_topk_users", nU, k, 64));
     if (nU == 0) return M2D_OK;
-    if (!users || !out_scores || !out_ids) return fail(h, M2D_ERR_INVALID_ARG, "m2d_topk_users: null buffer");
-    if (!h->dish_cats) return fail(h, M2D_ERR_NOT_CONFIGURED, "call m2d_set_dish_categories first");
-    M2D_HIP_TRY(h, hipSetDevice(h->device));
+    if (!users || !out_scores || !out_ids) return null_buffer(h, "m2d_topk_users");
+    M2D_REQUIRE(enter(h, NEEDS_MASKS));
     return m2d_launch_topk_users(h, users, nU, k, out_scores, out_ids, (hipStream_t)stream);
 }
 
@@ -533,10 +506,8 @@ int m2d_catalogue_rank(m2d_engine *h, const int32_t *users, const int32_t *items
     if (!h) return M2D_ERR_INVALID_ARG;
     if (n < 0) return fail(h, M2D_ERR_INVALID_ARG, "m2d_catalogue_rank: need n >= 0");
     if (n == 0) return M2D_OK;
-    if (!users || !items || !out_rank || (excl_off && !excl_ids))
-        return fail(h, M2D_ERR_INVALID_ARG, "m2d_catalogue_rank: null buffer");
-    if (!h->dish_cats) return fail(h, M2D_ERR_NOT_CONFIGURED, "call m2d_set_dish_categories first");
-    M2D_HIP_TRY(h, hipSetDevice(h->device));
+    if (!users || !items || !out_rank || (excl_off && !excl_ids)) return null_buffer(h, "m2d_catalogue_rank");
+    M2D_REQUIRE(enter(h, NEEDS_MASKS));
     return m2d_launch_catalogue_rank(h, users, items, n, excl_off, excl_ids, out_rank, out_scores, (hipStream_t)stream);
 }
 
@@ -544,13 +515,10 @@ int m2d_topk_users_excluding(m2d_engine *h, const int32_t *users, int64_t nU, in
                              const int32_t *excl_ids, float *out_scores, int32_t *out_ids, void *stream)
 {
     if (!h) return M2D_ERR_INVALID_ARG;
-    if (nU < 0 || k < 1 || k > 16 || (int64_t)k > h->I)
-        return fail(h, M2D_ERR_INVALID_ARG, "m2d_topk_users_excluding: need nU >= 0 and 1 <= k <= min(16, I)");
+    M2D_REQUIRE(topk_range(h, "m2d_topk_users_excluding", nU, k, 16));
     if (nU == 0) return M2D_OK;
-    if (!users || !out_scores || !out_ids || (excl_off && !excl_ids))
-        return fail(h, M2D_ERR_INVALID_ARG, "m2d_topk_users_excluding: null buffer");
-    if (!h->dish_cats) return fail(h, M2D_ERR_NOT_CONFIGURED, "call m2d_set_dish_categories first");
-    M2D_HIP_TRY(h, hipSetDevice(h->device));
+    if (!users || !out_scores || !out_ids || (excl_off && !excl_ids)) return null_buffer(h, "m2d_topk_users_excluding");
+    M2D_REQUIRE(enter(h, NEEDS_MASKS));
     return m2d_launch_topk_users_excluding(h, users, nU, k, excl_off, excl_ids, out_scores, out_ids, (hipStream_t)stream);
 }
 
@@ -559,9 +527,8 @@ int m2d_score_slate(m2d_engine *h, const int32_t *users, int64_t nU, const int32
     if (!h) return M2D_ERR_INVALID_ARG;
     if (nU < 0 || nD < 1 || nD > h->I) return fail(h, M2D_ERR_INVALID_ARG, "m2d_score_slate: need nU >= 0 and 1 <= nD <= I");
     if (nU == 0) return M2D_OK;
-    if (!users || !slate || !out) return fail(h, M2D_ERR_INVALID_ARG, "m2d_score_slate: null buffer");
-    if (!h->dish_cats) return fail(h, M2D_ERR_NOT_CONFIGURED, "call m2d_set_dish_categories first");
-    M2D_HIP_TRY(h, hipSetDevice(h->device));
+    if (!users || !slate || !out) return null_buffer(h, "m2d_score_slate");
+    M2D_REQUIRE(enter(h, NEEDS_MASKS));
     return m2d_launch_slate(h, "m2d_score_slate", users, nU, slate, nD, 0, out, nullptr, nullptr, (hipStream_t)stream);
 }
 
@@ -572,9 +539,8 @@ int m2d_topk_slate(m2d_engine *h, const int32_t *users, int64_t nU, const int32_
     if (nU < 0 || nD < 1 || nD > h->I || k < 1 || k > 64 || (int64_t)k > nD)
         return fail(h, M2D_ERR_INVALID_ARG, "m2d_topk_slate: need nU >= 0, 1 <= nD <= I and 1 <= k <= min(64, nD)");
     if (nU == 0) return M2D_OK;
-    if (!users || !slate || !out_scores || !out_ids) return fail(h, M2D_ERR_INVALID_ARG, "m2d_topk_slate: null buffer");
-    if (!h->dish_cats) return fail(h, M2D_ERR_NOT_CONFIGURED, "call m2d_set_dish_categories first");
-    M2D_HIP_TRY(h, hipSetDevice(h->device));
+    if (!users || !slate || !out_scores || !out_ids) return null_buffer(h, "m2d_topk_slate");
+    M2D_REQUIRE(enter(h, NEEDS_MASKS));
     return m2d_launch_slate(h, "m2d_topk_slate", users, nU, slate, nD, k, nullptr, out_scores, out_ids, (hipStream_t)stream);
 }
 
@@ -583,67 +549,42 @@ int m2d_clear_ingredients(m2d_engine *h)
     if (!h) return M2D_ERR_INVALID_ARG;
     (void)hipSetDevice(h->device);
     (void)hipDeviceSynchronize();
-    if (h->own_ing) {
-        if (h->ing) (void)hipFree((void *)h->ing);
-        if (h->ing_off) (void)hipFree((void *)h->ing_off);
-        if (h->ing_ids) (void)hipFree((void *)h->ing_ids);
-        if (h->ing_w) (void)hipFree((void *)h->ing_w);
-    }
-    if (h->dish_high) (void)hipFree(h->dish_high);
-    h->ing = nullptr; h->ing_off = nullptr; h->ing_ids = nullptr; h->ing_w = nullptr; h->dish_high = nullptr;
-    h->own_ing = false; h->ing_rows = 0; h->ing_nnz = 0;
+    h->ing.reset(); h->ing_off.reset(); h->ing_ids.reset(); h->ing_w.reset(); h->dish_high.reset();
+    h->ing_rows = 0; h->ing_nnz = 0;
     m2d_mark_written(h, M2D_TAB_ING, M2D_BY_CALLER);       // H[d] was part of the scan
     return M2D_OK;
 }
 
+// (failure contract: m2d.h, "Setters".  None of the four arrays has an alignment rule, so nothing of a borrowed one is refused.)
 int m2d_set_ingredients(m2d_engine *h, const float *ing, int64_t R, const int32_t *off, const int32_t *ids,
                         const float *w, int64_t nnz, int table_flags)
 {
     if (!h || !ing || !off || (!ids && nnz > 0) || R <= 0 || nnz < 0 || nnz > INT32_MAX)
         return fail(h, M2D_ERR_INVALID_ARG, "m2d_set_ingredients: bad argument");
-    if (table_flags != M2D_TABLES_HOST && table_flags != M2D_TABLES_DEVICE)
-        return fail(h, M2D_ERR_INVALID_ARG, "m2d_set_ingredients: bad table_flags");
+    if (!table_flags_ok(table_flags)) return fail(h, M2D_ERR_INVALID_ARG, "m2d_set_ingredients: bad table_flags");
     // an id error latched by an earlier launch is reported as what it is, before the CSR check can mislabel it
-    int rc = m2d_check(h, nullptr, nullptr, nullptr);
-    if (rc != M2D_OK) return rc;
-    if ((rc = m2d_clear_ingredients(h)) != M2D_OK) return rc;
-    M2D_HIP_TRY(h, hipSetDevice(h->device));
-    if (table_flags == M2D_TABLES_DEVICE) {
-        h->ing = ing; h->ing_off = off; h->ing_ids = ids; h->ing_w = w; h->own_ing = false;
-    } else {
-        bool own = false;
-        const float *t = nullptr;
-        if ((rc = adopt_table(h, ing, (size_t)R * h->E, table_flags, &h->ing, &own)) != M2D_OK) return rc;
-        h->own_ing = true;
-        if ((rc = adopt_table(h, reinterpret_cast<const float *>(off), (size_t)h->I + 1, table_flags, &t, &own)) != M2D_OK) return rc;
-        h->ing_off = reinterpret_cast<const int32_t *>(t);
-        if (nnz > 0) {
-            if ((rc = adopt_table(h, reinterpret_cast<const float *>(ids), (size_t)nnz, table_flags, &t, &own)) != M2D_OK) return rc;
-            h->ing_ids = reinterpret_cast<const int32_t *>(t);
-            if (w) {
-                if ((rc = adopt_table(h, w, (size_t)nnz, table_flags, &h->ing_w, &own)) != M2D_OK) return rc;
-            }
-        }
-    }
+    M2D_REQUIRE(m2d_check(h, nullptr, nullptr, nullptr));
+    M2D_REQUIRE(m2d_clear_ingredients(h));      // replacement begins: from here on a failure leaves no ingredient table
+    M2D_REQUIRE(enter(h));
+    m2d_table<float> t_ing, t_w;
+    m2d_table<int32_t> t_off, t_ids;
+    m2d_dev_buf<float> high;
+    M2D_REQUIRE(adopt(h, ing, (size_t)R * h->E, table_flags, t_ing));
+    M2D_REQUIRE(adopt(h, off, (size_t)h->I + 1, table_flags, t_off));
+    M2D_REQUIRE(adopt(h, ids, (size_t)nnz, table_flags, t_ids));
+    M2D_REQUIRE(adopt(h, w, (size_t)nnz, table_flags, t_w));
+    M2D_REQUIRE(high.grow(h, (size_t)h->I * h->E));
+    if (!aligned16(high)) return fail(h, M2D_ERR_HIP, "dish_high not aligned");
+    M2D_REQUIRE(m2d_launch_check_csr(h, t_off, nnz, nullptr));
+    if (m2d_check(h, nullptr, nullptr, nullptr) != M2D_OK)
+        return fail(h, M2D_ERR_BAD_INGREDIENT,
+                    "m2d_set_ingredients: offsets are not a CSR row pointer (off[0] = 0, non-decreasing, off[I] = nnz)");
+    M2D_REQUIRE(m2d_launch_build_dish_high(h, t_ing, t_off, t_ids, t_w, R, high, nullptr));
+    if (m2d_check(h, nullptr, nullptr, nullptr) != M2D_OK) return fail(h, M2D_ERR_BAD_INGREDIENT, "m2d_set_ingredients: " + h->last_error);
+    h->ing = std::move(t_ing); h->ing_off = std::move(t_off); h->ing_ids = std::move(t_ids); h->ing_w = std::move(t_w);
+    h->dish_high = std::move(high);
     h->ing_rows = R;
     h->ing_nnz = nnz;
-    M2D_HIP_TRY(h, hipMalloc((void **)&h->dish_high, (size_t)h->I * h->E * sizeof(float)));
-    if (!aligned16(h->dish_high)) return fail(h, M2D_ERR_HIP, "dish_high not aligned");
-    if ((rc = m2d_launch_check_csr(h, nullptr)) != M2D_OK) return rc;
-    rc = m2d_check(h, nullptr, nullptr, nullptr);
-    if (rc != M2D_OK) {
-        (void)m2d_clear_ingredients(h);
-        h->last_error = "m2d_set_ingredients: offsets are not a CSR row pointer (off[0] = 0, non-decreasing, off[I] = nnz)";
-        return M2D_ERR_BAD_INGREDIENT;
-    }
-    if ((rc = m2d_launch_build_dish_high(h, nullptr)) != M2D_OK) return rc;
-    rc = m2d_check(h, nullptr, nullptr, nullptr);
-    if (rc != M2D_OK) {
-        std::string msg = h->last_error;
-        (void)m2d_clear_ingredients(h);
-        h->last_error = "m2d_set_ingredients: " + msg;
-        return M2D_ERR_BAD_INGREDIENT;
-    }
     m2d_mark_written(h, M2D_TAB_ING, M2D_BY_CALLER);       // H[d] is part of the scan
     return M2D_OK;
 }
@@ -653,54 +594,35 @@ int m2d_clear_recipes(m2d_engine *h)
     if (!h) return M2D_ERR_INVALID_ARG;
     (void)hipSetDevice(h->device);
     (void)hipDeviceSynchronize();
-    if (h->own_rcp) {
-        if (h->rcp_off) (void)hipFree((void *)h->rcp_off);
-        if (h->rcp_ids) (void)hipFree((void *)h->rcp_ids);
-    }
-    h->rcp_off = nullptr; h->rcp_ids = nullptr;
-    h->rcp_set = h->own_rcp = false; h->rcp_rows = 0; h->rcp_nnz = 0;
+    h->rcp_off.reset(); h->rcp_ids.reset();
+    h->rcp_set = false; h->rcp_rows = 0; h->rcp_nnz = 0;
     return M2D_OK;
 }
 
+// (failure contract: m2d.h, "Setters")
 int m2d_set_recipes(m2d_engine *h, int64_t R, const int32_t *off, const int32_t *ids, int64_t nnz, int32_t flags)
 {
     if (!h || !off || (!ids && nnz > 0) || R < 1 || R > INT32_MAX || nnz < 0 || nnz > INT32_MAX)
         return fail(h, M2D_ERR_INVALID_ARG, "m2d_set_recipes: bad argument (need 1 <= R, 0 <= nnz, both within int32, offsets, and ids where nnz > 0)");
-    if (flags != M2D_TABLES_HOST && flags != M2D_TABLES_DEVICE) return fail(h, M2D_ERR_INVALID_ARG, "m2d_set_recipes: bad flags");
+    if (!table_flags_ok(flags)) return fail(h, M2D_ERR_INVALID_ARG, "m2d_set_recipes: bad flags");
     // an id error latched by an earlier launch is reported as what it is, before the checks below can mislabel it
-    int rc = m2d_check(h, nullptr, nullptr, nullptr);
-    if (rc != M2D_OK) return rc;
-    if ((rc = m2d_clear_recipes(h)) != M2D_OK) return rc;
-    M2D_HIP_TRY(h, hipSetDevice(h->device));
-    if (flags == M2D_TABLES_DEVICE) {
-        h->rcp_off = off; h->rcp_ids = ids;
-    } else {
-        bool own = false;
-        const float *t = nullptr;
-        h->own_rcp = true;
-        if ((rc = adopt_table(h, reinterpret_cast<const float *>(off), (size_t)h->I + 1, flags, &t, &own)) != M2D_OK) return rc;
-        h->rcp_off = reinterpret_cast<const int32_t *>(t);
-        if (nnz > 0) {
-            if ((rc = adopt_table(h, reinterpret_cast<const float *>(ids), (size_t)nnz, flags, &t, &own)) != M2D_OK) {
-                (void)m2d_clear_recipes(h);
-                return rc;
-            }
-            h->rcp_ids = reinterpret_cast<const int32_t *>(t);
-        }
-    }
+    M2D_REQUIRE(m2d_check(h, nullptr, nullptr, nullptr));
+    M2D_REQUIRE(m2d_clear_recipes(h));          // replacement begins: from here on a failure leaves no recipes
+    M2D_REQUIRE(enter(h));
+    m2d_table<int32_t> t_off, t_ids;
+    M2D_REQUIRE(adopt(h, off, (size_t)h->I + 1, flags, t_off));
+    M2D_REQUIRE(adopt(h, ids, (size_t)nnz, flags, t_ids));
     // the row pointer first: the id pass reads ids[0, nnz) only, but nothing may call the lists valid before both have passed
-    // (every failure from here on leaves the recipes unset; one that is not the check's own finding -- a HIP error -- keeps its code)
-    auto unset = [&](int code, const std::string &msg) {
-        (void)m2d_clear_recipes(h);
-        h->last_error = "m2d_set_recipes: " + msg;
-        return code;
-    };
-    if ((rc = m2d_launch_check_csr(h, h->rcp_off, nnz, nullptr)) != M2D_OK) return unset(rc, h->last_error);
+    // (a failure that is not the check's own finding -- a HIP error -- keeps its code)
+    auto refused = [&](int code, const std::string &msg) { return fail(h, code, "m2d_set_recipes: " + msg); };
+    int rc;
+    if ((rc = m2d_launch_check_csr(h, t_off, nnz, nullptr)) != M2D_OK) return refused(rc, h->last_error);
     if ((rc = m2d_check(h, nullptr, nullptr, nullptr)) != M2D_OK)
-        return rc == M2D_ERR_BAD_INGREDIENT ? unset(rc, "offsets are not a CSR row pointer (off[0] = 0, non-decreasing, off[I] = nnz)")
-                                            : unset(rc, h->last_error);
-    if ((rc = m2d_launch_check_recipe_ids(h, h->rcp_ids, nnz, R, nullptr)) != M2D_OK) return unset(rc, h->last_error);
-    if ((rc = m2d_check(h, nullptr, nullptr, nullptr)) != M2D_OK) return unset(rc, h->last_error);
+        return rc == M2D_ERR_BAD_INGREDIENT ? refused(rc, "offsets are not a CSR row pointer (off[0] = 0, non-decreasing, off[I] = nnz)")
+                                            : refused(rc, h->last_error);
+    if ((rc = m2d_launch_check_recipe_ids(h, t_ids, nnz, R, nullptr)) != M2D_OK) return refused(rc, h->last_error);
+    if ((rc = m2d_check(h, nullptr, nullptr, nullptr)) != M2D_OK) return refused(rc, h->last_error);
+    h->rcp_off = std::move(t_off); h->rcp_ids = std::move(t_ids);
     h->rcp_rows = R;
     h->rcp_nnz = nnz;
     h->rcp_set = true;
@@ -713,60 +635,52 @@ int m2d_cookable_dishes(m2d_engine *h, const int32_t *market, int64_t nM, int32_
     if (!h) return M2D_ERR_INVALID_ARG;
     if (nM < 0 || nM > INT32_MAX || max_missing < 0)
         return fail(h, M2D_ERR_INVALID_ARG, "m2d_cookable_dishes: need 0 <= nM < 2^31 and max_missing >= 0");
-    if ((!market && nM > 0) || !out_ids || !out_count) return fail(h, M2D_ERR_INVALID_ARG, "m2d_cookable_dishes: null buffer");
-    if (!h->rcp_set) return fail(h, M2D_ERR_NOT_CONFIGURED, "call m2d_set_recipes first");
-    M2D_HIP_TRY(h, hipSetDevice(h->device));
+    if ((!market && nM > 0) || !out_ids || !out_count) return null_buffer(h, "m2d_cookable_dishes");
+    M2D_REQUIRE(enter(h, NEEDS_RECIPES));
     return m2d_launch_cookable(h, market, nM, max_missing, out_ids, out_missing, out_count, (hipStream_t)stream);
+}
+
+// m2d_topk_markets and m2d_topk_markets_excluding (excl_off, excl_ids, out_missing: the latter's)
+static int topk_markets(m2d_engine *h, const char *entry, const int32_t *users, int64_t nQ, const int64_t *market_off, const int32_t *market_ids,
+                        int64_t nnzM, const int64_t *excl_off, const int32_t *excl_ids, int32_t k, int32_t max_missing, float *out_scores,
+                        int32_t *out_ids, int32_t *out_counts, int32_t *out_missing, void *stream)
+{
+    if (!h) return M2D_ERR_INVALID_ARG;
+    if (nQ < 0 || nnzM < 0 || k < 1 || k > 64 || max_missing < 0)
+        return fail(h, M2D_ERR_INVALID_ARG, std::string(entry) + ": need nQ >= 0, nnzM >= 0, 1 <= k <= 64 and max_missing >= 0");
+    if (nQ == 0) return M2D_OK;
+    if (!users || !market_off || (!market_ids && nnzM > 0) || !out_scores || !out_ids) return null_buffer(h, entry);
+    M2D_REQUIRE(enter(h, NEEDS_RECIPES | NEEDS_MASKS | PLAIN_SCORES_ONLY, entry));
+    return m2d_launch_topk_markets(h, users, nQ, market_off, market_ids, nnzM, k, max_missing, out_scores, out_ids, out_counts,
+                                   (hipStream_t)stream, excl_off, excl_ids, out_missing);
 }
 
 int m2d_topk_markets(m2d_engine *h, const int32_t *users, int64_t nQ, const int64_t *market_off, const int32_t *market_ids, int64_t nnzM,
                      int32_t k, int32_t max_missing, float *out_scores, int32_t *out_ids, int32_t *out_counts, void *stream)
 {
-    if (!h) return M2D_ERR_INVALID_ARG;
-    if (nQ < 0 || nnzM < 0 || k < 1 || k > 64 || max_missing < 0)
-        return fail(h, M2D_ERR_INVALID_ARG, "m2d_topk_markets: need nQ >= 0, nnzM >= 0, 1 <= k <= 64 and max_missing >= 0");
-    if (nQ == 0) return M2D_OK;
-    if (!users || !market_off || (!market_ids && nnzM > 0) || !out_scores || !out_ids)
-        return fail(h, M2D_ERR_INVALID_ARG, "m2d_topk_markets: null buffer");
-    if (!h->rcp_set) return fail(h, M2D_ERR_NOT_CONFIGURED, "call m2d_set_recipes first");
-    if (!h->dish_cats) return fail(h, M2D_ERR_NOT_CONFIGURED, "call m2d_set_dish_categories first");
-    if (h->ing) return fail(h, M2D_ERR_UNSUPPORTED, "m2d_topk_markets: the ingredient table is set");
-    if (h->mlp_w1) return fail(h, M2D_ERR_UNSUPPORTED, "m2d_topk_markets: the MLP head is set");
-    M2D_HIP_TRY(h, hipSetDevice(h->device));
-    return m2d_launch_topk_markets(h, users, nQ, market_off, market_ids, nnzM, k, max_missing, out_scores, out_ids, out_counts,
-                                   (hipStream_t)stream);
+    return topk_markets(h, "m2d_topk_markets", users, nQ, market_off, market_ids, nnzM, nullptr, nullptr, k, max_missing, out_scores, out_ids,
+                        out_counts, nullptr, stream);
 }
 
 int m2d_topk_markets_excluding(m2d_engine *h, const int32_t *users, int64_t nQ, const int64_t *market_off, const int32_t *market_ids,
                                int64_t nnzM, const int64_t *excl_off, const int32_t *excl_ids, int32_t k, int32_t max_missing,
                                float *out_scores, int32_t *out_ids, int32_t *out_counts, int32_t *out_missing, void *stream)
 {
-    if (!h) return M2D_ERR_INVALID_ARG;
-    if (nQ < 0 || nnzM < 0 || k < 1 || k > 64 || max_missing < 0)
-        return fail(h, M2D_ERR_INVALID_ARG, "m2d_topk_markets_excluding: need nQ >= 0, nnzM >= 0, 1 <= k <= 64 and max_missing >= 0");
-    if (nQ == 0) return M2D_OK;
-    if (!users || !market_off || (!market_ids && nnzM > 0) || !out_scores || !out_ids)
-        return fail(h, M2D_ERR_INVALID_ARG, "m2d_topk_markets_excluding: null buffer");
-    if (!h->rcp_set) return fail(h, M2D_ERR_NOT_CONFIGURED, "call m2d_set_recipes first");
-    if (!h->dish_cats) return fail(h, M2D_ERR_NOT_CONFIGURED, "call m2d_set_dish_categories first");
-    if (h->ing) return fail(h, M2D_ERR_UNSUPPORTED, "m2d_topk_markets_excluding: the ingredient table is set");
-    if (h->mlp_w1) return fail(h, M2D_ERR_UNSUPPORTED, "m2d_topk_markets_excluding: the MLP head is set");
-    M2D_HIP_TRY(h, hipSetDevice(h->device));
-    return m2d_launch_topk_markets(h, users, nQ, market_off, market_ids, nnzM, k, max_missing, out_scores, out_ids, out_counts,
-                                   (hipStream_t)stream, excl_off, excl_ids, out_missing);
+    return topk_markets(h, "m2d_topk_markets_excluding", users, nQ, market_off, market_ids, nnzM, excl_off, excl_ids, k, max_missing,
+                        out_scores, out_ids, out_counts, out_missing, stream);
 }
 
 int m2d_score_pairs_ingredients(m2d_engine *h, const int32_t *users, const int32_t *items, const float *cats,
                                 int64_t B, float *out, void *stream)
 {
     if (!h) return M2D_ERR_INVALID_ARG;
-    if (B < 0) return fail(h, M2D_ERR_INVALID_ARG, "m2d_score_pairs_ingredients: negative batch");
+    if (B < 0) return negative_batch(h, "m2d_score_pairs_ingredients");
     if (B == 0) return M2D_OK;
-    if (!users || !items || !out) return fail(h, M2D_ERR_INVALID_ARG, "m2d_score_pairs_ingredients: null buffer");
+    if (!users || !items || !out) return null_buffer(h, "m2d_score_pairs_ingredients");
     if (!h->dish_high) return fail(h, M2D_ERR_NOT_CONFIGURED, "call m2d_set_ingredients first");
     if (!cats && !h->dish_cats) return fail(h, M2D_ERR_NOT_CONFIGURED, "cats == NULL needs m2d_set_dish_categories");
     if (cats && h->C == 4 && !aligned16(cats)) return fail(h, M2D_ERR_INVALID_ARG, "cats must be 16-byte aligned");
-    M2D_HIP_TRY(h, hipSetDevice(h->device));
+    M2D_REQUIRE(enter(h));
     return m2d_launch_score_pairs(h, users, items, cats ? cats : h->dish_cats, cats == nullptr, B, out,
                                   (hipStream_t)stream, /*use_ingredients=*/true);
 }
@@ -780,8 +694,8 @@ int m2d_write_memory(m2d_engine *h, const int32_t *users, const int32_t *items, 
     if (which <= 0 || (which & ~(M2D_WRITE_PERSONAL | M2D_WRITE_GENERAL)))
         return fail(h, M2D_ERR_INVALID_ARG, "m2d_write_memory: which must be M2D_WRITE_PERSONAL, M2D_WRITE_GENERAL or both");
     if (!general_memory || (B > 0 && (!users || !items || !cats || !write_sign || !labels)))
-        return fail(h, M2D_ERR_INVALID_ARG, "m2d_write_memory: null buffer");
-    M2D_HIP_TRY(h, hipSetDevice(h->device));
+        return null_buffer(h, "m2d_write_memory");
+    M2D_REQUIRE(enter(h));
     return m2d_launch_write_memory(h, users, items, cats, write_sign, labels, B, L, general_memory, beta_1, beta_2,
                                    alpha, which, out_sums, (hipStream_t)stream);
 }
@@ -791,36 +705,33 @@ int m2d_clear_mlp_head(m2d_engine *h)
     if (!h) return M2D_ERR_INVALID_ARG;
     (void)hipSetDevice(h->device);
     (void)hipDeviceSynchronize();
-    if (h->own_mlp) {
-        for (const float *q : {h->mlp_w1, h->mlp_b1, h->mlp_w2, h->mlp_b2, h->mlp_w3})
-            if (q) (void)hipFree((void *)q);
-    }
-    m2d_mlp_free_derived(h, false);
-    h->mlp_w1 = h->mlp_b1 = h->mlp_w2 = h->mlp_b2 = h->mlp_w3 = nullptr;
-    h->own_mlp = false;
+    h->mlp_w1.reset(); h->mlp_b1.reset(); h->mlp_w2.reset(); h->mlp_b2.reset(); h->mlp_w3.reset();
+    m2d_mlp_free_derived(h);
     h->mlp_h1 = h->mlp_h2 = 0;
     return M2D_OK;
 }
 
+// (failure contract: m2d.h, "Setters")
 int m2d_set_mlp_head(m2d_engine *h, const float *W1, const float *b1, const float *W2, const float *b2,
                      const float *w3, float b3, int32_t H1, int32_t H2, int table_flags)
 {
     if (!h || !W1 || !b1 || !W2 || !b2 || !w3 || H1 <= 0 || H2 <= 0)
         return fail(h, M2D_ERR_INVALID_ARG, "m2d_set_mlp_head: bad argument");
-    if (table_flags != M2D_TABLES_HOST && table_flags != M2D_TABLES_DEVICE)
-        return fail(h, M2D_ERR_INVALID_ARG, "m2d_set_mlp_head: bad table_flags");
-    int rc = m2d_clear_mlp_head(h);
-    if (rc != M2D_OK) return rc;
-    M2D_HIP_TRY(h, hipSetDevice(h->device));
+    if (!table_flags_ok(table_flags)) return fail(h, M2D_ERR_INVALID_ARG, "m2d_set_mlp_head: bad table_flags");
+    if (borrowed_misaligned(W1, table_flags) || borrowed_misaligned(W2, table_flags))
+        return fail(h, M2D_ERR_INVALID_ARG, "MLP weights must be 16-byte aligned");
+    M2D_REQUIRE(m2d_clear_mlp_head(h));         // replacement begins: from here on a failure leaves no head
+    M2D_REQUIRE(enter(h));
     const size_t K = (size_t)(h->C + 1) * h->E;
-    bool own = false;
-    if ((rc = adopt_table(h, W1, K * H1, table_flags, &h->mlp_w1, &own)) != M2D_OK) return rc;
-    h->own_mlp = own;
-    if ((rc = adopt_table(h, b1, (size_t)H1, table_flags, &h->mlp_b1, &own)) != M2D_OK) return rc;
-    if ((rc = adopt_table(h, W2, (size_t)H1 * H2, table_flags, &h->mlp_w2, &own)) != M2D_OK) return rc;
-    if ((rc = adopt_table(h, b2, (size_t)H2, table_flags, &h->mlp_b2, &own)) != M2D_OK) return rc;
-    if ((rc = adopt_table(h, w3, (size_t)H2, table_flags, &h->mlp_w3, &own)) != M2D_OK) return rc;
-    if (!aligned16(h->mlp_w1) || !aligned16(h->mlp_w2)) return fail(h, M2D_ERR_INVALID_ARG, "MLP weights must be 16-byte aligned");
+    m2d_table<float> t_w1, t_b1, t_w2, t_b2, t_w3;
+    M2D_REQUIRE(adopt(h, W1, K * H1, table_flags, t_w1));
+    M2D_REQUIRE(adopt(h, b1, (size_t)H1, table_flags, t_b1));
+    M2D_REQUIRE(adopt(h, W2, (size_t)H1 * H2, table_flags, t_w2));
+    M2D_REQUIRE(adopt(h, b2, (size_t)H2, table_flags, t_b2));
+    M2D_REQUIRE(adopt(h, w3, (size_t)H2, table_flags, t_w3));
+    if (!aligned16(t_w1) || !aligned16(t_w2)) return fail(h, M2D_ERR_INVALID_ARG, "MLP weights must be 16-byte aligned");
+    h->mlp_w1 = std::move(t_w1); h->mlp_b1 = std::move(t_b1); h->mlp_w2 = std::move(t_w2); h->mlp_b2 = std::move(t_b2);
+    h->mlp_w3 = std::move(t_w3);
     h->mlp_b3 = b3;
     h->mlp_h1 = H1;
     h->mlp_h2 = H2;
@@ -831,12 +742,10 @@ int m2d_score_pairs_mlp(m2d_engine *h, const int32_t *users, const int32_t *item
                         void *stream)
 {
     if (!h) return M2D_ERR_INVALID_ARG;
-    if (B < 0) return fail(h, M2D_ERR_INVALID_ARG, "m2d_score_pairs_mlp: negative batch");
+    if (B < 0) return negative_batch(h, "m2d_score_pairs_mlp");
     if (B == 0) return M2D_OK;
-    if (!users || !items || !out) return fail(h, M2D_ERR_INVALID_ARG, "m2d_score_pairs_mlp: null buffer");
-    if (!h->mlp_w1) return fail(h, M2D_ERR_NOT_CONFIGURED, "call m2d_set_mlp_head first");
-    if (!h->dish_cats) return fail(h, M2D_ERR_NOT_CONFIGURED, "call m2d_set_dish_categories first");
-    M2D_HIP_TRY(h, hipSetDevice(h->device));
+    if (!users || !items || !out) return null_buffer(h, "m2d_score_pairs_mlp");
+    M2D_REQUIRE(enter(h, NEEDS_HEAD | NEEDS_MASKS));
     return m2d_launch_score_pairs_mlp(h, users, items, B, out, (hipStream_t)stream);
 }
 
@@ -844,15 +753,11 @@ int m2d_topk_users_mlp(m2d_engine *h, const int32_t *users, int64_t nU, int32_t 
                        int32_t *out_ids, void *stream)
 {
     if (!h) return M2D_ERR_INVALID_ARG;
-    if (nU < 0 || k < 1 || k > 64 || (int64_t)k > h->I)
-        return fail(h, M2D_ERR_INVALID_ARG, "m2d_topk_users_mlp: need nU >= 0 and 1 <= k <= min(64, I)");
-    if (candidates != 0 && (candidates < k || candidates > 64 || (int64_t)candidates > h->I))
-        return fail(h, M2D_ERR_INVALID_ARG, "m2d_topk_users_mlp: candidates must be 0 (exact) or k <= candidates <= min(64, I)");
+    M2D_REQUIRE(topk_range(h, "m2d_topk_users_mlp", nU, k, 64));
+    M2D_REQUIRE(candidates_range(h, "m2d_topk_users_mlp", k, candidates, 64));
     if (nU == 0) return M2D_OK;
-    if (!users || !out_scores || !out_ids) return fail(h, M2D_ERR_INVALID_ARG, "m2d_topk_users_mlp: null buffer");
-    if (!h->mlp_w1) return fail(h, M2D_ERR_NOT_CONFIGURED, "call m2d_set_mlp_head first");
-    if (!h->dish_cats) return fail(h, M2D_ERR_NOT_CONFIGURED, "call m2d_set_dish_categories first");
-    M2D_HIP_TRY(h, hipSetDevice(h->device));
+    if (!users || !out_scores || !out_ids) return null_buffer(h, "m2d_topk_users_mlp");
+    M2D_REQUIRE(enter(h, NEEDS_HEAD | NEEDS_MASKS));
     return m2d_launch_topk_users_mlp(h, users, nU, k, candidates, nullptr, nullptr, out_scores, out_ids, /*deep=*/false, (hipStream_t)stream);
 }
 
@@ -862,15 +767,11 @@ int m2d_topk_users_mlp_excluding(m2d_engine *h, const int32_t *users, int64_t nU
     if (!h) return M2D_ERR_INVALID_ARG;
     if (!excl_off)                                  // no exclusions: m2d_topk_users_mlp's launches and words, its argument rules
         return m2d_topk_users_mlp(h, users, nU, k, candidates, out_scores, out_ids, stream);
-    if (nU < 0 || k < 1 || k > 64 || (int64_t)k > h->I)
-        return fail(h, M2D_ERR_INVALID_ARG, "m2d_topk_users_mlp_excluding: need nU >= 0 and 1 <= k <= min(64, I)");
-    if (candidates != 0 && (candidates < k || candidates > 16 || (int64_t)candidates > h->I))
-        return fail(h, M2D_ERR_INVALID_ARG, "m2d_topk_users_mlp_excluding: with exclusions candidates must be 0 (exact) or k <= candidates <= min(16, I)");
+    M2D_REQUIRE(topk_range(h, "m2d_topk_users_mlp_excluding", nU, k, 64));
+    M2D_REQUIRE(candidates_range(h, "m2d_topk_users_mlp_excluding", k, candidates, 16, "with exclusions "));
     if (nU == 0) return M2D_OK;
-    if (!users || !out_scores || !out_ids || !excl_ids) return fail(h, M2D_ERR_INVALID_ARG, "m2d_topk_users_mlp_excluding: null buffer");
-    if (!h->mlp_w1) return fail(h, M2D_ERR_NOT_CONFIGURED, "call m2d_set_mlp_head first");
-    if (!h->dish_cats) return fail(h, M2D_ERR_NOT_CONFIGURED, "call m2d_set_dish_categories first");
-    M2D_HIP_TRY(h, hipSetDevice(h->device));
+    if (!users || !out_scores || !out_ids || !excl_ids) return null_buffer(h, "m2d_topk_users_mlp_excluding");
+    M2D_REQUIRE(enter(h, NEEDS_HEAD | NEEDS_MASKS));
     return m2d_launch_topk_users_mlp(h, users, nU, k, candidates, excl_off, excl_ids, out_scores, out_ids, /*deep=*/false, (hipStream_t)stream);
 }
 
@@ -878,12 +779,10 @@ int m2d_topk_users_deep(m2d_engine *h, const int32_t *users, int64_t nU, int32_t
                         float *out_scores, int32_t *out_ids, void *stream)
 {
     if (!h) return M2D_ERR_INVALID_ARG;
-    if (nU < 0 || k < 1 || k > 1024 || (int64_t)k > h->I)
-        return fail(h, M2D_ERR_INVALID_ARG, "m2d_topk_users_deep: need nU >= 0 and 1 <= k <= min(1024, I)");
+    M2D_REQUIRE(topk_range(h, "m2d_topk_users_deep", nU, k, 1024));
     if (nU == 0) return M2D_OK;
-    if (!users || !out_scores || !out_ids || (excl_off && !excl_ids)) return fail(h, M2D_ERR_INVALID_ARG, "m2d_topk_users_deep: null buffer");
-    if (!h->dish_cats) return fail(h, M2D_ERR_NOT_CONFIGURED, "call m2d_set_dish_categories first");
-    M2D_HIP_TRY(h, hipSetDevice(h->device));
+    if (!users || !out_scores || !out_ids || (excl_off && !excl_ids)) return null_buffer(h, "m2d_topk_users_deep");
+    M2D_REQUIRE(enter(h, NEEDS_MASKS));
     return m2d_launch_topk_users_deep(h, users, nU, k, excl_off, excl_ids, out_scores, out_ids, (hipStream_t)stream);
 }
 
@@ -900,12 +799,11 @@ int m2d_topk_groups(m2d_engine *h, const int32_t *members, int64_t nG, int32_t M
                     const int32_t *excl_ids, float *out_scores, int32_t *out_ids, void *stream)
 {
     if (!h) return M2D_ERR_INVALID_ARG;
-    if (const char *why = group_args_wrong(nG, M, mode)) return fail(h, M2D_ERR_INVALID_ARG, (std::string("m2d_topk_groups: ") + why).c_str());
+    if (const char *why = group_args_wrong(nG, M, mode)) return fail(h, M2D_ERR_INVALID_ARG, std::string("m2d_topk_groups: ") + why);
     if (k < 1 || k > 1024 || (int64_t)k > h->I) return fail(h, M2D_ERR_INVALID_ARG, "m2d_topk_groups: need 1 <= k <= min(1024, I)");
     if (nG == 0) return M2D_OK;
-    if (!members || !out_scores || !out_ids || (excl_off && !excl_ids)) return fail(h, M2D_ERR_INVALID_ARG, "m2d_topk_groups: null buffer");
-    if (!h->dish_cats) return fail(h, M2D_ERR_NOT_CONFIGURED, "call m2d_set_dish_categories first");
-    M2D_HIP_TRY(h, hipSetDevice(h->device));
+    if (!members || !out_scores || !out_ids || (excl_off && !excl_ids)) return null_buffer(h, "m2d_topk_groups");
+    M2D_REQUIRE(enter(h, NEEDS_MASKS));
     return m2d_launch_groups(h, "m2d_topk_groups", members, nG, M, mode, nullptr, 0, k, excl_off, excl_ids, nullptr, out_scores, out_ids,
                              (hipStream_t)stream);
 }
@@ -914,12 +812,11 @@ int m2d_score_groups_slate(m2d_engine *h, const int32_t *members, int64_t nG, in
                            float *out, void *stream)
 {
     if (!h) return M2D_ERR_INVALID_ARG;
-    if (const char *why = group_args_wrong(nG, M, mode)) return fail(h, M2D_ERR_INVALID_ARG, (std::string("m2d_score_groups_slate: ") + why).c_str());
+    if (const char *why = group_args_wrong(nG, M, mode)) return fail(h, M2D_ERR_INVALID_ARG, std::string("m2d_score_groups_slate: ") + why);
     if (nD < 1 || nD > h->I) return fail(h, M2D_ERR_INVALID_ARG, "m2d_score_groups_slate: need 1 <= nD <= I");
     if (nG == 0) return M2D_OK;
-    if (!members || !slate || !out) return fail(h, M2D_ERR_INVALID_ARG, "m2d_score_groups_slate: null buffer");
-    if (!h->dish_cats) return fail(h, M2D_ERR_NOT_CONFIGURED, "call m2d_set_dish_categories first");
-    M2D_HIP_TRY(h, hipSetDevice(h->device));
+    if (!members || !slate || !out) return null_buffer(h, "m2d_score_groups_slate");
+    M2D_REQUIRE(enter(h, NEEDS_MASKS));
     return m2d_launch_groups(h, "m2d_score_groups_slate", members, nG, M, mode, slate, nD, 0, nullptr, nullptr, out, nullptr, nullptr,
                              (hipStream_t)stream);
 }
@@ -928,13 +825,12 @@ int m2d_topk_groups_slate(m2d_engine *h, const int32_t *members, int64_t nG, int
                           int32_t k, float *out_scores, int32_t *out_ids, void *stream)
 {
     if (!h) return M2D_ERR_INVALID_ARG;
-    if (const char *why = group_args_wrong(nG, M, mode)) return fail(h, M2D_ERR_INVALID_ARG, (std::string("m2d_topk_groups_slate: ") + why).c_str());
+    if (const char *why = group_args_wrong(nG, M, mode)) return fail(h, M2D_ERR_INVALID_ARG, std::string("m2d_topk_groups_slate: ") + why);
     if (nD < 1 || nD > h->I || k < 1 || k > 1024 || (int64_t)k > nD)
         return fail(h, M2D_ERR_INVALID_ARG, "m2d_topk_groups_slate: need 1 <= nD <= I and 1 <= k <= min(1024, nD)");
     if (nG == 0) return M2D_OK;
-    if (!members || !slate || !out_scores || !out_ids) return fail(h, M2D_ERR_INVALID_ARG, "m2d_topk_groups_slate: null buffer");
-    if (!h->dish_cats) return fail(h, M2D_ERR_NOT_CONFIGURED, "call m2d_set_dish_categories first");
-    M2D_HIP_TRY(h, hipSetDevice(h->device));
+    if (!members || !slate || !out_scores || !out_ids) return null_buffer(h, "m2d_topk_groups_slate");
+    M2D_REQUIRE(enter(h, NEEDS_MASKS));
     return m2d_launch_groups(h, "m2d_topk_groups_slate", members, nG, M, mode, slate, nD, k, nullptr, nullptr, nullptr, out_scores, out_ids,
                              (hipStream_t)stream);
 }
@@ -943,15 +839,11 @@ int m2d_topk_users_mlp_deep(m2d_engine *h, const int32_t *users, int64_t nU, int
                             const int32_t *excl_ids, float *out_scores, int32_t *out_ids, void *stream)
 {
     if (!h) return M2D_ERR_INVALID_ARG;
-    if (nU < 0 || k < 1 || k > 1024 || (int64_t)k > h->I)
-        return fail(h, M2D_ERR_INVALID_ARG, "m2d_topk_users_mlp_deep: need nU >= 0 and 1 <= k <= min(1024, I)");
-    if (candidates != 0 && (candidates < k || candidates > 1024 || (int64_t)candidates > h->I))
-        return fail(h, M2D_ERR_INVALID_ARG, "m2d_topk_users_mlp_deep: candidates must be 0 (exact) or k <= candidates <= min(1024, I)");
+    M2D_REQUIRE(topk_range(h, "m2d_topk_users_mlp_deep", nU, k, 1024));
+    M2D_REQUIRE(candidates_range(h, "m2d_topk_users_mlp_deep", k, candidates, 1024));
     if (nU == 0) return M2D_OK;
-    if (!users || !out_scores || !out_ids || (excl_off && !excl_ids)) return fail(h, M2D_ERR_INVALID_ARG, "m2d_topk_users_mlp_deep: null buffer");
-    if (!h->mlp_w1) return fail(h, M2D_ERR_NOT_CONFIGURED, "call m2d_set_mlp_head first");
-    if (!h->dish_cats) return fail(h, M2D_ERR_NOT_CONFIGURED, "call m2d_set_dish_categories first");
-    M2D_HIP_TRY(h, hipSetDevice(h->device));
+    if (!users || !out_scores || !out_ids || (excl_off && !excl_ids)) return null_buffer(h, "m2d_topk_users_mlp_deep");
+    M2D_REQUIRE(enter(h, NEEDS_HEAD | NEEDS_MASKS));
     return m2d_launch_topk_users_mlp(h, users, nU, k, candidates, excl_off, excl_ids, out_scores, out_ids, /*deep=*/true, (hipStream_t)stream);
 }
 
@@ -961,8 +853,8 @@ int m2d_select_probe(m2d_engine *h, const float *scores, int64_t rows, int64_t W
     if (!h) return M2D_ERR_INVALID_ARG;
     if (rows < 1 || rows > 0x7fffffff || W < 1 || W > 0x7fffffff || k < 1 || (int64_t)k > W || k > (form ? 64 : 1024) || form < 0 || form > 1)
         return fail(h, M2D_ERR_INVALID_ARG, "m2d_select_probe: need rows >= 1, 1 <= k <= min(W, 1024) (form 1: 64), form 0 / 1");
-    if (!scores || !out_scores || !out_ids) return fail(h, M2D_ERR_INVALID_ARG, "m2d_select_probe: null buffer");
-    M2D_HIP_TRY(h, hipSetDevice(h->device));
+    if (!scores || !out_scores || !out_ids) return null_buffer(h, "m2d_select_probe");
+    M2D_REQUIRE(enter(h));
     SelectJob job = SelectJob::row_major(scores, rows, W, nullptr, 0);
     job.k = k; job.out_scores = out_scores; job.out_ids = out_ids;
     return m2d_launch_select(h, job, /*deep=*/form == 0, (hipStream_t)stream);
@@ -974,37 +866,25 @@ int m2d_catalogue_rank_mlp(m2d_engine *h, const int32_t *users, const int32_t *i
     if (!h) return M2D_ERR_INVALID_ARG;
     if (n < 0) return fail(h, M2D_ERR_INVALID_ARG, "m2d_catalogue_rank_mlp: need n >= 0");
     if (n == 0) return M2D_OK;
-    if (!users || !items || !out_rank || (excl_off && !excl_ids))
-        return fail(h, M2D_ERR_INVALID_ARG, "m2d_catalogue_rank_mlp: null buffer");
-    if (!h->mlp_w1) return fail(h, M2D_ERR_NOT_CONFIGURED, "call m2d_set_mlp_head first");
-    if (!h->dish_cats) return fail(h, M2D_ERR_NOT_CONFIGURED, "call m2d_set_dish_categories first");
-    M2D_HIP_TRY(h, hipSetDevice(h->device));
+    if (!users || !items || !out_rank || (excl_off && !excl_ids)) return null_buffer(h, "m2d_catalogue_rank_mlp");
+    M2D_REQUIRE(enter(h, NEEDS_HEAD | NEEDS_MASKS));
     return m2d_launch_catalogue_rank_mlp(h, users, items, n, excl_off, excl_ids, out_rank, out_scores, (hipStream_t)stream);
 }
 
 int m2d_rank_candidates_mlp(m2d_engine *h, const int32_t *users, const int32_t *items, const int32_t *lens, int64_t nseg, int32_t L,
                             int32_t k, float *out_scores, int32_t *out_items, int32_t *out_flags, void *stream)
 {
-    if (!h) return M2D_ERR_INVALID_ARG;
-    if (nseg < 0 || L < 1 || L > 1024 || k < 1 || k > 64)
-        return fail(h, M2D_ERR_INVALID_ARG, "m2d_rank_candidates_mlp: need nseg >= 0, 1 <= L <= 1024, 1 <= k <= 64");
-    if (nseg == 0) return M2D_OK;
-    if (!users || !items || !out_scores || !out_items || !out_flags)
-        return fail(h, M2D_ERR_INVALID_ARG, "m2d_rank_candidates_mlp: null buffer");
-    if (!h->mlp_w1) return fail(h, M2D_ERR_NOT_CONFIGURED, "call m2d_set_mlp_head first");
-    if (!h->dish_cats) return fail(h, M2D_ERR_NOT_CONFIGURED, "call m2d_set_dish_categories first");
-    M2D_HIP_TRY(h, hipSetDevice(h->device));
-    return m2d_launch_rank_candidates(h, users, items, lens, nseg, L, k, out_scores, out_items, out_flags, (hipStream_t)stream,
-                                      /*head=*/true);
+    return rank_candidates(h, "m2d_rank_candidates_mlp", true, users, items, lens, nseg, L, k, out_scores, out_items, out_flags, stream);
 }
 
+// (failure contract: m2d.h, "Setters" -- m2d_train_setup builds the state aside)
 int m2d_train_begin(m2d_engine *h, int32_t learner, float lr, float clip_norm, void *stream)
 {
     if (!h) return M2D_ERR_INVALID_ARG;
     if (learner < M2D_LEARNER_SGD || learner > M2D_LEARNER_ADAM) return fail(h, M2D_ERR_INVALID_ARG, "m2d_train_begin: unknown learner");
     if (!(clip_norm > 0.f)) return fail(h, M2D_ERR_INVALID_ARG, "m2d_train_begin: clip_norm must be positive");
     if (h->ing) return fail(h, M2D_ERR_UNSUPPORTED, "m2d_train_begin: the ingredient extension has no training step");
-    M2D_HIP_TRY(h, hipSetDevice(h->device));
+    M2D_REQUIRE(enter(h));
     return m2d_train_setup(h, learner, lr, clip_norm, (hipStream_t)stream);
 }
 
@@ -1014,8 +894,8 @@ int m2d_train_step(m2d_engine *h, const int32_t *users, const int32_t *items, co
     if (!h) return M2D_ERR_INVALID_ARG;
     if (!h->train) return fail(h, M2D_ERR_NOT_CONFIGURED, "m2d_train_step: call m2d_train_begin first");
     if (B <= 0) return fail(h, M2D_ERR_INVALID_ARG, "m2d_train_step: need B > 0 (the mean of an empty batch is NaN)");
-    if (!users || !items || !cats || !labels) return fail(h, M2D_ERR_INVALID_ARG, "m2d_train_step: null buffer");
-    M2D_HIP_TRY(h, hipSetDevice(h->device));
+    if (!users || !items || !cats || !labels) return null_buffer(h, "m2d_train_step");
+    M2D_REQUIRE(enter(h));
     return m2d_launch_train_step(h, users, items, cats, labels, B, apply, out, (hipStream_t)stream);
 }
 
@@ -1028,7 +908,7 @@ int m2d_train_slot(m2d_engine *h, int32_t table, int32_t slot, float *buf, int32
     int64_t count = 0;
     (void)m2d_train_get_slot(h, table, slot, &dev, &count);
     if (!dev) return fail(h, M2D_ERR_INVALID_ARG, "m2d_train_slot: this learner has no such slot");
-    M2D_HIP_TRY(h, hipSetDevice(h->device));
+    M2D_REQUIRE(enter(h));
     M2D_HIP_TRY(h, hipMemcpyAsync(restore ? dev : buf, restore ? buf : dev, (size_t)count * 4, hipMemcpyDeviceToDevice, (hipStream_t)stream));
     return M2D_OK;
 }
@@ -1036,10 +916,9 @@ int m2d_train_slot(m2d_engine *h, int32_t table, int32_t slot, float *buf, int32
 int m2d_pm_bf16(m2d_engine *h, uint16_t *buf, void *stream)
 {
     if (!h) return M2D_ERR_INVALID_ARG;
-    if (!buf) return fail(h, M2D_ERR_INVALID_ARG, "m2d_pm_bf16: null buffer");
-    M2D_HIP_TRY(h, hipSetDevice(h->device));
-    const int rc = m2d_ensure_pm_bf16(h, (hipStream_t)stream);
-    if (rc != M2D_OK) return rc;
+    if (!buf) return null_buffer(h, "m2d_pm_bf16");
+    M2D_REQUIRE(enter(h));
+    M2D_REQUIRE(m2d_ensure_pm_bf16(h, (hipStream_t)stream));
     M2D_HIP_TRY(h, hipMemcpyAsync(buf, h->pm_bf16, (size_t)m2d_table_floats(h, 0) * sizeof(uint16_t), hipMemcpyDeviceToDevice, (hipStream_t)stream));
     return M2D_OK;
 }
@@ -1072,7 +951,7 @@ int m2d_check(m2d_engine *h, void *stream, int64_t *bad_value, int64_t *bad_inde
 {
     if (!h) return M2D_ERR_INVALID_ARG;
     hipStream_t st = (hipStream_t)stream;
-    M2D_HIP_TRY(h, hipSetDevice(h->device));
+    M2D_REQUIRE(enter(h));
     M2D_HIP_TRY(h, hipMemcpyAsync(h->err_host, h->err_dev, 4 * sizeof(int32_t), hipMemcpyDeviceToHost, st));
     M2D_HIP_TRY(h, hipStreamSynchronize(st));
     const int code = h->err_host[0];
@@ -1108,148 +987,162 @@ int m2d_stream_read_probe(m2d_engine *h, const void *buf, int64_t bytes, float *
 {
     if (!h || !buf || !sink || bytes <= 0 || (bytes & 15) || !aligned16(buf))
         return fail(h, M2D_ERR_INVALID_ARG, "m2d_stream_read_probe: need a 16-byte aligned buffer and size");
-    M2D_HIP_TRY(h, hipSetDevice(h->device));
+    M2D_REQUIRE(enter(h));
     hipLaunchKernelGGL(m2d_stream_read, dim3(h->num_cu * 2), dim3(256), 0, (hipStream_t)stream,
                        reinterpret_cast<const v4f *>(buf), bytes / 16, sink);
     M2D_HIP_TRY(h, hipGetLastError());
     return M2D_OK;
 }
 
+}  // extern "C"
+
+// ---- options: one table serves m2d_set_option and m2d_get_option (include/m2d.h lists values and defaults) ----
+// The variant option carries unrelated switches, each read where it acts:
+//     7   retrieval on the dense MFMA kernel (the choice: m2d_catalogue_plan.hip; the kernel: m2d_catalogue_dense.hip)
+//     9   retrieval on the one-block-per-user kernel (same places); also the generic pair, head and slate kernels (m2d_score.hip,
+//         m2d_mlp.hip, m2d_slate.hip)
+//    11 / 12   the pair kernel's throughput / latency form whatever the batch size (m2d_score.hip)
+//    13   the tie repair's one-block-per-user tier from the third listed user on (m2d_catalogue_plan.hip)
+//    14   the nine-launch training step (m2d_train.hip)
+//    15   the retrieval scan's progress-word wait gives up at once: M2D_ERR_KERNEL_TIMEOUT, a test hook (m2d_catalogue_plan.hip)
+//    16   the MLP head's row offsets in 16-byte units, the instantiation of tables of 4 GiB and more (m2d_mlp.hip)
+//   100 + n   n dish-range splits in retrieval, 1 <= n <= 64; also switches the pruned launch off (m2d_catalogue_plan.hip,
+//         m2d_catalogue_dense.hip)
+//   any value but 0 keeps m2d_topk_users_excluding off its filtered first tier (m2d_catalogue_excl.hip)
+namespace {
+
+// two device words of T behind `p` after a device synchronisation (the diagnostics' way to read a counter); null: zeros
+template <typename T> int read_words(const m2d_engine *h, const T *p, T (&v)[2], const int n = 2)
+{
+    v[0] = v[1] = 0;
+    if (!p) return M2D_OK;
+    if (hipSetDevice(h->device) != hipSuccess || hipDeviceSynchronize() != hipSuccess ||
+        hipMemcpy(v, p, n * sizeof(T), hipMemcpyDeviceToHost) != hipSuccess)
+        return M2D_ERR_HIP;
+    return M2D_OK;
+}
+
+template <typename T> int read_word(const m2d_engine *h, const T *p, const int word, int64_t *value)
+{
+    T v[2];
+    M2D_REQUIRE(read_words(h, p, v, word + 1));
+    *value = (int64_t)v[word];
+    return M2D_OK;
+}
+
+// the hi x hi first form's count of (wave, tile) pairs whose cross products were multiplied; -1: another form ran
+int read_tiles_completed(const m2d_engine *h, int64_t *value)
+{
+    M2D_REQUIRE(read_word(h, h->topk_tiles_counter, 1, value));
+    if (!h->topk_tiles_counter || !h->topk_apx_last) *value = -1;
+    return M2D_OK;
+}
+
+// users the last m2d_topk_users_excluding call sent to the exact scan: a host count when it sent all of them
+int read_excl_short(const m2d_engine *h, int64_t *value)
+{
+    if (h->excl_all_short < 0) return read_word(h, h->excl_short, 0, value);
+    *value = h->excl_all_short;
+    return M2D_OK;
+}
+
+// One option: an int or int64 member of the engine, or a reader (the diagnostics; they synchronise the device).  Writable members
+// with lo <= hi refuse values outside [lo, hi] with "m2d_set_option: <name> takes <takes>"; the others store what they are given.
+struct m2d_option {
+    const char *name;
+    int m2d_engine::*i;
+    int64_t m2d_engine::*l;
+    int (*read)(const m2d_engine *, int64_t *);
+    bool writable;
+    int64_t lo, hi;
+    const char *takes;
+};
+constexpr m2d_option opt(const char *name, int m2d_engine::*m, int64_t lo = 1, int64_t hi = 0, const char *takes = "")
+{
+    return {name, m, nullptr, nullptr, true, lo, hi, takes};
+}
+constexpr m2d_option opt(const char *name, int64_t m2d_engine::*m, int64_t lo, int64_t hi, const char *takes)
+{
+    return {name, nullptr, m, nullptr, true, lo, hi, takes};
+}
+constexpr m2d_option read_only(const char *name, int m2d_engine::*m) { return {name, m, nullptr, nullptr, false, 1, 0, ""}; }
+constexpr m2d_option read_only(const char *name, int64_t m2d_engine::*m) { return {name, nullptr, m, nullptr, false, 1, 0, ""}; }
+constexpr m2d_option read_only(const char *name, int (*read)(const m2d_engine *, int64_t *))
+{
+    return {name, nullptr, nullptr, read, false, 1, 0, ""};
+}
+
+const m2d_option OPTIONS[] = {
+    opt("prefetch", &m2d_engine::opt_prefetch),
+    opt("nt_loads", &m2d_engine::opt_nt),
+    opt("blocks_per_cu", &m2d_engine::opt_blocks_per_cu),
+    opt("variant", &m2d_engine::opt_variant),
+    opt("topk_bf16x3", &m2d_engine::opt_topk_bf16x3),
+    opt("topk_form", &m2d_engine::opt_topk_form),
+    opt("topk_prune", &m2d_engine::opt_topk_prune),
+    opt("topk_block", &m2d_engine::opt_topk_block),
+    opt("topk_refine", &m2d_engine::opt_topk_refine),
+    opt("topk_grouped", &m2d_engine::opt_topk_grouped),
+    opt("topk_excl_tier", &m2d_engine::opt_topk_excl_tier),
+    opt("market_shares", &m2d_engine::opt_market_shares, 0, 64, "0 ... 64"),
+    opt("topk_mlp_chunk_pairs", &m2d_engine::opt_topk_mlp_chunk_pairs, 256, 1 << 24, "256 ... 2^24"),
+    opt("slate_chunk_pairs", &m2d_engine::opt_slate_chunk_pairs, 256, 1 << 24, "256 ... 2^24"),
+    opt("deep_chunk_pairs", &m2d_engine::opt_deep_chunk_pairs, 256, 1 << 24, "256 ... 2^24"),
+    opt("mlp_bf16x3", &m2d_engine::opt_mlp_bf16x3),
+    opt("mlp_form", &m2d_engine::opt_mlp_form),
+    opt("skip_masked", &m2d_engine::opt_skip_masked),
+    opt("user_high_table", &m2d_engine::opt_user_high),
+    opt("pm_bf16", &m2d_engine::opt_pm_bf16, 0, 1, "0 or 1"),
+    opt("host_zero_copy", &m2d_engine::opt_host_zero_copy),
+    read_only("num_cu", &m2d_engine::num_cu),
+    read_only("topk_block_users", &m2d_engine::topk_block_users),
+    read_only("market_shares_used", &m2d_engine::market_shares_used),
+    read_only("topk_mlp_launches", &m2d_engine::topk_mlp_launches),
+    // of the last pattern-grouped m2d_topk_users call: users the refinement finished / sent on to the tie repair, users the repair
+    // re-ranked, 32-dish tiles the blocks of the pipelined launch stepped through and would have stepped through without pruning
+    read_only("topk_refined", [](const m2d_engine *h, int64_t *v) { return read_word(h, h->topk_refine_counter, 0, v); }),
+    read_only("topk_refine_repaired", [](const m2d_engine *h, int64_t *v) { return read_word(h, h->topk_refine_counter, 1, v); }),
+    read_only("topk_repaired", [](const m2d_engine *h, int64_t *v) { return read_word(h, h->topk_tie_list, 0, v); }),
+    read_only("topk_tiles_scanned", [](const m2d_engine *h, int64_t *v) { return read_word(h, h->topk_tiles_counter, 0, v); }),
+    read_only("topk_tiles_full", &m2d_engine::topk_tiles_full),
+    read_only("topk_tiles_completed", read_tiles_completed),
+    // of the last m2d_catalogue_rank call: tiles the count kernel multiplied, (query, dish) pairs decided in the exact arithmetic
+    read_only("rank_tiles_scanned", [](const m2d_engine *h, int64_t *v) { return read_word(h, h->rank_counters, 0, v); }),
+    read_only("rank_resolved", [](const m2d_engine *h, int64_t *v) { return read_word(h, h->rank_counters, 1, v); }),
+    // of the last m2d_topk_users_excluding call: users sent to the exact scan, tiles that scan multiplied
+    read_only("topk_excl_short", read_excl_short),
+    read_only("topk_excl_tiles_scanned", [](const m2d_engine *h, int64_t *v) { return read_word(h, h->excl_counters, 0, v); }),
+};
+
+const m2d_option *find_option(const char *name)
+{
+    for (const m2d_option &o : OPTIONS)
+        if (!strcmp(name, o.name)) return &o;
+    return nullptr;
+}
+
+}  // namespace
+
+extern "C" {
+
 int m2d_set_option(m2d_engine *h, const char *name, int64_t value)
 {
     if (!h || !name) return M2D_ERR_INVALID_ARG;
-    if (!strcmp(name, "prefetch")) h->opt_prefetch = (int)value;
-    else if (!strcmp(name, "nt_loads")) h->opt_nt = (int)value;
-    else if (!strcmp(name, "blocks_per_cu")) h->opt_blocks_per_cu = (int)value;
-    else if (!strcmp(name, "variant")) h->opt_variant = (int)value;
-    else if (!strcmp(name, "topk_bf16x3")) h->opt_topk_bf16x3 = (int)value;
-    else if (!strcmp(name, "topk_form")) h->opt_topk_form = (int)value;
-    else if (!strcmp(name, "topk_prune")) h->opt_topk_prune = (int)value;
-    else if (!strcmp(name, "topk_block")) h->opt_topk_block = (int)value;
-    else if (!strcmp(name, "topk_refine")) h->opt_topk_refine = (int)value;
-    else if (!strcmp(name, "topk_grouped")) h->opt_topk_grouped = (int)value;
-    else if (!strcmp(name, "topk_excl_tier")) h->opt_topk_excl_tier = (int)value;
-    else if (!strcmp(name, "market_shares")) {
-        if (value < 0 || value > 64) return fail(h, M2D_ERR_INVALID_ARG, "m2d_set_option: market_shares takes 0 ... 64");
-        h->opt_market_shares = (int)value;
-    }
-    else if (!strcmp(name, "topk_mlp_chunk_pairs")) {
-        if (value < 256 || value > (1 << 24)) return fail(h, M2D_ERR_INVALID_ARG, "m2d_set_option: topk_mlp_chunk_pairs takes 256 ... 2^24");
-        h->opt_topk_mlp_chunk_pairs = value;
-    }
-    else if (!strcmp(name, "slate_chunk_pairs")) {
-        if (value < 256 || value > (1 << 24)) return fail(h, M2D_ERR_INVALID_ARG, "m2d_set_option: slate_chunk_pairs takes 256 ... 2^24");
-        h->opt_slate_chunk_pairs = value;
-    }
-    else if (!strcmp(name, "deep_chunk_pairs")) {
-        if (value < 256 || value > (1 << 24)) return fail(h, M2D_ERR_INVALID_ARG, "m2d_set_option: deep_chunk_pairs takes 256 ... 2^24");
-        h->opt_deep_chunk_pairs = value;
-    }
-    else if (!strcmp(name, "mlp_bf16x3")) h->opt_mlp_bf16x3 = (int)value;
-    else if (!strcmp(name, "mlp_form")) h->opt_mlp_form = (int)value;
-    else if (!strcmp(name, "skip_masked")) h->opt_skip_masked = (int)value;
-    else if (!strcmp(name, "user_high_table")) h->opt_user_high = (int)value;
-    else if (!strcmp(name, "pm_bf16")) {
-        if (value != 0 && value != 1) return fail(h, M2D_ERR_INVALID_ARG, "m2d_set_option: pm_bf16 takes 0 or 1");
-        h->opt_pm_bf16 = (int)value;
-    }
-    else if (!strcmp(name, "host_zero_copy")) h->opt_host_zero_copy = (int)value;
-    else return fail(h, M2D_ERR_INVALID_ARG, "m2d_set_option: unknown option");
+    const m2d_option *o = find_option(name);
+    if (!o || !o->writable) return fail(h, M2D_ERR_INVALID_ARG, "m2d_set_option: unknown option");
+    if (o->lo <= o->hi && (value < o->lo || value > o->hi))
+        return fail(h, M2D_ERR_INVALID_ARG, std::string("m2d_set_option: ") + name + " takes " + o->takes);
+    if (o->i) h->*(o->i) = (int)value; else h->*(o->l) = value;
     return M2D_OK;
 }
 
 int m2d_get_option(const m2d_engine *h, const char *name, int64_t *value)
 {
     if (!h || !name || !value) return M2D_ERR_INVALID_ARG;
-    if (!strcmp(name, "prefetch")) *value = h->opt_prefetch;
-    else if (!strcmp(name, "nt_loads")) *value = h->opt_nt;
-    else if (!strcmp(name, "blocks_per_cu")) *value = h->opt_blocks_per_cu;
-    else if (!strcmp(name, "variant")) *value = h->opt_variant;
-    else if (!strcmp(name, "topk_bf16x3")) *value = h->opt_topk_bf16x3;
-    else if (!strcmp(name, "topk_form")) *value = h->opt_topk_form;
-    else if (!strcmp(name, "topk_prune")) *value = h->opt_topk_prune;
-    else if (!strcmp(name, "topk_block")) *value = h->opt_topk_block;
-    else if (!strcmp(name, "topk_block_users")) *value = h->topk_block_users;
-    else if (!strcmp(name, "topk_refine")) *value = h->opt_topk_refine;
-    else if (!strcmp(name, "topk_refined") || !strcmp(name, "topk_refine_repaired")) {
-        int32_t c[2] = {0, 0};
-        if (h->topk_refine_counter) {
-            if (hipSetDevice(h->device) != hipSuccess || hipDeviceSynchronize() != hipSuccess ||
-                hipMemcpy(c, h->topk_refine_counter, sizeof(c), hipMemcpyDeviceToHost) != hipSuccess)
-                return M2D_ERR_HIP;
-        }
-        *value = !strcmp(name, "topk_refined") ? c[0] : c[1];
-    }
-    else if (!strcmp(name, "topk_tiles_scanned") || !strcmp(name, "topk_tiles_full") || !strcmp(name, "topk_tiles_completed")) {
-        // diagnostic (synchronises the device): 32-dish tiles the blocks of the last pipelined retrieval launch stepped
-        // through, and what they would have stepped through without pattern pruning
-        *value = 0;
-        if (!strcmp(name, "topk_tiles_full")) *value = h->topk_tiles_full;
-        else if (h->topk_tiles_counter) {
-            unsigned long long v[2] = {0, 0};
-            if (hipSetDevice(h->device) != hipSuccess || hipDeviceSynchronize() != hipSuccess ||
-                hipMemcpy(v, h->topk_tiles_counter, sizeof v, hipMemcpyDeviceToHost) != hipSuccess)
-                return M2D_ERR_HIP;
-            // (word 1: the hi x hi first form's count of (wave, tile) pairs whose cross products were multiplied; -1: another form ran)
-            *value = !strcmp(name, "topk_tiles_completed") ? (h->topk_apx_last ? (int64_t)v[1] : -1) : (int64_t)v[0];
-        }
-        else if (!strcmp(name, "topk_tiles_completed")) *value = -1;
-    }
-    else if (!strcmp(name, "rank_tiles_scanned") || !strcmp(name, "rank_resolved")) {
-        // diagnostic (synchronises the device): the last m2d_catalogue_rank call's 32-dish tiles multiplied by the count kernel,
-        // and the (query, dish) pairs it decided in the exact arithmetic
-        *value = 0;
-        if (h->rank_counters) {
-            unsigned long long v[2] = {0, 0};
-            if (hipSetDevice(h->device) != hipSuccess || hipDeviceSynchronize() != hipSuccess ||
-                hipMemcpy(v, h->rank_counters, sizeof v, hipMemcpyDeviceToHost) != hipSuccess)
-                return M2D_ERR_HIP;
-            *value = (int64_t)v[!strcmp(name, "rank_resolved") ? 1 : 0];
-        }
-    }
-    else if (!strcmp(name, "topk_excl_tier")) *value = h->opt_topk_excl_tier;
-    else if (!strcmp(name, "topk_excl_short") || !strcmp(name, "topk_excl_tiles_scanned")) {
-        // diagnostic (synchronises the device): users the last m2d_topk_users_excluding call sent to the exact scan, and the
-        // 32-dish tiles that scan multiplied
-        *value = 0;
-        const bool tiles = !strcmp(name, "topk_excl_tiles_scanned");
-        if (!tiles && h->excl_all_short >= 0) *value = h->excl_all_short;
-        else if (tiles ? h->excl_counters != nullptr : h->excl_short != nullptr) {
-            unsigned long long v = 0;
-            int32_t c = 0;
-            if (hipSetDevice(h->device) != hipSuccess || hipDeviceSynchronize() != hipSuccess ||
-                (tiles ? hipMemcpy(&v, h->excl_counters, sizeof v, hipMemcpyDeviceToHost) : hipMemcpy(&c, h->excl_short, sizeof c, hipMemcpyDeviceToHost)) != hipSuccess)
-                return M2D_ERR_HIP;
-            *value = tiles ? (int64_t)v : (int64_t)c;
-        }
-    }
-    else if (!strcmp(name, "market_shares")) *value = h->opt_market_shares;
-    else if (!strcmp(name, "market_shares_used")) *value = h->market_shares_used;
-    else if (!strcmp(name, "topk_grouped")) *value = h->opt_topk_grouped;
-    else if (!strcmp(name, "topk_mlp_chunk_pairs")) *value = h->opt_topk_mlp_chunk_pairs;
-    else if (!strcmp(name, "topk_mlp_launches")) *value = h->topk_mlp_launches;
-    else if (!strcmp(name, "slate_chunk_pairs")) *value = h->opt_slate_chunk_pairs;
-    else if (!strcmp(name, "deep_chunk_pairs")) *value = h->opt_deep_chunk_pairs;
-    else if (!strcmp(name, "mlp_bf16x3")) *value = h->opt_mlp_bf16x3;
-    else if (!strcmp(name, "mlp_form")) *value = h->opt_mlp_form;
-    else if (!strcmp(name, "skip_masked")) *value = h->opt_skip_masked;
-    else if (!strcmp(name, "user_high_table")) *value = h->opt_user_high;
-    else if (!strcmp(name, "pm_bf16")) *value = h->opt_pm_bf16;
-    else if (!strcmp(name, "host_zero_copy")) *value = h->opt_host_zero_copy;
-    else if (!strcmp(name, "num_cu")) *value = h->num_cu;
-    else if (!strcmp(name, "topk_repaired")) {
-        // diagnostic (synchronises the device): users of the last pattern-grouped m2d_topk_users call that the tie repair re-ranked
-        // over their patterns (a tie at the list's end; with the refinement on: three or more dishes that close)
-        *value = 0;
-        if (h->topk_tie_list) {
-            int32_t c = 0;
-            if (hipSetDevice(h->device) != hipSuccess || hipDeviceSynchronize() != hipSuccess ||
-                hipMemcpy(&c, h->topk_tie_list, sizeof(c), hipMemcpyDeviceToHost) != hipSuccess)
-                return M2D_ERR_HIP;
-            *value = c;
-        }
-    }
-    else return M2D_ERR_INVALID_ARG;
+    const m2d_option *o = find_option(name);
+    if (!o) return M2D_ERR_INVALID_ARG;
+    if (o->read) return o->read(h, value);
+    *value = o->i ? (int64_t)(h->*(o->i)) : h->*(o->l);
     return M2D_OK;
 }
 

@@ -483,7 +483,7 @@ int launch_mfma(m2d_engine *h, TopkArgs &a, float *final_s, int32_t *final_i, hi
     a.nsplit = nsplit;
     if (nsplit > 1) {
         const size_t need = (size_t)a.nU * nsplit * a.k * 8 + 256;
-        if (int rc = m2d_grow(h, h->scratch, h->scratch_bytes, need, 1)) return rc;
+        if (int rc = h->scratch.grow(h, need)) return rc;
         a.out_scores = h->scratch;
         a.out_ids = reinterpret_cast<int32_t *>(h->scratch + (size_t)a.nU * nsplit * a.k);
     } else {
@@ -515,9 +515,8 @@ int m2d_ensure_dish_vectors(m2d_engine *h, hipStream_t st)
     const int64_t rows = (h->I + 31) / 32 * 32;
     const size_t K = (size_t)(h->C + 1) * h->E;
     if (h->dish_vec_rows != rows || !h->dish_vec) {
-        if (h->dish_vec) M2D_HIP_TRY(h, hipFree(h->dish_vec));
-        h->dish_vec = nullptr;
-        M2D_HIP_TRY(h, hipMalloc((void **)&h->dish_vec, (size_t)rows * K * sizeof(float)));
+        h->dish_vec.reset();
+        if (int rc = h->dish_vec.grow(h, (size_t)rows * K)) return rc;
         h->dish_vec_rows = rows;
     }
     hipLaunchKernelGGL(m2d_build_dish_vectors, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, st, h->re, h->ce,

@@ -418,7 +418,7 @@ int m2d_launch_topk_users_excluding(m2d_engine *h, const int32_t *users, int64_t
     const size_t n4 = ((size_t)nU + 3) & ~(size_t)3;
     const size_t part = (size_t)items * (h->E <= 128 ? 64 : 1) * k;
     const size_t need = (size_t)nU * 32 + (4 + n4) + rank_scratch(nullptr, nU).floats + 2 * part;
-    if ((rc = m2d_grow(h, h->excl_buf, h->excl_cap, need, sizeof(float), h->excl_counters, h->excl_short)) != M2D_OK) return rc;
+    if ((rc = h->excl_buf.grow(h, need, h->excl_counters, h->excl_short)) != M2D_OK) return rc;
     ExclArgs a;
     a.t = rank_tables(h);
     a.users = users; a.excl_off = excl_off; a.excl_ids = excl_ids;

@@ -634,15 +634,13 @@ int ensure_grouped(m2d_engine *h, hipStream_t st)
     const int64_t cap_rows = (max_tiles + 16) * 32;          // + one stage of zero rows past the last tile
     const int EW = h->dish_high ? 2 * h->E : grouped_row_width(h->E);   // ingredient extension: rows are [H[d] | RE[d]]
     if (h->grp_cap_rows != cap_rows || h->grp_ew != EW || !h->grp_rs) {
-        for (void *q : {(void *)h->grp_rs, (void *)h->grp_rs16, (void *)h->grp_perm, (void *)h->grp_tile_info, (void *)h->grp_work})
-            if (q) M2D_HIP_TRY(h, hipFree(q));
-        h->grp_rs = nullptr; h->grp_rs16 = nullptr; h->grp_perm = nullptr; h->grp_tile_info = nullptr; h->grp_work = nullptr;
-        M2D_HIP_TRY(h, hipMalloc((void **)&h->grp_rs, (size_t)cap_rows * EW * sizeof(float)));
-        M2D_HIP_TRY(h, hipMalloc((void **)&h->grp_rs16, (size_t)cap_rows * EW * 4));
-        M2D_HIP_TRY(h, hipMalloc((void **)&h->grp_perm, (size_t)cap_rows * sizeof(int32_t)));
-        M2D_HIP_TRY(h, hipMalloc((void **)&h->grp_tile_info, (size_t)max_tiles * sizeof(int32_t)));
-        M2D_HIP_TRY(h, hipMalloc((void **)&h->grp_work, ((size_t)nblk * GRP_KEYS + GRP_WORDS + 2 * 2) * sizeof(int32_t) +
-                                                        (size_t)I * sizeof(float) + (size_t)GRP_MAXPAT * GRP_FIRST * sizeof(int32_t)));
+        h->grp_rs.reset(); h->grp_rs16.reset(); h->grp_perm.reset(); h->grp_tile_info.reset(); h->grp_work.reset();   // (another row width)
+        int rc;
+        if ((rc = h->grp_rs.grow(h, (size_t)cap_rows * EW)) != M2D_OK || (rc = h->grp_rs16.grow(h, (size_t)cap_rows * EW * 4)) != M2D_OK ||
+            (rc = h->grp_perm.grow(h, (size_t)cap_rows)) != M2D_OK || (rc = h->grp_tile_info.grow(h, (size_t)max_tiles)) != M2D_OK ||
+            (rc = h->grp_work.grow(h, ((size_t)nblk * GRP_KEYS + GRP_WORDS + 2 * 2) * sizeof(int32_t) + (size_t)I * sizeof(float) +
+                                          (size_t)GRP_MAXPAT * GRP_FIRST * sizeof(int32_t))) != M2D_OK)
+            return rc;
         h->grp_cap_rows = cap_rows;
         h->grp_ew = EW;
     }
@@ -664,7 +662,7 @@ int ensure_grouped(m2d_engine *h, hipStream_t st)
     hipLaunchKernelGGL(m2d_grp_scatter, dim3(nblk), dim3(256), 0, st, h->dish_cats, norm, stat, I, h->C, blk_hist, grp, h->grp_perm);
     hipLaunchKernelGGL(m2d_grp_first_ids, dim3(GRP_MAXPAT), dim3(256), 0, st, h->dish_cats, I, h->C, grouped_first_ids(h));
     hipLaunchKernelGGL(m2d_grp_gather, dim3((unsigned)((cap_rows + 3) / 4)), dim3(256), 0, st, h->re, h->dish_high,
-                       h->grp_perm, cap_rows, h->E, EW, h->grp_rs, reinterpret_cast<__bf16 *>(h->grp_rs16));
+                       h->grp_perm, cap_rows, h->E, EW, h->grp_rs, static_cast<__bf16 *>(h->grp_rs16.get()));
     M2D_HIP_TRY(h, hipGetLastError());
     int32_t host[4] = {0, 0, 0, 0};   // tiles, slots, flags, "a table value is not finite"  (a table build may synchronise)
     M2D_HIP_TRY(h, hipMemcpyAsync(host, grp + 16, 2 * sizeof(int32_t), hipMemcpyDeviceToHost, st));
@@ -784,7 +782,7 @@ int launch_grouped(m2d_engine *h, const int E8, const int KR, const bool BF16X3,
     const size_t lds = (size_t)2 * TPS * 32 * E * sizeof(float);
     h->topk_block_users = 32 * WV;
     GroupedArgs a;
-    a.pm = h->pm; a.ce = h->ce; a.rs = h->grp_rs; a.rs16 = reinterpret_cast<const __bf16 *>(h->grp_rs16);
+    a.pm = h->pm; a.ce = h->ce; a.rs = h->grp_rs; a.rs16 = static_cast<const __bf16 *>(h->grp_rs16.get());
     a.perm = h->grp_perm; a.tile_info = h->grp_tile_info;
     a.grp = grouped_grp(h);
     a.users = users; a.nU = nU; a.U = h->U; a.user_base = h->user_base; a.k = k; a.tiles = h->grp_tiles;
@@ -830,7 +828,7 @@ int launch_grouped(m2d_engine *h, const int E8, const int KR, const bool BF16X3,
     int rc;
     // tie values (a float per slot); behind them the repair list (int32: count, users) and the repair's partial lists
     const size_t tie_need = slots + 1 + (size_t)nU + (size_t)2 * REPAIR_CAP * REPAIR_SPLITS * k;
-    if ((rc = m2d_grow(h, h->topk_flags, h->topk_flags_cap, tie_need, sizeof(float), h->topk_tie_list, h->topk_tie_final)) != M2D_OK) return rc;
+    if ((rc = h->topk_flags.grow(h, tie_need, h->topk_tie_list, h->topk_tie_final)) != M2D_OK) return rc;
     float *tie_final = h->topk_flags + slots_before;
     a.tie_val = h->topk_flags;
     int32_t *tie_list = reinterpret_cast<int32_t *>(h->topk_flags + slots);
@@ -845,7 +843,7 @@ int launch_grouped(m2d_engine *h, const int E8, const int KR, const bool BF16X3,
     float *ex_final = nullptr;
     if (ext) {
         const size_t ex_need = slots * 8 + (size_t)nU + 8;   // records of 8 floats in the tie values' layout | counters | a word per user
-        if ((rc = m2d_grow(h, h->topk_ex, h->topk_ex_cap, ex_need, sizeof(float), h->topk_refine_counter)) != M2D_OK) return rc;
+        if ((rc = h->topk_ex.grow(h, ex_need, h->topk_refine_counter)) != M2D_OK) return rc;
         a.ex_out = h->topk_ex;
         ex_final = h->topk_ex + slots_before * 8;
         h->topk_refine_counter = reinterpret_cast<int32_t *>(h->topk_ex + ex_need - (size_t)nU - 8);     // [0] refined [1] sent to the repair; [8 + u] user u's word
@@ -856,7 +854,7 @@ int launch_grouped(m2d_engine *h, const int E8, const int KR, const bool BF16X3,
     const size_t tmp_entries = nsplit > 64 ? (size_t)nU * (nsplit / 64) * k : 0;
     if (nsplit > 1) {
         const size_t need = ((size_t)nU * nsplit * k + tmp_entries) * 8 + 256;
-        if ((rc = m2d_grow(h, h->scratch, h->scratch_bytes, need, 1)) != M2D_OK) return rc;
+        if ((rc = h->scratch.grow(h, need)) != M2D_OK) return rc;
         a.out_scores = h->scratch;
         a.out_ids = reinterpret_cast<int32_t *>(h->scratch + (size_t)nU * nsplit * k);
     } else {
@@ -872,7 +870,7 @@ int launch_grouped(m2d_engine *h, const int E8, const int KR, const bool BF16X3,
         // top-k; users sorted by mask so that a block's 256 users share their patterns (a single block: no sort)
         const size_t nitems = (size_t)ublocks * nsplit;
         const size_t need = (size_t)nU * 8 + (size_t)nU + PLAN_KEYS + 8 + 2 * nitems;
-        if ((rc = m2d_grow(h, h->topk_plan, h->topk_plan_cap, need, sizeof(float), h->topk_tiles_counter)) != M2D_OK) return rc;
+        if ((rc = h->topk_plan.grow(h, need, h->topk_tiles_counter)) != M2D_OK) return rc;
         float *plan = h->topk_plan;
         int32_t *order = reinterpret_cast<int32_t *>(plan + (size_t)nU * 8), *hist = order + ((nU + 3) & ~(int64_t)3);      // hist: 16-B aligned
         unsigned long long *counter = reinterpret_cast<unsigned long long *>(hist + PLAN_KEYS);

@@ -244,7 +244,7 @@ int m2d_rank_prepare(m2d_engine *h, const char *entry, hipStream_t st, bool unde
     if (h->grp_nonfinite) return refuse("needs finite tables (a table value is inf or NaN)");
     const int64_t tiles = h->grp_tiles;
     if (h->rank_tnorm_gen != h->grp_gen) {
-        if ((rc = m2d_grow(h, h->rank_tnorm, h->rank_tnorm_cap, (size_t)(tiles + 1), sizeof(float))) != M2D_OK) return rc;
+        if ((rc = h->rank_tnorm.grow(h, (size_t)(tiles + 1))) != M2D_OK) return rc;
         if (tiles > 0)
             hipLaunchKernelGGL(m2d_rank_tile_norms, dim3((unsigned)((tiles + 3) / 4)), dim3(256), 0, st, h->grp_rs, tiles, h->E, h->grp_ew, h->rank_tnorm);
         M2D_HIP_TRY(h, hipGetLastError());
@@ -258,7 +258,7 @@ int m2d_launch_catalogue_rank(m2d_engine *h, const int32_t *users, const int32_t
 {
     int rc;
     if ((rc = m2d_rank_prepare(h, "m2d_catalogue_rank", st)) != M2D_OK) return rc;
-    if ((rc = m2d_grow(h, h->rank_buf, h->rank_cap, rank_scratch(nullptr, n).floats, sizeof(float), h->rank_counters)) != M2D_OK) return rc;
+    if ((rc = h->rank_buf.grow(h, rank_scratch(nullptr, n).floats, h->rank_counters)) != M2D_OK) return rc;
     const RankScratch sc = rank_scratch(h->rank_buf, n);
     RankArgs a;
     a.t = rank_tables(h);

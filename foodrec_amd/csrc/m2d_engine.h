@@ -12,18 +12,108 @@
 #include "../../include/m2d.h"
 
 struct m2d_train_state;   // csrc/m2d_train.hip
+struct m2d_engine;
 
 typedef float v4f __attribute__((ext_vector_type(4)));
 typedef float v16f __attribute__((ext_vector_type(16)));
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 
+// ---- engine-owned memory ----
+// Everything the engine allocates lives in one of the owner types below: pointer and capacity travel together, and the block is
+// freed when its owner goes (with the engine, or with the state it is built into) -- nothing is freed by hand anywhere else.
+#define M2D_HIP_TRY(h, expr)                                                                   \
+    do {                                                                                       \
+        hipError_t e_ = (expr);                                                                \
+        if (e_ != hipSuccess) return m2d_hip_failed(h, #expr, e_);                             \
+    } while (0)
+int m2d_hip_failed(m2d_engine *h, const char *expr, hipError_t e);   // sets last_error, returns M2D_ERR_HIP
+
+// A device block of T (capacity in units of UNIT bytes: sizeof(T), or 1 for blocks that are carved up by hand).  It converts to T *,
+// so launchers read it like the plain pointer it replaces.
+template <typename T> struct m2d_unit { static constexpr size_t bytes = sizeof(T); };
+template <> struct m2d_unit<void> { static constexpr size_t bytes = 1; };
+template <typename T, size_t UNIT = m2d_unit<T>::bytes>
+struct m2d_dev_buf {
+    T *p = nullptr;
+    size_t cap = 0;
+    m2d_dev_buf() = default;
+    m2d_dev_buf(m2d_dev_buf &&o) noexcept : p(o.p), cap(o.cap) { o.p = nullptr; o.cap = 0; }
+    m2d_dev_buf &operator=(m2d_dev_buf &&o) noexcept
+    {
+        if (this != &o) { reset(); p = o.p; cap = o.cap; o.p = nullptr; o.cap = 0; }
+        return *this;
+    }
+    ~m2d_dev_buf() { reset(); }
+    operator T *() const { return p; }
+    T *get() const { return p; }
+    hipError_t release()                // null with capacity 0 afterwards, whatever hipFree says
+    {
+        const hipError_t e = p ? hipFree(p) : hipSuccess;
+        p = nullptr; cap = 0;
+        return e;
+    }
+    void reset() { (void)release(); }
+    // Grow to `need` units; nothing happens while the capacity suffices.  `inside` are the engine's pointers into the old block:
+    // they are null before it is freed and stay null when the allocation fails -- m2d_get_option reads through them -- and the
+    // buffer is then null with capacity 0.
+    template <typename... Inside> int grow(m2d_engine *h, const size_t need, Inside *&...inside)
+    {
+        if (cap >= need) return M2D_OK;
+        ((inside = nullptr), ...);
+        M2D_HIP_TRY(h, release());
+        M2D_HIP_TRY(h, hipMalloc((void **)&p, need * UNIT));
+        cap = need;
+        return M2D_OK;
+    }
+};
+
+// the same for a pinned host block, allocated once
+template <typename T> struct m2d_host_buf {
+    T *p = nullptr;
+    m2d_host_buf() = default;
+    m2d_host_buf(const m2d_host_buf &) = delete;
+    m2d_host_buf &operator=(const m2d_host_buf &) = delete;
+    ~m2d_host_buf() { reset(); }
+    operator T *() const { return p; }
+    void reset()
+    {
+        if (p) (void)hipHostFree(p);
+        p = nullptr;
+    }
+    int alloc(m2d_engine *h, const size_t count, const unsigned flags = hipHostMallocDefault)
+    {
+        reset();
+        M2D_HIP_TRY(h, hipHostMalloc((void **)&p, count * sizeof(T), flags));
+        return M2D_OK;
+    }
+};
+
+// an event, created on first use
+struct m2d_event {
+    hipEvent_t e = nullptr;
+    m2d_event() = default;
+    m2d_event(const m2d_event &) = delete;
+    m2d_event &operator=(const m2d_event &) = delete;
+    ~m2d_event() { if (e) (void)hipEventDestroy(e); }
+    operator hipEvent_t() const { return e; }
+};
+
+// A table the caller handed over: `p` is what the launchers read -- the caller's own array (M2D_TABLES_DEVICE: borrowed, `own` is
+// empty) or the engine's copy of it (M2D_TABLES_HOST: `own`).  Filled by adopt() in m2d_abi.hip; a setter builds its tables aside
+// and moves them in when everything has passed.
+template <typename T> struct m2d_table {
+    const T *p = nullptr;
+    m2d_dev_buf<T> own;
+    operator const T *() const { return p; }
+    void reset() { p = nullptr; own.reset(); }
+};
+
 struct m2d_engine {
     // tables in HBM, row-major, float32 (Model_Recommender.py:45-53)
-    const float *pm = nullptr;  // [U, C+1, E]
-    const float *re = nullptr;  // [I, E]
-    const float *ce = nullptr;  // [C, E]
-    const float *dish_cats = nullptr;  // [I, C] or null
-    bool own_pm = false, own_re = false, own_ce = false, own_dish_cats = false;
+    m2d_table<float> pm;         // [U, C+1, E]
+    m2d_table<float> re;         // [I, E]
+    m2d_table<float> ce;         // [C, E]
+    m2d_table<float> dish_cats;  // [I, C] or null
     int64_t U = 0, I = 0;
     int32_t C = 0, E = 0;
     int64_t user_base = 0;
@@ -33,8 +123,8 @@ struct m2d_engine {
     int num_cu = 256;
 
     // id-error latch: {code, bad value, index lo, index hi}; cleared by m2d_check (kernels write it with m2d_latch_error below)
-    int32_t *err_dev = nullptr;
-    int32_t *err_host = nullptr;  // pinned
+    m2d_dev_buf<int32_t> err_dev;
+    m2d_host_buf<int32_t> err_host;
 
     // "some value of Personal_Memory / Recipe_Embedding / Category_Embedding is not finite, or some H[d] of the ingredient table is
     // +-inf" (device word, sticky until the next full scan).  Model_Recommender.py:82-90 multiplies the row of a category a dish does not have by 0, and
@@ -46,102 +136,92 @@ struct m2d_engine {
     bool finite_scan_pending = true;
 
     // build-defined extension: multi-hot ingredient table
-    const float *ing = nullptr;        // [R, E]
-    const int32_t *ing_off = nullptr;  // [I+1] CSR offsets per dish
-    const int32_t *ing_ids = nullptr;  // [nnz]
-    const float *ing_w = nullptr;      // [nnz] or null (all ones)
-    bool own_ing = false;
+    m2d_table<float> ing;              // [R, E]
+    m2d_table<int32_t> ing_off;        // [I+1] CSR offsets per dish
+    m2d_table<int32_t> ing_ids;        // [nnz]
+    m2d_table<float> ing_w;            // [nnz] or null (all ones)
     int64_t ing_rows = 0, ing_nnz = 0;
-    float *dish_high = nullptr;        // [I, E]  H[d] = sum_j w_j ING[id_j] / sum_j w_j
+    m2d_dev_buf<float> dish_high;      // [I, E]  H[d] = sum_j w_j ING[id_j] / sum_j w_j
 
     // build-defined extension: 3-layer scoring head
-    const float *mlp_w1 = nullptr, *mlp_b1 = nullptr, *mlp_w2 = nullptr, *mlp_b2 = nullptr, *mlp_w3 = nullptr;
+    m2d_table<float> mlp_w1, mlp_b1, mlp_w2, mlp_b2, mlp_w3;   // "the head is set" is mlp_w1 != null
     float mlp_b3 = 0.f;
     int32_t mlp_h1 = 0, mlp_h2 = 0;
-    bool own_mlp = false;
-    void *mlp_w1x3 = nullptr;           // split-bf16 image of W1 for the bf16x3 layer-1 path (built lazily)
-    float *mlp_w1pad = nullptr;         // W1 zero-padded to a multiple of 64 rows, for K = (C + 1) E that is not one (built lazily)
-    void *mlp_w1pc = nullptr;           // W1 | W2 image of the producer / consumer kernel (built lazily)
-    int32_t *mlp_pg = nullptr;          // per-launch pair grouping of that kernel: histogram | tile count | tile blocks | slot -> pair
-    uint8_t *mlp_pat8 = nullptr;        // [I] a dish's pattern of non-zero mask weights (all blocks for n = 0 / NaN): what the grouping reads per pair
+    m2d_dev_buf<void> mlp_w1x3;         // split-bf16 image of W1 for the bf16x3 layer-1 path (built lazily)
+    m2d_dev_buf<float> mlp_w1pad;       // W1 zero-padded to a multiple of 64 rows, for K = (C + 1) E that is not one (built lazily)
+    m2d_dev_buf<void> mlp_w1pc;         // W1 | W2 image of the producer / consumer kernel (built lazily)
+    m2d_dev_buf<int32_t> mlp_pg;        // per-launch pair grouping of that kernel: histogram | tile count | tile blocks | slot -> pair
+    m2d_dev_buf<uint8_t> mlp_pat8;      // [I] a dish's pattern of non-zero mask weights (all blocks for n = 0 / NaN): what the grouping reads per pair
     uint64_t mlp_pat8_gen = 0;          // the dish-vector build it belongs to (dish_vec_gen)
-    size_t mlp_pg_cap = 0;              // ints
 
     // m2d_topk_users_mlp (m2d_topk_mlp.hip): a chunk's pair ids (users | items), its head scores and, in the two-stage form, stage 1's
     // candidate ids (with exclusions: the whole call's, ids [nU, K1] | stage 1's scores [nU, K1]) -- buffers of their own: stage 1
     // writes `scratch`, the head's pair grouping writes mlp_pg
-    int32_t *topk_mlp_ids = nullptr;
-    float *topk_mlp_scores = nullptr;
-    int32_t *topk_mlp_cand = nullptr;
-    size_t topk_mlp_ids_cap = 0, topk_mlp_scores_cap = 0, topk_mlp_cand_cap = 0;   // ints / floats / ints
-    float *topk_mlp_held = nullptr;               // m2d_catalogue_rank_mlp: the held-out pairs' scores when the caller takes none
-    size_t topk_mlp_held_cap = 0;                 // floats
+    m2d_dev_buf<int32_t> topk_mlp_ids;
+    m2d_dev_buf<float> topk_mlp_scores;
+    m2d_dev_buf<int32_t> topk_mlp_cand;
+    m2d_dev_buf<float> topk_mlp_held;             // m2d_catalogue_rank_mlp: the held-out pairs' scores when the caller takes none
     int64_t opt_topk_mlp_chunk_pairs = 1 << 22;   // pairs per head launch of that call (diagnostic: the lists do not depend on it)
     int64_t topk_mlp_launches = 0;                // head launches of the last call
 
     // m2d_score_slate / m2d_topk_slate (m2d_slate.hip): the call's slate vectors Dt_s -- rows of K rounded up to the kernel's k chunk
     // floats, zero beyond K: the slate's nD rows, zero rows up to the dish-tile multiple and one more zero row that pads the
     // user operand -- rebuilt by every call (they hang on the call's slate and on every table); and a user block's scores of m2d_topk_slate
-    float *slate_dt = nullptr;
-    float *slate_scores = nullptr;
-    size_t slate_dt_cap = 0, slate_scores_cap = 0;   // floats
+    m2d_dev_buf<float> slate_dt;
+    m2d_dev_buf<float> slate_scores;
     int64_t opt_slate_chunk_pairs = 1 << 22;         // pairs of score scratch per m2d_topk_slate pass (the lists do not depend on it)
     int64_t opt_deep_chunk_pairs = 1 << 22;          // the same for m2d_topk_users_deep: ranges of min(I, P, 65536) dishes, blocks of P / W users
 
     // m2d_topk_groups / m2d_*_groups_slate (m2d_groups.hip): the call's dense member array i32[nG * M] (valid ids only) | cnt i32[nG];
     // the members' score rows go to slate_scores above
-    int32_t *group_ids = nullptr;
-    size_t group_cap = 0;                            // ints
+    m2d_dev_buf<int32_t> group_ids;
 
     // m2d_set_recipes / m2d_cookable_dishes (m2d_market.hip): every dish's ingredient list, CSR, validated once by the setter (CSR
     // shape, every id in [0, R)); lists only -- no table, no weights, nothing the scoring path reads, and no tie to `ing` above.
     // market_buf: the call's scratch -- bitmap of R bits | missing[I] (unless the caller gives a buffer) | kept dishes per block |
     // their exclusive scan | the total (8 bytes)
-    const int32_t *rcp_off = nullptr;  // [I+1]
-    const int32_t *rcp_ids = nullptr;  // [nnz]
-    bool rcp_set = false, own_rcp = false;
+    m2d_table<int32_t> rcp_off;        // [I+1]
+    m2d_table<int32_t> rcp_ids;        // [nnz]
+    bool rcp_set = false;
     int64_t rcp_rows = 0, rcp_nnz = 0;
-    int32_t *market_buf = nullptr;
-    size_t market_cap = 0;             // ints
-    int64_t *market_count_host = nullptr;   // pinned: the count of the last call
+    m2d_dev_buf<int32_t> market_buf;
+    m2d_host_buf<int64_t> market_count_host;   // the count of the last call
 
     // m2d_topk_markets (m2d_market_requests.hip): the shares' partial lists, ids [nQ, S k] | score words [nQ, S k], and in the
     // through-L2 form (R > 65 536) one bitmap of ceil(R / 32) words per request behind them
-    int32_t *markets_buf = nullptr;
-    size_t markets_cap = 0;            // ints
+    m2d_dev_buf<int32_t> markets_buf;
     int opt_market_shares = 0;         // shares of the catalogue per request: 0 = the launcher's rule, 1 ... 64 forced (A/B: same words)
     int market_shares_used = 0;        // what the last call used
 
     // m2d_*_profiles (m2d_profiles.hip): the call's composed rows [n, C+1, E] and, behind them, the ids 0 .. n-1 its launchers are
     // handed as users (m2d_rows_view below)
-    float *profile_buf = nullptr;
-    size_t profile_cap = 0;            // floats
+    m2d_dev_buf<float> profile_buf;
 
     // derived table for pair scoring: <U_high[u], CE_c> per user and category (built lazily by large m2d_score_pairs calls;
     // stale after any write to Personal_Memory / Category_Embedding: the engine's own writers and m2d_tables_updated reset it)
-    float *user_high = nullptr;  // [U, 4]
+    m2d_dev_buf<float> user_high;  // [U, 4]
     bool user_high_valid = false;
 
     // serving mirror of Personal_Memory (option "pm_bf16"): its round-to-nearest-even bf16 image, rows indexed like the table's own
     // (u - user_base); built lazily by m2d_ensure_pm_bf16, stale after any write to Personal_Memory.  Rounding can make an inf the
     // f32 table does not hold, so the mirror has a non-finite word of its own: the builder sets it from what it writes, and the
     // mirror kernels leave out weight-0 rows only while this word and nonfinite_dev are both 0
-    uint16_t *pm_bf16 = nullptr;          // [U, C+1, E]
+    m2d_dev_buf<uint16_t> pm_bf16;        // [U, C+1, E]
     bool pm_bf16_valid = false;
     int32_t *pm_bf16_nonfinite = nullptr; // device word (inside err_dev's allocation)
 
     // factored dish vectors for catalogue retrieval (built lazily by m2d_topk_users)
-    float *dish_vec = nullptr;  // [I_pad, (C+1)*E]
+    m2d_dev_buf<float> dish_vec;  // [I_pad, (C+1)*E]
     int64_t dish_vec_rows = 0;
     bool dish_vec_valid = false;
     uint64_t dish_vec_gen = 0;          // counts m2d_ensure_dish_vectors' rebuilds (what hangs on the dish masks rebuilds with it)
 
     // pattern-grouped retrieval tables (0/1 masks only; built lazily by m2d_topk_users)
-    float *grp_rs = nullptr;            // [grp_cap_rows, E] Recipe_Embedding rows sorted by (mask pattern, dish id)
-    void *grp_rs16 = nullptr;           // the same rows split into bf16 hi | lo blocks per 32-row tile
-    int32_t *grp_perm = nullptr;        // [grp_cap_rows]    slot -> dish id, -1 = padding
-    int32_t *grp_tile_info = nullptr;   // [tiles]           pattern | valid rows << 8
-    int32_t *grp_work = nullptr;        // block histograms / group offsets / flags
+    m2d_dev_buf<float> grp_rs;          // [grp_cap_rows, E] Recipe_Embedding rows sorted by (mask pattern, dish id)
+    m2d_dev_buf<void> grp_rs16;         // the same rows split into bf16 hi | lo blocks per 32-row tile
+    m2d_dev_buf<int32_t> grp_perm;      // [grp_cap_rows]    slot -> dish id, -1 = padding
+    m2d_dev_buf<int32_t> grp_tile_info; // [tiles]           pattern | valid rows << 8
+    m2d_dev_buf<int32_t, 1> grp_work;   // block histograms / group offsets / flags (bytes)
     int64_t grp_tiles = 0, grp_cap_rows = 0;
     int grp_ew = 0;                     // row width of grp_rs: E, or 2 E with the ingredient extension ([H[d] | RE[d]])
     bool grp_valid = false, grp_binary = false;
@@ -150,16 +230,13 @@ struct m2d_engine {
     uint64_t grp_gen = 0;               // counts the sorted table's builds (what is derived from it rebuilds with it)
 
     // m2d_catalogue_rank (m2d_catalogue_rank.hip): per-query records | sort | counters, and the per-tile row-norm table
-    float *rank_buf = nullptr;
-    size_t rank_cap = 0;                // floats
+    m2d_dev_buf<float> rank_buf;
     unsigned long long *rank_counters = nullptr;   // [0] tiles multiplied, [1] (query, dish) pairs decided exactly, of the last call
-    float *rank_tnorm = nullptr;        // [tiles] largest row norm of each 32-row tile of the sorted table
-    int64_t rank_tnorm_cap = 0;
+    m2d_dev_buf<float> rank_tnorm;      // [tiles] largest row norm of each 32-row tile of the sorted table
     uint64_t rank_tnorm_gen = ~0ull;    // the grp_gen it was built for
 
     // m2d_topk_users_excluding (m2d_catalogue_excl.hip): unfiltered lists | short users | records | sort | counters | partial lists
-    float *excl_buf = nullptr;
-    size_t excl_cap = 0;                // floats
+    m2d_dev_buf<float> excl_buf;
     unsigned long long *excl_counters = nullptr;   // [0] tiles the exact scan multiplied in the last call
     int32_t *excl_short = nullptr;      // [0] users the last call's filter sent to the exact scan
     int64_t excl_all_short = -1;        // >= 0: the last call sent every user there (this many), the device word is not used
@@ -169,19 +246,16 @@ struct m2d_engine {
     m2d_train_state *train = nullptr;
 
     // staging for m2d_score_pairs_host: one pinned block and its device twin
-    unsigned char *stage_host = nullptr, *stage_dev = nullptr;
-    size_t stage_bytes = 0;
-    hipEvent_t stage_ev[2] = {nullptr, nullptr};   // chunked host feeds: a block's chunk has been delivered
+    m2d_host_buf<unsigned char> stage_host;
+    m2d_dev_buf<unsigned char> stage_dev;  // its capacity is the size of both
+    m2d_event stage_ev[2];              // chunked host feeds: a block's chunk has been delivered
     uint32_t stage_ticket = 0;          // completion word of the last m2d_score_pairs_host call (wraps)
 
     // scratch for rank_candidates
-    float *scratch = nullptr;
-    size_t scratch_bytes = 0;
-    float *topk_flags = nullptr;        // pattern-grouped retrieval: tie values per (user, split) / per user (NaN: no tie at the k-th score)
-    size_t topk_flags_cap = 0;          // floats
+    m2d_dev_buf<float, 1> scratch;      // (bytes)
+    m2d_dev_buf<float> topk_flags;      // pattern-grouped retrieval: tie values per (user, split) / per user (NaN: no tie at the k-th score)
     float *topk_tie_final = nullptr;    // the per-user values of the last call, inside topk_flags
-    float *topk_plan = nullptr;         // pipelined retrieval kernel: per-user plan records | launch order | sort histogram | tile counter
-    size_t topk_plan_cap = 0;           // floats
+    m2d_dev_buf<float> topk_plan;       // pipelined retrieval kernel: per-user plan records | launch order | sort histogram | tile counter
     unsigned long long *topk_tiles_counter = nullptr;   // tiles the blocks of the last pipelined launch stepped through (inside topk_plan)
     bool topk_apx_last = false;         // the last pipelined retrieval launch took the hi x hi first form (see "topk_tiles_completed")
     int64_t topk_tiles_full = 0;        // ... and what they would have stepped through without pattern pruning
@@ -203,8 +277,7 @@ struct m2d_engine {
     int opt_topk_grouped = 1;           // 0/1-mask catalogues: pattern-grouped retrieval (contraction over E); 0 = dense kernel
     int opt_topk_form = 0;              // split-bf16 retrieval kernel: 0 / 2 = pipelined form, 1 = first form; 3 / 4 = hi x hi first form always / never
     int opt_topk_refine = 1;            // near-tied lists are finished in the tie repair's plain-f32 arithmetic (m2d_topk_refine): 0 = off (A/B)
-    float *topk_ex = nullptr;           // what the lists leave out, per (user, dish range) / (user, group) / user: 4 floats each
-    size_t topk_ex_cap = 0;             // floats
+    m2d_dev_buf<float> topk_ex;         // what the lists leave out, per (user, dish range) / (user, group) / user: 4 floats each
     int32_t *topk_refine_counter = nullptr;   // [2] users refined, users sent on to the repair (inside topk_ex's allocation)
     int opt_topk_block = 0;             // users per block of a pruned split-bf16 launch: 0 = the launcher's choice, 128 / 256 forced (A/B)
     int topk_block_users = 256;         // what the last pattern-grouped launch used (the tile counters count tiles of blocks this size)
@@ -212,6 +285,9 @@ struct m2d_engine {
 
     std::string last_error;
     const char *last_kernel = "";
+
+    m2d_engine() = default;
+    ~m2d_engine();                      // m2d_train.hip (the training state's type lives there); the engine's device is current
 };
 
 // the id-error latch (m2d_engine::err_dev): the first error of a call wins -- its code, the bad value, where it stood
@@ -273,47 +349,29 @@ static inline void m2d_mark_written(m2d_engine *h, unsigned tables, m2d_written_
 //   m2d_ensure_finite_scan runs BEFORE the view is entered (inside, a queued scan would walk `rows` instead of the table);
 //   user_high, pm_bf16, their validity flags and m2d_mark_written are neither read, rebuilt nor touched inside it -- with both
 //   options at 0 no launcher asks for them; the rows are finite while the engine's non-finite word is 0 (the composer sees to it).
+// Only the table's plain pointer is swapped (pm.p): what the engine owns stays where it is, and the pointer goes back as found.
 struct m2d_rows_view {
     m2d_engine *const h;
     const float *const pm;
     const int64_t U, user_base;
     const int opt_user_high, opt_pm_bf16;
     m2d_rows_view(m2d_engine *e, const float *rows, int64_t n)
-        : h(e), pm(e->pm), U(e->U), user_base(e->user_base), opt_user_high(e->opt_user_high), opt_pm_bf16(e->opt_pm_bf16)
+        : h(e), pm(e->pm.p), U(e->U), user_base(e->user_base), opt_user_high(e->opt_user_high), opt_pm_bf16(e->opt_pm_bf16)
     {
-        e->pm = rows; e->U = n; e->user_base = 0; e->opt_user_high = 0; e->opt_pm_bf16 = 0;
+        e->pm.p = rows; e->U = n; e->user_base = 0; e->opt_user_high = 0; e->opt_pm_bf16 = 0;
     }
     ~m2d_rows_view()
     {
-        h->pm = pm; h->U = U; h->user_base = user_base; h->opt_user_high = opt_user_high; h->opt_pm_bf16 = opt_pm_bf16;
+        h->pm.p = pm; h->U = U; h->user_base = user_base; h->opt_user_high = opt_user_high; h->opt_pm_bf16 = opt_pm_bf16;
     }
     m2d_rows_view(const m2d_rows_view &) = delete;
     m2d_rows_view &operator=(const m2d_rows_view &) = delete;
 };
 
-#define M2D_HIP_TRY(h, expr)                                                                   \
-    do {                                                                                       \
-        hipError_t e_ = (expr);                                                                \
-        if (e_ != hipSuccess) {                                                                \
-            (h)->last_error = std::string(#expr) + ": " + hipGetErrorString(e_);               \
-            return M2D_ERR_HIP;                                                                \
-        }                                                                                      \
-    } while (0)
-
-// Grow one of the engine's device buffers to `need` units of `unit` bytes (`cap` counts the same units); nothing happens while
-// the capacity suffices.  `inside` are the engine's pointers into the old block: they are null before it is freed and stay null
-// when the allocation fails -- m2d_get_option reads through them -- and the buffer is then null with capacity 0.
-template <typename T, typename Cap, typename... Inside>
-static inline int m2d_grow(m2d_engine *h, T *&buf, Cap &cap, const size_t need, const size_t unit, Inside *&...inside)
+inline int m2d_hip_failed(m2d_engine *h, const char *expr, const hipError_t e)
 {
-    if ((size_t)cap >= need) return M2D_OK;
-    ((inside = nullptr), ...);
-    if (buf) M2D_HIP_TRY(h, hipFree(buf));
-    buf = nullptr;
-    cap = 0;
-    M2D_HIP_TRY(h, hipMalloc((void **)&buf, need * unit));
-    cap = (Cap)need;
-    return M2D_OK;
+    h->last_error = std::string(expr) + ": " + hipGetErrorString(e);
+    return M2D_ERR_HIP;
 }
 
 // hipFuncSetAttribute(MaxDynamicSharedMemorySize) once per kernel and size: a retrieval call makes six such calls, each a
@@ -428,11 +486,12 @@ int m2d_launch_score_pairs(m2d_engine *h, const int32_t *users, const int32_t *i
                            bool use_ingredients = false, bool may_use_mirror = true);   // false: exact f32 rows whatever "pm_bf16" says
 int m2d_ensure_finite_scan(m2d_engine *h, hipStream_t stream);   // m2d_abi.hip: runs the queued table scan, if any
 int m2d_launch_rows_finite_check(m2d_engine *h, const int32_t *users, int64_t B, hipStream_t stream);   // Personal_Memory rows of a batch
-int m2d_launch_build_dish_high(m2d_engine *h, hipStream_t stream);
+// m2d_ingredients.hip: H[d] of an ingredient table that is not the engine's yet (m2d_set_ingredients builds it aside) into `high` [I, E]
+int m2d_launch_build_dish_high(m2d_engine *h, const float *ing, const int32_t *off, const int32_t *ids, const float *w, int64_t R,
+                               float *high, hipStream_t stream);
 int m2d_ensure_user_high(m2d_engine *h, hipStream_t stream);
 int m2d_ensure_pm_bf16(m2d_engine *h, hipStream_t stream);
-int m2d_launch_check_csr(m2d_engine *h, hipStream_t stream);                                          // the ingredient table's offsets
-int m2d_launch_check_csr(m2d_engine *h, const int32_t *off, int64_t nnz, hipStream_t stream);        // any row pointer of I + 1 entries
+int m2d_launch_check_csr(m2d_engine *h, const int32_t *off, int64_t nnz, hipStream_t stream);        // a row pointer of I + 1 entries
 // m2d_market.hip: latches the first recipe id outside [0, R); the filter behind m2d_cookable_dishes
 int m2d_launch_check_recipe_ids(m2d_engine *h, const int32_t *ids, int64_t nnz, int64_t R, hipStream_t stream);
 int m2d_launch_cookable(m2d_engine *h, const int32_t *market, int64_t nM, int32_t max_missing, int32_t *out_ids, int32_t *out_missing,
@@ -448,16 +507,15 @@ int m2d_launch_write_memory(m2d_engine *h, const int32_t *users, const int32_t *
                             const float *sign, const float *labels, int64_t B, int32_t L, float *gm, float beta_1,
                             float beta_2, float alpha, int32_t which, double *out_sums, hipStream_t stream);
 int m2d_train_setup(m2d_engine *h, int32_t learner, float lr, float clip_norm, hipStream_t stream);
-void m2d_train_release(m2d_engine *h);
+void m2d_train_release(m2d_engine *h);   // deletes h->train, which frees what it owns
 int m2d_launch_train_step(m2d_engine *h, const int32_t *users, const int32_t *items, const float *cats, const float *labels,
                           int64_t B, int32_t apply, float *out, hipStream_t stream);
 int m2d_train_get_slot(m2d_engine *h, int32_t table, int32_t slot, float **dev, int64_t *count);
 int m2d_train_step_count(m2d_engine *h, int64_t *steps, int32_t set);
 int m2d_launch_score_pairs_mlp(m2d_engine *h, const int32_t *users, const int32_t *items, int64_t B, float *out,
                                hipStream_t stream);
-// m2d_mlp.hip: frees what is derived from the head's weights (mlp_w1x3, mlp_w1pad, mlp_w1pc: a new head rebuilds them), and with
-// `grouping` the pair grouping's buffers as well (mlp_pg, mlp_pat8: they outlive a head)
-void m2d_mlp_free_derived(m2d_engine *h, bool grouping);
+// m2d_mlp.hip: frees what is derived from the head's weights (mlp_w1x3, mlp_w1pad, mlp_w1pc: a new head rebuilds them)
+void m2d_mlp_free_derived(m2d_engine *h);
 int m2d_launch_rank_candidates(m2d_engine *h, const int32_t *users, const int32_t *items,
                                const int32_t *lens, int64_t nseg, int32_t L, int32_t k, float *out_scores,
                                int32_t *out_items, int32_t *out_flags, hipStream_t stream, bool head = false);

@@ -179,7 +179,7 @@ int m2d_launch_groups(m2d_engine *h, const char *entry, const int32_t *members, 
     int rc;
     if ((rc = m2d_deep_conditions(h, entry, st)) != M2D_OK) return rc;
     const int64_t slots = nG * M;
-    if ((rc = m2d_grow(h, h->group_ids, h->group_cap, (size_t)(slots + nG), sizeof(int32_t))) != M2D_OK) return rc;
+    if ((rc = h->group_ids.grow(h, (size_t)(slots + nG))) != M2D_OK) return rc;
     int32_t *dense = h->group_ids, *cnt = h->group_ids + slots;
     hipLaunchKernelGGL(m2d_group_members, dim3((unsigned)((slots + 255) / 256)), dim3(256), 0, st, members, nG, M, h->U, h->user_base, dense,
                        cnt, h->err_dev);
@@ -189,7 +189,7 @@ int m2d_launch_groups(m2d_engine *h, const char *entry, const int32_t *members, 
     const int64_t P = h->opt_deep_chunk_pairs, total = slate ? nD : h->I;
     const int64_t W0 = total < P ? total : P, W = slate ? nD : W0 < 65536 ? W0 : 65536;
     const int64_t Gb = m2d_block_rows(P, (int64_t)M * W, nG);
-    if ((rc = m2d_grow(h, h->slate_scores, h->slate_scores_cap, (size_t)Gb * M * W, sizeof(float))) != M2D_OK) return rc;
+    if ((rc = h->slate_scores.grow(h, (size_t)Gb * M * W)) != M2D_OK) return rc;
     // ranges outside, blocks inside: a range's dish vectors are built ONCE for all blocks (a row's list lives in the outputs between
     // its ranges, so the order of the two loops does not show in it)
     for (int64_t d0 = 0; d0 < total; d0 += W) {

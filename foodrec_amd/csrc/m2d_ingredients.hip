@@ -141,15 +141,13 @@ int m2d_launch_check_csr(m2d_engine *h, const int32_t *off, int64_t nnz, hipStre
     return M2D_OK;
 }
 
-int m2d_launch_check_csr(m2d_engine *h, hipStream_t stream) { return m2d_launch_check_csr(h, h->ing_off, h->ing_nnz, stream); }
-
-int m2d_launch_build_dish_high(m2d_engine *h, hipStream_t stream)
+int m2d_launch_build_dish_high(m2d_engine *h, const float *ing, const int32_t *off, const int32_t *ids, const float *w, const int64_t R,
+                               float *high, hipStream_t stream)
 {
     const int64_t waves = (h->I + DB - 1) / DB;
     const dim3 grid((unsigned)((waves + 3) / 4));
 #define M2D_DISH_HIGH(NQ)                                                                                          \
-    hipLaunchKernelGGL(m2d_dish_high_from_ingredients<NQ>, grid, dim3(256), 0, stream, h->ing, h->ing_off, h->ing_ids, \
-                       h->ing_w, h->I, h->ing_rows, h->E, h->dish_high, h->err_dev)
+    hipLaunchKernelGGL(m2d_dish_high_from_ingredients<NQ>, grid, dim3(256), 0, stream, ing, off, ids, w, h->I, R, h->E, high, h->err_dev)
     if (h->E <= 64) M2D_DISH_HIGH(1);
     else if (h->E <= 128) M2D_DISH_HIGH(2);
     else M2D_DISH_HIGH(4);

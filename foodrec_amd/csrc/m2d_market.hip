@@ -167,9 +167,9 @@ int m2d_launch_cookable(m2d_engine *h, const int32_t *market, int64_t nM, int32_
     const int64_t o_missing = even(words), o_counts = o_missing + even(out_missing ? 0 : I), o_base = o_counts + even(nb),
                   o_total = o_base + even(nb);
     int rc;
-    if ((rc = m2d_grow(h, h->market_buf, h->market_cap, (size_t)(o_total + 2), sizeof(int32_t))) != M2D_OK) return rc;
-    if (!h->market_count_host) M2D_HIP_TRY(h, hipHostMalloc((void **)&h->market_count_host, sizeof(int64_t)));
-    uint32_t *bitmap = reinterpret_cast<uint32_t *>(h->market_buf);
+    if ((rc = h->market_buf.grow(h, (size_t)(o_total + 2))) != M2D_OK) return rc;
+    if (!h->market_count_host && (rc = h->market_count_host.alloc(h, 1)) != M2D_OK) return rc;
+    uint32_t *bitmap = reinterpret_cast<uint32_t *>(h->market_buf.get());
     int32_t *missing = out_missing ? out_missing : h->market_buf + o_missing;
     int32_t *counts = h->market_buf + o_counts, *base = h->market_buf + o_base;
     int64_t *total = reinterpret_cast<int64_t *>(h->market_buf + o_total);

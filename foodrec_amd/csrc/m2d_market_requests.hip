@@ -305,7 +305,7 @@ int m2d_launch_topk_markets(m2d_engine *h, const int32_t *users, int64_t nQ, con
     // partial ids | partial score words | bitmaps
     const int64_t part = S > 1 ? nQ * S * k : 0, o_bm = 2 * part;
     const int64_t need = o_bm + (lds ? 0 : nQ * words);
-    if ((rc = m2d_grow(h, h->markets_buf, h->markets_cap, (size_t)(need > 1 ? need : 1), sizeof(int32_t))) != M2D_OK) return rc;
+    if ((rc = h->markets_buf.grow(h, (size_t)(need > 1 ? need : 1))) != M2D_OK) return rc;
 
     MarketsArgs a;
     a.pm = h->pm; a.re = h->re; a.ce = h->ce; a.cats = h->dish_cats;

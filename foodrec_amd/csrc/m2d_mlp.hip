@@ -1187,12 +1187,14 @@ MlpChoice mlp_choose(const m2d_engine *h, const int K, const int64_t B)
 int mlp_ensure_pc_image(m2d_engine *h, const int K, hipStream_t stream)
 {
     if (h->mlp_w1pc) return M2D_OK;
-    M2D_HIP_TRY(h, hipMalloc((void **)&h->mlp_w1pc, (size_t)(2 * (K / 64) + 2) * PC_STAGE));
-    hipLaunchKernelGGL(m2d_mlp_image_pc_w1, dim3((unsigned)(((int64_t)K * MH1 + 255) / 256)), dim3(256), 0, stream,
-                       h->mlp_w1, K, reinterpret_cast<__bf16 *>(h->mlp_w1pc));
+    m2d_dev_buf<void> image;            // the engine's once its launches are queued: a failure leaves no image behind (m2d.h, "Setters")
+    if (int rc = image.grow(h, (size_t)(2 * (K / 64) + 2) * PC_STAGE)) return rc;
+    __bf16 *const w = static_cast<__bf16 *>(image.get());
+    hipLaunchKernelGGL(m2d_mlp_image_pc_w1, dim3((unsigned)(((int64_t)K * MH1 + 255) / 256)), dim3(256), 0, stream, h->mlp_w1, K, w);
     hipLaunchKernelGGL(m2d_mlp_image_pc_w2, dim3(MH1 * MH2 / 256), dim3(256), 0, stream, h->mlp_w2,
-                       reinterpret_cast<__bf16 *>(h->mlp_w1pc) + (size_t)(2 * (K / 64)) * (PC_STAGE / 2));
+                       w + (size_t)(2 * (K / 64)) * (PC_STAGE / 2));
     M2D_HIP_TRY(h, hipGetLastError());
+    h->mlp_w1pc = std::move(image);
     return M2D_OK;
 }
 
@@ -1200,9 +1202,9 @@ int mlp_ensure_pc_image(m2d_engine *h, const int K, hipStream_t stream)
 int mlp_group_pairs(m2d_engine *h, MlpArgs &a, const int64_t tiles_max, hipStream_t stream)
 {
     const size_t need = (size_t)(PG_MAXPAT + 4) + (size_t)tiles_max + (size_t)tiles_max * PC_PAIRS;
-    if (int rc = m2d_grow(h, h->mlp_pg, h->mlp_pg_cap, need, sizeof(int32_t))) return rc;
+    if (int rc = h->mlp_pg.grow(h, need)) return rc;
     if (!h->mlp_pat8 || h->mlp_pat8_gen != h->dish_vec_gen) {      // once per mask table
-        if (!h->mlp_pat8) M2D_HIP_TRY(h, hipMalloc((void **)&h->mlp_pat8, (size_t)h->I));
+        if (int rc = h->mlp_pat8.grow(h, (size_t)h->I)) return rc;
         hipLaunchKernelGGL(m2d_mlp_pg_pat8, dim3((unsigned)((h->I + 255) / 256)), dim3(256), 0, stream, h->dish_cats, h->C, h->I,
                            h->nonfinite_dev, h->mlp_pat8);
         M2D_HIP_TRY(h, hipGetLastError());
@@ -1227,7 +1229,7 @@ int mlp_group_pairs(m2d_engine *h, MlpArgs &a, const int64_t tiles_max, hipStrea
 int mlp_launch_pc(m2d_engine *h, MlpArgs &a, const MlpChoice &c, hipStream_t stream)
 {
     if (int rc = mlp_ensure_pc_image(h, a.K, stream)) return rc;
-    a.w1x3 = reinterpret_cast<const __bf16 *>(h->mlp_w1pc);
+    a.w1x3 = static_cast<const __bf16 *>(h->mlp_w1pc.get());
     a.pshift = __builtin_ctz((unsigned)(h->E / 32));
     // E = 32: a block is one period, keep every block; small batches: three more launches and mostly-empty tiles
     // cost more than the skipped periods save
@@ -1257,20 +1259,20 @@ int mlp_launch_gather(m2d_engine *h, MlpArgs &a, const MlpChoice &c, hipStream_t
     const int64_t ntiles = (a.B + 32 * MWAVES - 1) / (32 * MWAVES);
     const unsigned grid = (unsigned)(ntiles < h->num_cu ? ntiles : h->num_cu);
     if (c.padded && !h->mlp_w1pad) {       // built once per head (m2d_set_mlp_head resets it)
-        M2D_HIP_TRY(h, hipMalloc((void **)&h->mlp_w1pad, (size_t)Kp * MH1 * sizeof(float)));
+        if (int rc = h->mlp_w1pad.grow(h, (size_t)Kp * MH1)) return rc;
         M2D_HIP_TRY(h, hipMemsetAsync(h->mlp_w1pad, 0, (size_t)Kp * MH1 * sizeof(float), stream));
         M2D_HIP_TRY(h, hipMemcpyAsync(h->mlp_w1pad, h->mlp_w1, (size_t)a.K * MH1 * sizeof(float), hipMemcpyDeviceToDevice, stream));
     }
     if (c.padded) a.w1 = h->mlp_w1pad;
     if (c.x3 && !h->mlp_w1x3) {            // built once per head, from the W1 the kernel reads
-        M2D_HIP_TRY(h, hipMalloc((void **)&h->mlp_w1x3, (size_t)Kp * MH1 * 4 + (size_t)MH1 * MH2 * 4));
+        if (int rc = h->mlp_w1x3.grow(h, (size_t)Kp * MH1 * 4 + (size_t)MH1 * MH2 * 4)) return rc;
         hipLaunchKernelGGL(m2d_mlp_split_w1, dim3((unsigned)(((int64_t)Kp * MH1 + 255) / 256)), dim3(256), 0, stream,
-                           a.w1, Kp, reinterpret_cast<__bf16 *>(h->mlp_w1x3));
+                           a.w1, Kp, static_cast<__bf16 *>(h->mlp_w1x3.get()));
         hipLaunchKernelGGL(m2d_mlp_split_w2, dim3(MH1 * MH2 / 256), dim3(256), 0, stream, h->mlp_w2,
-                           reinterpret_cast<__bf16 *>(h->mlp_w1x3) + (size_t)Kp * MH1 * 2);
+                           static_cast<__bf16 *>(h->mlp_w1x3.get()) + (size_t)Kp * MH1 * 2);
         M2D_HIP_TRY(h, hipGetLastError());
     }
-    a.w1x3 = reinterpret_cast<const __bf16 *>(h->mlp_w1x3);
+    a.w1x3 = static_cast<const __bf16 *>(h->mlp_w1x3.get());
     a.w2x3 = a.w1x3 ? a.w1x3 + (size_t)Kp * MH1 * 2 : nullptr;
     MlpKernel fn = nullptr;
 #define M2D_MLP_CASE(N, PADK) \
@@ -1301,17 +1303,7 @@ int mlp_launch_generic(m2d_engine *h, const MlpArgs &a, hipStream_t stream)
 
 }  // namespace
 
-void m2d_mlp_free_derived(m2d_engine *h, const bool grouping)
-{
-    auto drop = [](auto *&p) {
-        if (p) (void)hipFree(p);
-        p = nullptr;
-    };
-    drop(h->mlp_w1x3); drop(h->mlp_w1pad); drop(h->mlp_w1pc);
-    if (!grouping) return;
-    drop(h->mlp_pg); drop(h->mlp_pat8);
-    h->mlp_pg_cap = 0;
-}
+void m2d_mlp_free_derived(m2d_engine *h) { h->mlp_w1x3.reset(); h->mlp_w1pad.reset(); h->mlp_w1pc.reset(); }
 
 int m2d_launch_score_pairs_mlp(m2d_engine *h, const int32_t *users, const int32_t *items, int64_t B, float *out,
                                hipStream_t stream)

@@ -261,7 +261,7 @@ int launch_compose(m2d_engine *h, const m2d_profile_batch *p, float *out, int32_
 int compose_to_scratch(m2d_engine *h, const m2d_profile_batch *p, const int32_t *&ids, hipStream_t st)
 {
     const size_t rows = (size_t)p->n * (h->C + 1) * h->E;
-    int rc = m2d_grow(h, h->profile_buf, h->profile_cap, rows + (size_t)p->n, sizeof(float));
+    int rc = h->profile_buf.grow(h, rows + (size_t)p->n);
     if (rc != M2D_OK) return rc;
     int32_t *made = reinterpret_cast<int32_t *>(h->profile_buf + rows);
     if ((rc = launch_compose(h, p, h->profile_buf, made, st)) != M2D_OK) return rc;

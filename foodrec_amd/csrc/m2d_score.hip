@@ -574,7 +574,7 @@ int launch_any(m2d_engine *h, const ScoreArgs &a, hipStream_t st)
 int m2d_ensure_user_high(m2d_engine *h, hipStream_t stream)
 {
     if (h->user_high_valid) return M2D_OK;
-    if (!h->user_high) M2D_HIP_TRY(h, hipMalloc((void **)&h->user_high, (size_t)h->U * 4 * sizeof(float)));
+    if (int rc = h->user_high.grow(h, (size_t)h->U * 4)) return rc;
     const int E4 = h->E >> 2;
     const dim3 grid(m2d_blocks_for(h, h->U * lpp_for(E4) / 64 + 4, 4, 16));
     with_width(E4, [&](auto lpp, auto) {
@@ -591,7 +591,7 @@ int m2d_ensure_pm_bf16(m2d_engine *h, hipStream_t stream)
 {
     if (h->pm_bf16_valid) return M2D_OK;
     const int64_t n = m2d_table_floats(h, 0);
-    if (!h->pm_bf16) M2D_HIP_TRY(h, hipMalloc((void **)&h->pm_bf16, (size_t)n * sizeof(uint16_t)));
+    if (int rc = h->pm_bf16.grow(h, (size_t)n)) return rc;
     M2D_HIP_TRY(h, hipMemsetAsync(h->pm_bf16_nonfinite, 0, sizeof(int32_t), stream));
     hipLaunchKernelGGL(m2d_build_pm_bf16, dim3(m2d_blocks_for(h, n / 4, 256)), dim3(256), 0, stream, h->pm, n, h->pm_bf16, h->pm_bf16_nonfinite);
     M2D_HIP_TRY(h, hipGetLastError());

@@ -223,7 +223,7 @@ int slate_prepare(m2d_engine *h, const int32_t *slate, int32_t d0, int64_t nD, S
     const int K = (h->C + 1) * h->E, Kp = (K + SL_KC - 1) / SL_KC * SL_KC;
     const int64_t rows = (nD + SL_DPAD - 1) / SL_DPAD * SL_DPAD + 1;          // the slate, zero rows up to the tile multiple, the zero row
     int rc;
-    if ((rc = m2d_grow(h, h->slate_dt, h->slate_dt_cap, (size_t)rows * Kp, sizeof(float))) != M2D_OK) return rc;
+    if ((rc = h->slate_dt.grow(h, (size_t)rows * Kp)) != M2D_OK) return rc;
     hipLaunchKernelGGL(m2d_build_slate_vectors, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, st, h->re, h->ce, h->dish_cats, slate, d0, nD,
                        rows, h->I, h->C, h->E, h->a, h->b, h->slate_dt, Kp, h->err_dev);
     M2D_HIP_TRY(h, hipGetLastError());
@@ -270,7 +270,7 @@ int m2d_launch_slate(m2d_engine *h, const char *entry, const int32_t *users, int
     }
     // m2d_topk_slate: user blocks of max(1, P / nD) rows are scored into scratch and selected from there
     const int64_t R = m2d_block_rows(h->opt_slate_chunk_pairs, nD, nU);
-    if ((rc = m2d_grow(h, h->slate_scores, h->slate_scores_cap, (size_t)R * nD, sizeof(float))) != M2D_OK) return rc;
+    if ((rc = h->slate_scores.grow(h, (size_t)R * nD)) != M2D_OK) return rc;
     for (int64_t u0 = 0; u0 < nU; u0 += R) {
         const int64_t n = nU - u0 < R ? nU - u0 : R;
         a.users = users + u0; a.nU = n; a.index_base = u0; a.out = h->slate_scores;
@@ -292,7 +292,7 @@ int m2d_launch_deep_lists(m2d_engine *h, const int32_t *users, int64_t nU, int32
     const int64_t W0 = h->I < P ? h->I : P, W = W0 < 65536 ? W0 : 65536;
     const int64_t R = m2d_block_rows(P, W, nU);
     int rc;
-    if ((rc = m2d_grow(h, h->slate_scores, h->slate_scores_cap, (size_t)R * W, sizeof(float))) != M2D_OK) return rc;
+    if ((rc = h->slate_scores.grow(h, (size_t)R * W)) != M2D_OK) return rc;
     for (int64_t u0 = 0; u0 < nU; u0 += R) {
         const int64_t n = nU - u0 < R ? nU - u0 : R;
         for (int64_t d0 = 0; d0 < h->I; d0 += W) {

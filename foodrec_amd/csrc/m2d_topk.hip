@@ -9,8 +9,8 @@ namespace {
 // ---- scratch ------------------------------------------------------------------------------------
 int ensure_scratch(m2d_engine *h, size_t bytes)
 {
-    if (h->scratch_bytes >= bytes) return M2D_OK;
-    return m2d_grow(h, h->scratch, h->scratch_bytes, bytes + (bytes >> 2), 1);      // a quarter more than asked for
+    if (h->scratch.cap >= bytes) return M2D_OK;
+    return h->scratch.grow(h, bytes + (bytes >> 2));      // a quarter more than asked for
 }
 
 // users[s] -> one id per candidate slot; padded slots (pos >= len) score dish 0 and are ignored later
@@ -111,7 +111,7 @@ int m2d_launch_rank_candidates(m2d_engine *h, const int32_t *users, const int32_
     // scratch: users_x i32[total] | items_x i32[total] | scores f32[total]
     int rc = ensure_scratch(h, (size_t)total * 12 + 256);
     if (rc != M2D_OK) return rc;
-    int32_t *users_x = reinterpret_cast<int32_t *>(h->scratch);
+    int32_t *users_x = reinterpret_cast<int32_t *>(h->scratch.get());
     int32_t *items_x = users_x + total;
     float *scores = reinterpret_cast<float *>(items_x + total);
 

@@ -95,10 +95,10 @@ struct HeadScratch {
 int head_scratch(m2d_engine *h, const size_t n, const size_t ncand, const size_t nheld, HeadScratch &s)
 {
     int rc;
-    if ((rc = m2d_grow(h, h->topk_mlp_ids, h->topk_mlp_ids_cap, 2 * n, sizeof(int32_t))) != M2D_OK) return rc;
-    if ((rc = m2d_grow(h, h->topk_mlp_scores, h->topk_mlp_scores_cap, n, sizeof(float))) != M2D_OK) return rc;
-    if (ncand && (rc = m2d_grow(h, h->topk_mlp_cand, h->topk_mlp_cand_cap, ncand, sizeof(int32_t))) != M2D_OK) return rc;
-    if (nheld && (rc = m2d_grow(h, h->topk_mlp_held, h->topk_mlp_held_cap, nheld, sizeof(float))) != M2D_OK) return rc;
+    if ((rc = h->topk_mlp_ids.grow(h, 2 * n)) != M2D_OK) return rc;
+    if ((rc = h->topk_mlp_scores.grow(h, n)) != M2D_OK) return rc;
+    if (ncand && (rc = h->topk_mlp_cand.grow(h, ncand)) != M2D_OK) return rc;
+    if (nheld && (rc = h->topk_mlp_held.grow(h, nheld)) != M2D_OK) return rc;
     s.users_x = h->topk_mlp_ids;
     s.items_x = s.users_x + n;
     s.scores = h->topk_mlp_scores;

@@ -45,6 +45,8 @@
 // differ in how slots are claimed, where dCE goes and who finishes the step) and apply_row<VEC> (one row's update; the apply
 // kernels differ in how rows are found and released).  m2d_launch_train_step chooses between train_step_fused / _staged; both
 // take the tables from apply_tabs and the learner from rule_args.  What a step makes stale: m2d_mark_written (m2d_engine.h).
+#include <memory>
+
 #include "m2d_engine.h"
 
 namespace {
@@ -578,65 +580,62 @@ __global__ __launch_bounds__(256) void m2d_fill_i32_kernel(int32_t *x, int64_t n
 struct m2d_train_state {
     int32_t learner = M2D_LEARNER_ADAM;
     float lr = 0.001f, clip = 5.0f;
-    OptState *opt = nullptr;            // device: step count and Adam's beta powers (see OptState)
-    float *slot[3][2] = {{nullptr, nullptr}, {nullptr, nullptr}, {nullptr, nullptr}};   // [PM, RE, CE][slot]
-    int32_t *map_u = nullptr, *map_d = nullptr, *slot_u = nullptr, *slot_d = nullptr, *cnt = nullptr;
-    float *gu = nullptr, *gd = nullptr, *gce = nullptr, *scal = nullptr;
-    float *part_ce = nullptr;           // [num_cu * 8, C, E]
-    double *part_acc = nullptr;         // [num_cu * 8, 2]
+    m2d_dev_buf<OptState> opt;          // device: step count and Adam's beta powers (see OptState)
+    m2d_dev_buf<float> slot[3][2];      // [PM, RE, CE][slot]
+    m2d_dev_buf<int32_t> map_u, map_d, slot_u, slot_d, cnt;
+    m2d_dev_buf<float> gu, gd, gce, scal;
+    m2d_dev_buf<float> part_ce;         // [num_cu * 8, C, E]
+    m2d_dev_buf<double> part_acc;       // [num_cu * 8, 2]
     int64_t cap = 0;                    // pairs the compact buffers hold
-    int32_t *done = nullptr;            // fused form: ticket counter of m2d_train_grad_fused
+    m2d_dev_buf<int32_t> done;          // fused form: ticket counter of m2d_train_grad_fused
     int parity = 0;                     // fused form: which pair of slot counters the next step uses
 };
 
 void m2d_train_release(m2d_engine *h)
 {
-    m2d_train_state *t = h->train;
-    if (!t) return;
-    for (auto &tb : t->slot)
-        for (float *q : tb)
-            if (q) (void)hipFree(q);
-    for (void *q : {(void *)t->map_u, (void *)t->map_d, (void *)t->slot_u, (void *)t->slot_d, (void *)t->cnt, (void *)t->gu,
-                    (void *)t->gd, (void *)t->gce, (void *)t->scal, (void *)t->part_ce, (void *)t->part_acc, (void *)t->opt, (void *)t->done})
-        if (q) (void)hipFree(q);
-    delete t;
+    delete h->train;
     h->train = nullptr;
 }
 
+m2d_engine::~m2d_engine() { m2d_train_release(this); }
+
+// The new state is built aside and becomes the engine's when everything has passed: a failure leaves no training state, as
+// m2d_train_end does (m2d.h, "Setters")
 int m2d_train_setup(m2d_engine *h, int32_t learner, float lr, float clip_norm, hipStream_t stream)
 {
     m2d_train_release(h);
-    m2d_train_state *t = new m2d_train_state;
-    h->train = t;
+    std::unique_ptr<m2d_train_state> built(new m2d_train_state);
+    m2d_train_state *const t = built.get();
+    int rc;
     t->learner = learner; t->lr = lr; t->clip = clip_norm;
     const int64_t n[3] = {m2d_table_floats(h, 0), m2d_table_floats(h, 1), m2d_table_floats(h, 2)};
     const int nslots = (learner == M2D_LEARNER_ADAM || learner == M2D_LEARNER_RMSPROP) ? 2 : learner == M2D_LEARNER_ADAGRAD ? 1 : 0;
     for (int tb = 0; tb < 3; ++tb)
         for (int s = 0; s < nslots; ++s) {
-            M2D_HIP_TRY(h, hipMalloc((void **)&t->slot[tb][s], (size_t)n[tb] * 4));
+            if ((rc = t->slot[tb][s].grow(h, (size_t)n[tb])) != M2D_OK) return rc;
             // slot initial values: adam m = v = 0; adagrad accumulator 0.1; rmsprop rms = 1, momentum = 0
             const float v0 = learner == M2D_LEARNER_ADAGRAD ? 0.1f : (learner == M2D_LEARNER_RMSPROP && s == 0) ? 1.0f : 0.0f;
             hipLaunchKernelGGL(m2d_fill_kernel, dim3(m2d_blocks_for(h, n[tb] / 64 + 1, 4)), dim3(256), 0, stream, t->slot[tb][s], n[tb], v0);
         }
-    M2D_HIP_TRY(h, hipMalloc((void **)&t->map_u, (size_t)h->U * 4));
-    M2D_HIP_TRY(h, hipMalloc((void **)&t->map_d, (size_t)h->I * 4));
+    if ((rc = t->map_u.grow(h, (size_t)h->U)) != M2D_OK || (rc = t->map_d.grow(h, (size_t)h->I)) != M2D_OK) return rc;
     hipLaunchKernelGGL(m2d_fill_i32_kernel, dim3(m2d_blocks_for(h, h->U / 64 + 1, 4)), dim3(256), 0, stream, t->map_u, h->U, -1);
     hipLaunchKernelGGL(m2d_fill_i32_kernel, dim3(m2d_blocks_for(h, h->I / 64 + 1, 4)), dim3(256), 0, stream, t->map_d, h->I, -1);
-    M2D_HIP_TRY(h, hipMalloc((void **)&t->cnt, 4 * 4));                 // two pairs: the fused form alternates between them
+    if ((rc = t->cnt.grow(h, 4)) != M2D_OK) return rc;                  // two pairs: the fused form alternates between them
     M2D_HIP_TRY(h, hipMemsetAsync(t->cnt, 0, 16, stream));
-    M2D_HIP_TRY(h, hipMalloc((void **)&t->done, 4));
+    if ((rc = t->done.grow(h, 1)) != M2D_OK) return rc;
     M2D_HIP_TRY(h, hipMemsetAsync(t->done, 0, 4, stream));
-    M2D_HIP_TRY(h, hipMalloc((void **)&t->gce, (size_t)n[2] * 4));
+    if ((rc = t->gce.grow(h, (size_t)n[2])) != M2D_OK) return rc;
     M2D_HIP_TRY(h, hipMemsetAsync(t->gce, 0, (size_t)n[2] * 4, stream));
-    M2D_HIP_TRY(h, hipMalloc((void **)&t->scal, 8 * 4));
-    M2D_HIP_TRY(h, hipMalloc((void **)&t->part_ce, (size_t)h->num_cu * 8 * n[2] * 4));
-    M2D_HIP_TRY(h, hipMalloc((void **)&t->part_acc, (size_t)h->num_cu * 8 * 2 * 8));
+    if ((rc = t->scal.grow(h, 8)) != M2D_OK || (rc = t->part_ce.grow(h, (size_t)h->num_cu * 8 * n[2])) != M2D_OK ||
+        (rc = t->part_acc.grow(h, (size_t)h->num_cu * 8 * 2)) != M2D_OK)
+        return rc;
     M2D_HIP_TRY(h, hipMemsetAsync(t->scal, 0, 32, stream));
-    M2D_HIP_TRY(h, hipMalloc((void **)&t->opt, sizeof(OptState)));
+    if ((rc = t->opt.grow(h, 1)) != M2D_OK) return rc;
     const OptState st0 = {0.9f, 0.999f, 0};
     M2D_HIP_TRY(h, hipMemcpyAsync(t->opt, &st0, sizeof st0, hipMemcpyHostToDevice, stream));
     M2D_HIP_TRY(h, hipStreamSynchronize(stream));      // st0 is on this frame
     M2D_HIP_TRY(h, hipGetLastError());
+    h->train = built.release();
     return M2D_OK;
 }
 
@@ -649,10 +648,10 @@ int grow_compact(m2d_engine *h, m2d_train_state *t, int64_t B, hipStream_t strea
     const size_t W = (size_t)(h->C + 1) * h->E, E = (size_t)h->E;
     M2D_HIP_TRY(h, hipStreamSynchronize(stream));      // steps in flight use the blocks about to be freed
     t->cap = 0;
-    auto grow = [&](auto *&buf, size_t unit) { int64_t held = 0; return m2d_grow(h, buf, held, (size_t)B, unit); };   // (frees what buf holds)
+    t->slot_u.reset(); t->slot_d.reset(); t->gu.reset(); t->gd.reset();
     int rc;
-    if ((rc = grow(t->slot_u, 4)) != M2D_OK || (rc = grow(t->slot_d, 4)) != M2D_OK || (rc = grow(t->gu, W * 4)) != M2D_OK ||
-        (rc = grow(t->gd, E * 4)) != M2D_OK)
+    if ((rc = t->slot_u.grow(h, (size_t)B)) != M2D_OK || (rc = t->slot_d.grow(h, (size_t)B)) != M2D_OK ||
+        (rc = t->gu.grow(h, (size_t)B * W)) != M2D_OK || (rc = t->gd.grow(h, (size_t)B * E)) != M2D_OK)
         return rc;
     M2D_HIP_TRY(h, hipMemsetAsync(t->gu, 0, (size_t)B * W * 4, stream));
     M2D_HIP_TRY(h, hipMemsetAsync(t->gd, 0, (size_t)B * E * 4, stream));
@@ -664,7 +663,7 @@ TrainArgs train_args(const m2d_engine *h, const m2d_train_state *t, const int32_
                      const float *labels, int64_t B, int32_t apply, float *out)
 {
     TrainArgs a;
-    a.pm = const_cast<float *>(h->pm); a.re = const_cast<float *>(h->re); a.ce = const_cast<float *>(h->ce);
+    a.pm = const_cast<float *>(h->pm.p); a.re = const_cast<float *>(h->re.p); a.ce = const_cast<float *>(h->ce.p);
     a.users = users; a.items = items; a.cats = cats; a.labels = labels;
     a.B = B; a.U = h->U; a.I = h->I; a.user_base = h->user_base; a.C = h->C; a.E = h->E; a.a = h->a; a.b = h->b;
     a.map_u = t->map_u; a.map_d = t->map_d; a.slot_u = t->slot_u; a.slot_d = t->slot_d; a.cnt = t->cnt;
@@ -690,9 +689,9 @@ RuleArgs rule_args(const m2d_train_state *t)
 void apply_tabs(const m2d_engine *h, const m2d_train_state *t, const int32_t *cnt, ApplyTab tb[3])
 {
     const int32_t all = t->learner == M2D_LEARNER_ADAM, W = (h->C + 1) * h->E;
-    tb[0] = {const_cast<float *>(h->pm), t->slot[0][0], t->slot[0][1], t->gu, t->map_u, t->slot_u, cnt + 0, h->U, W, all};
-    tb[1] = {const_cast<float *>(h->re), t->slot[1][0], t->slot[1][1], t->gd, t->map_d, t->slot_d, cnt + 1, h->I, h->E, all};
-    tb[2] = {const_cast<float *>(h->ce), t->slot[2][0], t->slot[2][1], t->gce, nullptr, nullptr, nullptr, h->C, h->E, 1};
+    tb[0] = {const_cast<float *>(h->pm.p), t->slot[0][0], t->slot[0][1], t->gu, t->map_u, t->slot_u, cnt + 0, h->U, W, all};
+    tb[1] = {const_cast<float *>(h->re.p), t->slot[1][0], t->slot[1][1], t->gd, t->map_d, t->slot_d, cnt + 1, h->I, h->E, all};
+    tb[2] = {const_cast<float *>(h->ce.p), t->slot[2][0], t->slot[2][1], t->gce, nullptr, nullptr, nullptr, h->C, h->E, 1};
 }
 
 // two launches (batches of up to 1024 pairs whose dCE fits in LDS four times)

@@ -180,7 +180,7 @@ int m2d_launch_write_memory(m2d_engine *h, const int32_t *users, const int32_t *
     // Personal_Memory is about to change, and may receive inf / NaN: retrieval reads the device word again
     if (which & M2D_WRITE_PERSONAL) m2d_mark_written(h, M2D_TAB_PM, M2D_BY_ENGINE);
     WriteArgs a;
-    a.pm = const_cast<float *>(h->pm); a.re = h->re; a.ce = h->ce; a.gm = gm;
+    a.pm = const_cast<float *>(h->pm.p); a.re = h->re; a.ce = h->ce; a.gm = gm;
     a.users = users; a.items = items; a.cats = cats; a.sign = sign; a.labels = labels;
     a.B = B; a.U = h->U; a.I = h->I; a.user_base = h->user_base; a.C = h->C; a.E = h->E; a.L = L;
     a.beta_1 = beta_1; a.beta_2 = beta_2; a.alpha = alpha; a.err = h->err_dev; a.nonfinite = h->nonfinite_dev;

@@ -14,6 +14,17 @@
  *     device and reported by m2d_check(), which does synchronise;
  *   - an engine is not thread-safe; distinct engines / streams are independent;
  *   - all arithmetic is float32; ids are int32 (Model_Recommender.py:26-32).
+ *
+ * Setters (m2d_set_dish_categories, m2d_set_ingredients, m2d_set_recipes, m2d_set_mlp_head, m2d_train_begin) fail in one of two ways:
+ *   - refused BEFORE anything is replaced -- whatever the arguments alone decide: a null pointer, a size, bad `table_flags`, a
+ *     BORROWED array (M2D_TABLES_DEVICE) that must be 16-byte aligned and is not (the dish masks; W1 and W2 of the head), and, where
+ *     the setter reads the id-error latch first, an id error still latched from an earlier launch, returned under its own code.
+ *     The previous table / head / ingredients / recipes / training state stays set and served, its borrowed arrays still borrowed;
+ *   - failed AFTER replacement has begun -- a HIP error, a copy of the engine's own that is not aligned, a malformed CSR, a bad id:
+ *     the feature is left UNSET, exactly as the matching m2d_clear_* / m2d_train_end leaves it, and the call returns its own code and
+ *     text.  The engine never keeps a pointer from a call it refused, and never serves a half-set feature.
+ * What a setter builds lazily from its tables later follows the same rule: a build that fails leaves nothing behind that a later
+ * call would take for built.
  */
 #ifndef M2D_H_
 #define M2D_H_
@@ -63,7 +74,8 @@ const char *m2d_last_error(const m2d_engine *h);
 int m2d_set_user_base(m2d_engine *h, int64_t user_base);
 
 /* Resident per-dish category masks [I, C] -- the device-side form of dish_to_category.json
- * (Train_recommender.py:132, evaluate.py:43,50).  Needed by the *_bydish / rank / topk calls. */
+ * (Train_recommender.py:132, evaluate.py:43,50).  Needed by the *_bydish / rank / topk calls.  The table is read 16 bytes at a
+ * time: a borrowed one must be 16-byte aligned.  Failures: "Setters" above. */
 int m2d_set_dish_categories(m2d_engine *h, const float *cats, int table_flags);
 
 /* Predict.  Replaces sess.run([model.logits], feed_dict) (evaluate.py:55-59) = Model.inference
@@ -273,7 +285,8 @@ int m2d_train_end(m2d_engine *h);
  * The call gathers and segment-sums the rows into H once (it synchronises and reports a malformed CSR /
  * bad id as M2D_ERR_BAD_INGREDIENT; an id error still latched from an earlier launch is returned first, under its own
  * code, exactly as m2d_check would); all four arrays use `table_flags`.  A dish with an empty list
- * scores NaN, like an empty category mask. */
+ * scores NaN, like an empty category mask.  Failures: "Setters" above -- after M2D_ERR_BAD_INGREDIENT or a HIP error there is no
+ * ingredient table, as after m2d_clear_ingredients. */
 int m2d_set_ingredients(m2d_engine *h, const float *ing, int64_t R, const int32_t *off, const int32_t *ids,
                         const float *w, int64_t nnz, int table_flags);
 int m2d_clear_ingredients(m2d_engine *h);
@@ -291,7 +304,8 @@ int m2d_score_pairs_ingredients(m2d_engine *h, const int32_t *users, const int32
  * run on the MFMA kernels (split-bf16 layers 1-2 by default, exact f32 with option "mlp_bf16x3" = 0), and so do
  * K % 4 == 0, K <= 1280 on a W1 copy zero-padded to whole 64-row chunks (the reference's embed_size 200 gives
  * K = 1000); other sizes run a generic kernel.  Dish masks must be resident
- * (m2d_set_dish_categories); the ingredient table, when set, feeds Dt's high-level part. */
+ * (m2d_set_dish_categories); the ingredient table, when set, feeds Dt's high-level part.  W1 and W2 are read 16 bytes at a time:
+ * borrowed ones must be 16-byte aligned.  Failures: "Setters" above. */
 int m2d_set_mlp_head(m2d_engine *h, const float *W1, const float *b1, const float *W2, const float *b2,
                      const float *w3, float b3, int32_t H1, int32_t H2, int table_flags);
 int m2d_clear_mlp_head(m2d_engine *h);
@@ -502,7 +516,7 @@ int m2d_select_probe(m2d_engine *h, const float *scores /* device */, int64_t ro
  * return M2D_ERR_BAD_INGREDIENT and leave the recipes UNSET, and so does a HIP error met on the way (under M2D_ERR_HIP, its own
  * text kept).  A call refused BEFORE anything is replaced leaves the previous recipes set and served, its borrowed arrays still
  * borrowed: M2D_ERR_INVALID_ARG (below), and an id error still latched from an earlier launch, which is returned first, under its
- * own code.  No later kernel range-checks a recipe id.  A second m2d_set_recipes replaces the first; m2d_clear_recipes
+ * own code ("Setters" above).  No later kernel range-checks a recipe id.  A second m2d_set_recipes replaces the first; m2d_clear_recipes
  * returns the engine to "not configured"; m2d_destroy frees owned copies.  R > INT32_MAX, nnz > INT32_MAX, a null pointer or bad
  * flags: M2D_ERR_INVALID_ARG.
  *

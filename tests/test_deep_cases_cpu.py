@@ -41,9 +41,11 @@ def test_symbols_are_declared_in_the_header_and_the_ctypes_table():
 def test_option_bounds_as_the_source_states_them():
     """deep_chunk_pairs: 256 ... 2^24, default 2^22, set and read like slate_chunk_pairs"""
     abi = _read("foodrec_amd", "csrc", "m2d_abi.hip")
-    m = re.search(r'"deep_chunk_pairs"\)\) \{\s*if \(value < (\d+) \|\| value > \(1 << (\d+)\)\) return fail\(h, M2D_ERR_INVALID_ARG', abi)
+    # one row of the option table serves m2d_set_option (the range, refused with M2D_ERR_INVALID_ARG) and m2d_get_option (the member)
+    m = re.search(r'opt\("deep_chunk_pairs", &m2d_engine::opt_deep_chunk_pairs, (\d+), 1 << (\d+), "256 \.\.\. 2\^24"\)', abi)
     assert m and (int(m.group(1)), int(m.group(2))) == (256, 24)
-    assert 'else if (!strcmp(name, "deep_chunk_pairs")) *value = h->opt_deep_chunk_pairs;' in abi
+    assert abi.count('"deep_chunk_pairs"') == 1
+    assert 'return fail(h, M2D_ERR_INVALID_ARG, std::string("m2d_set_option: ") + name + " takes " + o->takes);' in abi
     eng = _read("foodrec_amd", "csrc", "m2d_engine.h")
     assert "int64_t opt_deep_chunk_pairs = 1 << 22;" in eng and dc.DEFAULT_P == 1 << 22
     assert "deep_chunk_pairs" in _read("include", "m2d.h") and "deep_chunk_pairs" in _read("README.md")
