@@ -1002,12 +1002,12 @@ int m2d_stream_read_probe(m2d_engine *h, const void *buf, int64_t bytes, float *
 //     9   retrieval on the one-block-per-user kernel (same places); also the generic pair, head and slate kernels (m2d_score.hip,
 //         m2d_mlp.hip, m2d_slate.hip)
 //    11 / 12   the pair kernel's throughput / latency form whatever the batch size (m2d_score.hip)
-//    13   the tie repair's one-block-per-user tier from the third listed user on (m2d_catalogue_plan.hip)
+//    13   the tie repair's one-block-per-user tier from the third listed user on (m2d_grouped_policy.h)
 //    14   the nine-launch training step (m2d_train.hip)
-//    15   the retrieval scan's progress-word wait gives up at once: M2D_ERR_KERNEL_TIMEOUT, a test hook (m2d_catalogue_plan.hip)
+//    15   the retrieval scan's progress-word wait gives up at once: M2D_ERR_KERNEL_TIMEOUT, a test hook (m2d_grouped_policy.h)
 //    16   the MLP head's row offsets in 16-byte units, the instantiation of tables of 4 GiB and more (m2d_mlp.hip)
-//   100 + n   n dish-range splits in retrieval, 1 <= n <= 64; also switches the pruned launch off (m2d_catalogue_plan.hip,
-//         m2d_catalogue_dense.hip)
+//   100 + n   n dish-range splits in retrieval, 1 <= n <= 64; also switches the pruned launch off (topk_split_hook,
+//         m2d_grouped_policy.h)
 //   any value but 0 keeps m2d_topk_users_excluding off its filtered first tier (m2d_catalogue_excl.hip)
 namespace {
 

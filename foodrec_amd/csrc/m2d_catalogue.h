@@ -22,6 +22,7 @@
 #include <type_traits>
 
 #include "m2d_engine.h"
+#include "m2d_grouped_policy.h"
 
 // What is written is what runs: no floating-point contraction in this file.  hipcc's default (-ffp-contract=fast) fuses a
 // multiply into a following add wherever it sees one -- ALSO through __fmul_rn / __fadd_rn, and not in every copy of an
@@ -131,15 +132,17 @@ M2D_INTERNAL void m2d_launch_merge_splits(const float *ps, const int32_t *pi, in
                                           hipStream_t st, const float *tie_in = nullptr, float *tie_out = nullptr, int32_t *tie_list = nullptr,
                                           int64_t I = 0, const float *ex_in = nullptr, float *ex_out = nullptr, const float *plan = nullptr,
                                           int32_t *rcount = nullptr);
-M2D_INTERNAL void m2d_launch_merge_splits2(const float *ps, const int32_t *pi, int64_t nU, int nsplit, int k, float *tmp_s, int32_t *tmp_i,
-                                           float *out_s, int32_t *out_i, hipStream_t st, float *tie, float *tie_final, int32_t *tie_list,
-                                           int64_t I, float *ex = nullptr, float *ex_final = nullptr, const float *plan = nullptr,
-                                           int32_t *rcount = nullptr);
 M2D_INTERNAL void m2d_topk_launch_fill_absent(float *scores, int32_t *ids, int64_t nU, int k, int64_t I, hipStream_t st);
 M2D_INTERNAL void m2d_topk_launch_tie_compact(const float *tie_final, int64_t nU, int32_t *tie_list, float *scores, int32_t *ids, int k,
                                               int64_t I, int refined, hipStream_t st);
 M2D_INTERNAL void m2d_topk_launch_refine(const RefineArgs &f, bool flag_pass, hipStream_t st);
 M2D_INTERNAL int m2d_topk_launch_repair(m2d_engine *h, const RepairArgs &r, bool hv, hipStream_t st);
+// a retrieval launch with no tie repair, refinement or pruning: "topk_repaired", "topk_refined", "topk_tiles_scanned" and
+// "topk_tiles_full" answer 0, not the last pattern-grouped call's numbers
+inline void m2d_topk_no_diagnostics(m2d_engine *h)
+{
+    h->topk_tie_list = nullptr; h->topk_refine_counter = nullptr; h->topk_tiles_counter = nullptr; h->topk_tiles_full = 0;
+}
 // m2d_catalogue_plan.hip, for m2d_catalogue_rank: the sorted dish table (ensure_grouped, refresh_grouped_nonfinite), and the
 // sort of 8-float plan records by their word-5 pattern mask (m2d_plan_hist / _scan / _scatter; `hist`: PLAN_KEYS words)
 constexpr int PLAN_KEYS = 1 << 15;                         // a mask holds bits 1..15: key = mask >> 1
@@ -932,7 +935,7 @@ __device__ __forceinline__ unsigned long long walk_tiles(const RankTables &p, co
 }
 
 #ifndef M2D_TOPK_HALF_BLOCKS
-#define M2D_TOPK_HALF_BLOCKS 1                             // the launcher's own choice of 128-user blocks (see launch_grouped)
+#define M2D_TOPK_HALF_BLOCKS 1                             // the launcher's own choice of 128-user blocks (see grouped_policy)
 #endif
 constexpr int grouped_tiles_per_stage(int E) { return E <= 32 ? 16 : (E == 64 ? 8 : (E == 128 ? 4 : 2)); }   // 64 KiB stages
 

@@ -475,12 +475,7 @@ int launch_mfma(m2d_engine *h, TopkArgs &a, float *final_s, int32_t *final_i, hi
         if (ns > cap) ns = cap;
         nsplit = (int)ns;
     }
-    if (h->opt_variant >= 100) {   // test hook: force the number of dish-range splits
-        nsplit = h->opt_variant - 100;
-        if (nsplit < 1) nsplit = 1;
-        if (nsplit > 64) nsplit = 64;
-    }
-    a.nsplit = nsplit;
+    a.nsplit = nsplit = topk_split_hook(h->opt_variant, nsplit, 64);
     if (nsplit > 1) {
         const size_t need = (size_t)a.nU * nsplit * a.k * 8 + 256;
         if (int rc = h->scratch.grow(h, need)) return rc;
@@ -490,9 +485,7 @@ int launch_mfma(m2d_engine *h, TopkArgs &a, float *final_s, int32_t *final_i, hi
         a.out_scores = final_s;
         a.out_ids = final_i;
     }
-    h->topk_tie_list = nullptr;                             // (no tie repair, refinement or pruning on this path: "topk_repaired",
-    h->topk_refine_counter = nullptr;                       //  "topk_refined" and "topk_tiles_scanned" answer 0, not the last
-    h->topk_tiles_counter = nullptr; h->topk_tiles_full = 0;      //  pattern-grouped call's numbers)
+    m2d_topk_no_diagnostics(h);
     auto kern = m2d_topk_mfma<NB, WAVES, KR>;
     M2D_HIP_TRY(h, m2d_lds_limit((const void *)kern, (int)lds));
     hipLaunchKernelGGL(kern, dim3((unsigned)ublocks, (unsigned)nsplit), dim3(WAVES * 64), lds, st, a);
@@ -537,7 +530,7 @@ int m2d_topk_literal_launch(m2d_engine *h, const int32_t *users, int64_t nU, int
     a.pm = h->pm; a.re = h->re; a.ce = h->ce; a.cats = h->dish_cats; a.hv = h->dish_high; a.users = users;
     a.U = h->U; a.I = h->I; a.user_base = h->user_base; a.C = h->C; a.E = h->E; a.k = k; a.a = h->a; a.b = h->b;
     a.out_scores = out_scores; a.out_ids = out_ids; a.err = h->err_dev;
-    h->topk_tie_list = nullptr; h->topk_refine_counter = nullptr; h->topk_tiles_counter = nullptr; h->topk_tiles_full = 0;
+    m2d_topk_no_diagnostics(h);
     hipLaunchKernelGGL(m2d_topk_literal, dim3((unsigned)nU), dim3(256), (size_t)4 * 2 * k * sizeof(float), stream, a);
     M2D_HIP_TRY(h, hipGetLastError());
     h->last_kernel = "m2d_topk_literal";
@@ -573,7 +566,7 @@ int m2d_topk_dense_launch(m2d_engine *h, const int32_t *users, int64_t nU, int32
 #undef M2D_TOPK
     }
     const size_t lds = (size_t)4 * 2 * k * sizeof(float);
-    h->topk_tie_list = nullptr; h->topk_refine_counter = nullptr; h->topk_tiles_counter = nullptr; h->topk_tiles_full = 0;
+    m2d_topk_no_diagnostics(h);
     hipLaunchKernelGGL(m2d_topk_generic, dim3((unsigned)nU), dim3(256), lds, stream, a, K);
     M2D_HIP_TRY(h, hipGetLastError());
     h->last_kernel = "m2d_topk_generic";

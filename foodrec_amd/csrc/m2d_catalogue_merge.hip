@@ -381,28 +381,6 @@ void m2d_launch_merge_splits(const float *ps, const int32_t *pi, int64_t nU, int
 #undef M2D_MERGE
 }
 
-// More than 64 partial lists per user: two passes of the merge above -- groups of 64 consecutive splits first (a
-// "user" of that pass is one (user, group)), then the per-group winners.  nsplit must be a multiple of 64 then;
-// tmp_s / tmp_i hold nU * (nsplit / 64) * k entries.  Consecutive groups are consecutive dish ranges, so the
-// lower-split-wins tie rule carries through both passes.
-// tie: [nU * nsplit] values of the splits, then room for the nU * (nsplit / 64) of the first pass, then the nU final ones
-// ex: [nU * nsplit] x 8 floats of the splits' left-out scores (LeftOut), then room for the first pass's nU * (nsplit / 64), then the
-// nU final ones -- laid out like `tie`; null = not kept
-void m2d_launch_merge_splits2(const float *ps, const int32_t *pi, int64_t nU, int nsplit, int k, float *tmp_s, int32_t *tmp_i,
-                              float *out_s, int32_t *out_i, hipStream_t st, float *tie, float *tie_final, int32_t *tie_list, int64_t I,
-                              float *ex, float *ex_final, const float *plan, int32_t *rcount)
-{
-    if (nsplit <= 64) {
-        m2d_launch_merge_splits(ps, pi, nU, nsplit, k, out_s, out_i, st, tie, tie_final, tie_list, I, ex, ex_final, plan, rcount);
-        return;
-    }
-    const int G = nsplit / 64;
-    float *tie_mid = tie + (size_t)nU * nsplit;
-    float *ex_mid = ex ? ex + (size_t)nU * nsplit * 8 : nullptr;
-    m2d_launch_merge_splits(ps, pi, nU * G, 64, k, tmp_s, tmp_i, st, tie, tie_mid, nullptr, 0, ex, ex_mid);      // a "user" of this pass is (user, group)
-    m2d_launch_merge_splits(tmp_s, tmp_i, nU, G, k, out_s, out_i, st, tie_mid, tie_final, tie_list, I, ex_mid, ex_final, plan, rcount);
-}
-
 void m2d_topk_launch_fill_absent(float *scores, int32_t *ids, int64_t nU, int k, int64_t I, hipStream_t st)
 {
     hipLaunchKernelGGL(m2d_topk_fill_absent, dim3((unsigned)((nU + 127) / 128)), dim3(128), 0, st, scores, ids, nU, k, I);

@@ -699,248 +699,208 @@ int refresh_grouped_nonfinite(m2d_engine *h, hipStream_t st)
     return M2D_OK;
 }
 
-// shared tail of every MFMA retrieval launch: dish-range splits -> partial lists in scratch.  The grouped kernels run
-// ONE block per CU (128 KiB of LDS), so the grid is ublocks x nsplit blocks dealt out in rounds of num_cu: the fewest
-// splits whose last round is at least 90 % full are taken (each split repeats the early, insertion-heavy part of a
-// scan and adds a merge pass: 65 536 users x 100 k dishes ran 3.69 ms with 2 splits and 2.91 ms with 1).  Few users:
-// up to max_splits blocks per user block, so that a single query still uses the whole chip.
-int pick_splits(m2d_engine *h, int64_t ublocks, int64_t tiles, int64_t min_tiles_per_split, int max_splits = 64)
+// The scratch of one pattern-grouped call, stated once: what each of the four buffers must hold, and -- after the grows -- where
+// every stage finds its part of them.
+//   topk_flags  tie values, a float per slot | the repair list (int32: count, users) | the repair's partial lists
+//   topk_ex     the left-out records, 8 floats per slot | the refine counters [8] | a word per user
+//   scratch     the dish ranges' partial lists: scores | ids | the two-pass merge's scores | ids          (bytes)
+//   topk_plan   records [nU, 8] | order [nU, rounded up to 4] | sort histogram [PLAN_KEYS] | counter (two 64-bit words) | work | items
+// What is kept per (user, dish range) -- a tie value, the left-out record -- has one layout: per user `nsplit` slots of the
+// ranges, `nsplit / 64` slots of the groups of 64 when the merge takes two passes, then one final slot per user.
+struct GroupedLayout {
+    size_t tie_need, ex_need, scratch_need, plan_need;      // units of the buffer's grow(); 0: the call does not use it
+    float *tie_val, *tie_group, *tie_final;                 // tie values of the ranges, of the groups of 64, per user
+    int32_t *tie_list;                                      // [0] listed users, [1 + f] their positions in the call
+    float *part_s;                                          // the repair's partial lists [REPAIR_CAP, REPAIR_SPLITS, k]
+    int32_t *part_i;
+    float *ex, *ex_group, *ex_final;                        // left-out records in the tie values' layout; null = not kept
+    int32_t *refine_counter;                                // [0] refined [1] sent to the repair; [8 + u] user u's word; null = not kept
+    float *lists_s, *tmp_s;                                 // partial lists of the ranges (null: one range), of the groups of 64 (null
+    int32_t *lists_i, *tmp_i;                               //  unless nsplit > 64)
+    float *plan;                                            // null = the scan takes no plan
+    int32_t *shared_thr, *order, *hist;                     // shared_thr: word 6 of the plan records; hist: 16-B aligned
+    unsigned long long *counter;                            // two words (tiles, completed)
+    int32_t *work, *items;
+
+    GroupedLayout(const int64_t nU, const int k, const int nsplit, const bool ext, const bool planned, const int64_t ublocks)
+        : n(nU), k(k), groups(nsplit > 64 ? (size_t)nU * (nsplit / 64) : 0), slots_before(nsplit > 1 ? (size_t)nU * nsplit + groups : 0),
+          lists(nsplit > 1 ? (size_t)nU * nsplit * k : 0), part((size_t)REPAIR_CAP * REPAIR_SPLITS * k), nitems((size_t)ublocks * nsplit)
+    {
+        tie_need = slots_before + n + 1 + n + 2 * part;
+        ex_need = ext ? (slots_before + n) * 8 + n + 8 : 0;
+        scratch_need = nsplit > 1 ? (lists + groups * k) * 8 + 256 : 0;
+        plan_need = planned ? n * 8 + n + PLAN_KEYS + 8 + 2 * nitems : 0;
+    }
+    void bind(float *flags, float *exb, float *scratch, float *planb)
+    {
+        tie_val = flags; tie_group = flags + (slots_before - groups); tie_final = flags + slots_before;
+        tie_list = reinterpret_cast<int32_t *>(tie_final + n);
+        part_s = tie_final + n + 1 + n;
+        part_i = reinterpret_cast<int32_t *>(part_s + part);
+        ex = ex_need ? exb : nullptr;
+        ex_group = ex ? ex + (slots_before - groups) * 8 : nullptr;
+        ex_final = ex ? ex + slots_before * 8 : nullptr;
+        refine_counter = ex ? reinterpret_cast<int32_t *>(ex_final + n * 8) : nullptr;
+        lists_s = lists ? scratch : nullptr;
+        lists_i = reinterpret_cast<int32_t *>(lists ? lists_s + lists : nullptr);
+        tmp_s = groups ? scratch + 2 * lists : nullptr;
+        tmp_i = reinterpret_cast<int32_t *>(groups ? tmp_s + groups * k : nullptr);
+        plan = plan_need ? planb : nullptr;
+        if (!plan) { shared_thr = order = hist = work = items = nullptr; counter = nullptr; return; }
+        shared_thr = reinterpret_cast<int32_t *>(plan) + 6;
+        order = reinterpret_cast<int32_t *>(plan + n * 8);
+        hist = order + ((n + 3) & ~(size_t)3);
+        counter = reinterpret_cast<unsigned long long *>(hist + PLAN_KEYS);
+        work = reinterpret_cast<int32_t *>(counter + 2);
+        items = work + nitems;
+    }
+
+private:
+    size_t n, k, groups, slots_before, lists, part, nitems;      // users; list depth; (user, group) slots; slots before the final ones;
+                                                                 // entries of the ranges' lists, of the repair's; (user block, range) items
+};
+
+// the call's plan: per user the scan-start bound, <U_high, CE_c> and the mask of patterns that can reach the top-k; users sorted by
+// mask so that a block's users share their patterns; (user block, dish range) items longest first
+int plan_stage(m2d_engine *h, const GroupedPolicyIn &in, const GroupedPolicy &p, const GroupedLayout &L, GroupedArgs &a, hipStream_t st)
 {
-    const int64_t cus = h->num_cu;
-    int64_t cap = tiles / min_tiles_per_split > 1 ? tiles / min_tiles_per_split : 1;
-    if (cap > max_splits) cap = max_splits;
-    int64_t lim = (2 * cus + ublocks - 1) / ublocks;        // beyond two rounds' worth of blocks nothing is gained
-    if (lim < 1) lim = 1;
-    if (lim > cap) lim = cap;
-    int nsplit = 1;
-    double best = 0.0;
-    for (int64_t ns = 1; ns <= lim; ++ns) {
-        const int64_t blocks = ublocks * ns, rounds = (blocks + cus - 1) / cus;
-        const double fill = (double)blocks / (double)(rounds * cus);
-        if (fill > best + 1e-9) { best = fill; nsplit = (int)ns; }
-        if (fill >= 0.9) break;
+    int32_t *tie_list = L.tie_list;
+    if (!p.planned) {                                        // (the first-form bf16 kernel takes no plan: no plan kernel zeroes the list's count)
+        M2D_HIP_TRY(h, hipMemsetAsync(tie_list, 0, sizeof(int32_t), st));
+        return M2D_OK;
     }
-    if (h->opt_variant >= 100) {   // test hook: force the number of dish-range splits
-        nsplit = h->opt_variant - 100;
-        if (nsplit < 1) nsplit = 1;
-        if (nsplit > max_splits) nsplit = max_splits;
+    const float *probes = p.pmode == 1 ? nullptr : h->grp_rs.get();
+    const dim3 pgrid((unsigned)((a.nU * 16 + 255) / 256));
+    auto pk = p.plan_quads == 1 ? m2d_topk_user_plan<1> : (p.plan_quads == 2 ? m2d_topk_user_plan<2> : m2d_topk_user_plan<4>);
+    hipLaunchKernelGGL(pk, pgrid, dim3(256), 0, st, h->pm, h->ce, a.users, a.nU, h->U, h->user_base, h->E, a.grp, (int)a.k, h->a, h->b, p.pmode,
+                       L.plan, tie_list, L.counter, p.sorted ? L.hist : nullptr, PLAN_KEYS, probes, h->grp_ew, p.nprobe, in.BF16X3 ? 0 : 1,
+                       L.refine_counter);                    // (which it zeroes: no memset launch)
+    a.plan = L.plan;
+    if (p.share_thresholds) a.shared_thr = L.shared_thr;
+    if (p.sorted) {                                          // (the plan kernel has zeroed the histogram: three memset launches less per call)
+        if (int rc = m2d_plan_sort_launch(h, L.plan, a.nU, L.hist, L.order, st, true)) return rc;
+        a.order = L.order;
     }
-    if (nsplit > 64) nsplit &= ~63;    // two-pass merge: whole groups of 64
-    return nsplit;
+    if (p.deal_items) {
+        const size_t nitems = (size_t)p.ublocks * p.nsplit;
+        hipLaunchKernelGGL(m2d_plan_items_work, dim3((unsigned)((p.ublocks + 3) / 4)), dim3(256), 0, st, L.plan, L.order, a.nU, a.grp, a.tiles,
+                           p.nsplit, L.work, 32 * p.WV);
+        hipLaunchKernelGGL(m2d_plan_items_sort, dim3(1), dim3(1024), 0, st, L.work, (int64_t)nitems, a.tiles, p.nsplit, L.items);
+        a.items = L.items;
+    }
+    a.tiles_scanned = L.counter;
+    h->topk_tiles_counter = L.counter;
+    h->topk_tiles_full = p.ublocks * a.tiles;
+    M2D_HIP_TRY(h, hipGetLastError());
+    return M2D_OK;
 }
 
-// One pattern-grouped call: plan -> scan -> merge of the dish ranges -> refinement / tie repair.
+// dish ranges' partial lists -> the users' lists.  More than 64 ranges: two passes -- groups of 64 consecutive ranges first (a "user"
+// of that pass is one (user, group)), then the per-group winners; consecutive groups are consecutive dish ranges, so the
+// lower-range-wins tie rule carries through both passes.  The last pass lists the tied and flags the near-tied users.
+void merge_stage(const GroupedPolicy &p, const GroupedLayout &L, const GroupedArgs &a, float *final_s, int32_t *final_i, int64_t I, hipStream_t st)
+{
+    const float *plan = p.ext ? a.plan : nullptr;
+    if (p.nsplit <= 64) {
+        m2d_launch_merge_splits(L.lists_s, L.lists_i, a.nU, p.nsplit, a.k, final_s, final_i, st, L.tie_val, L.tie_final, L.tie_list, I, L.ex,
+                                L.ex_final, plan, L.refine_counter);
+        return;
+    }
+    const int G = p.nsplit / 64;
+    m2d_launch_merge_splits(L.lists_s, L.lists_i, a.nU * G, 64, a.k, L.tmp_s, L.tmp_i, st, L.tie_val, L.tie_group, nullptr, 0, L.ex, L.ex_group);
+    m2d_launch_merge_splits(L.tmp_s, L.tmp_i, a.nU, G, a.k, final_s, final_i, st, L.tie_group, L.tie_final, L.tie_list, I, L.ex_group, L.ex_final,
+                            plan, L.refine_counter);
+}
+
+// tie compaction, refinement of the near-tied lists (m2d_topk_refine), and the repair of the users whose final k-th score is tied
+// with a score left out: re-ranked in dish-id order (none is the common case)
+int finish_stage(m2d_engine *h, const GroupedPolicyIn &in, const GroupedPolicy &p, const GroupedLayout &L, const GroupedArgs &a, float *final_s,
+                 int32_t *final_i, hipStream_t st)
+{
+    if (p.nsplit == 1)                                       // (with dish ranges the last merge pass has listed the tied users)
+        m2d_topk_launch_tie_compact(L.tie_final, a.nU, L.tie_list, final_s, final_i, (int)a.k, h->I, p.ext ? 1 : 0, st);
+    if (p.ext) {                                             // (may add to the repair's list; with dish ranges the last merge pass has
+        RefineArgs f;                                        //  flagged the near-tied users)
+        f.pm = h->pm; f.re = h->re; f.ce = h->ce; f.cats = h->dish_cats; f.plan = a.plan; f.tie_final = L.tie_final; f.ex = L.ex_final;
+        f.users = a.users; f.tie_list = L.tie_list; f.counter = L.refine_counter; f.nU = a.nU; f.U = h->U; f.I = h->I;
+        f.user_base = h->user_base; f.E = h->E; f.k = a.k; f.a = h->a; f.b = h->b; f.out_scores = final_s; f.out_ids = final_i;
+        m2d_topk_launch_refine(f, p.nsplit == 1, st);
+    }
+    RepairArgs r;
+    r.pm = h->pm; r.re = h->re; r.ce = h->ce; r.cats = h->dish_cats; r.hv = in.HV ? h->dish_high : nullptr;
+    r.users = a.users; r.tie_list = L.tie_list; r.nU = a.nU; r.U = h->U; r.I = h->I; r.user_base = h->user_base;
+    r.C = h->C; r.E = h->E; r.k = a.k; r.a = h->a; r.b = h->b; r.out_scores = final_s; r.out_ids = final_i;
+    r.rows = h->grp_rs; r.perm = h->grp_perm; r.grp = a.grp; r.ew = h->grp_ew;
+    r.plan = a.plan;
+    r.all_patterns = p.all_patterns;
+    r.cap = p.cap;
+    r.part_s = L.part_s;
+    r.part_i = L.part_i;
+    return m2d_topk_launch_repair(h, r, in.HV, st);
+}
+
+// One pattern-grouped call: policy -> scratch -> plan -> scan -> merge of the dish ranges -> refinement / tie repair.
 //   E8: the scan kernel's row width / 8 (the tables' E, or the next instantiated width when PAD; 2 E / 8 with HV)
 //   KR: list slots per lane (10 or 16 >= k)      BF16X3: split-bf16 MFMA, else exact f32
 //   HV: rows [H[d] | RE[d]] of the ingredient table (pipelined split-bf16 kernel only)      PAD: zero-padded rows (exact f32 only)
 int launch_grouped(m2d_engine *h, const int E8, const int KR, const bool BF16X3, const bool HV, const bool PAD, const int32_t *users,
                    int64_t nU, int32_t k, float *final_s, int32_t *final_i, hipStream_t st)
 {
-    constexpr int WAVES = 8;                                 // waves per block unless the launcher takes blocks of 128 users (`half`)
     if ((HV && !BF16X3) || (PAD && BF16X3)) {
         h->last_error = "launch_grouped: the ingredient form is split bf16 only, zero-padded rows exact f32 only";
         return M2D_ERR_UNSUPPORTED;
     }
-    const int E = E8 * 8;
     if (h->b == 0.f && !HV) {
         // high_level_score_coefficient = 1: every dish of a pattern scores alpha_P -- the lists are read off the patterns' first ids
         // (m2d_topk_high_level_only above), whatever kernel the options name
         hipLaunchKernelGGL(m2d_topk_high_level_only, dim3((unsigned)((nU * 16 + 255) / 256)), dim3(256), 0, st, h->pm, h->ce, users, nU, h->U,
                            h->user_base, h->E, grouped_first_ids(h), (int)k, h->a, h->I, final_s, final_i, h->err_dev);
         M2D_HIP_TRY(h, hipGetLastError());
-        h->topk_tie_list = nullptr; h->topk_refine_counter = nullptr; h->topk_tiles_counter = nullptr;      // (diagnostics: nothing was scanned)
-        h->topk_tiles_full = 0;
+        m2d_topk_no_diagnostics(h);                          // (nothing was scanned)
         h->last_kernel = "m2d_topk_high_level_only";
         return M2D_OK;
     }
-    const bool pipe = HV || h->opt_topk_form != 1;           // "topk_form", split-bf16 kernels: see below
-    // Blocks of 128 users (four waves, half-size stages, two blocks per CU) for pruned launches of the pipelined kernel at
-    // E = 64: a stage barrier holds up four waves instead of eight, the CU's other block runs meanwhile, and 128 users share
-    // fewer patterns than 256 (tiles stepped through 0.109 -> 0.100 of the catalogue).  Measured, k = 10: 65 536 users x 100 k
-    // dishes 0.629 -> 0.584 ms, 262 144 users 2.10 -> 1.99 ms, 16 384 users 0.384 -> 0.376 ms; but every block streams its own
-    // copy of the tiles, and once the catalogue image (8 KiB a tile) no longer sits in the Infinity Cache that costs more than
-    // the barriers did -- 1 M dishes: 65 536 users 3.19 -> 3.24 ms, 262 144 users 10.7 -> 11.4 ms -- so: catalogues up to 8 192
-    // tiles (64 MiB of image).  "topk_block" = 128 / 256 forces either.
-    const bool half_ok = BF16X3 && !HV && E == 64 && pipe;
-    // (k > 10 with the left-out bookkeeping: 232 registers since the launch bounds say two waves per SIMD -- it took 261 and one
-    //  wave per SIMD before, and the launcher kept eight-wave blocks for it: 65 536 users x 100 k dishes, k = 16: 0.764 -> 0.666 ms)
-    // The hi x hi first form of that kernel (APX in m2d_catalogue_scan_bf16.hip) for the catalogues where a tile with a candidate is
-    // the exception.  It pays once fewer than about a quarter (E = 64) / a half (E = 128) of the (wave, tile) pairs still need their
-    // cross products -- 65 536 users, pruned, three-product form against it: E = 64 200 k dishes 0.73 / 0.88 ms, 500 k 1.51 / 1.63,
-    // 1 M 2.81 / 2.63; E = 128 300 k 1.94 / 1.94, 500 k 2.96 / 2.75, 1 M 6.16 / 4.95 -- so: more than 24 576 tiles at E = 64, more
-    // than 10 240 at E = 128.  The rule looks at the catalogue alone: that form's scores are not the three-product kernels' bits, and
-    // every launch shape of one problem must return the same lists (blocks of 256 users there: "topk_block" = 128 is not
-    // honoured).  "topk_form" 3 / 4 (diagnostic): that form for any catalogue / never.
-    // (The ingredient form multiplies every tile -- no pattern can be pruned -- so tiles with a candidate are the exception from
-    //  small catalogues on: 65 536 users x 20 k dishes 0.89 -> 0.64 ms, 100 k 3.79 -> 2.09 ms, 1 M 36.3 -> 18.5; more than 256 tiles.)
-    const bool apx = BF16X3 && pipe && (E == 64 || E == 128) && h->opt_topk_form != 4 &&
-                     (h->grp_tiles > (HV ? 256 : (E == 64 ? 24576 : 10240)) || h->opt_topk_form == 3);
-    const bool half = half_ok && !apx && (h->opt_topk_block == 128 || (h->opt_topk_block == 0 && M2D_TOPK_HALF_BLOCKS && h->opt_topk_prune != 0 &&
-                                                              h->opt_variant < 100 && nU >= 16384 && h->grp_tiles <= 8192));
-    const int WV = half ? 4 : WAVES;                         // waves per block
-    const int TPS = grouped_tiles_per_stage(E) * WV / WAVES;
-    const size_t lds = (size_t)2 * TPS * 32 * E * sizeof(float);
-    h->topk_block_users = 32 * WV;
+    const GroupedPolicyIn in{h->E, E8, KR, BF16X3, HV, PAD, k, nU, h->grp_tiles, h->num_cu, h->opt_topk_form, h->opt_topk_prune, h->opt_topk_block,
+                             h->opt_topk_refine, h->opt_variant, grouped_tiles_per_stage(E8 * 8), M2D_TOPK_HALF_BLOCKS != 0, PLAN_PROBES, REPAIR_CAP};
+    const GroupedPolicy p = grouped_policy(in);
+    GroupedLayout L(nU, k, p.nsplit, p.ext, p.planned, p.ublocks);
+    int rc;
+    if ((rc = h->topk_flags.grow(h, L.tie_need, h->topk_tie_list, h->topk_tie_final)) != M2D_OK) return rc;
+    if (p.ext && (rc = h->topk_ex.grow(h, L.ex_need, h->topk_refine_counter)) != M2D_OK) return rc;
+    if (p.nsplit > 1 && (rc = h->scratch.grow(h, L.scratch_need)) != M2D_OK) return rc;
+    if (p.planned && (rc = h->topk_plan.grow(h, L.plan_need, h->topk_tiles_counter)) != M2D_OK) return rc;
+    L.bind(h->topk_flags, h->topk_ex, h->scratch, h->topk_plan);
+    h->topk_tie_final = L.tie_final;
+    h->topk_tie_list = L.tie_list;
+    h->topk_refine_counter = L.refine_counter;
+    h->topk_block_users = 32 * p.WV;
+    h->topk_apx_last = p.apx;
+
     GroupedArgs a;
     a.pm = h->pm; a.ce = h->ce; a.rs = h->grp_rs; a.rs16 = static_cast<const __bf16 *>(h->grp_rs16.get());
     a.perm = h->grp_perm; a.tile_info = h->grp_tile_info;
     a.grp = grouped_grp(h);
     a.users = users; a.nU = nU; a.U = h->U; a.user_base = h->user_base; a.k = k; a.tiles = h->grp_tiles;
     a.a = h->a; a.b = h->b; a.err = h->err_dev; a.dbg = g_m2d_diag_buffer; a.e_real = h->E;
-    a.prog_limit = h->opt_variant == 15 ? 0 : (1 << 24);   // "variant" 15: test hook of the progress-word timeout
-    a.plan = nullptr; a.order = nullptr; a.tiles_scanned = nullptr; a.items = nullptr; a.shared_thr = nullptr; a.ex_out = nullptr;
-    const int64_t ublocks = (nU + 32 * WV - 1) / (32 * WV);
-    int nsplit = pick_splits(h, ublocks, a.tiles, 2 * TPS, 512);
-    if ((!BF16X3 || (!HV && h->opt_topk_form != 1)) && h->opt_topk_prune != 0 && h->opt_variant < 100) {
-        // Pattern pruning makes the blocks unequal -- a block of users with one relevant pattern steps through a fifteenth of
-        // the catalogue, one whose users need most patterns through all of it -- so a launch with many user blocks is cut into
-        // dish ranges and the (block, range) items are handed out longest first (m2d_plan_items_*).  The longest item bounds
-        // the launch, every piece starts its lists from the scan-start bound again (more pieces re-insert more): measured
-        // best at 100 k dishes, E = 64 -- 16 / 32 user blocks: 32 ranges (0.30 / 0.33 ms; 8 ranges 0.56), 64 blocks: 16
-        // (0.42 ms; 8: 0.59, 32: 0.49), 128 blocks: 12 (0.58 ms; 8: 0.62, 24: 0.68), 256 blocks: 8 (0.85 ms; 16: 1.0).
-        // 8 blocks: 64 (0.21 ms; 32: 0.25).  A handful of blocks (serving): most ranges hold no tile of the users' patterns and
-        // return at once, the others are short -- 1 user: 512 ranges 0.056 ms (192, the unpruned launch's count: 0.066), 32
-        // users 0.068 (0.091), 256 users: 256 ranges 0.101 (0.113), 1 024 users: 128 ranges 0.167 (0.185).
-        if (ublocks >= 6) {
-            nsplit = ublocks >= 192 ? 8 : (ublocks >= 96 ? 12 : (ublocks >= 48 ? 16 : (ublocks >= 24 ? 32 : (int)(512 / ublocks))));
-            // long catalogues: since a user's ranges share their thresholds, twice the ranges cost little and balance better
-            // (65 536 users x 1 M dishes: 8 ranges 3.41 ms, 16 ranges 3.19 ms, 24: 3.32; 262 144 users: 8 ranges 10.7, 16: 11.2)
-            if (BF16X3 && E == 64 && a.tiles >= 16384 && ublocks >= 192 && ublocks < 768) nsplit = 16;
-            // blocks of 128 users, many of them: about 4 096 items is what balances (8 rounds of the 512 block slots); more only
-            // adds item prologues, partial stages and merge work -- 131 072 users x 100 k dishes: 4 ranges 0.87 ms (3: 0.95, 6:
-            // 0.90, 8: 0.95); 262 144 users: 2 ranges 1.59 (1: 2.11, 3: 1.65, 4: 1.66, 8: 1.85); 524 288 users: 1 range 2.86
-            // (2: 2.99, 4: 3.24, 8: 3.67).  (Blocks of 256 users over 1 M dishes: 8 stays -- 262 144 users 10.2 ms against 10.6
-            // with 3 ... 6; 524 288 users 19.3 ... 20.2 for 2 ... 8, within the noise.)
-            if (half && ublocks >= 768) nsplit = ublocks >= 3072 ? 1 : (ublocks >= 1536 ? 2 : 4);
-            const int64_t most = a.tiles / (4 * TPS);        // at least four stages per range
-            if (most < nsplit) nsplit = most > 1 ? (int)most : 1;
-        } else {
-            nsplit = ublocks == 1 ? (nU <= 64 ? 512 : 256) : (int)(512 / ublocks);
-            const int64_t most = a.tiles / 4;                // at least four tiles per range
-            if (most < nsplit) nsplit = most > 1 ? (int)most : 1;
-        }
-        if (nsplit > 64) nsplit &= ~63;                      // two-pass merge: whole groups of 64 (6 or 7 blocks: 85 / 73 -> 64)
-    }
-    a.nsplit = nsplit;
-    // What is kept per (user, dish range) -- a tie value, the left-out record -- has one layout: per user `nsplit` slots of the
-    // ranges, `nsplit / 64` slots of the groups of 64 when the merge takes two passes, then one final slot per user
-    const size_t slots_before = nsplit > 1 ? (size_t)nU * (nsplit + (nsplit > 64 ? nsplit / 64 : 0)) : 0, slots = slots_before + (size_t)nU;
-    int rc;
-    // tie values (a float per slot); behind them the repair list (int32: count, users) and the repair's partial lists
-    const size_t tie_need = slots + 1 + (size_t)nU + (size_t)2 * REPAIR_CAP * REPAIR_SPLITS * k;
-    if ((rc = h->topk_flags.grow(h, tie_need, h->topk_tie_list, h->topk_tie_final)) != M2D_OK) return rc;
-    float *tie_final = h->topk_flags + slots_before;
-    a.tie_val = h->topk_flags;
-    int32_t *tie_list = reinterpret_cast<int32_t *>(h->topk_flags + slots);
-    const bool planned = !BF16X3 || pipe;                    // (the first-form bf16 kernel takes no plan)
-    if (!planned) M2D_HIP_TRY(h, hipMemsetAsync(tie_list, 0, sizeof(int32_t), st));
-    h->topk_tie_final = tie_final;
-    h->topk_tie_list = tie_list;
-    // what the lists leave out, for m2d_topk_refine (kernels that keep it: see EXT in the scan kernels)
-    // (a user's word is its position in the call | left-out dishes to take along << 30: calls of 2^30 users or more go without)
-    const bool ext = planned && h->opt_topk_refine != 0 && !HV && !PAD && nU < ((int64_t)1 << 30) &&
-                     (BF16X3 ? (pipe && !(E == 128 && KR == 16)) : E8 <= 16);
-    float *ex_final = nullptr;
-    if (ext) {
-        const size_t ex_need = slots * 8 + (size_t)nU + 8;   // records of 8 floats in the tie values' layout | counters | a word per user
-        if ((rc = h->topk_ex.grow(h, ex_need, h->topk_refine_counter)) != M2D_OK) return rc;
-        a.ex_out = h->topk_ex;
-        ex_final = h->topk_ex + slots_before * 8;
-        h->topk_refine_counter = reinterpret_cast<int32_t *>(h->topk_ex + ex_need - (size_t)nU - 8);     // [0] refined [1] sent to the repair; [8 + u] user u's word
-                                                                                                       // (zeroed by the plan kernel: no memset launch)
-    } else {
-        h->topk_refine_counter = nullptr;
-    }
-    const size_t tmp_entries = nsplit > 64 ? (size_t)nU * (nsplit / 64) * k : 0;
-    if (nsplit > 1) {
-        const size_t need = ((size_t)nU * nsplit * k + tmp_entries) * 8 + 256;
-        if ((rc = h->scratch.grow(h, need)) != M2D_OK) return rc;
-        a.out_scores = h->scratch;
-        a.out_ids = reinterpret_cast<int32_t *>(h->scratch + (size_t)nU * nsplit * k);
-    } else {
-        a.out_scores = final_s;
-        a.out_ids = final_i;
-    }
-    float *tmp_s = h->scratch ? h->scratch + (size_t)2 * nU * nsplit * k : nullptr;
-    int32_t *tmp_i = reinterpret_cast<int32_t *>(tmp_s ? tmp_s + tmp_entries : nullptr);
-    // "topk_form" (split-bf16 kernels): 0 or 2 = pipelined form (E = 64: 2.55 ms against 3.3 at 100 k dishes; E = 128:
-    // 38.3 ms against 45.4 at 1 M dishes), 1 = first form (kept as the A/B reference; it takes no plan)
-    if (planned) {
-        // the call's plan: per user the scan-start bound, <U_high, CE_c> and the mask of patterns that can reach the
-        // top-k; users sorted by mask so that a block's 256 users share their patterns (a single block: no sort)
-        const size_t nitems = (size_t)ublocks * nsplit;
-        const size_t need = (size_t)nU * 8 + (size_t)nU + PLAN_KEYS + 8 + 2 * nitems;
-        if ((rc = h->topk_plan.grow(h, need, h->topk_tiles_counter)) != M2D_OK) return rc;
-        float *plan = h->topk_plan;
-        int32_t *order = reinterpret_cast<int32_t *>(plan + (size_t)nU * 8), *hist = order + ((nU + 3) & ~(int64_t)3);      // hist: 16-B aligned
-        unsigned long long *counter = reinterpret_cast<unsigned long long *>(hist + PLAN_KEYS);
-        const bool prune = h->opt_topk_prune != 0;
-        const bool sorted = prune && !HV && nU > 32 * WV;
-        {
-            const int pmode = (HV || !prune) ? 1 : (h->opt_topk_prune == 2 ? 2 : (h->opt_topk_prune == 4 ? 4 : 0));
-            const float *probes = (HV || !prune) ? nullptr : h->grp_rs;
-            const dim3 pgrid((unsigned)((nU * 16 + 255) / 256));
-            // probe rows per user: each costs a row read per user (16: +18 us for 65 536 users) and buys a tighter bound -- 16 rows
-            // at 100 k dishes (0.71 ms; 32: 0.73), 32 at 1 M (3.83 ms; 16: 4.02)
-            const int nprobe = a.tiles < 8192 ? 16 : (a.tiles < 65536 ? 32 : PLAN_PROBES);
-            auto pk = h->E <= 64 ? m2d_topk_user_plan<1> : (h->E <= 128 ? m2d_topk_user_plan<2> : m2d_topk_user_plan<4>);
-            hipLaunchKernelGGL(pk, pgrid, dim3(256), 0, st, h->pm, h->ce, users, nU, h->U, h->user_base, h->E, a.grp, (int)k, h->a, h->b, pmode,
-                               plan, tie_list, counter, sorted ? hist : nullptr, PLAN_KEYS, probes, h->grp_ew, nprobe, BF16X3 ? 0 : 1, ext ? h->topk_refine_counter : nullptr);
-        }
-        a.plan = plan;
-        // dish ranges of a user share their thresholds (pipelined kernel; "topk_prune" = 7 keeps them apart: A/B)
-        if (BF16X3 && pipe && !HV && E == 64 && nsplit > 1 && h->opt_topk_prune != 7) a.shared_thr = reinterpret_cast<int32_t *>(plan) + 6;
-        if (sorted) {                                        // (the plan kernel has zeroed the histogram: three memset launches less per call)
-            if ((rc = m2d_plan_sort_launch(h, plan, nU, hist, order, st, true)) != M2D_OK) return rc;
-            a.order = order;
-        }
-        if (a.order && nitems > (size_t)h->num_cu && h->opt_topk_prune != 5) {      // 5: grid order (A/B)
-            int32_t *work = reinterpret_cast<int32_t *>(counter + 2), *items = work + nitems;      // counter: two words (tiles, completed)
-            hipLaunchKernelGGL(m2d_plan_items_work, dim3((unsigned)((ublocks + 3) / 4)), dim3(256), 0, st, plan, order, nU, a.grp, a.tiles,
-                               nsplit, work, 32 * WV);
-            hipLaunchKernelGGL(m2d_plan_items_sort, dim3(1), dim3(1024), 0, st, work, (int64_t)nitems, a.tiles, nsplit, items);
-            a.items = items;
-        }
-        a.tiles_scanned = counter;
-        h->topk_tiles_counter = counter;
-        h->topk_tiles_full = (int64_t)ublocks * a.tiles;
-        M2D_HIP_TRY(h, hipGetLastError());
-    }
-    const dim3 grid = a.items ? dim3((unsigned)(ublocks * nsplit)) : dim3((unsigned)ublocks, (unsigned)nsplit);
-    {
-        const ScanShape shape{E, KR, BF16X3, HV, PAD, pipe, WV, a.ex_out != nullptr, apx};
-        h->topk_apx_last = apx;
-        rc = BF16X3 ? m2d_topk_scan_bf16_launch(h, a, shape, grid, lds, st) : m2d_topk_scan_f32_launch(h, a, shape, grid, lds, st);
-        if (rc != M2D_OK) return rc;
-    }
+    a.prog_limit = p.prog_limit;
+    a.nsplit = p.nsplit;
+    a.tie_val = L.tie_val;
+    a.ex_out = L.ex;
+    a.out_scores = p.nsplit > 1 ? L.lists_s : final_s;
+    a.out_ids = p.nsplit > 1 ? L.lists_i : final_i;
+    a.plan = nullptr; a.order = nullptr; a.tiles_scanned = nullptr; a.items = nullptr; a.shared_thr = nullptr;
+    if ((rc = plan_stage(h, in, p, L, a, st)) != M2D_OK) return rc;
+
+    const dim3 grid = a.items ? dim3((unsigned)(p.ublocks * p.nsplit)) : dim3((unsigned)p.ublocks, (unsigned)p.nsplit);
+    const ScanShape shape{E8 * 8, KR, BF16X3, HV, PAD, p.pipe, p.WV, p.ext, p.apx};
+    rc = BF16X3 ? m2d_topk_scan_bf16_launch(h, a, shape, grid, p.lds, st) : m2d_topk_scan_f32_launch(h, a, shape, grid, p.lds, st);
+    if (rc != M2D_OK) return rc;
     M2D_HIP_TRY(h, hipGetLastError());
-    RefineArgs f;                                            // near-tied lists: finished in the repair's arithmetic (m2d_topk_refine)
-    f.pm = h->pm; f.re = h->re; f.ce = h->ce; f.cats = h->dish_cats; f.plan = a.plan; f.tie_final = tie_final; f.ex = ex_final;
-    f.users = users; f.tie_list = tie_list; f.counter = h->topk_refine_counter; f.nU = nU; f.U = h->U; f.I = h->I;
-    f.user_base = h->user_base; f.E = h->E; f.k = k; f.a = h->a; f.b = h->b; f.out_scores = final_s; f.out_ids = final_i;
-    if (nsplit > 1) {
-        m2d_launch_merge_splits2(a.out_scores, a.out_ids, nU, nsplit, k, tmp_s, tmp_i, final_s, final_i, st, h->topk_flags, tie_final, tie_list,
-                                 h->I, a.ex_out, ex_final, ext ? a.plan : nullptr, ext ? h->topk_refine_counter : nullptr);
+    if (p.nsplit > 1) {
+        merge_stage(p, L, a, final_s, final_i, h->I, st);
         M2D_HIP_TRY(h, hipGetLastError());
     }
-    {   // users whose final k-th score is tied with a score left out: re-ranked in dish-id order (none is the common case)
-        RepairArgs r;
-        r.pm = h->pm; r.re = h->re; r.ce = h->ce; r.cats = h->dish_cats; r.hv = HV ? h->dish_high : nullptr;
-        r.users = users; r.tie_list = tie_list; r.nU = nU; r.U = h->U; r.I = h->I; r.user_base = h->user_base;
-        r.C = h->C; r.E = h->E; r.k = k; r.a = h->a; r.b = h->b; r.out_scores = final_s; r.out_ids = final_i;
-        r.rows = h->grp_rs; r.perm = h->grp_perm; r.grp = a.grp; r.ew = h->grp_ew;
-        r.plan = a.plan;
-        r.all_patterns = h->opt_topk_prune == 9 ? 1 : 0;                     // "topk_prune" = 9: the repair reads every pattern (A/B)
-        r.cap = h->opt_variant == 13 ? 2 : REPAIR_CAP;      // test hook: send all but two listed users to the one-block-per-user kernel
-        r.part_s = h->topk_flags + slots + 1 + (size_t)nU;
-        r.part_i = reinterpret_cast<int32_t *>(r.part_s + (size_t)REPAIR_CAP * REPAIR_SPLITS * k);
-        if (nsplit == 1)                                     // (with dish ranges the last merge pass has listed the tied users)
-            m2d_topk_launch_tie_compact(tie_final, nU, tie_list, final_s, final_i, (int)k, h->I, ext ? 1 : 0, st);
-        if (ext)                                             // (may add to the repair's list; with dish ranges the last merge pass has
-            m2d_topk_launch_refine(f, nsplit == 1, st);      //  flagged the near-tied users)
-        rc = m2d_topk_launch_repair(h, r, HV, st);
-        if (rc != M2D_OK) return rc;
-    }
+    if ((rc = finish_stage(h, in, p, L, a, final_s, final_i, st)) != M2D_OK) return rc;
     h->last_kernel = BF16X3 ? "m2d_topk_grouped_bf16x3" : "m2d_topk_grouped";      // both bf16 forms report this name
     return M2D_OK;
 }

@@ -46,12 +46,16 @@ def test_restated_launcher_rules_match_their_source_lines():
                  "const int64_t cap = a.tiles / 8 > 1 ? a.tiles / 8 : 1;",
                  "if (ns > 64) ns = 64;",
                  "if (ns > cap) ns = cap;",
-                 "if (h->opt_variant >= 100) {",                                            # forced_nsplit
-                 "nsplit = h->opt_variant - 100;",
-                 "if (nsplit < 1) nsplit = 1;",
-                 "if (nsplit > 64) nsplit = 64;",
+                 "a.nsplit = nsplit = topk_split_hook(h->opt_variant, nsplit, 64);",        # forced_nsplit: the shared hook, capped at 64
                  "for (int64_t d = wave; d < p.I; d += 4) {"):                              # m2d_topk_generic: four waves stride the dishes
         assert _squeeze(line) in src, line
+    hook = _source("m2d_grouped_policy.h")
+    for line in ("inline int topk_split_hook(const int variant, int nsplit, const int max_splits)",
+                 "if (variant >= 100) {",
+                 "nsplit = variant - 100;",
+                 "if (nsplit < 1) nsplit = 1;",
+                 "if (nsplit > max_splits) nsplit = max_splits;"):
+        assert _squeeze(line) in hook, line
     assert "while (lpu < nsplit) lpu <<= 1;" in _source("m2d_catalogue_merge.hip")
     plan = _source("m2d_catalogue_plan.hip")
     assert "h->opt_topk_grouped != 0 && h->opt_variant != 7 && h->opt_variant != 9;" in plan and "h->C == 4 &&" in plan

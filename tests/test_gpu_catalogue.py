@@ -344,6 +344,46 @@ def test_every_user_tied(variant):
     assert np.all(ids.cpu().numpy() == want[None, :]) and np.all(s.cpu().numpy() == 0)
 
 
+@pytest.mark.parametrize("k", [10, 16])
+def test_tied_lists_through_every_scratch_layout(k):
+    """One call's scratch -- tie slots, left-out records, partial lists, the repair's partial lists -- is laid out by the number
+    of dish ranges (1; up to 64; more: the two-pass merge keeps slots per group of 64 as well), by whether the left-out records
+    are kept ("topk_refine") and by k.  Every dish row here exists three times (k = 3 n + 1: the k-th score is tied with two
+    scores left out, for every user), so each layout's tie values, tie list and repair lists decide every list: the same
+    lists bit for bit in each, which are the oracle's.  Two blocks of users; "variant" 13 sends all but two users to the
+    one-block-per-user repair (its automatic 256 ranges take the two-pass merge too)."""
+    import torch
+    from foodrec_amd import ScoringEngine
+    U, I, E = 300, 4096, 64
+    PM, RE, CE, cats = _tables(U, I, 4, E, seed=k + 500)
+    n = I // 3
+    for c in (1, 2):
+        RE[c * n:(c + 1) * n] = RE[:n]
+        cats[c * n:(c + 1) * n] = cats[:n]
+    cats[3 * n:] = 0                                         # the dish left over: empty mask, NaN, in no list
+    eng = ScoringEngine(PM, RE, CE)
+    eng.set_dish_categories(cats)
+    users = torch.arange(U, dtype=torch.int32, device="cuda")
+    for refine in (1, 0):
+        eng.set_option("topk_refine", refine)
+        out = {}
+        for forced in (101, 108, 228, 13):                   # 1, 8, 128 dish ranges; 13: see above
+            eng.set_option("variant", forced)
+            s, i = eng.topk_users(users, k); eng.check()
+            assert eng.last_kernel() == "m2d_topk_grouped_bf16x3"
+            settled = eng.get_option("topk_repaired") + (eng.get_option("topk_refined") if refine else 0)
+            assert settled >= U, (refine, forced, settled)   # every user's k-th score is tied: re-ranked by the repair, or refined
+            out[forced] = (s.cpu().numpy(), i.cpu().numpy())
+        s0, i0 = out[101]
+        for forced, (s, i) in out.items():
+            assert np.array_equal(i, i0) and np.array_equal(s.view(np.int32), s0.view(np.int32)), (refine, forced)
+        assert np.all(i0[:, -1] < n)                         # the copy kept at the tied k-th place is the lowest id of its three
+        eng.set_option("variant", 0)
+        _check(eng, PM, RE, CE, cats, np.arange(0, U, 8), k)
+        _assert_ids_are_the_oracles_where_clear(i0[::8], PM, RE, CE, cats, np.arange(0, U, 8), k, eng.coef, gap=3e-5, what=refine)
+    eng.set_option("topk_refine", 1)
+
+
 @pytest.mark.parametrize("E", [32, 64, 128, 200])
 def test_exact_f32_lists_equal_the_oracle_where_gaps_are_clear(E):
     """Exact-f32 pattern-grouped kernel ("topk_bf16x3" = 0): the id at every position whose score is more than 1e-6 away
