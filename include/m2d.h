@@ -12,6 +12,25 @@
  *   - `stream` is a hipStream_t passed as void* (NULL = the null stream); kernels are enqueued and
  *     the call returns without synchronising.  Id errors found by a kernel are latched on the
  *     device and reported by m2d_check(), which does synchronise;
+ *     WHERE A CALL DOES WAIT.  Always, by design: m2d_check and m2d_train_begin wait for `stream`; m2d_score_pairs_host waits for
+ *     its own work on `stream`; m2d_cookable_dishes waits for `stream` once, for the count (and with it whatever calls it first:
+ *     the Python layer's topk_market); the setters (m2d_set_*) work on the NULL stream and wait for it, which orders nothing for a
+ *     stream created non-blocking: call them with no work of the engine in flight; m2d_clear_*, m2d_train_end, m2d_train_steps and
+ *     the read-only diagnostics of m2d_get_option wait for the whole device.
+ *     Once, and then not again until the cause recurs: the first call that runs on m2d_topk_users' retrieval plan (that call and
+ *     the calls defined through it) after m2d_create, a setter, m2d_train_step or m2d_tables_updated waits for `stream` once it
+ *     has queued the build of the pattern-grouped dish rows (it reads the tile count, the "masks are 0/1" flag and the "a table
+ *     value is not finite" word); the first such call after the table scan or after m2d_write_memory waits for the whole device
+ *     before it reads that word again; a call that has to grow one of the engine's buffers (the first call of a size;
+ *     m2d_train_step with a larger batch than any before) frees the old block, which waits for the device.  A call that finds its
+ *     tables built and its buffers large enough returns without waiting: the pair-scoring calls from their second call of a size
+ *     on, m2d_topk_markets and the others that say "never synchronises" below.
+ *     Wherever a call waits, it waits for `stream` BEFORE it reads the device on the host, and everything it queues -- a lazy build
+ *     included -- it queues on `stream`: inputs that an earlier copy on `stream` is still writing when the call is made are read as
+ *     that copy leaves them.  tests/test_gpu_stream_order.py holds the entry points that take device buffers to this on a
+ *     non-default stream, as an engine's first call and again on the engine so warmed: the inputs are overwritten by copies queued
+ *     behind a 0.1 s blocker, the call is made while the blocker runs, and the result must be the one a second engine returns for
+ *     the late inputs on the null stream.  (m2d_write_memory and m2d_train_step: as a first call only);
  *   - an engine is not thread-safe; distinct engines / streams are independent;
  *   - all arithmetic is float32; ids are int32 (Model_Recommender.py:26-32).
  *
