@@ -835,6 +835,19 @@ int m2d_topk_groups_slate(m2d_engine *h, const int32_t *members, int64_t nG, int
                              (hipStream_t)stream);
 }
 
+int m2d_topk_menu(m2d_engine *h, const int32_t *users, int64_t nU, int32_t k, const int32_t *caps, float *out_scores, int32_t *out_ids,
+                  void *stream)
+{
+    if (!h) return M2D_ERR_INVALID_ARG;
+    M2D_REQUIRE(topk_range(h, "m2d_topk_menu", nU, k, 64));
+    if (nU == 0) return M2D_OK;
+    if (!users || !caps || !out_scores || !out_ids) return null_buffer(h, "m2d_topk_menu");
+    M2D_REQUIRE(enter(h, NEEDS_MASKS));
+    if (h->C > M2D_MENU_MAX_CATEGORIES)
+        return fail(h, M2D_ERR_UNSUPPORTED, "m2d_topk_menu: more than 6 categories (one signature per lane of a wave: C <= M2D_MENU_MAX_CATEGORIES)");
+    return m2d_launch_topk_menu(h, users, nU, k, caps, out_scores, out_ids, (hipStream_t)stream);
+}
+
 int m2d_topk_users_mlp_deep(m2d_engine *h, const int32_t *users, int64_t nU, int32_t k, int32_t candidates, const int64_t *excl_off,
                             const int32_t *excl_ids, float *out_scores, int32_t *out_ids, void *stream)
 {
@@ -926,7 +939,9 @@ int m2d_pm_bf16(m2d_engine *h, uint16_t *buf, void *stream)
 int m2d_tables_updated(m2d_engine *h)
 {
     if (!h) return M2D_ERR_INVALID_ARG;
-    m2d_mark_written(h, M2D_TAB_PM | M2D_TAB_RE | M2D_TAB_CE, M2D_BY_CALLER);   // "every table value is finite" has to be established again
+    // "every table value is finite" has to be established again; the masks are named for what hangs on them alone (the menu call's
+    // signature index): a borrowed mask table may have been rewritten in place
+    m2d_mark_written(h, M2D_TAB_PM | M2D_TAB_RE | M2D_TAB_CE | M2D_TAB_MASKS, M2D_BY_CALLER);
     return M2D_OK;
 }
 
@@ -974,7 +989,8 @@ int m2d_check(m2d_engine *h, void *stream, int64_t *bad_value, int64_t *bad_inde
                         " m2d_topk_markets: the end offset of a market segment that decreases or reaches outside [0, nnzM], at its request;"
                         " m2d_topk_markets_excluding: also an excluded id below its predecessor, at its index in excl_ids, or the end offset of an"
                         " exclusion segment that decreases or reaches outside the array, at its index in excl_off;"
-                        " m2d_topk_users_mlp_excluding / m2d_catalogue_rank_mlp: the exclusion lists as m2d_catalogue_rank reports them)";
+                        " m2d_topk_users_mlp_excluding / m2d_catalogue_rank_mlp: the exclusion lists as m2d_catalogue_rank reports them;"
+                        " m2d_topk_menu: a cap below 0, at its position u * C + c in caps)";
         return code;
     }
     const char *what = code == M2D_ERR_BAD_USER_ID ? "user" : code == M2D_ERR_BAD_ITEM_ID ? "item" : "ingredient";
@@ -1088,6 +1104,7 @@ const m2d_option OPTIONS[] = {
     opt("topk_mlp_chunk_pairs", &m2d_engine::opt_topk_mlp_chunk_pairs, 256, 1 << 24, "256 ... 2^24"),
     opt("slate_chunk_pairs", &m2d_engine::opt_slate_chunk_pairs, 256, 1 << 24, "256 ... 2^24"),
     opt("deep_chunk_pairs", &m2d_engine::opt_deep_chunk_pairs, 256, 1 << 24, "256 ... 2^24"),
+    opt("menu_select", &m2d_engine::opt_menu_select, 0, 1, "0 or 1"),
     opt("mlp_bf16x3", &m2d_engine::opt_mlp_bf16x3),
     opt("mlp_form", &m2d_engine::opt_mlp_form),
     opt("skip_masked", &m2d_engine::opt_skip_masked),

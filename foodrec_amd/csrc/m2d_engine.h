@@ -176,6 +176,19 @@ struct m2d_engine {
     // the members' score rows go to slate_scores above
     m2d_dev_buf<int32_t> group_ids;
 
+    // m2d_topk_menu (m2d_menu.hip): the signature index of the dish masks -- perm i32[I], the dish ids by (signature, id) | seg_off
+    // i32[65] behind it, with seg_off's host copy (menu_seg; read once per build through the pinned block) -- built by the first call
+    // after a mask write; the build's scratch (sig u8[I] | block counts i32[nb, 64] | block bases i32[nb, 64], in words); and a user
+    // block's candidate lists [S', Ub, k] (S' non-empty segments).  The score rows go to slate_scores above
+    m2d_dev_buf<int32_t> menu_perm;
+    m2d_dev_buf<int32_t> menu_work;
+    m2d_host_buf<int32_t> menu_seg_host;
+    int32_t menu_seg[65] = {};
+    bool menu_valid = false;
+    m2d_dev_buf<float> menu_list_scores;
+    m2d_dev_buf<int32_t> menu_list_ids;
+    int opt_menu_select = 0;           // the per-segment selection: 0 = the list across a wave's lanes (m2d_topk_mlp_select), 1 = the radix select (A/B: same words)
+
     // m2d_set_recipes / m2d_cookable_dishes (m2d_market.hip): every dish's ingredient list, CSR, validated once by the setter (CSR
     // shape, every id in [0, R)); lists only -- no table, no weights, nothing the scoring path reads, and no tie to `ing` above.
     // market_buf: the call's scratch -- bitmap of R bits | missing[I] (unless the caller gives a buffer) | kept dishes per block |
@@ -326,6 +339,8 @@ static inline unsigned m2d_blocks_for(const m2d_engine *h, int64_t items, int64_
 //   pm_bf16 (the bf16 mirror) and its non-finite word           hang on Personal_Memory (rebuilt as a whole, word included);
 //   dish_vec and the sorted retrieval tables (grp_*)            hang on Recipe_Embedding, Category_Embedding, the dish masks and
 //                                                               the ingredient table (H[d] rides in the sorted rows);
+//   the menu call's signature index (menu_*)                    hangs on the dish masks (m2d_tables_updated names them too: a
+//                                                               borrowed mask table may have been rewritten in place);
 //   the non-finite word (nonfinite_dev)                         covers every table value and H[d]:
 //     M2D_BY_ENGINE  one of the engine's own kernels wrote, and looked at what it wrote: the word is up to date on the device, but
 //                    the retrieval launcher's host copy of it (grp_nonfinite) is not -- it reads the word again;
@@ -339,6 +354,7 @@ static inline void m2d_mark_written(m2d_engine *h, unsigned tables, m2d_written_
     if (tables & (M2D_TAB_PM | M2D_TAB_CE)) h->user_high_valid = false;
     if (tables & M2D_TAB_PM) h->pm_bf16_valid = false;
     if (tables & (M2D_TAB_RE | M2D_TAB_CE | M2D_TAB_MASKS | M2D_TAB_ING)) h->dish_vec_valid = h->grp_valid = false;
+    if (tables & M2D_TAB_MASKS) h->menu_valid = false;
     if (who == M2D_BY_ENGINE) h->grp_nonfinite_known = false;
     if (who == M2D_BY_CALLER) h->finite_scan_pending = true;
 }
@@ -611,6 +627,9 @@ int m2d_launch_slate_scores(m2d_engine *h, SlateArgs &a, bool mfma, hipStream_t 
 int m2d_launch_groups(m2d_engine *h, const char *entry, const int32_t *members, int64_t nG, int32_t M, int32_t mode, const int32_t *slate,
                       int64_t nD, int32_t k, const int64_t *excl_off, const int32_t *excl_ids, float *out, float *out_scores,
                       int32_t *out_ids, hipStream_t stream);
+// m2d_menu.hip: m2d_topk_menu behind the ABI layer's argument checks -- caps i32[nU, C], C <= M2D_MENU_MAX_CATEGORIES
+int m2d_launch_topk_menu(m2d_engine *h, const int32_t *users, int64_t nU, int32_t k, const int32_t *caps, float *out_scores,
+                         int32_t *out_ids, hipStream_t stream);
 // m2d_slate.hip: out == null: the scores of user blocks go to scratch and the lists of k to out_scores / out_ids
 int m2d_launch_slate(m2d_engine *h, const char *entry, const int32_t *users, int64_t nU, const int32_t *slate, int64_t nD, int32_t k,
                      float *out, float *out_scores, int32_t *out_ids, hipStream_t stream);

@@ -1,0 +1,309 @@
+// Build-defined extension (no reference counterpart): m2d_topk_menu, the k best dishes of the whole catalogue
+// under per-category caps -- at most cap[u][c] listed dishes of category c.
+//
+//   sig(d)  = the C-bit mask of dish d's categories (cats[d][c] != 0.0f; C <= 6: at most 64 signatures, one per lane of a wave)
+//   menu(u) = the greedy walk of m2d_topk_users' order that takes a dish iff none of its categories is at its cap
+//
+// The identity the call rests on (tests/test_menu_cases_cpu.py): a category that is at its cap stays there, so a signature that
+// stops being admissible never returns, and while it is admissible the walk takes its dishes in the order's own sequence -- the walk
+// never reaches past the k best dishes OF A SIGNATURE.  The menu over the full order is therefore the menu over the merge of each
+// signature's own top-k list, and those lists are what the engine already computes: a signature's dishes, ascending, are a slate.
+//
+// Signature index (once per mask table): perm[I], the dish ids by (signature, id), and seg_off[65].  The market filter's three passes,
+// ascending by construction -- no sort, no atomic cursor, no block waits for another:
+//   m2d_menu_flag    a lane per dish: sig[d], and per block of 256 dishes the number of dishes of each signature (six ballots give
+//                    lane s the wave's dishes of signature s)
+//   m2d_menu_scan    one block: per signature the exclusive scan of the block counts, offset by the signatures in front: every
+//                    (block, signature) base, and seg_off
+//   m2d_menu_write   each dish lands at its block's base for its signature + the waves in front + the popcount of its signature's
+//                    ballot below its lane
+// The build reads seg_off to the host (ONE stream synchronisation per mask table); the calls after it do not synchronise.
+//
+// A call (m2d_launch_topk_menu): per block of Ub users and non-empty segment, ranges of W = min(n_s, P, 65536) dishes go through
+// m2d_slate_prepare / m2d_launch_slate_scores / m2d_launch_select (ids = the range of perm, one id row for all) into list scratch
+// [S', Ub, k]; m2d_menu_merge then walks the S' lists of a user in one wave.
+#include "m2d_engine.h"
+
+namespace {
+
+constexpr int MN_WAVES = 4;                    // waves per block of the index passes
+constexpr int MN_DB = 64 * MN_WAVES;           // dishes per block (one per lane)
+constexpr int MN_SIGS = 64;                    // signatures: 2^M2D_MENU_MAX_CATEGORIES
+constexpr int MN_SCAN_WAVES = 16;
+
+// The live lanes of the wave whose signature is `t` (t may differ per lane): six ballots, one per category bit.  Every lane of the
+// wave calls it (full EXEC).
+__device__ __forceinline__ unsigned long long menu_same_sig(const unsigned sig, const bool live, const unsigned t)
+{
+    unsigned long long m = __ballot(live);
+#pragma unroll
+    for (int c = 0; c < M2D_MENU_MAX_CATEGORIES; ++c) {
+        const unsigned long long b = __ballot(live && ((sig >> c) & 1u));
+        m &= ((t >> c) & 1u) ? b : ~b;
+    }
+    return m;
+}
+
+__global__ __launch_bounds__(MN_DB) void m2d_menu_flag(const float *cats, int64_t I, int C, uint8_t *sig, int32_t *counts)
+{
+    __shared__ int32_t wave_cnt[MN_WAVES][MN_SIGS];
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int64_t d = ((int64_t)blockIdx.x * MN_WAVES + wave) * 64 + lane;
+    const bool live = d < I;
+    unsigned s = 0;
+    if (live) {
+        const float *row = cats + (size_t)d * C;
+        for (int c = 0; c < C; ++c) s |= row[c] != 0.0f ? 1u << c : 0u;      // -0.0 is no member, a NaN weight is one
+        sig[d] = (uint8_t)s;
+    }
+    wave_cnt[wave][lane] = __popcll(menu_same_sig(s, live, (unsigned)lane));
+    __syncthreads();
+    if (threadIdx.x < MN_SIGS) {
+        int32_t n = 0;
+        for (int w = 0; w < MN_WAVES; ++w) n += wave_cnt[w][threadIdx.x];
+        counts[(size_t)blockIdx.x * MN_SIGS + threadIdx.x] = n;
+    }
+}
+
+// one block of 16 waves: lane s of wave w owns signature s over the w-th share of the blocks
+__global__ __launch_bounds__(64 * MN_SCAN_WAVES) void m2d_menu_scan(const int32_t *counts, int64_t nb, int32_t *base, int32_t *seg_off)
+{
+    __shared__ int32_t part[MN_SCAN_WAVES][MN_SIGS];
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int64_t per = (nb + MN_SCAN_WAVES - 1) / MN_SCAN_WAVES;
+    const int64_t b0 = wave * per < nb ? wave * per : nb, b1 = b0 + per < nb ? b0 + per : nb;
+    int32_t s = 0;
+    for (int64_t b = b0; b < b1; ++b) s += counts[(size_t)b * MN_SIGS + lane];
+    part[wave][lane] = s;
+    __syncthreads();
+    int32_t total = 0, before = 0;
+    for (int w = 0; w < MN_SCAN_WAVES; ++w) {
+        const int32_t v = part[w][lane];
+        before += w < wave ? v : 0;
+        total += v;
+    }
+    int32_t upto = total;                       // inclusive scan of the signatures' sizes over the lanes (every lane takes part)
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const int32_t v = __shfl_up(upto, o, 64);
+        upto += lane >= o ? v : 0;
+    }
+    if (wave == 0) {
+        seg_off[lane] = upto - total;
+        if (lane == 63) seg_off[MN_SIGS] = upto;
+    }
+    int32_t run = upto - total + before;
+    for (int64_t b = b0; b < b1; ++b) {
+        base[(size_t)b * MN_SIGS + lane] = run;
+        run += counts[(size_t)b * MN_SIGS + lane];
+    }
+}
+
+__global__ __launch_bounds__(MN_DB) void m2d_menu_write(const uint8_t *sig, const int32_t *base, int64_t I, int32_t *perm)
+{
+    __shared__ int32_t wave_cnt[MN_WAVES][MN_SIGS];
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int64_t d = ((int64_t)blockIdx.x * MN_WAVES + wave) * 64 + lane;
+    const bool live = d < I;
+    const unsigned s = live ? sig[d] & (MN_SIGS - 1) : 0u;
+    const unsigned long long mine = menu_same_sig(s, live, s);
+    wave_cnt[wave][lane] = __popcll(menu_same_sig(s, live, (unsigned)lane));
+    __syncthreads();
+    if (live) {
+        int64_t at = base[(size_t)blockIdx.x * MN_SIGS + s];
+        for (int w = 0; w < wave; ++w) at += wave_cnt[w][s];
+        at += __popcll(mine & ((1ull << lane) - 1ull));
+        if (at >= 0 && at < I) perm[at] = (int32_t)d;       // (the counts make it so: perm cannot be overrun whatever they are)
+    }
+}
+
+// ---- the constrained merge -----------------------------------------------------------------------------------------------------
+// One wave per user.  Lane s is signature s: a cursor into segment s's list of k (the j-th list of the scratch, j = the non-empty
+// segments in front of s) and the tkm_key of the entry under it.  `full` -- wave-uniform -- holds the categories at their cap; a lane
+// is admissible while its signature shares no bit with it and its list has an entry left.  A step takes the least key over the
+// admissible lanes (a butterfly of 64-bit minima), lane t of the wave keeps the t-th entry taken, the winner moves on, the winner's
+// categories count.  Ids are distinct across segments, so the minimum names one lane.  The row is written once, k lanes side by
+// side; what no step filled is id -1 / the fill NaN.  A cap below 0 is latched (value: the cap, position: u C + c) and counts as 0.
+struct MenuMergeArgs {
+    const float *list_scores;           // [S', Ub, k]
+    const int32_t *list_ids;
+    const int32_t *seg_off;             // [65]
+    const int32_t *caps;                // [n, C]: the block's rows
+    int64_t n, Ub, index_base;
+    int32_t k, C;
+    float *out_scores;                  // [n, k]: the block's rows
+    int32_t *out_ids;
+    int32_t *err;
+};
+
+__global__ __launch_bounds__(256) void m2d_menu_merge(const MenuMergeArgs p)
+{
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
+    const int64_t r = (int64_t)blockIdx.x * 4 + wave;
+    if (r >= p.n) return;                       // wave-uniform
+    const int k = p.k;
+
+    const bool have = p.seg_off[lane + 1] > p.seg_off[lane];
+    const int j = __popcll(__ballot(have) & ((1ull << lane) - 1ull));
+
+    int32_t capv = 0;
+    if (lane < p.C) {
+        capv = p.caps[(size_t)r * p.C + lane];
+        if (capv < 0) m2d_latch_error(p.err, M2D_ERR_INVALID_ARG, capv, (p.index_base + r) * p.C + lane);
+    }
+    int32_t cap[M2D_MENU_MAX_CATEGORIES], cnt[M2D_MENU_MAX_CATEGORIES];
+    unsigned full = 0;
+#pragma unroll
+    for (int c = 0; c < M2D_MENU_MAX_CATEGORIES; ++c) {
+        cap[c] = __builtin_amdgcn_readlane(capv, c);
+        cnt[c] = 0;
+        if (c < p.C && cap[c] <= 0) full |= 1u << c;
+    }
+
+    const size_t lrow = ((size_t)j * p.Ub + r) * k;
+    int cur = 0;
+    uint64_t key = TKM_NONE;
+    uint32_t word = 0x7FC00000u;
+    const auto load = [&]() {                   // the entry under the cursor, or no entry: the list's end, an id below 0
+        key = TKM_NONE;
+        if (have && cur < k) {
+            const int32_t id = p.list_ids[lrow + cur];
+            if (id >= 0) {
+                const float s = p.list_scores[lrow + cur];
+                word = __float_as_uint(s);
+                key = tkm_key(s, id);
+            }
+        }
+    };
+    load();
+
+    int32_t oid = -1;
+    uint32_t ow = 0x7FC00000u;
+    for (int t = 0; t < k; ++t) {               // wave-uniform: best, win and full are the same in every lane
+        const bool adm = key != TKM_NONE && ((unsigned)lane & full) == 0u;
+        uint64_t best = adm ? key : TKM_NONE;
+#pragma unroll
+        for (int off = 32; off >= 1; off >>= 1) {
+            const uint64_t o = __shfl_xor((unsigned long long)best, off, 64);
+            best = o < best ? o : best;
+        }
+        if (best == TKM_NONE) break;
+        const int win = __ffsll((unsigned long long)__ballot(adm && key == best)) - 1;
+        const uint32_t bw = (uint32_t)__shfl((int)word, win, 64);
+        if (lane == t) {
+            oid = (int32_t)(uint32_t)(best & 0xFFFFFFFFu);
+            ow = bw;
+        }
+#pragma unroll
+        for (int c = 0; c < M2D_MENU_MAX_CATEGORIES; ++c)
+            if ((win >> c) & 1) {
+                cnt[c] += 1;
+                if (cnt[c] >= cap[c]) full |= 1u << c;
+            }
+        if (lane == win) {
+            ++cur;
+            load();
+        }
+    }
+    if (lane < k) {
+        p.out_ids[(size_t)r * k + lane] = oid;
+        p.out_scores[(size_t)r * k + lane] = __uint_as_float(ow);
+    }
+}
+
+// the signature index of the resident masks, built when they changed: perm | seg_off behind it, and seg_off's host copy
+int menu_ensure_index(m2d_engine *h, hipStream_t st)
+{
+    if (h->menu_valid) return M2D_OK;
+    const int64_t I = h->I, nb = (I + MN_DB - 1) / MN_DB;
+    const size_t o_counts = ((size_t)I + 3) / 4, o_base = o_counts + (size_t)nb * MN_SIGS;      // in words: sig u8[I] | counts | bases
+    int rc;
+    if ((rc = h->menu_perm.grow(h, (size_t)I + MN_SIGS + 1)) != M2D_OK) return rc;
+    if ((rc = h->menu_work.grow(h, o_base + (size_t)nb * MN_SIGS)) != M2D_OK) return rc;
+    if (!h->menu_seg_host && (rc = h->menu_seg_host.alloc(h, MN_SIGS + 1)) != M2D_OK) return rc;
+    uint8_t *sig = reinterpret_cast<uint8_t *>(h->menu_work.get());
+    int32_t *counts = h->menu_work + o_counts, *base = h->menu_work + o_base, *seg_off = h->menu_perm + I;
+
+    hipLaunchKernelGGL(m2d_menu_flag, dim3((unsigned)nb), dim3(MN_DB), 0, st, h->dish_cats, I, h->C, sig, counts);
+    hipLaunchKernelGGL(m2d_menu_scan, dim3(1), dim3(64 * MN_SCAN_WAVES), 0, st, counts, nb, base, seg_off);
+    hipLaunchKernelGGL(m2d_menu_write, dim3((unsigned)nb), dim3(MN_DB), 0, st, sig, base, I, h->menu_perm);
+    M2D_HIP_TRY(h, hipGetLastError());
+    // the build's one synchronisation: the 64 segment sizes decide the launches of every call that follows
+    M2D_HIP_TRY(h, hipMemcpyAsync(h->menu_seg_host, seg_off, (MN_SIGS + 1) * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    M2D_HIP_TRY(h, hipStreamSynchronize(st));
+    bool ok = h->menu_seg_host[0] == 0 && (int64_t)h->menu_seg_host[MN_SIGS] == I;
+    for (int s = 0; s < MN_SIGS; ++s) {
+        h->menu_seg[s] = h->menu_seg_host[s];
+        ok = ok && h->menu_seg_host[s] <= h->menu_seg_host[s + 1];
+    }
+    h->menu_seg[MN_SIGS] = h->menu_seg_host[MN_SIGS];
+    if (!ok) {
+        h->last_error = "m2d_topk_menu: the signature index does not cover the catalogue";
+        return M2D_ERR_HIP;
+    }
+    h->menu_valid = true;
+    return M2D_OK;
+}
+
+}  // namespace
+
+int m2d_launch_topk_menu(m2d_engine *h, const int32_t *users, int64_t nU, int32_t k, const int32_t *caps, float *out_scores,
+                         int32_t *out_ids, hipStream_t st)
+{
+    int rc;
+    if ((rc = m2d_deep_conditions(h, "m2d_topk_menu", st)) != M2D_OK) return rc;
+    if ((rc = menu_ensure_index(h, st)) != M2D_OK) return rc;
+
+    const int64_t P = h->opt_deep_chunk_pairs;
+    const auto range_of = [&](const int64_t n_s) {
+        const int64_t W0 = n_s < P ? n_s : P;
+        return W0 < 65536 ? W0 : 65536;
+    };
+    int64_t S = 0, Wmax = 1;
+    for (int s = 0; s < MN_SIGS; ++s) {
+        const int64_t n_s = h->menu_seg[s + 1] - h->menu_seg[s];
+        if (n_s <= 0) continue;
+        ++S;
+        if (range_of(n_s) > Wmax) Wmax = range_of(n_s);
+    }
+    // user blocks: score scratch [Ub, W] and list scratch [S', Ub, k] both within P words
+    const int64_t Ub = m2d_block_rows(P, Wmax > S * k ? Wmax : S * k, nU);
+    if ((rc = h->slate_scores.grow(h, (size_t)Ub * Wmax)) != M2D_OK) return rc;
+    if ((rc = h->menu_list_scores.grow(h, (size_t)S * Ub * k)) != M2D_OK) return rc;
+    if ((rc = h->menu_list_ids.grow(h, (size_t)S * Ub * k)) != M2D_OK) return rc;
+    const bool deep = h->opt_menu_select != 0;
+
+    for (int64_t u0 = 0; u0 < nU; u0 += Ub) {
+        const int64_t n = nU - u0 < Ub ? nU - u0 : Ub;
+        int64_t j = 0;
+        for (int s = 0; s < MN_SIGS; ++s) {
+            const int64_t n_s = h->menu_seg[s + 1] - h->menu_seg[s];
+            if (n_s <= 0) continue;
+            const int64_t W = range_of(n_s);
+            for (int64_t r0 = 0; r0 < n_s; r0 += W) {
+                const int64_t Wc = n_s - r0 > W ? W : n_s - r0;
+                const int32_t *ids = h->menu_perm + h->menu_seg[s] + r0;        // ascending: a slate
+                SlateArgs a;
+                bool mfma;
+                if ((rc = m2d_slate_prepare(h, ids, 0, Wc, a, mfma, st)) != M2D_OK) return rc;
+                a.users = users + u0; a.nU = n; a.index_base = u0; a.out = h->slate_scores;
+                if ((rc = m2d_launch_slate_scores(h, a, mfma, st)) != M2D_OK) return rc;
+                SelectJob job = SelectJob::row_major(h->slate_scores, n, Wc, ids, 0);
+                job.first = r0 == 0 ? 1 : 0;
+                job.k = k;
+                job.out_scores = h->menu_list_scores + (size_t)j * Ub * k;
+                job.out_ids = h->menu_list_ids + (size_t)j * Ub * k;
+                if ((rc = m2d_launch_select(h, job, deep, st)) != M2D_OK) return rc;
+            }
+            ++j;
+        }
+        MenuMergeArgs m;
+        m.list_scores = h->menu_list_scores; m.list_ids = h->menu_list_ids; m.seg_off = h->menu_perm + h->I;
+        m.caps = caps + (size_t)u0 * h->C; m.n = n; m.Ub = Ub; m.index_base = u0; m.k = k; m.C = h->C;
+        m.out_scores = out_scores + (size_t)u0 * k; m.out_ids = out_ids + (size_t)u0 * k; m.err = h->err_dev;
+        hipLaunchKernelGGL(m2d_menu_merge, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, st, m);
+        M2D_HIP_TRY(h, hipGetLastError());
+    }
+    h->last_kernel = "m2d_menu_merge";
+    return M2D_OK;
+}

@@ -542,6 +542,36 @@ class ScoringEngine:
         dishes of each user and segment.  Does not synchronise."""
         return self._topk_deep("topk_users_mlp_deep", users, k, exclude, candidates)
 
+    def _topk_menu(self, users: torch.Tensor, k: int, caps: torch.Tensor):
+        """What ``torch.ops.m2d.topk_menu`` and ``Model.topk_menu`` call (not a public method: every public method of this class has a row
+        in the stream-order table of tests/stream_cases.py, and this call has its own stream-order case in tests/test_gpu_menu.py).
+        EXTENSION, build-defined (``m2d_topk_menu``, include/m2d.h): the first k dishes of ``topk_users``'
+        order over the whole catalogue with at most caps[u][c] dishes of category c in user u's list -> (scores f32[nU, k], dish ids
+        i32[nU, k]).  ``caps``: an int32 device tensor [nU, C], or [C] -- one row for every user, broadcast on the device.  1 <= k <= 64;
+        rows end in id -1 / NaN where the caps leave fewer than k dishes.  The first call after the dish masks changed builds the
+        signature index and waits for the stream once; otherwise it does not synchronise.  A cap below 0 surfaces from ``check()``."""
+        if users.dtype != torch.int32 or users.device != self.device:
+            raise TypeError("topk_menu: users must be an int32 tensor on %s" % self.device)
+        if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or not 1 <= int(k) <= 64:
+            raise ValueError("topk_menu: 1 <= k <= 64, got %r" % (k,))
+        if not isinstance(caps, torch.Tensor) or caps.dtype != torch.int32 or caps.device != self.device:
+            raise TypeError("topk_menu: caps must be an int32 tensor on %s" % self.device)
+        users = users.contiguous().reshape(-1)
+        nU, k = users.numel(), int(k)
+        if caps.dim() == 1 and caps.shape[0] == self.C:
+            caps = caps.reshape(1, self.C).expand(nU, self.C)
+        if caps.dim() != 2 or tuple(caps.shape) != (nU, self.C):
+            raise ValueError("topk_menu: caps must be [%d, %d] or [%d], got %s" % (nU, self.C, self.C, tuple(caps.shape)))
+        caps = caps.contiguous()
+        out_s = torch.empty((nU, k), dtype=torch.float32, device=self.device)
+        out_i = torch.empty((nU, k), dtype=torch.int32, device=self.device)
+        with torch.cuda.device(self.device):
+            rc = _native.lib().m2d_topk_menu(self._h, users.data_ptr(), nU, k, caps.data_ptr(), out_s.data_ptr(), out_i.data_ptr(),
+                                             _stream_ptr())
+        _native.raise_for(rc, self._h)
+        self._menu_keep = (users, caps)                  # stay alive until the queued kernels have read them
+        return out_s, out_i
+
     def _slate_ids(self, users: torch.Tensor, slate: torch.Tensor, what: str):
         for t, name in ((users, "users"), (slate, "slate")):
             if not isinstance(t, torch.Tensor) or t.dtype != torch.int32 or t.device != self.device:
@@ -1090,6 +1120,19 @@ def topk_users_deep_op(engine: int, users: torch.Tensor, k: int, excl_off: Optio
 
 @topk_users_deep_op.register_fake
 def _(engine, users, k, excl_off=None, excl_ids=None):
+    return _deep_fake(users, k)
+
+
+@torch.library.custom_op("m2d::topk_menu", mutates_args=(), device_types="cuda")
+def topk_menu_op(engine: int, users: torch.Tensor, caps: torch.Tensor, k: int) -> tuple[torch.Tensor, torch.Tensor]:
+    """EXTENSION, build-defined (``m2d_topk_menu``, include/m2d.h): the engine-level menu call -- users i32[nU],
+    caps i32[nU, C] or [C] (one row for every user), device tensors; 1 <= k <= 64 -> (scores f32[nU, k], dish ids i32[nU, k])."""
+    s, i = _engine(engine)._topk_menu(users, k, caps)
+    return s, i
+
+
+@topk_menu_op.register_fake
+def _(engine, users, caps, k):
     return _deep_fake(users, k)
 
 

@@ -576,6 +576,48 @@ class Model:
         self.engine.check()
         return s.cpu().numpy(), i.cpu().numpy()
 
+    def topk_menu(self, users, k: int = 10, caps=None):
+        """EXTENSION, build-defined (no reference counterpart): a MENU per user -- the k best dishes over the
+        whole catalogue in `topk`'s order with at most cap[c] dishes of category c in a list (a dish counts in every category of its
+        mask).  `caps`: a dict {category index: cap} (missing categories are uncapped), a list of C ints, or a list of either aligned
+        with `users`; None is uncapped.  1 <= k <= 64; rows end in id -1 / NaN where the caps leave fewer than k dishes.  Returns
+        numpy (scores float32 [n, k], dish ids int32 [n, k]).  (``torch.ops.m2d.topk_menu``.)"""
+        if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or not 1 <= int(k) <= 64:
+            raise ValueError("topk_menu: 1 <= k <= 64, got %r" % (k,))
+        k = int(k)
+        u = _ids(users, "user")
+        ut = u.to(self.device, torch.int32) if isinstance(u, torch.Tensor) else torch.from_numpy(u).to(self.device)
+        n, C = int(ut.numel()), self.engine.C
+
+        def row(spec):
+            if spec is None:
+                return [k] * C
+            if isinstance(spec, dict):
+                r = [k] * C
+                for c, cap in spec.items():
+                    if isinstance(c, bool) or not isinstance(c, (int, np.integer)) or not 0 <= int(c) < C:
+                        raise ValueError("topk_menu: category index %r outside [0, %d)" % (c, C))
+                    r[int(c)] = int(cap)
+                return r
+            r = [int(cap) for cap in spec]
+            if len(r) != C:
+                raise ValueError("topk_menu: a cap row has %d entries for %d categories" % (len(r), C))
+            return r
+
+        per_user = (isinstance(caps, (list, tuple)) and len(caps) > 0
+                    and all(c is None or isinstance(c, (dict, list, tuple, np.ndarray)) for c in caps))
+        if per_user:
+            if len(caps) != n:
+                raise ValueError("topk_menu: %d cap rows for %d users" % (len(caps), n))
+            table = np.asarray([row(c) for c in caps], dtype=np.int64).reshape(n, C)
+        else:
+            table = np.asarray(row(caps), dtype=np.int64).reshape(C)
+        if table.size and (table.min() < 0 or table.max() > np.iinfo(np.int32).max):
+            raise ValueError("topk_menu: caps must be >= 0")
+        s, i = self.engine._topk_menu(ut, k, torch.from_numpy(table.astype(np.int32)).to(self.device))
+        self.engine.check()
+        return s.cpu().numpy(), i.cpu().numpy()
+
     def topk_group(self, groups, k: int = 10, mode: str = "least", exclude=None, among=None, market=None, max_missing: int = 0):
         """EXTENSION, build-defined (no reference counterpart): ONE list of k dishes per household -- `groups` a
         list of lists of user ids (str or int, at most 64 each, repeats count twice in the mean).  `mode`: "least" (least misery: a

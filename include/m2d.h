@@ -515,6 +515,44 @@ int m2d_topk_groups_slate(m2d_engine *h, const int32_t *members /* [nG, M] */, i
                           const int32_t *slate, int64_t nD, int32_t k,
                           float *out_scores /* [nG, k] */, int32_t *out_ids /* [nG, k] */, void *stream);
 
+/* ---- build-defined extension, NO reference counterpart ----
+ * Menu retrieval: the k best dishes of the whole catalogue with AT MOST caps[u][c] DISHES OF CATEGORY c in user u's list.
+ *
+ * Membership.  Dish d is in category c iff cats[d][c] != 0.0f in C semantics, cats the table of m2d_set_dish_categories: -0.0 is no
+ * member, any other word is one (weighted masks, negative weights, a NaN weight).  sig(d) is the C-bit mask of d's categories.
+ * C <= M2D_MENU_MAX_CATEGORIES = 6: at most 64 signatures, one per lane of a wave.
+ *
+ * Menu of user u.  Walk all I dishes in m2d_topk_users' order -- score descending, bit-equal scores and -0 / +0 to the lower dish id, NaN
+ * last in id order; the score is the word m2d_score_slate writes for (u, d) -- with a count n[c] = 0 per category: dish d is taken iff
+ * n[c] < caps[u][c] for every c in sig(d); taking it adds 1 to n[c] for each of them; the walk stops at k dishes.  A dish with an empty
+ * mask is in no category and is never capped (its score is NaN: it comes last).  Rows end in id -1 / NaN where fewer than k dishes can
+ * be taken.  With every cap >= k the row is m2d_topk_users_deep's list for that user, bit for bit.
+ *
+ * m2d_topk_menu.  users i32[nU], device memory, global ids (m2d_set_user_base is honoured, users may repeat); caps i32[nU, C], device
+ * memory, row-major, one row per entry of `users`; 1 <= k <= min(64, I); out_ids i32[nU, k] / out_scores f32[nU, k].  nU == 0 returns
+ * M2D_OK and launches nothing.  A null pointer or k out of range: M2D_ERR_INVALID_ARG.  No dish masks: M2D_ERR_NOT_CONFIGURED.  Refused
+ * with M2D_ERR_UNSUPPORTED under the call's own name, the condition in m2d_last_error: C > 6, the ingredient table set, a table value
+ * that is not finite (m2d_topk_users_deep's conditions; an MLP head is ignored).
+ * Diagnostics (latched, first error wins; m2d_check reports them).  A bad user id: M2D_ERR_BAD_USER_ID with its index in `users`; a cap
+ * below 0: M2D_ERR_INVALID_ARG with the cap as value and u * C + c as position.  The rows of a call with a latched error are
+ * unspecified; no kernel reads or writes out of bounds and the engine stays usable.
+ * The lists do not depend on option "deep_chunk_pairs", on nU, on the row's position or on how the launcher cuts the work.
+ * How.  The menu over the full order equals the menu over the merge of each signature's own first k dishes (a category at its cap
+ * stays there, so a signature that stops being admissible never returns).  The signature index -- the dish ids sorted by
+ * (signature, id) and 65 segment offsets -- is built by the first call after the masks were set or changed (m2d_set_dish_categories,
+ * m2d_tables_updated): three launches, no sort, and ONE STREAM SYNCHRONISATION that reads the 64 segment sizes to the host.  After
+ * that a call synchronises no more than m2d_topk_slate does and allocates only on growth: per block of users and non-empty segment,
+ * ranges of W = min(segment size, P, 65536) dishes (P = option "deep_chunk_pairs") are scored as slates into engine scratch and
+ * listed (option "menu_select") into list scratch [segments, users of a block, k]; m2d_menu_merge, one wave per user with lane s
+ * holding the cursor into signature s's list, then takes the best admissible head k times.  User blocks keep the score scratch and
+ * the list scratch within P words each.
+ * Not offered: per-user exclusion lists (the selection's exclusion cursor works on contiguous dish ranges, not on id tables), slates
+ * (`among`), minimum quotas, the MLP head, k above 64. */
+#define M2D_MENU_MAX_CATEGORIES 6
+int m2d_topk_menu(m2d_engine *h, const int32_t *users /* device [nU] */, int64_t nU, int32_t k,
+                  const int32_t *caps /* device [nU, C] */,
+                  float *out_scores /* [nU, k] */, int32_t *out_ids /* [nU, k] */, void *stream);
+
 /* Diagnostic (scripts/deep_time.py): one selection launch over a resident row-major score block f32[rows, W], ids 0 .. W - 1, no
  * exclusions, into out_scores / out_ids [rows, k] -- form 0: m2d_select_deep (k <= 1024), form 1: m2d_topk_mlp_select (k <= 64).
  * Reads no table.  Bad arguments: M2D_ERR_INVALID_ARG. */
@@ -783,7 +821,9 @@ int m2d_check(m2d_engine *h, void *stream, int64_t *bad_value, int64_t *bad_inde
  *                                        are M2D_ERR_INVALID_ARG.  Same ids, same score bits.
  * deep_chunk_pairs   4194304  256 ... 2^24  m2d_topk_users_deep (and stage 1 of m2d_topk_users_mlp_deep): dish ranges of W = min(I, P, 65536) dishes, user
  *                                        blocks of max(1, P / W) rows; other values are M2D_ERR_INVALID_ARG.  Same ids, same score bits.
- * variant         0        7 9 11 12 13 14 15 16, 100 + n
+ * menu_select      0        0 / 1        m2d_topk_menu: the selection behind each signature's candidate list: 0 = the list across a wave's lanes
+ *                                        (m2d_topk_mlp_select), 1 = the radix select (m2d_select_deep).  Same ids, same score bits.
+ * variant        0        7 9 11 12 13 14 15 16, 100 + n
  *                                        7 / 9: retrieval on the dense MFMA kernel / on the one-block-per-user kernel; 9 also forces the generic pair,
  *                                        head and slate kernels; 11 / 12: the pair kernel's throughput / latency form whatever the batch size; 13: tie
  *                                        repair's one-block-per-user tier from the third listed user on; 14: the nine-launch training step;
