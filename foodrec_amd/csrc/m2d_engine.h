@@ -188,6 +188,10 @@ struct m2d_engine {
     m2d_dev_buf<float> menu_list_scores;
     m2d_dev_buf<int32_t> menu_list_ids;
     int opt_menu_select = 0;           // the per-segment selection: 0 = the list across a wave's lanes (m2d_topk_mlp_select), 1 = the radix select (A/B: same words)
+    // m2d_topk_menu_filtered with a slate: the call's own index -- slate_perm i32[nD], the slate's ids by (signature, id) | seg_off i32[65]
+    // behind it -- and its build's scratch (sig u8[nD] | block counts | block bases, in words); rebuilt by every call with a slate
+    m2d_dev_buf<int32_t> menu_slate_perm;
+    m2d_dev_buf<int32_t> menu_slate_work;
 
     // m2d_set_recipes / m2d_cookable_dishes (m2d_market.hip): every dish's ingredient list, CSR, validated once by the setter (CSR
     // shape, every id in [0, R)); lists only -- no table, no weights, nothing the scoring path reads, and no tie to `ing` above.
@@ -557,7 +561,8 @@ struct SelectJob {
     int32_t first;                      // 1: the lists start with this block; 0: the k entries the outputs hold take part as k more candidates
     float *out_scores;
     int32_t *out_ids;
-    // row r leaves out the ascending dish ids xids[xoff[r] .. xoff[r + 1]), *xend = the array's length (ids == null only; null: none)
+    // row r leaves out the ascending dish ids xids[xoff[r] .. xoff[r + 1]), *xend = the array's length (null: none).  With `ids` the id
+    // row must be ascending (m2d_topk_menu_filtered); without, the strike works on the dish range d0 + e
     const int64_t *xoff;
     const int32_t *xids;
     const int64_t *xend;
@@ -630,6 +635,11 @@ int m2d_launch_groups(m2d_engine *h, const char *entry, const int32_t *members, 
 // m2d_menu.hip: m2d_topk_menu behind the ABI layer's argument checks -- caps i32[nU, C], C <= M2D_MENU_MAX_CATEGORIES
 int m2d_launch_topk_menu(m2d_engine *h, const int32_t *users, int64_t nU, int32_t k, const int32_t *caps, float *out_scores,
                          int32_t *out_ids, hipStream_t stream);
+// m2d_topk_menu_filtered: the same loop over slate \ exclusions (excl_off null: no exclusions; slate null: the whole catalogue; both
+// null: m2d_launch_topk_menu's launches under the name `entry`)
+int m2d_launch_topk_menu_filtered(m2d_engine *h, const char *entry, const int32_t *users, int64_t nU, int32_t k, const int32_t *caps,
+                                  const int64_t *excl_off, const int32_t *excl_ids, const int32_t *slate, int64_t nD, float *out_scores,
+                                  int32_t *out_ids, hipStream_t stream);
 // m2d_slate.hip: out == null: the scores of user blocks go to scratch and the lists of k to out_scores / out_ids
 int m2d_launch_slate(m2d_engine *h, const char *entry, const int32_t *users, int64_t nU, const int32_t *slate, int64_t nD, int32_t k,
                      float *out, float *out_scores, int32_t *out_ids, hipStream_t stream);

@@ -140,4 +140,28 @@ struct ExclCursor {
             if (at < w1 && xids[at] == id) slot[q] = none;
         }
     }
+
+    // The same step over an ASCENDING ID TABLE (m2d_topk_menu_filtered: a range of a signature's segment of the index): slice q, lane l
+    // holds id[q] where live[q].  The step's ids lie in [id_lo, id_hi] -- the ids under its first and its last live column, wave-uniform
+    // -- and the ids of the steps behind it are above id_hi, so the window is [lower bound of id_lo, lower bound of id_hi + 1) and the
+    // cursor moves to its end: what lies between two of the table's ids (the row's excluded dishes of OTHER signatures) is passed over
+    // by the bounds, never counted off.  Ids are only compared; a table that is not ascending gives an empty or a wrong window, and
+    // nothing outside [xw, x1) is read.
+    template <int N, typename T>
+    __device__ __forceinline__ void strike_ids(const int32_t *xids, const int32_t id_lo, const int32_t id_hi, const int32_t (&id)[N],
+                                               const bool (&live)[N], T (&slot)[N], const T none)
+    {
+        if (xv > id_hi) return;                              // scalar: xv is the smallest id the wave has not passed
+        const int64_t w0 = uni64(csr_lower_bound(xids, xw, x1, (int64_t)id_lo)),
+                      w1 = uni64(csr_lower_bound(xids, w0, x1, (int64_t)id_hi + 1));
+        xw = w1;
+        xv = w1 < x1 ? __builtin_amdgcn_readfirstlane(xids[w1]) : INT32_MAX;
+        if (w1 == w0) return;                                // scalar: nothing of the segment in this step
+#pragma unroll
+        for (int q = 0; q < N; ++q) {
+            if (!live[q]) continue;
+            const int64_t at = csr_lower_bound(xids, w0, w1, (int64_t)id[q]);
+            if (at < w1 && xids[at] == id[q]) slot[q] = none;
+        }
+    }
 };

@@ -22,6 +22,13 @@
 // A call (m2d_launch_topk_menu): per block of Ub users and non-empty segment, ranges of W = min(n_s, P, 65536) dishes go through
 // m2d_slate_prepare / m2d_launch_slate_scores / m2d_launch_select (ids = the range of perm, one id row for all) into list scratch
 // [S', Ub, k]; m2d_menu_merge then walks the S' lists of a user in one wave.
+//
+// m2d_topk_menu_filtered: the same walk over the dishes of a slate, less each user's exclusion segment.
+// Removing dishes leaves the identity intact -- the menu over the allowed order is the menu over the merge of each signature's first
+// k ALLOWED dishes.  Exclusions: a range of a segment is an ascending id table, so the selection strikes the row's ascending exclusion
+// segment against it (SelectJob::xoff with ids; ExclCursor::strike_ids).  Slate: its own index (menu_slate_index: the three passes
+// over the slate, reading the resident signature bytes), ONE STREAM SYNCHRONISATION PER CALL WITH A SLATE for the 64 segment sizes.
+// One loop (menu_walk) serves both forms; with null filters it is m2d_topk_menu's launches.
 #include "m2d_engine.h"
 
 namespace {
@@ -99,7 +106,8 @@ __global__ __launch_bounds__(64 * MN_SCAN_WAVES) void m2d_menu_scan(const int32_
     }
 }
 
-__global__ __launch_bounds__(MN_DB) void m2d_menu_write(const uint8_t *sig, const int32_t *base, int64_t I, int32_t *perm)
+// `src` (the slate form): entry d of the index is the slate's d-th id, not d itself
+__global__ __launch_bounds__(MN_DB) void m2d_menu_write(const uint8_t *sig, const int32_t *base, int64_t I, const int32_t *src, int32_t *perm)
 {
     __shared__ int32_t wave_cnt[MN_WAVES][MN_SIGS];
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
@@ -113,7 +121,41 @@ __global__ __launch_bounds__(MN_DB) void m2d_menu_write(const uint8_t *sig, cons
         int64_t at = base[(size_t)blockIdx.x * MN_SIGS + s];
         for (int w = 0; w < wave; ++w) at += wave_cnt[w][s];
         at += __popcll(mine & ((1ull << lane) - 1ull));
-        if (at >= 0 && at < I) perm[at] = (int32_t)d;       // (the counts make it so: perm cannot be overrun whatever they are)
+        if (at >= 0 && at < I) perm[at] = src ? src[d] : (int32_t)d;       // (the counts make it so: perm cannot be overrun whatever they are)
+    }
+}
+
+// The flag pass over a slate (m2d_topk_menu_filtered): lane i reads sig[slate[i]] from the catalogue index's resident signature bytes
+// into ssig[i], and checks the caller's slate by m2d_topk_slate's convention -- an id outside [0, I) is M2D_ERR_BAD_ITEM_ID at its
+// index (it indexes nothing: signature 0), an entry not above its predecessor M2D_ERR_INVALID_ARG at its index (a predecessor that is
+// itself out of range is reported by its own lane).
+__global__ __launch_bounds__(MN_DB) void m2d_menu_flag_slate(const int32_t *slate, int64_t nD, int64_t I, const uint8_t *sig, uint8_t *ssig,
+                                                             int32_t *counts, int32_t *err)
+{
+    __shared__ int32_t wave_cnt[MN_WAVES][MN_SIGS];
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int64_t i = ((int64_t)blockIdx.x * MN_WAVES + wave) * 64 + lane;
+    const bool live = i < nD;
+    unsigned s = 0;
+    if (live) {
+        const int32_t d = slate[i];
+        if (d < 0 || (int64_t)d >= I) {
+            m2d_latch_error(err, M2D_ERR_BAD_ITEM_ID, d, i);
+        } else {
+            s = sig[d] & (MN_SIGS - 1);
+            if (i > 0) {
+                const int32_t prev = slate[i - 1];
+                if (prev >= 0 && (int64_t)prev < I && prev >= d) m2d_latch_error(err, M2D_ERR_INVALID_ARG, d, i);
+            }
+        }
+        ssig[i] = (uint8_t)s;
+    }
+    wave_cnt[wave][lane] = __popcll(menu_same_sig(s, live, (unsigned)lane));
+    __syncthreads();
+    if (threadIdx.x < MN_SIGS) {
+        int32_t n = 0;
+        for (int w = 0; w < MN_WAVES; ++w) n += wave_cnt[w][threadIdx.x];
+        counts[(size_t)blockIdx.x * MN_SIGS + threadIdx.x] = n;
     }
 }
 
@@ -226,7 +268,7 @@ int menu_ensure_index(m2d_engine *h, hipStream_t st)
 
     hipLaunchKernelGGL(m2d_menu_flag, dim3((unsigned)nb), dim3(MN_DB), 0, st, h->dish_cats, I, h->C, sig, counts);
     hipLaunchKernelGGL(m2d_menu_scan, dim3(1), dim3(64 * MN_SCAN_WAVES), 0, st, counts, nb, base, seg_off);
-    hipLaunchKernelGGL(m2d_menu_write, dim3((unsigned)nb), dim3(MN_DB), 0, st, sig, base, I, h->menu_perm);
+    hipLaunchKernelGGL(m2d_menu_write, dim3((unsigned)nb), dim3(MN_DB), 0, st, sig, base, I, nullptr, h->menu_perm);
     M2D_HIP_TRY(h, hipGetLastError());
     // the build's one synchronisation: the 64 segment sizes decide the launches of every call that follows
     M2D_HIP_TRY(h, hipMemcpyAsync(h->menu_seg_host, seg_off, (MN_SIGS + 1) * sizeof(int32_t), hipMemcpyDeviceToHost, st));
@@ -245,15 +287,54 @@ int menu_ensure_index(m2d_engine *h, hipStream_t st)
     return M2D_OK;
 }
 
-}  // namespace
+// What a call walks: the dish ids by (signature, id), the 65 offsets on the device (the merge reads them) and on the host (they
+// decide the launches).  The catalogue's index, or a slate's own.
+struct MenuIndex {
+    const int32_t *perm;
+    const int32_t *seg_off;             // device [65]
+    const int32_t *seg;                 // host [65]
+};
 
-int m2d_launch_topk_menu(m2d_engine *h, const int32_t *users, int64_t nU, int32_t k, const int32_t *caps, float *out_scores,
-                         int32_t *out_ids, hipStream_t st)
+// The signature index of a strictly ascending slate i32[nD]: slate_perm[nD], the slate's ids by (signature, id), | seg_off[65] -- the
+// catalogue index's three passes, the flag pass reading the resident signature bytes (menu_ensure_index has run) and checking the
+// caller's slate, the write pass storing slate[i].  The 64 segment sizes decide the launches: they are read to the host HERE, ONE
+// STREAM SYNCHRONISATION PER CALL WITH A SLATE.
+int menu_slate_index(m2d_engine *h, const int32_t *slate, const int64_t nD, int32_t (&seg)[MN_SIGS + 1], hipStream_t st)
+{
+    const int64_t nb = (nD + MN_DB - 1) / MN_DB;
+    const size_t o_counts = ((size_t)nD + 3) / 4, o_base = o_counts + (size_t)nb * MN_SIGS;     // in words: ssig u8[nD] | counts | bases
+    int rc;
+    if ((rc = h->menu_slate_perm.grow(h, (size_t)nD + MN_SIGS + 1)) != M2D_OK) return rc;
+    if ((rc = h->menu_slate_work.grow(h, o_base + (size_t)nb * MN_SIGS)) != M2D_OK) return rc;
+    const uint8_t *sig = reinterpret_cast<const uint8_t *>(h->menu_work.get());
+    uint8_t *ssig = reinterpret_cast<uint8_t *>(h->menu_slate_work.get());
+    int32_t *counts = h->menu_slate_work + o_counts, *base = h->menu_slate_work + o_base, *seg_off = h->menu_slate_perm + nD;
+
+    hipLaunchKernelGGL(m2d_menu_flag_slate, dim3((unsigned)nb), dim3(MN_DB), 0, st, slate, nD, h->I, sig, ssig, counts, h->err_dev);
+    hipLaunchKernelGGL(m2d_menu_scan, dim3(1), dim3(64 * MN_SCAN_WAVES), 0, st, counts, nb, base, seg_off);
+    hipLaunchKernelGGL(m2d_menu_write, dim3((unsigned)nb), dim3(MN_DB), 0, st, ssig, base, nD, slate, h->menu_slate_perm);
+    M2D_HIP_TRY(h, hipGetLastError());
+    M2D_HIP_TRY(h, hipMemcpyAsync(h->menu_seg_host, seg_off, (MN_SIGS + 1) * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    M2D_HIP_TRY(h, hipStreamSynchronize(st));
+    bool ok = h->menu_seg_host[0] == 0 && (int64_t)h->menu_seg_host[MN_SIGS] == nD;
+    for (int s = 0; s <= MN_SIGS; ++s) {
+        seg[s] = h->menu_seg_host[s];
+        ok = ok && (s == MN_SIGS || h->menu_seg_host[s] <= h->menu_seg_host[s + 1]);
+    }
+    if (!ok) {
+        h->last_error = "m2d_topk_menu_filtered: the signature index does not cover the slate";
+        return M2D_ERR_HIP;
+    }
+    return M2D_OK;
+}
+
+// One loop for both forms: per block of Ub users and non-empty segment of `ix`, ranges of W dishes -- vectors, scores, selection into
+// the segment's lists (excl_off: each row's exclusion segment is struck on the range's ascending ids; a later range merges into the
+// list of the ranges before it, whose entries were struck when they were listed) -- then the merge under the caps.
+int menu_walk(m2d_engine *h, const MenuIndex &ix, const int32_t *users, int64_t nU, int32_t k, const int32_t *caps, const int64_t *excl_off,
+              const int32_t *excl_ids, float *out_scores, int32_t *out_ids, hipStream_t st)
 {
     int rc;
-    if ((rc = m2d_deep_conditions(h, "m2d_topk_menu", st)) != M2D_OK) return rc;
-    if ((rc = menu_ensure_index(h, st)) != M2D_OK) return rc;
-
     const int64_t P = h->opt_deep_chunk_pairs;
     const auto range_of = [&](const int64_t n_s) {
         const int64_t W0 = n_s < P ? n_s : P;
@@ -261,7 +342,7 @@ int m2d_launch_topk_menu(m2d_engine *h, const int32_t *users, int64_t nU, int32_
     };
     int64_t S = 0, Wmax = 1;
     for (int s = 0; s < MN_SIGS; ++s) {
-        const int64_t n_s = h->menu_seg[s + 1] - h->menu_seg[s];
+        const int64_t n_s = ix.seg[s + 1] - ix.seg[s];
         if (n_s <= 0) continue;
         ++S;
         if (range_of(n_s) > Wmax) Wmax = range_of(n_s);
@@ -277,12 +358,12 @@ int m2d_launch_topk_menu(m2d_engine *h, const int32_t *users, int64_t nU, int32_
         const int64_t n = nU - u0 < Ub ? nU - u0 : Ub;
         int64_t j = 0;
         for (int s = 0; s < MN_SIGS; ++s) {
-            const int64_t n_s = h->menu_seg[s + 1] - h->menu_seg[s];
+            const int64_t n_s = ix.seg[s + 1] - ix.seg[s];
             if (n_s <= 0) continue;
             const int64_t W = range_of(n_s);
             for (int64_t r0 = 0; r0 < n_s; r0 += W) {
                 const int64_t Wc = n_s - r0 > W ? W : n_s - r0;
-                const int32_t *ids = h->menu_perm + h->menu_seg[s] + r0;        // ascending: a slate
+                const int32_t *ids = ix.perm + ix.seg[s] + r0;                   // ascending: a slate
                 SlateArgs a;
                 bool mfma;
                 if ((rc = m2d_slate_prepare(h, ids, 0, Wc, a, mfma, st)) != M2D_OK) return rc;
@@ -293,12 +374,15 @@ int m2d_launch_topk_menu(m2d_engine *h, const int32_t *users, int64_t nU, int32_
                 job.k = k;
                 job.out_scores = h->menu_list_scores + (size_t)j * Ub * k;
                 job.out_ids = h->menu_list_ids + (size_t)j * Ub * k;
+                if (excl_off) {
+                    job.xoff = excl_off + u0; job.xids = excl_ids; job.xend = excl_off + nU;
+                }
                 if ((rc = m2d_launch_select(h, job, deep, st)) != M2D_OK) return rc;
             }
             ++j;
         }
         MenuMergeArgs m;
-        m.list_scores = h->menu_list_scores; m.list_ids = h->menu_list_ids; m.seg_off = h->menu_perm + h->I;
+        m.list_scores = h->menu_list_scores; m.list_ids = h->menu_list_ids; m.seg_off = ix.seg_off;
         m.caps = caps + (size_t)u0 * h->C; m.n = n; m.Ub = Ub; m.index_base = u0; m.k = k; m.C = h->C;
         m.out_scores = out_scores + (size_t)u0 * k; m.out_ids = out_ids + (size_t)u0 * k; m.err = h->err_dev;
         hipLaunchKernelGGL(m2d_menu_merge, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, st, m);
@@ -307,3 +391,30 @@ int m2d_launch_topk_menu(m2d_engine *h, const int32_t *users, int64_t nU, int32_
     h->last_kernel = "m2d_menu_merge";
     return M2D_OK;
 }
+
+}  // namespace
+
+int m2d_launch_topk_menu_filtered(m2d_engine *h, const char *entry, const int32_t *users, int64_t nU, int32_t k, const int32_t *caps,
+                                  const int64_t *excl_off, const int32_t *excl_ids, const int32_t *slate, int64_t nD, float *out_scores,
+                                  int32_t *out_ids, hipStream_t st)
+{
+    int rc;
+    if ((rc = m2d_deep_conditions(h, entry, st)) != M2D_OK) return rc;
+    if ((rc = menu_ensure_index(h, st)) != M2D_OK) return rc;
+    // the callers' lists are checked before any scoring launch in stream order: the positions the latch reports are the caller's
+    if (excl_off && (rc = m2d_launch_check_exclusions(h, excl_off, excl_ids, nU, st)) != M2D_OK) return rc;
+    MenuIndex ix{h->menu_perm, h->menu_perm + h->I, h->menu_seg};
+    int32_t seg[MN_SIGS + 1];
+    if (slate) {
+        if ((rc = menu_slate_index(h, slate, nD, seg, st)) != M2D_OK) return rc;
+        ix = MenuIndex{h->menu_slate_perm, h->menu_slate_perm + nD, seg};
+    }
+    return menu_walk(h, ix, users, nU, k, caps, excl_off, excl_ids, out_scores, out_ids, st);
+}
+
+int m2d_launch_topk_menu(m2d_engine *h, const int32_t *users, int64_t nU, int32_t k, const int32_t *caps, float *out_scores,
+                         int32_t *out_ids, hipStream_t st)
+{
+    return m2d_launch_topk_menu_filtered(h, "m2d_topk_menu", users, nU, k, caps, nullptr, nullptr, nullptr, 0, out_scores, out_ids, st);
+}
+

@@ -4,8 +4,9 @@
 //   m2d_select_deep       1 <= k <= 1024: a radix select on the key, O(W) work per row for any k
 // Both: one workgroup per score row -- column e at scores[row * rs + e * es], its id ids[row * ids_stride + e] or d0 + e when `ids` is
 // null -- merged into the row's list of k (score, id) in out_scores / out_ids (`first`: the list starts with this block, otherwise its k
-// entries take part as k more candidates).  EXCL (ids == null only): row r leaves out xids[xoff[r] .. xoff[r + 1]), ascending dish ids,
-// the array's length at *xend.  HOLES (the candidate form behind a retrieval with exclusions): an id below 0 in `ids` is no entry,
+// entries take part as k more candidates: they were struck when they were listed).  EXCL: row r leaves out xids[xoff[r] .. xoff[r + 1]),
+// ascending dish ids, the array's length at *xend -- 1 (ids == null): struck on the dish range d0 + e; 2 (ids != null, the id row
+// ASCENDING: m2d_topk_menu_filtered's ranges of a signature's segment): struck on the id table.  HOLES (the candidate form behind a retrieval with exclusions): an id below 0 in `ids` is no entry,
 // whatever its score.  Both make a candidate TKM_NONE, which takes part in nothing.  No global atomics, no block waits for another; the
 // score written is the word that was read (a NaN's payload, a -0).
 #include "m2d_select.h"
@@ -19,7 +20,7 @@ namespace {
 // k ln(W / k) candidates pass per wave, the rest costs a load, a compare and a ballot per 64 scores.  The waves' lists and the
 // running list meet in LDS ((waves + 1) k keys of 8 B and score words of 4 B), where every entry counts the entries in front of
 // it and the first k write themselves out.  <false, false> is the kernel as it stood before exclusions.
-template <bool EXCL, bool HOLES>
+template <int EXCL, bool HOLES>
 __global__ __launch_bounds__(1024) void m2d_topk_mlp_select(const SelectJob job)
 {
     extern __shared__ __align__(16) unsigned char smem[];
@@ -127,7 +128,7 @@ struct SdCut {
     }
 };
 
-template <bool EXCL, bool HOLES>
+template <int EXCL, bool HOLES>
 __global__ __launch_bounds__(1024) void m2d_select_deep(const SelectJob job)
 {
     extern __shared__ __align__(16) unsigned char smem[];
@@ -286,7 +287,8 @@ int m2d_launch_select(m2d_engine *h, const SelectJob &job, const bool deep, hipS
         return M2D_OK;
     };
     const auto form = [&](auto list, auto radix) { return deep ? launch(radix) : launch(list); };
-    return job.xoff  ? form(m2d_topk_mlp_select<true, false>, m2d_select_deep<true, false>)
+    return job.xoff  ? (job.ids ? form(m2d_topk_mlp_select<SELECT_EXCL_IDS, false>, m2d_select_deep<SELECT_EXCL_IDS, false>)
+                                : form(m2d_topk_mlp_select<true, false>, m2d_select_deep<true, false>))
          : job.holes ? form(m2d_topk_mlp_select<false, true>, m2d_select_deep<false, true>)
                      : form(m2d_topk_mlp_select<false, false>, m2d_select_deep<false, false>);
 }

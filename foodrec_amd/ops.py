@@ -572,6 +572,50 @@ class ScoringEngine:
         self._menu_keep = (users, caps)                  # stay alive until the queued kernels have read them
         return out_s, out_i
 
+    def _topk_menu_filtered(self, users: torch.Tensor, k: int, caps: torch.Tensor, exclude=None, among=None):
+        """What ``torch.ops.m2d.topk_menu_filtered`` and ``Model.topk_menu_filtered`` call (not a public method, for ``_topk_menu``'s
+        reason; its stream-order case is in tests/test_gpu_menu_filtered.py).  EXTENSION, build-defined (``m2d_topk_menu_filtered``,
+        include/m2d.h): ``_topk_menu`` over the dishes of ``among`` -- an int32 device tensor of STRICTLY
+        ASCENDING dish ids, None: the whole catalogue -- less users[i]'s excluded dishes -- ``exclude``: an ``(offsets, ids)`` pair of
+        device tensors as ``topk_users_deep`` takes it, or its host forms; None: none.  A dish that is left out counts against no cap.
+        With a slate THE CALL WAITS FOR THE STREAM ONCE (the slate's 64 segment sizes decide the launches); without one it
+        synchronises as ``_topk_menu`` does.  Bad lists surface from ``check()``."""
+        what = "topk_menu_filtered"
+        if users.dtype != torch.int32 or users.device != self.device:
+            raise TypeError("%s: users must be an int32 tensor on %s" % (what, self.device))
+        if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or not 1 <= int(k) <= 64:
+            raise ValueError("%s: 1 <= k <= 64, got %r" % (what, k))
+        if not isinstance(caps, torch.Tensor) or caps.dtype != torch.int32 or caps.device != self.device:
+            raise TypeError("%s: caps must be an int32 tensor on %s" % (what, self.device))
+        users = users.contiguous().reshape(-1)
+        nU, k = users.numel(), int(k)
+        if caps.dim() == 1 and caps.shape[0] == self.C:
+            caps = caps.reshape(1, self.C).expand(nU, self.C)
+        if caps.dim() != 2 or tuple(caps.shape) != (nU, self.C):
+            raise ValueError("%s: caps must be [%d, %d] or [%d], got %s" % (what, nU, self.C, self.C, tuple(caps.shape)))
+        caps = caps.contiguous()
+        off = ids = None
+        if exclude is not None:
+            off, ids = exclusions_on_device(exclude, nU, self.device, what)
+        slate, nD = None, 0
+        if among is not None:
+            if not isinstance(among, torch.Tensor) or among.dtype != torch.int32 or among.device != self.device:
+                raise TypeError("%s: among must be an int32 tensor on %s" % (what, self.device))
+            slate = among.contiguous().reshape(-1)
+            nD = slate.numel()
+            if nD < 1:
+                raise ValueError("%s: among must hold at least one dish" % what)
+        out_s = torch.empty((nU, k), dtype=torch.float32, device=self.device)
+        out_i = torch.empty((nU, k), dtype=torch.int32, device=self.device)
+        xo, xi = (off.data_ptr(), ids.data_ptr()) if off is not None else (None, None)
+        with torch.cuda.device(self.device):
+            rc = _native.lib().m2d_topk_menu_filtered(self._h, users.data_ptr(), nU, k, caps.data_ptr(), xo, xi,
+                                                      slate.data_ptr() if slate is not None else None, nD, out_s.data_ptr(),
+                                                      out_i.data_ptr(), _stream_ptr())
+        _native.raise_for(rc, self._h)
+        self._menu_filtered_keep = (users, caps, off, ids, slate)      # stay alive until the queued kernels have read them
+        return out_s, out_i
+
     def _slate_ids(self, users: torch.Tensor, slate: torch.Tensor, what: str):
         for t, name in ((users, "users"), (slate, "slate")):
             if not isinstance(t, torch.Tensor) or t.dtype != torch.int32 or t.device != self.device:
@@ -1133,6 +1177,21 @@ def topk_menu_op(engine: int, users: torch.Tensor, caps: torch.Tensor, k: int) -
 
 @topk_menu_op.register_fake
 def _(engine, users, caps, k):
+    return _deep_fake(users, k)
+
+
+@torch.library.custom_op("m2d::topk_menu_filtered", mutates_args=(), device_types="cuda")
+def topk_menu_filtered_op(engine: int, users: torch.Tensor, caps: torch.Tensor, k: int, excl_off: Optional[torch.Tensor] = None,
+                          excl_ids: Optional[torch.Tensor] = None, among: Optional[torch.Tensor] = None) -> tuple[torch.Tensor, torch.Tensor]:
+    """EXTENSION, build-defined (``m2d_topk_menu_filtered``, include/m2d.h): ``topk_menu`` over the strictly
+    ascending dish ids of `among` (None: the catalogue) less each user's excluded dishes (`excl_off` / `excl_ids`: device tensors,
+    ascending per segment, taken as they are)."""
+    s, i = _engine(engine)._topk_menu_filtered(users, k, caps, _excl_pair(excl_off, excl_ids), among)
+    return s, i
+
+
+@topk_menu_filtered_op.register_fake
+def _(engine, users, caps, k, excl_off=None, excl_ids=None, among=None):
     return _deep_fake(users, k)
 
 

@@ -576,6 +576,37 @@ class Model:
         self.engine.check()
         return s.cpu().numpy(), i.cpu().numpy()
 
+    def _menu_caps(self, caps, k: int, n: int, what: str) -> torch.Tensor:
+        """`caps` of `topk_menu` and `topk_menu_filtered` -> an int32 device tensor [n, C], or [C] (one row for every user)"""
+        C = self.engine.C
+
+        def row(spec):
+            if spec is None:
+                return [k] * C
+            if isinstance(spec, dict):
+                r = [k] * C
+                for c, cap in spec.items():
+                    if isinstance(c, bool) or not isinstance(c, (int, np.integer)) or not 0 <= int(c) < C:
+                        raise ValueError(what + ": category index %r outside [0, %d)" % (c, C))
+                    r[int(c)] = int(cap)
+                return r
+            r = [int(cap) for cap in spec]
+            if len(r) != C:
+                raise ValueError(what + ": a cap row has %d entries for %d categories" % (len(r), C))
+            return r
+
+        per_user = (isinstance(caps, (list, tuple)) and len(caps) > 0
+                    and all(c is None or isinstance(c, (dict, list, tuple, np.ndarray)) for c in caps))
+        if per_user:
+            if len(caps) != n:
+                raise ValueError(what + ": %d cap rows for %d users" % (len(caps), n))
+            table = np.asarray([row(c) for c in caps], dtype=np.int64).reshape(n, C)
+        else:
+            table = np.asarray(row(caps), dtype=np.int64).reshape(C)
+        if table.size and (table.min() < 0 or table.max() > np.iinfo(np.int32).max):
+            raise ValueError(what + ": caps must be >= 0")
+        return torch.from_numpy(table.astype(np.int32)).to(self.device)
+
     def topk_menu(self, users, k: int = 10, caps=None):
         """EXTENSION, build-defined (no reference counterpart): a MENU per user -- the k best dishes over the
         whole catalogue in `topk`'s order with at most cap[c] dishes of category c in a list (a dish counts in every category of its
@@ -587,34 +618,46 @@ class Model:
         k = int(k)
         u = _ids(users, "user")
         ut = u.to(self.device, torch.int32) if isinstance(u, torch.Tensor) else torch.from_numpy(u).to(self.device)
-        n, C = int(ut.numel()), self.engine.C
+        table = self._menu_caps(caps, k, int(ut.numel()), "topk_menu")
+        s, i = self.engine._topk_menu(ut, k, table)
+        self.engine.check()
+        return s.cpu().numpy(), i.cpu().numpy()
 
-        def row(spec):
-            if spec is None:
-                return [k] * C
-            if isinstance(spec, dict):
-                r = [k] * C
-                for c, cap in spec.items():
-                    if isinstance(c, bool) or not isinstance(c, (int, np.integer)) or not 0 <= int(c) < C:
-                        raise ValueError("topk_menu: category index %r outside [0, %d)" % (c, C))
-                    r[int(c)] = int(cap)
-                return r
-            r = [int(cap) for cap in spec]
-            if len(r) != C:
-                raise ValueError("topk_menu: a cap row has %d entries for %d categories" % (len(r), C))
-            return r
-
-        per_user = (isinstance(caps, (list, tuple)) and len(caps) > 0
-                    and all(c is None or isinstance(c, (dict, list, tuple, np.ndarray)) for c in caps))
-        if per_user:
-            if len(caps) != n:
-                raise ValueError("topk_menu: %d cap rows for %d users" % (len(caps), n))
-            table = np.asarray([row(c) for c in caps], dtype=np.int64).reshape(n, C)
-        else:
-            table = np.asarray(row(caps), dtype=np.int64).reshape(C)
-        if table.size and (table.min() < 0 or table.max() > np.iinfo(np.int32).max):
-            raise ValueError("topk_menu: caps must be >= 0")
-        s, i = self.engine._topk_menu(ut, k, torch.from_numpy(table.astype(np.int32)).to(self.device))
+    def topk_menu_filtered(self, users, k: int = 10, caps=None, exclude=None, among=None, market=None, max_missing: int = 0):
+        """EXTENSION, build-defined (no reference counterpart): `topk_menu` chosen from what the shopper may
+        have today -- `among=dishes`: those dishes only (str or int ids, any order, repeats ignored, as in `topk`);
+        `market=ingredients`: the dishes `cookable(market, max_missing)` lists; neither: the whole catalogue -- and leaving out what
+        they have already had -- `exclude`: a dict keyed by the user as given in `users` (a missing key excludes nothing) or a list
+        aligned with `users`, as in `topk_deep`; an excluded dish outside the slate is ignored.  A dish that is left out counts against
+        no cap.  `caps` as in `topk_menu`.  `among` together with `market` raises; `exclude` goes with either (exclusions are per
+        user: they cannot be taken out of a shared slate).  1 <= k <= 64; rows end in id -1 / NaN where fewer than k dishes can be
+        taken -- all of them when the slate is empty (the engine is not called).  Returns numpy (scores float32 [n, k], dish ids int32
+        [n, k]).  (``torch.ops.m2d.topk_menu_filtered``.)"""
+        if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or not 1 <= int(k) <= 64:
+            raise ValueError("topk_menu_filtered: 1 <= k <= 64, got %r" % (k,))
+        k = int(k)
+        if among is not None and market is not None:
+            raise ValueError("topk_menu_filtered: among together with market is not supported")
+        u = _ids(users, "user")
+        ut = u.to(self.device, torch.int32) if isinstance(u, torch.Tensor) else torch.from_numpy(u).to(self.device)
+        n = int(ut.numel())
+        table = self._menu_caps(caps, k, n, "topk_menu_filtered")
+        off = ids = None
+        if exclude is not None:
+            from .ops import exclusions_on_device
+            had = [_ids(x, "item") for x in _exclusion_lists(exclude, users, "topk_menu_filtered")]
+            had = [x.cpu().numpy() if isinstance(x, torch.Tensor) else x for x in had]
+            off, ids = exclusions_on_device(had, n, self.device, "topk_menu_filtered")      # sorted and de-duplicated per user
+        slate = None
+        if market is not None:
+            slate = np.asarray(self.cookable(market, max_missing), dtype=np.int32)
+        elif among is not None:
+            d = _ids(among, "item")
+            slate = np.unique(np.asarray(d.cpu().numpy() if isinstance(d, torch.Tensor) else d, dtype=np.int32).reshape(-1))
+        if slate is not None and slate.size == 0:
+            return np.full((n, k), np.nan, dtype=np.float32), np.full((n, k), -1, dtype=np.int32)
+        st = None if slate is None else torch.from_numpy(slate).to(self.device)
+        s, i = torch.ops.m2d.topk_menu_filtered(self.engine.id, ut, table, k, off, ids, st)
         self.engine.check()
         return s.cpu().numpy(), i.cpu().numpy()
 

@@ -546,12 +546,43 @@ int m2d_topk_groups_slate(m2d_engine *h, const int32_t *members /* [nG, M] */, i
  * listed (option "menu_select") into list scratch [segments, users of a block, k]; m2d_menu_merge, one wave per user with lane s
  * holding the cursor into signature s's list, then takes the best admissible head k times.  User blocks keep the score scratch and
  * the list scratch within P words each.
- * Not offered: per-user exclusion lists (the selection's exclusion cursor works on contiguous dish ranges, not on id tables), slates
- * (`among`), minimum quotas, the MLP head, k above 64. */
+ * Not offered here: per-user exclusion lists and slates (`among`) -- m2d_topk_menu_filtered below takes both --; nowhere: minimum
+ * quotas, the MLP head, k above 64. */
 #define M2D_MENU_MAX_CATEGORIES 6
 int m2d_topk_menu(m2d_engine *h, const int32_t *users /* device [nU] */, int64_t nU, int32_t k,
                   const int32_t *caps /* device [nU, C] */,
                   float *out_scores /* [nU, k] */, int32_t *out_ids /* [nU, k] */, void *stream);
+
+/* ---- build-defined extension, NO reference counterpart ----
+ * Menu retrieval over a slate or market, with per-user exclusions: m2d_topk_menu's greedy walk over the dishes of `slate` (all I dishes
+ * when slate == NULL), less user u's exclusion segment.  A dish that is left out counts against no cap; listed scores are
+ * m2d_score_slate's words; rows end in id -1 / NaN where fewer than k dishes can be taken.
+ *
+ * Arguments.  users, caps, the outputs: as m2d_topk_menu.  excl_off i64[nU + 1] / excl_ids i32[excl_off[nU]], device memory, by
+ * m2d_catalogue_rank's conventions (offsets from 0 and non-decreasing, a segment's ids ascending, repeats allowed); an excluded id that
+ * is not in the slate is ignored.  slate i32[nD], device memory, STRICTLY ASCENDING dish ids, 1 <= nD <= I.  1 <= k <= min(64, I)
+ * whatever nD is.  nU == 0 returns M2D_OK and launches nothing.  nD out of range with a slate, excl_off without excl_ids, a null
+ * required pointer, k out of range: M2D_ERR_INVALID_ARG.  Refusals are m2d_topk_menu's, under this call's name.
+ * Diagnostics (latched, first error wins).  Exclusion lists are checked as m2d_topk_users_deep checks them: the same codes, values and
+ * positions.  A slate id outside [0, I): M2D_ERR_BAD_ITEM_ID with the id and its index in `slate`; a slate entry not above its
+ * predecessor: M2D_ERR_INVALID_ARG with the entry and its index (m2d_topk_slate's convention; both checks run before any scoring
+ * launch in stream order).  Bad users and caps below 0 as m2d_topk_menu.  The rows of a call with a latched error are unspecified; ids
+ * are only ever compared, so no kernel reads or writes out of bounds whatever the lists hold, and the engine stays usable.
+ * With excl_off == NULL and slate == NULL the call IS m2d_topk_menu: the same launches, the same words.  The lists do not depend on
+ * options "deep_chunk_pairs" and "menu_select", on nU or on the row's position.
+ * How.  Removing dishes from the order leaves m2d_topk_menu's identity intact: the menu over the allowed order is the menu over the
+ * merge of each signature's first k ALLOWED dishes.  Exclusions: a range of a signature's segment is an ascending id table, a row's
+ * exclusion segment is ascending, and the selection strikes one against the other with a forward-only cursor (a window between the
+ * lower bounds of the ids under a step's first and last column; one scalar compare where it is empty).  Slate: the slate is
+ * partitioned by signature with the index's three passes, the flag pass reading the catalogue index's resident signature bytes (so that
+ * index is built first, as m2d_topk_menu builds it) -- and the 64 segment sizes are read to the host: ONE STREAM SYNCHRONISATION PER
+ * CALL WITH A SLATE.  Without a slate the call synchronises as m2d_topk_menu does.  Scratch lives in engine buffers that grow only.
+ * Not offered: minimum quotas, the MLP head, sharding, k above 64, C above 6. */
+int m2d_topk_menu_filtered(m2d_engine *h, const int32_t *users /* device [nU] */, int64_t nU, int32_t k,
+                           const int32_t *caps /* device [nU, C] */,
+                           const int64_t *excl_off /* [nU + 1] or NULL */, const int32_t *excl_ids,
+                           const int32_t *slate /* [nD] strictly ascending, or NULL: the whole catalogue */, int64_t nD,
+                           float *out_scores /* [nU, k] */, int32_t *out_ids /* [nU, k] */, void *stream);
 
 /* Diagnostic (scripts/deep_time.py): one selection launch over a resident row-major score block f32[rows, W], ids 0 .. W - 1, no
  * exclusions, into out_scores / out_ids [rows, k] -- form 0: m2d_select_deep (k <= 1024), form 1: m2d_topk_mlp_select (k <= 64).
@@ -821,7 +852,7 @@ int m2d_check(m2d_engine *h, void *stream, int64_t *bad_value, int64_t *bad_inde
  *                                        are M2D_ERR_INVALID_ARG.  Same ids, same score bits.
  * deep_chunk_pairs   4194304  256 ... 2^24  m2d_topk_users_deep (and stage 1 of m2d_topk_users_mlp_deep): dish ranges of W = min(I, P, 65536) dishes, user
  *                                        blocks of max(1, P / W) rows; other values are M2D_ERR_INVALID_ARG.  Same ids, same score bits.
- * menu_select      0        0 / 1        m2d_topk_menu: the selection behind each signature's candidate list: 0 = the list across a wave's lanes
+ * menu_select      0        0 / 1        m2d_topk_menu, m2d_topk_menu_filtered: the selection behind each signature's candidate list: 0 = the list across a wave's lanes
  *                                        (m2d_topk_mlp_select), 1 = the radix select (m2d_select_deep).  Same ids, same score bits.
  * variant        0        7 9 11 12 13 14 15 16, 100 + n
  *                                        7 / 9: retrieval on the dense MFMA kernel / on the one-block-per-user kernel; 9 also forces the generic pair,
