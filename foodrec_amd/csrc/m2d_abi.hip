@@ -865,6 +865,25 @@ int m2d_topk_menu_filtered(m2d_engine *h, const int32_t *users, int64_t nU, int3
                                          (hipStream_t)stream);
 }
 
+int m2d_plan_menus(m2d_engine *h, const int32_t *users, int64_t nU, int32_t days, int32_t k, const int32_t *caps, const int32_t *plan_caps,
+                   const int64_t *excl_off, const int32_t *excl_ids, const int32_t *slate, int64_t nD, float *out_scores, int32_t *out_ids,
+                   void *stream)
+{
+    if (!h) return M2D_ERR_INVALID_ARG;
+    M2D_REQUIRE(topk_range(h, "m2d_plan_menus", nU, k, 64));
+    if (days < 1 || (int64_t)days * k > M2D_PLAN_MAX_LIST)
+        return fail(h, M2D_ERR_INVALID_ARG, "m2d_plan_menus: need days >= 1 and days * k <= M2D_PLAN_MAX_LIST = 1024");
+    if (slate && (nD < 1 || nD > h->I)) return fail(h, M2D_ERR_INVALID_ARG, "m2d_plan_menus: with a slate need 1 <= nD <= I");
+    if (excl_off && !excl_ids) return fail(h, M2D_ERR_INVALID_ARG, "m2d_plan_menus: excl_off without excl_ids");
+    if (nU == 0) return M2D_OK;
+    if (!users || !caps || !out_scores || !out_ids) return null_buffer(h, "m2d_plan_menus");
+    M2D_REQUIRE(enter(h, NEEDS_MASKS));
+    if (h->C > M2D_MENU_MAX_CATEGORIES)
+        return fail(h, M2D_ERR_UNSUPPORTED, "m2d_plan_menus: more than 6 categories (one signature per lane of a wave: C <= M2D_MENU_MAX_CATEGORIES)");
+    return m2d_launch_plan_menus(h, users, nU, days, k, caps, plan_caps, excl_off, excl_ids, slate, nD, out_scores, out_ids,
+                                 (hipStream_t)stream);
+}
+
 int m2d_topk_users_mlp_deep(m2d_engine *h, const int32_t *users, int64_t nU, int32_t k, int32_t candidates, const int64_t *excl_off,
                             const int32_t *excl_ids, float *out_scores, int32_t *out_ids, void *stream)
 {

@@ -640,6 +640,11 @@ int m2d_launch_topk_menu(m2d_engine *h, const int32_t *users, int64_t nU, int32_
 int m2d_launch_topk_menu_filtered(m2d_engine *h, const char *entry, const int32_t *users, int64_t nU, int32_t k, const int32_t *caps,
                                   const int64_t *excl_off, const int32_t *excl_ids, const int32_t *slate, int64_t nD, float *out_scores,
                                   int32_t *out_ids, hipStream_t stream);
+// m2d_plan_menus: the same loop with lists of days * k and m2d_plan_merge behind it (plan_caps null: no cap over the plan); the
+// outputs are [nU, days, k]
+int m2d_launch_plan_menus(m2d_engine *h, const int32_t *users, int64_t nU, int32_t days, int32_t k, const int32_t *caps,
+                          const int32_t *plan_caps, const int64_t *excl_off, const int32_t *excl_ids, const int32_t *slate, int64_t nD,
+                          float *out_scores, int32_t *out_ids, hipStream_t stream);
 // m2d_slate.hip: out == null: the scores of user blocks go to scratch and the lists of k to out_scores / out_ids
 int m2d_launch_slate(m2d_engine *h, const char *entry, const int32_t *users, int64_t nU, const int32_t *slate, int64_t nD, int32_t k,
                      float *out, float *out_scores, int32_t *out_ids, hipStream_t stream);

@@ -29,6 +29,11 @@
 // segment against it (SelectJob::xoff with ids; ExclCursor::strike_ids).  Slate: its own index (menu_slate_index: the three passes
 // over the slate, reading the resident signature bytes), ONE STREAM SYNCHRONISATION PER CALL WITH A SLATE for the 64 segment sizes.
 // One loop (menu_walk) serves both forms; with null filters it is m2d_topk_menu's launches.
+//
+// m2d_plan_menus: `days` menus with no dish twice, day caps and caps over the whole plan.  A walk takes a
+// signature's dishes as a prefix of its own order, so the days are one walk over lists of L = days k with cursors that persist:
+// menu_walk with lists of L (above 64: the radix selection) and m2d_plan_merge behind them; days == 1 without plan caps is
+// m2d_topk_menu_filtered's launches.
 #include "m2d_engine.h"
 
 namespace {
@@ -253,6 +258,135 @@ __global__ __launch_bounds__(256) void m2d_menu_merge(const MenuMergeArgs p)
     }
 }
 
+// ---- the plan merge (m2d_plan_menus) ---------------------------------------------------------------------
+// D days of the constrained merge in one wave per user, over lists of L = D k.  The walk takes a signature's dishes as a PREFIX of its
+// own order (a cursor moves only on a take), so day d + 1 over the order less the dishes of days 1 .. d is the same walk with the
+// cursors where day d left them and the day counters back at 0.  `full` = the categories at their day cap | those at their plan cap:
+// the first come back the next morning, the second never.  Lane t keeps the day's t-th entry; a day's row is stored once, k lanes
+// side by side, and every row of [days, k] is written (id -1 / the fill NaN where no step filled it).
+// The window: the menu merge makes one dependent 8-byte load by one lane per step; over up to 1 024 steps with few waves in flight
+// that latency is the kernel.  A lane therefore holds its next PM_WIN entries (key and score word) in registers, filled by PM_WIN
+// independent pairs of loads in one go; a take shifts the window (static indices: registers), and only an empty window loads
+// again.  Lists have row stride L, any alignment: the loads are dwords.  A list ends at an id below 0 or at L (key TKM_NONE: such
+// a lane is never taken from, so it never shifts).  No LDS, no atomics but the error latch.
+constexpr int PM_WIN = 8;
+
+struct PlanMergeArgs {
+    const float *list_scores;           // [S', Ub, L]
+    const int32_t *list_ids;
+    const int32_t *seg_off;             // [65]
+    const int32_t *caps;                // [n, C]: the block's rows, per day
+    const int32_t *plan_caps;           // [n, C]: the block's rows, over the plan; null: none
+    int64_t n, Ub, index_base, nU;      // nU: the call's rows (a plan cap's position is nU C + u C + c)
+    int32_t days, k, L, C;
+    float *out_scores;                  // [n, days, k]: the block's rows
+    int32_t *out_ids;
+    int32_t *err;
+};
+
+__global__ __launch_bounds__(256) void m2d_plan_merge(const PlanMergeArgs p)
+{
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
+    const int64_t r = (int64_t)blockIdx.x * 4 + wave;
+    if (r >= p.n) return;                       // wave-uniform
+    const int k = p.k, L = p.L;
+
+    const bool have = p.seg_off[lane + 1] > p.seg_off[lane];
+    const int j = __popcll(__ballot(have) & ((1ull << lane) - 1ull));
+
+    int32_t capv = 0, planv = 0x7FFFFFFF;
+    if (lane < p.C) {
+        capv = p.caps[(size_t)r * p.C + lane];
+        if (capv < 0) m2d_latch_error(p.err, M2D_ERR_INVALID_ARG, capv, (p.index_base + r) * p.C + lane);
+        if (p.plan_caps) {
+            planv = p.plan_caps[(size_t)r * p.C + lane];
+            if (planv < 0) m2d_latch_error(p.err, M2D_ERR_INVALID_ARG, planv, (p.nU + p.index_base + r) * p.C + lane);
+        }
+    }
+    int32_t cap[M2D_MENU_MAX_CATEGORIES], pcap[M2D_MENU_MAX_CATEGORIES], cnt[M2D_MENU_MAX_CATEGORIES], pcnt[M2D_MENU_MAX_CATEGORIES];
+#pragma unroll
+    for (int c = 0; c < M2D_MENU_MAX_CATEGORIES; ++c) {
+        cap[c] = __builtin_amdgcn_readlane(capv, c);
+        pcap[c] = __builtin_amdgcn_readlane(planv, c);      // no plan caps: INT32_MAX, which no count reaches
+        pcnt[c] = 0;
+    }
+
+    const size_t lrow = ((size_t)j * p.Ub + r) * L;
+    int next = 0, held = 0;                     // the list position behind the window; the window's entries not yet taken
+    uint64_t wkey[PM_WIN];
+    uint32_t wword[PM_WIN];
+    const auto refill = [&]() {                 // PM_WIN entries from `next` on: the loads do not depend on one another
+        int32_t id[PM_WIN];
+        float sc[PM_WIN];
+#pragma unroll
+        for (int i = 0; i < PM_WIN; ++i) {
+            const bool in = have && next + i < L;
+            id[i] = in ? p.list_ids[lrow + next + i] : -1;
+            sc[i] = in ? p.list_scores[lrow + next + i] : 0.0f;
+        }
+#pragma unroll
+        for (int i = 0; i < PM_WIN; ++i) {
+            wkey[i] = id[i] >= 0 ? tkm_key(sc[i], id[i]) : TKM_NONE;
+            wword[i] = __float_as_uint(sc[i]);
+        }
+        next += PM_WIN;
+        held = PM_WIN;
+    };
+    refill();
+
+    bool done = false;                          // a day took nothing: so will every day after it (wave-uniform)
+    for (int d = 0; d < p.days; ++d) {
+        unsigned full = 0;
+#pragma unroll
+        for (int c = 0; c < M2D_MENU_MAX_CATEGORIES; ++c) {
+            cnt[c] = 0;
+            if (c < p.C && (cap[c] <= 0 || pcnt[c] >= pcap[c])) full |= 1u << c;
+        }
+        int32_t oid = -1;
+        uint32_t ow = 0x7FC00000u;
+        int t = 0;
+        for (; t < k && !done; ++t) {           // wave-uniform: best, win and full are the same in every lane
+            const uint64_t key = wkey[0];
+            const bool adm = key != TKM_NONE && ((unsigned)lane & full) == 0u;
+            uint64_t best = adm ? key : TKM_NONE;
+#pragma unroll
+            for (int off = 32; off >= 1; off >>= 1) {
+                const uint64_t o = __shfl_xor((unsigned long long)best, off, 64);
+                best = o < best ? o : best;
+            }
+            if (best == TKM_NONE) break;
+            const int win = __ffsll((unsigned long long)__ballot(adm && key == best)) - 1;
+            const uint32_t bw = (uint32_t)__shfl((int)wword[0], win, 64);
+            if (lane == t) {
+                oid = (int32_t)(uint32_t)(best & 0xFFFFFFFFu);
+                ow = bw;
+            }
+#pragma unroll
+            for (int c = 0; c < M2D_MENU_MAX_CATEGORIES; ++c)
+                if ((win >> c) & 1) {
+                    cnt[c] += 1;
+                    pcnt[c] += 1;
+                    if (cnt[c] >= cap[c] || pcnt[c] >= pcap[c]) full |= 1u << c;
+                }
+            if (lane == win) {
+#pragma unroll
+                for (int i = 0; i + 1 < PM_WIN; ++i) {
+                    wkey[i] = wkey[i + 1];
+                    wword[i] = wword[i + 1];
+                }
+                wkey[PM_WIN - 1] = TKM_NONE;
+                if (--held == 0) refill();
+            }
+        }
+        if (t == 0) done = true;
+        if (lane < k) {
+            const size_t at = ((size_t)r * p.days + d) * k + lane;
+            p.out_ids[at] = oid;
+            p.out_scores[at] = __uint_as_float(ow);
+        }
+    }
+}
+
 // the signature index of the resident masks, built when they changed: perm | seg_off behind it, and seg_off's host copy
 int menu_ensure_index(m2d_engine *h, hipStream_t st)
 {
@@ -331,10 +465,14 @@ int menu_slate_index(m2d_engine *h, const int32_t *slate, const int64_t nD, int3
 // One loop for both forms: per block of Ub users and non-empty segment of `ix`, ranges of W dishes -- vectors, scores, selection into
 // the segment's lists (excl_off: each row's exclusion segment is struck on the range's ascending ids; a later range merges into the
 // list of the ranges before it, whose entries were struck when they were listed) -- then the merge under the caps.
-int menu_walk(m2d_engine *h, const MenuIndex &ix, const int32_t *users, int64_t nU, int32_t k, const int32_t *caps, const int64_t *excl_off,
-              const int32_t *excl_ids, float *out_scores, int32_t *out_ids, hipStream_t st)
+// m2d_plan_menus: the lists are L = days k long (above 64 the selection is the radix form whatever the option says) and the merge is
+// m2d_plan_merge into [nU, days, k]; with days == 1 and no plan caps L = k and every launch is the menu call's.
+int menu_walk(m2d_engine *h, const MenuIndex &ix, const int32_t *users, int64_t nU, int32_t days, int32_t k, const int32_t *caps,
+              const int32_t *plan_caps, const int64_t *excl_off, const int32_t *excl_ids, float *out_scores, int32_t *out_ids, hipStream_t st)
 {
     int rc;
+    const int32_t L = days * k;
+    const bool plan = days != 1 || plan_caps;
     const int64_t P = h->opt_deep_chunk_pairs;
     const auto range_of = [&](const int64_t n_s) {
         const int64_t W0 = n_s < P ? n_s : P;
@@ -347,12 +485,12 @@ int menu_walk(m2d_engine *h, const MenuIndex &ix, const int32_t *users, int64_t 
         ++S;
         if (range_of(n_s) > Wmax) Wmax = range_of(n_s);
     }
-    // user blocks: score scratch [Ub, W] and list scratch [S', Ub, k] both within P words
-    const int64_t Ub = m2d_block_rows(P, Wmax > S * k ? Wmax : S * k, nU);
+    // user blocks: score scratch [Ub, W] and list scratch [S', Ub, L] both within P words
+    const int64_t Ub = m2d_block_rows(P, Wmax > S * L ? Wmax : S * L, nU);
     if ((rc = h->slate_scores.grow(h, (size_t)Ub * Wmax)) != M2D_OK) return rc;
-    if ((rc = h->menu_list_scores.grow(h, (size_t)S * Ub * k)) != M2D_OK) return rc;
-    if ((rc = h->menu_list_ids.grow(h, (size_t)S * Ub * k)) != M2D_OK) return rc;
-    const bool deep = h->opt_menu_select != 0;
+    if ((rc = h->menu_list_scores.grow(h, (size_t)S * Ub * L)) != M2D_OK) return rc;
+    if ((rc = h->menu_list_ids.grow(h, (size_t)S * Ub * L)) != M2D_OK) return rc;
+    const bool deep = L > 64 || h->opt_menu_select != 0;
 
     for (int64_t u0 = 0; u0 < nU; u0 += Ub) {
         const int64_t n = nU - u0 < Ub ? nU - u0 : Ub;
@@ -371,9 +509,9 @@ int menu_walk(m2d_engine *h, const MenuIndex &ix, const int32_t *users, int64_t 
                 if ((rc = m2d_launch_slate_scores(h, a, mfma, st)) != M2D_OK) return rc;
                 SelectJob job = SelectJob::row_major(h->slate_scores, n, Wc, ids, 0);
                 job.first = r0 == 0 ? 1 : 0;
-                job.k = k;
-                job.out_scores = h->menu_list_scores + (size_t)j * Ub * k;
-                job.out_ids = h->menu_list_ids + (size_t)j * Ub * k;
+                job.k = L;
+                job.out_scores = h->menu_list_scores + (size_t)j * Ub * L;
+                job.out_ids = h->menu_list_ids + (size_t)j * Ub * L;
                 if (excl_off) {
                     job.xoff = excl_off + u0; job.xids = excl_ids; job.xend = excl_off + nU;
                 }
@@ -381,22 +519,30 @@ int menu_walk(m2d_engine *h, const MenuIndex &ix, const int32_t *users, int64_t 
             }
             ++j;
         }
-        MenuMergeArgs m;
-        m.list_scores = h->menu_list_scores; m.list_ids = h->menu_list_ids; m.seg_off = ix.seg_off;
-        m.caps = caps + (size_t)u0 * h->C; m.n = n; m.Ub = Ub; m.index_base = u0; m.k = k; m.C = h->C;
-        m.out_scores = out_scores + (size_t)u0 * k; m.out_ids = out_ids + (size_t)u0 * k; m.err = h->err_dev;
-        hipLaunchKernelGGL(m2d_menu_merge, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, st, m);
+        if (plan) {
+            PlanMergeArgs m;
+            m.list_scores = h->menu_list_scores; m.list_ids = h->menu_list_ids; m.seg_off = ix.seg_off;
+            m.caps = caps + (size_t)u0 * h->C; m.plan_caps = plan_caps ? plan_caps + (size_t)u0 * h->C : nullptr;
+            m.n = n; m.Ub = Ub; m.index_base = u0; m.nU = nU; m.days = days; m.k = k; m.L = L; m.C = h->C;
+            m.out_scores = out_scores + (size_t)u0 * L; m.out_ids = out_ids + (size_t)u0 * L; m.err = h->err_dev;
+            hipLaunchKernelGGL(m2d_plan_merge, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, st, m);
+        } else {
+            MenuMergeArgs m;
+            m.list_scores = h->menu_list_scores; m.list_ids = h->menu_list_ids; m.seg_off = ix.seg_off;
+            m.caps = caps + (size_t)u0 * h->C; m.n = n; m.Ub = Ub; m.index_base = u0; m.k = k; m.C = h->C;
+            m.out_scores = out_scores + (size_t)u0 * k; m.out_ids = out_ids + (size_t)u0 * k; m.err = h->err_dev;
+            hipLaunchKernelGGL(m2d_menu_merge, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, st, m);
+        }
         M2D_HIP_TRY(h, hipGetLastError());
     }
-    h->last_kernel = "m2d_menu_merge";
+    h->last_kernel = plan ? "m2d_plan_merge" : "m2d_menu_merge";
     return M2D_OK;
 }
 
-}  // namespace
-
-int m2d_launch_topk_menu_filtered(m2d_engine *h, const char *entry, const int32_t *users, int64_t nU, int32_t k, const int32_t *caps,
-                                  const int64_t *excl_off, const int32_t *excl_ids, const int32_t *slate, int64_t nD, float *out_scores,
-                                  int32_t *out_ids, hipStream_t st)
+// what every entry does in front of the loop: the table conditions, the catalogue's index, the callers' lists, the slate's index
+int menu_call(m2d_engine *h, const char *entry, const int32_t *users, int64_t nU, int32_t days, int32_t k, const int32_t *caps,
+              const int32_t *plan_caps, const int64_t *excl_off, const int32_t *excl_ids, const int32_t *slate, int64_t nD, float *out_scores,
+              int32_t *out_ids, hipStream_t st)
 {
     int rc;
     if ((rc = m2d_deep_conditions(h, entry, st)) != M2D_OK) return rc;
@@ -409,7 +555,23 @@ int m2d_launch_topk_menu_filtered(m2d_engine *h, const char *entry, const int32_
         if ((rc = menu_slate_index(h, slate, nD, seg, st)) != M2D_OK) return rc;
         ix = MenuIndex{h->menu_slate_perm, h->menu_slate_perm + nD, seg};
     }
-    return menu_walk(h, ix, users, nU, k, caps, excl_off, excl_ids, out_scores, out_ids, st);
+    return menu_walk(h, ix, users, nU, days, k, caps, plan_caps, excl_off, excl_ids, out_scores, out_ids, st);
+}
+
+}  // namespace
+
+int m2d_launch_topk_menu_filtered(m2d_engine *h, const char *entry, const int32_t *users, int64_t nU, int32_t k, const int32_t *caps,
+                                  const int64_t *excl_off, const int32_t *excl_ids, const int32_t *slate, int64_t nD, float *out_scores,
+                                  int32_t *out_ids, hipStream_t st)
+{
+    return menu_call(h, entry, users, nU, 1, k, caps, nullptr, excl_off, excl_ids, slate, nD, out_scores, out_ids, st);
+}
+
+int m2d_launch_plan_menus(m2d_engine *h, const int32_t *users, int64_t nU, int32_t days, int32_t k, const int32_t *caps,
+                          const int32_t *plan_caps, const int64_t *excl_off, const int32_t *excl_ids, const int32_t *slate, int64_t nD,
+                          float *out_scores, int32_t *out_ids, hipStream_t st)
+{
+    return menu_call(h, "m2d_plan_menus", users, nU, days, k, caps, plan_caps, excl_off, excl_ids, slate, nD, out_scores, out_ids, st);
 }
 
 int m2d_launch_topk_menu(m2d_engine *h, const int32_t *users, int64_t nU, int32_t k, const int32_t *caps, float *out_scores,

@@ -616,6 +616,57 @@ class ScoringEngine:
         self._menu_filtered_keep = (users, caps, off, ids, slate)      # stay alive until the queued kernels have read them
         return out_s, out_i
 
+    def _plan_menus(self, users: torch.Tensor, days: int, k: int, caps: torch.Tensor, plan_caps=None, exclude=None, among=None):
+        """What ``torch.ops.m2d.plan_menus`` and ``Model.plan_menus`` call (not a public method, for ``_topk_menu``'s reason; its
+        stream-order case is in tests/test_gpu_plan.py).  EXTENSION, build-defined (``m2d_plan_menus``, include/m2d.h; DESIGN.md section
+        4.15): ``days`` menus of k dishes per user, no dish twice -- day d is ``_topk_menu_filtered`` with the dishes of the earlier
+        days left out, under ``caps`` per day and ``plan_caps`` over the whole plan (both int32 device tensors [nU, C] or [C];
+        ``plan_caps`` None: none) -> (scores f32[nU, days, k], dish ids i32[nU, days, k]), one scoring pass.  1 <= k <= 64, days >= 1,
+        days * k <= 1024.  ``exclude`` / ``among`` and the synchronisation: as ``_topk_menu_filtered``."""
+        what = "plan_menus"
+        if users.dtype != torch.int32 or users.device != self.device:
+            raise TypeError("%s: users must be an int32 tensor on %s" % (what, self.device))
+        if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or not 1 <= int(k) <= 64:
+            raise ValueError("%s: 1 <= k <= 64, got %r" % (what, k))
+        if isinstance(days, bool) or not isinstance(days, (int, np.integer)) or int(days) < 1 or int(days) * int(k) > 1024:
+            raise ValueError("%s: days >= 1 and days * k <= 1024, got days = %r, k = %r" % (what, days, k))
+        users = users.contiguous().reshape(-1)
+        nU, k, days = users.numel(), int(k), int(days)
+
+        def table(t, name):
+            if not isinstance(t, torch.Tensor) or t.dtype != torch.int32 or t.device != self.device:
+                raise TypeError("%s: %s must be an int32 tensor on %s" % (what, name, self.device))
+            if t.dim() == 1 and t.shape[0] == self.C:
+                t = t.reshape(1, self.C).expand(nU, self.C)
+            if t.dim() != 2 or tuple(t.shape) != (nU, self.C):
+                raise ValueError("%s: %s must be [%d, %d] or [%d], got %s" % (what, name, nU, self.C, self.C, tuple(t.shape)))
+            return t.contiguous()
+
+        caps = table(caps, "caps")
+        plan = table(plan_caps, "plan_caps") if plan_caps is not None else None
+        off = ids = None
+        if exclude is not None:
+            off, ids = exclusions_on_device(exclude, nU, self.device, what)
+        slate, nD = None, 0
+        if among is not None:
+            if not isinstance(among, torch.Tensor) or among.dtype != torch.int32 or among.device != self.device:
+                raise TypeError("%s: among must be an int32 tensor on %s" % (what, self.device))
+            slate = among.contiguous().reshape(-1)
+            nD = slate.numel()
+            if nD < 1:
+                raise ValueError("%s: among must hold at least one dish" % what)
+        out_s = torch.empty((nU, days, k), dtype=torch.float32, device=self.device)
+        out_i = torch.empty((nU, days, k), dtype=torch.int32, device=self.device)
+        xo, xi = (off.data_ptr(), ids.data_ptr()) if off is not None else (None, None)
+        with torch.cuda.device(self.device):
+            rc = _native.lib().m2d_plan_menus(self._h, users.data_ptr(), nU, days, k, caps.data_ptr(),
+                                              plan.data_ptr() if plan is not None else None, xo, xi,
+                                              slate.data_ptr() if slate is not None else None, nD, out_s.data_ptr(), out_i.data_ptr(),
+                                              _stream_ptr())
+        _native.raise_for(rc, self._h)
+        self._plan_keep = (users, caps, plan, off, ids, slate)         # stay alive until the queued kernels have read them
+        return out_s, out_i
+
     def _slate_ids(self, users: torch.Tensor, slate: torch.Tensor, what: str):
         for t, name in ((users, "users"), (slate, "slate")):
             if not isinstance(t, torch.Tensor) or t.dtype != torch.int32 or t.device != self.device:
@@ -1193,6 +1244,23 @@ def topk_menu_filtered_op(engine: int, users: torch.Tensor, caps: torch.Tensor, 
 @topk_menu_filtered_op.register_fake
 def _(engine, users, caps, k, excl_off=None, excl_ids=None, among=None):
     return _deep_fake(users, k)
+
+
+@torch.library.custom_op("m2d::plan_menus", mutates_args=(), device_types="cuda")
+def plan_menus_op(engine: int, users: torch.Tensor, caps: torch.Tensor, days: int, k: int, plan_caps: Optional[torch.Tensor] = None,
+                  excl_off: Optional[torch.Tensor] = None, excl_ids: Optional[torch.Tensor] = None,
+                  among: Optional[torch.Tensor] = None) -> tuple[torch.Tensor, torch.Tensor]:
+    """EXTENSION, build-defined (``m2d_plan_menus``, include/m2d.h): `days` menus of k dishes per user with no
+    dish twice, `caps` per day and `plan_caps` over the plan (None: none); `excl_off` / `excl_ids` / `among` as
+    ``topk_menu_filtered`` -> (scores f32[nU, days, k], dish ids i32[nU, days, k])."""
+    s, i = _engine(engine)._plan_menus(users, days, k, caps, plan_caps, _excl_pair(excl_off, excl_ids), among)
+    return s, i
+
+
+@plan_menus_op.register_fake
+def _(engine, users, caps, days, k, plan_caps=None, excl_off=None, excl_ids=None, among=None):
+    return (users.new_empty((users.numel(), days, k), dtype=torch.float32),
+            users.new_empty((users.numel(), days, k), dtype=torch.int32))
 
 
 @torch.library.custom_op("m2d::topk_users_mlp_deep", mutates_args=(), device_types="cuda")

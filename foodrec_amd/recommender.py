@@ -661,6 +661,46 @@ class Model:
         self.engine.check()
         return s.cpu().numpy(), i.cpu().numpy()
 
+    def plan_menus(self, users, days: int = 7, k: int = 3, caps=None, plan_caps=None, exclude=None, among=None, market=None,
+                   max_missing: int = 0):
+        """EXTENSION, build-defined (no reference counterpart): a MEAL PLAN per user -- `days` menus of k dishes,
+        no dish twice: day d is `topk_menu_filtered` with the dishes of the earlier days left out.  `caps` (as in `topk_menu`) hold on
+        every day; `plan_caps` (the same forms, missing categories bounded by days * k) hold over the whole plan -- "fish at most twice
+        this week" is ``plan_caps={fish: 2}``; None: no plan cap.  `exclude` / `among` / `market` / `max_missing` as in
+        `topk_menu_filtered`.  1 <= k <= 64, days >= 1, days * k <= 1024.  A day's row ends in id -1 / NaN where it cannot take k dishes
+        -- all of them when the slate is empty (the engine is not called).  Returns numpy (scores float32 [n, days, k], dish ids int32
+        [n, days, k]).  (``torch.ops.m2d.plan_menus``.)"""
+        if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or not 1 <= int(k) <= 64:
+            raise ValueError("plan_menus: 1 <= k <= 64, got %r" % (k,))
+        if isinstance(days, bool) or not isinstance(days, (int, np.integer)) or int(days) < 1 or int(days) * int(k) > 1024:
+            raise ValueError("plan_menus: days >= 1 and days * k <= 1024, got days = %r, k = %r" % (days, k))
+        k, days = int(k), int(days)
+        if among is not None and market is not None:
+            raise ValueError("plan_menus: among together with market is not supported")
+        u = _ids(users, "user")
+        ut = u.to(self.device, torch.int32) if isinstance(u, torch.Tensor) else torch.from_numpy(u).to(self.device)
+        n = int(ut.numel())
+        table = self._menu_caps(caps, k, n, "plan_menus")
+        plan = None if plan_caps is None else self._menu_caps(plan_caps, days * k, n, "plan_menus")
+        off = ids = None
+        if exclude is not None:
+            from .ops import exclusions_on_device
+            had = [_ids(x, "item") for x in _exclusion_lists(exclude, users, "plan_menus")]
+            had = [x.cpu().numpy() if isinstance(x, torch.Tensor) else x for x in had]
+            off, ids = exclusions_on_device(had, n, self.device, "plan_menus")      # sorted and de-duplicated per user
+        slate = None
+        if market is not None:
+            slate = np.asarray(self.cookable(market, max_missing), dtype=np.int32)
+        elif among is not None:
+            d = _ids(among, "item")
+            slate = np.unique(np.asarray(d.cpu().numpy() if isinstance(d, torch.Tensor) else d, dtype=np.int32).reshape(-1))
+        if slate is not None and slate.size == 0:
+            return np.full((n, days, k), np.nan, dtype=np.float32), np.full((n, days, k), -1, dtype=np.int32)
+        st = None if slate is None else torch.from_numpy(slate).to(self.device)
+        s, i = torch.ops.m2d.plan_menus(self.engine.id, ut, table, days, k, plan, off, ids, st)
+        self.engine.check()
+        return s.cpu().numpy(), i.cpu().numpy()
+
     def topk_group(self, groups, k: int = 10, mode: str = "least", exclude=None, among=None, market=None, max_missing: int = 0):
         """EXTENSION, build-defined (no reference counterpart): ONE list of k dishes per household -- `groups` a
         list of lists of user ids (str or int, at most 64 each, repeats count twice in the mean).  `mode`: "least" (least misery: a

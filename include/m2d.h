@@ -584,6 +584,40 @@ int m2d_topk_menu_filtered(m2d_engine *h, const int32_t *users /* device [nU] */
                            const int32_t *slate /* [nD] strictly ascending, or NULL: the whole catalogue */, int64_t nD,
                            float *out_scores /* [nU, k] */, int32_t *out_ids /* [nU, k] */, void *stream);
 
+/* ---- build-defined extension, NO reference counterpart ----
+ * Meal plans: `days` menus of k dishes per user with no dish twice, every day under caps[u][c] and the whole plan under plan_caps[u][c]
+ * dishes of category c -- in one call, with one scoring pass.
+ *
+ * Definition.  Day 1 is m2d_topk_menu_filtered's row.  Day d is that call with the dishes of days 1 .. d - 1 added to user u's
+ * exclusions and with the caps min(caps[u][c], plan_caps[u][c] - the dishes of category c listed on earlier days), floored at 0.
+ * out_ids i32[nU, days, k] / out_scores f32[nU, days, k]: each row of [days, k] ends in id -1 / the fill NaN where the day cannot take
+ * k dishes, and every row is written.  A day that takes nothing is followed by days that take nothing.
+ *
+ * Arguments.  1 <= k <= min(64, I); days >= 1; days * k <= M2D_PLAN_MAX_LIST = 1024 (days * k may exceed I or nD).  caps i32[nU, C] per
+ * day; plan_caps i32[nU, C] over the plan, or NULL: none.  users, excl_off / excl_ids, slate / nD: as m2d_topk_menu_filtered, and so
+ * are the refusals, the list checks, the slate check and bad users, under this call's name.  days or days * k out of range:
+ * M2D_ERR_INVALID_ARG.
+ * Diagnostics.  A cap below 0: M2D_ERR_INVALID_ARG with the cap and position u * C + c; a plan cap below 0: the same with position
+ * nU * C + u * C + c (the two tables as one array, caps first).  Either counts as 0.
+ * The words are m2d_score_slate's; the rows do not depend on options "deep_chunk_pairs" and "menu_select", on nU or on the row's
+ * position.  With days == 1 and plan_caps == NULL the call IS m2d_topk_menu_filtered: the same launches, the same words.
+ * How.  m2d_menu_merge moves a signature's cursor only when it takes the entry under it, so whatever the caps do the dishes a walk takes
+ * from a signature are a PREFIX of that signature's own order.  Day d + 1 over the order less what days 1 .. d took is therefore the
+ * same walk with the cursors where day d left them and the day counts back at 0; a plan takes at most days * k dishes, so it never
+ * reaches past a signature's first L = days * k allowed dishes.  The launcher is m2d_topk_menu_filtered's with lists of L (list
+ * scratch [segments, users of a block, L]; user blocks of max(1, P / max(W, segments * L)) rows; above L = 64 the selection is
+ * m2d_select_deep whatever "menu_select" says), and m2d_plan_merge -- one wave per user, lane s holding signature s's cursor and a
+ * window of its next 8 entries in registers, refilled by independent loads -- runs the days: `full` is the categories at their day
+ * cap (back the next morning) or at their plan cap (never back).  One scoring pass instead of `days`.
+ * Not offered: per-day cap tables, minimum quotas, the MLP head, sharding, k above 64, C above 6, households. */
+#define M2D_PLAN_MAX_LIST 1024
+int m2d_plan_menus(m2d_engine *h, const int32_t *users /* device [nU] */, int64_t nU, int32_t days, int32_t k,
+                   const int32_t *caps /* device [nU, C]: per day */,
+                   const int32_t *plan_caps /* device [nU, C] or NULL: over the whole plan */,
+                   const int64_t *excl_off /* [nU + 1] or NULL */, const int32_t *excl_ids,
+                   const int32_t *slate /* [nD] strictly ascending, or NULL: the whole catalogue */, int64_t nD,
+                   float *out_scores /* [nU, days, k] */, int32_t *out_ids /* [nU, days, k] */, void *stream);
+
 /* Diagnostic (scripts/deep_time.py): one selection launch over a resident row-major score block f32[rows, W], ids 0 .. W - 1, no
  * exclusions, into out_scores / out_ids [rows, k] -- form 0: m2d_select_deep (k <= 1024), form 1: m2d_topk_mlp_select (k <= 64).
  * Reads no table.  Bad arguments: M2D_ERR_INVALID_ARG. */
