@@ -70,6 +70,7 @@ SIGNATURES = {
     "m2d_topk_menu": (_c.c_int, [_vp, _vp, _i64, _i32, _vp, _vp, _vp, _vp]),
     "m2d_topk_menu_filtered": (_c.c_int, [_vp, _vp, _i64, _i32, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp]),
     "m2d_plan_menus": (_c.c_int, [_vp, _vp, _i64, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp]),
+    "m2d_plan_groups": (_c.c_int, [_vp, _vp, _i64, _i32, _i32, _i32, _i32, _vp, _vp, _i32, _vp, _vp, _vp, _i64, _vp, _vp, _vp]),
     "m2d_topk_users_mlp_deep": (_c.c_int, [_vp, _vp, _i64, _i32, _i32, _vp, _vp, _vp, _vp, _vp]),
     "m2d_select_probe": (_c.c_int, [_vp, _vp, _i64, _i64, _i32, _i32, _vp, _vp, _vp]),
     "m2d_set_recipes": (_c.c_int, [_vp, _i64, _vp, _vp, _i64, _i32]),

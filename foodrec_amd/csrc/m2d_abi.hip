@@ -884,6 +884,27 @@ int m2d_plan_menus(m2d_engine *h, const int32_t *users, int64_t nU, int32_t days
                                  (hipStream_t)stream);
 }
 
+int m2d_plan_groups(m2d_engine *h, const int32_t *members, int64_t nG, int32_t M, int32_t mode, int32_t days, int32_t k, const int32_t *caps,
+                    const int32_t *plan_caps, int32_t caps_per_member, const int64_t *excl_off, const int32_t *excl_ids, const int32_t *slate,
+                    int64_t nD, float *out_scores, int32_t *out_ids, void *stream)
+{
+    if (!h) return M2D_ERR_INVALID_ARG;
+    if (const char *why = group_args_wrong(nG, M, mode)) return fail(h, M2D_ERR_INVALID_ARG, std::string("m2d_plan_groups: ") + why);
+    if (k < 1 || k > 64 || (int64_t)k > h->I) return fail(h, M2D_ERR_INVALID_ARG, "m2d_plan_groups: need 1 <= k <= min(64, I)");
+    if (days < 1 || (int64_t)days * k > M2D_PLAN_MAX_LIST)
+        return fail(h, M2D_ERR_INVALID_ARG, "m2d_plan_groups: need days >= 1 and days * k <= M2D_PLAN_MAX_LIST = 1024");
+    if (caps_per_member != 0 && caps_per_member != 1) return fail(h, M2D_ERR_INVALID_ARG, "m2d_plan_groups: caps_per_member must be 0 or 1");
+    if (slate && (nD < 1 || nD > h->I)) return fail(h, M2D_ERR_INVALID_ARG, "m2d_plan_groups: with a slate need 1 <= nD <= I");
+    if (excl_off && !excl_ids) return fail(h, M2D_ERR_INVALID_ARG, "m2d_plan_groups: excl_off without excl_ids");
+    if (nG == 0) return M2D_OK;
+    if (!members || !caps || !out_scores || !out_ids) return null_buffer(h, "m2d_plan_groups");
+    M2D_REQUIRE(enter(h, NEEDS_MASKS));
+    if (h->C > M2D_MENU_MAX_CATEGORIES)
+        return fail(h, M2D_ERR_UNSUPPORTED, "m2d_plan_groups: more than 6 categories (one signature per lane of a wave: C <= M2D_MENU_MAX_CATEGORIES)");
+    return m2d_launch_plan_groups(h, members, nG, M, mode, days, k, caps, plan_caps, caps_per_member == 1, excl_off, excl_ids, slate, nD,
+                                  out_scores, out_ids, (hipStream_t)stream);
+}
+
 int m2d_topk_users_mlp_deep(m2d_engine *h, const int32_t *users, int64_t nU, int32_t k, int32_t candidates, const int64_t *excl_off,
                             const int32_t *excl_ids, float *out_scores, int32_t *out_ids, void *stream)
 {

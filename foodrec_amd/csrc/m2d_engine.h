@@ -172,8 +172,8 @@ struct m2d_engine {
     int64_t opt_slate_chunk_pairs = 1 << 22;         // pairs of score scratch per m2d_topk_slate pass (the lists do not depend on it)
     int64_t opt_deep_chunk_pairs = 1 << 22;          // the same for m2d_topk_users_deep: ranges of min(I, P, 65536) dishes, blocks of P / W users
 
-    // m2d_topk_groups / m2d_*_groups_slate (m2d_groups.hip): the call's dense member array i32[nG * M] (valid ids only) | cnt i32[nG];
-    // the members' score rows go to slate_scores above
+    // m2d_topk_groups / m2d_*_groups_slate (m2d_groups.hip): the call's dense member array i32[nG * M] (valid ids only) | cnt i32[nG]
+    // (m2d_plan_groups: | the folded caps i32[nG, C] | the folded plan caps i32[nG, C]); the members' score rows go to slate_scores above
     m2d_dev_buf<int32_t> group_ids;
 
     // m2d_topk_menu (m2d_menu.hip): the signature index of the dish masks -- perm i32[I], the dish ids by (signature, id) | seg_off
@@ -632,6 +632,15 @@ int m2d_launch_slate_scores(m2d_engine *h, SlateArgs &a, bool mfma, hipStream_t 
 int m2d_launch_groups(m2d_engine *h, const char *entry, const int32_t *members, int64_t nG, int32_t M, int32_t mode, const int32_t *slate,
                       int64_t nD, int32_t k, const int64_t *excl_off, const int32_t *excl_ids, float *out, float *out_scores,
                       int32_t *out_ids, hipStream_t stream);
+// m2d_groups.hip, for m2d_plan_groups' walk (m2d_menu.hip).  m2d_launch_group_prepare: the member check and, with member_caps, the cap
+// fold (m2d_group_caps) -- *dense i32[nG M] valid ids, *cnt i32[nG], *group_caps / *group_plan_caps i32[nG, C] (written only with
+// member_caps; the latter null without member_plan_caps).  m2d_launch_group_reduce: groups' first cnt rows of src [groups, M, W] folded
+// into dst + g dst_rs under `mode`
+int m2d_launch_group_prepare(m2d_engine *h, const int32_t *members, int64_t nG, int32_t M, const int32_t *member_caps,
+                             const int32_t *member_plan_caps, const int32_t **dense, const int32_t **cnt, const int32_t **group_caps,
+                             const int32_t **group_plan_caps, hipStream_t stream);
+int m2d_launch_group_reduce(m2d_engine *h, int mode, const float *src, const int32_t *cnt, int64_t groups, int M, int64_t W, float *dst,
+                            int64_t dst_rs, hipStream_t stream);
 // m2d_menu.hip: m2d_topk_menu behind the ABI layer's argument checks -- caps i32[nU, C], C <= M2D_MENU_MAX_CATEGORIES
 int m2d_launch_topk_menu(m2d_engine *h, const int32_t *users, int64_t nU, int32_t k, const int32_t *caps, float *out_scores,
                          int32_t *out_ids, hipStream_t stream);
@@ -645,6 +654,11 @@ int m2d_launch_topk_menu_filtered(m2d_engine *h, const char *entry, const int32_
 int m2d_launch_plan_menus(m2d_engine *h, const int32_t *users, int64_t nU, int32_t days, int32_t k, const int32_t *caps,
                           const int32_t *plan_caps, const int64_t *excl_off, const int32_t *excl_ids, const int32_t *slate, int64_t nD,
                           float *out_scores, int32_t *out_ids, hipStream_t stream);
+// m2d_plan_groups: the same loop with a group of M member slots per row -- the members' rows scored, reduced under `mode` into the
+// group's row 0 and listed from there; caps_per_member: both cap tables are [nG, M, C] and are folded first; the outputs are [nG, days, k]
+int m2d_launch_plan_groups(m2d_engine *h, const int32_t *members, int64_t nG, int32_t M, int32_t mode, int32_t days, int32_t k,
+                           const int32_t *caps, const int32_t *plan_caps, bool caps_per_member, const int64_t *excl_off,
+                           const int32_t *excl_ids, const int32_t *slate, int64_t nD, float *out_scores, int32_t *out_ids, hipStream_t stream);
 // m2d_slate.hip: out == null: the scores of user blocks go to scratch and the lists of k to out_scores / out_ids
 int m2d_launch_slate(m2d_engine *h, const char *entry, const int32_t *users, int64_t nU, const int32_t *slate, int64_t nD, int32_t k,
                      float *out, float *out_scores, int32_t *out_ids, hipStream_t stream);

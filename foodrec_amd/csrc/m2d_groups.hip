@@ -17,6 +17,11 @@
 //                       included: their cost grows with the padding, compaction is not part of this file -- into scratch [Gb M, W];
 //   m2d_group_reduce    folds each group's first cnt[g] rows into its row 0 (or into the caller's matrix), after which
 //                       m2d_select_deep lists row 0 of every group: a SelectJob with row stride M W.
+//
+// m2d_plan_groups (the walk is m2d_menu.hip's) takes the first and the third step from here
+// (m2d_launch_group_prepare, m2d_launch_group_reduce) and one kernel more:
+//   m2d_group_caps      once per call, right behind m2d_group_members: folds the members' cap rows i32[nG, M, C] into one row per group,
+//                       the minimum over the group's first cnt[g] members of max(cap, 0); a cap below 0 is latched with its position.
 #include "m2d_engine.h"
 
 #pragma clang fp contract(off)
@@ -66,6 +71,43 @@ __global__ __launch_bounds__(256) void m2d_group_members(const int32_t *members,
         while (c < M && row[c] >= 0) ++c;
         cnt[g] = c;
     }
+}
+
+// One thread per (group g, category c), both tables in one walk of the group's first cnt[g] slots -- a filler slot's row is never
+// read.  A cap below 0 of a real member: M2D_ERR_INVALID_ARG with the cap and its position (g M + j) C + c in `caps`, nG M C further
+// on in `plan_caps` (the two tables as one array, caps first); it counts as 0.  What is written is >= 0, so the merge that reads the
+// folded tables latches nothing.  cnt[g] = 0 (a latched call) leaves INT32_MAX: unspecified, in bounds.
+// The split: the tables are nG M C words -- 65 536 groups of 4 at C = 6 are 6 MB for both, read once, against a scoring pass of
+// nG M I products behind it.  A thread's loads are C words apart from its neighbour's within a group and M C words between groups, so
+// a wave's loads of one step fall into 64 / C groups' rows; nothing here is worth a wave per group (6 of 64 lanes live) or LDS.
+__global__ __launch_bounds__(256) void m2d_group_caps(const int32_t *caps, const int32_t *plan_caps, const int32_t *cnt, const int64_t nG,
+                                                      const int M, const int C, int32_t *gcaps, int32_t *gplan, int32_t *err)
+{
+    const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (t >= nG * C) return;
+    const int64_t g = t / C;
+    const int c = (int)(t - g * C);
+    const int n = cnt[g] < M ? cnt[g] : M;
+    int32_t lo = 0x7FFFFFFF, plo = 0x7FFFFFFF;
+    for (int j = 0; j < n; ++j) {
+        const int64_t at = ((int64_t)g * M + j) * C + c;
+        int32_t v = caps[at];
+        if (v < 0) {
+            m2d_latch_error(err, M2D_ERR_INVALID_ARG, v, at);
+            v = 0;
+        }
+        lo = v < lo ? v : lo;
+        if (plan_caps) {
+            int32_t w = plan_caps[at];
+            if (w < 0) {
+                m2d_latch_error(err, M2D_ERR_INVALID_ARG, w, nG * M * C + at);
+                w = 0;
+            }
+            plo = w < plo ? w : plo;
+        }
+    }
+    gcaps[t] = lo;
+    if (plan_caps) gplan[t] = plo;
 }
 
 struct GroupReduceArgs {
@@ -147,6 +189,8 @@ __global__ __launch_bounds__(256) void m2d_group_reduce(const GroupReduceArgs p)
     }
 }
 
+}  // namespace
+
 int m2d_launch_group_reduce(m2d_engine *h, const int mode, const float *src, const int32_t *cnt, const int64_t groups, const int M,
                             const int64_t W, float *dst, const int64_t dst_rs, hipStream_t st)
 {
@@ -167,7 +211,30 @@ int m2d_launch_group_reduce(m2d_engine *h, const int mode, const float *src, con
     return M2D_OK;
 }
 
-}  // namespace
+// What m2d_plan_groups runs in front of its walk: m2d_group_members, first in stream order, and -- member_caps != null -- m2d_group_caps
+// right behind it.  group_ids: dense i32[nG M] | cnt i32[nG] | folded caps i32[nG, C] | folded plan caps i32[nG, C].
+int m2d_launch_group_prepare(m2d_engine *h, const int32_t *members, const int64_t nG, const int32_t M, const int32_t *member_caps,
+                             const int32_t *member_plan_caps, const int32_t **dense, const int32_t **cnt, const int32_t **group_caps,
+                             const int32_t **group_plan_caps, hipStream_t st)
+{
+    int rc;
+    const int64_t slots = nG * M, table = nG * h->C;
+    if ((rc = h->group_ids.grow(h, (size_t)(slots + nG + 2 * table))) != M2D_OK) return rc;
+    int32_t *d = h->group_ids, *n = d + slots, *gc = n + nG, *gp = gc + table;
+    hipLaunchKernelGGL(m2d_group_members, dim3((unsigned)((slots + 255) / 256)), dim3(256), 0, st, members, nG, M, h->U, h->user_base, d, n,
+                       h->err_dev);
+    M2D_HIP_TRY(h, hipGetLastError());
+    *dense = d;
+    *cnt = n;
+    if (member_caps) {
+        hipLaunchKernelGGL(m2d_group_caps, dim3((unsigned)((table + 255) / 256)), dim3(256), 0, st, member_caps, member_plan_caps, n, nG, M,
+                           h->C, gc, gp, h->err_dev);
+        M2D_HIP_TRY(h, hipGetLastError());
+        *group_caps = gc;
+        *group_plan_caps = member_plan_caps ? gp : nullptr;
+    }
+    return M2D_OK;
+}
 
 // Blocks of Gb = max(1, P / (M W)) whole groups, P = option "deep_chunk_pairs"; catalogue form (slate == null): dish ranges of
 // W = min(I, P, 65536) dishes, the first range starts a row's list and the others merge into it (m2d_launch_deep_lists' rule); slate

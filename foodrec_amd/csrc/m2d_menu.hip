@@ -34,6 +34,11 @@
 // signature's dishes as a prefix of its own order, so the days are one walk over lists of L = days k with cursors that persist:
 // menu_walk with lists of L (above 64: the radix selection) and m2d_plan_merge behind them; days == 1 without plan caps is
 // m2d_topk_menu_filtered's launches.
+//
+// m2d_plan_groups: the same plan for a GROUP of users.  A row of the walk is a group of M member slots:
+// m2d_group_members / m2d_group_caps run first (m2d_groups.hip), a block's Gb M member rows are scored into [Gb M, W],
+// m2d_group_reduce folds each group's rows into its row 0 and the selection lists that row (row stride M W).  Everything behind the
+// lists -- the prefix argument, the merges -- sees score words per row and dish and nothing of where they came from.
 #include "m2d_engine.h"
 
 namespace {
@@ -462,16 +467,33 @@ int menu_slate_index(m2d_engine *h, const int32_t *slate, const int64_t nD, int3
     return M2D_OK;
 }
 
+// The rows of a walk that are groups (null: users): M member slots per row, `users` is then the dense member array i32[nU M] and cnt
+// i32[nU] the rows' member counts (m2d_launch_group_prepare).  members: the caller's matrix, for menu_call.
+struct MenuGroups {
+    const int32_t *members;
+    const int32_t *cnt;
+    int32_t M, mode;
+    bool caps_per_member;
+};
+
 // One loop for both forms: per block of Ub users and non-empty segment of `ix`, ranges of W dishes -- vectors, scores, selection into
 // the segment's lists (excl_off: each row's exclusion segment is struck on the range's ascending ids; a later range merges into the
 // list of the ranges before it, whose entries were struck when they were listed) -- then the merge under the caps.
 // m2d_plan_menus: the lists are L = days k long (above 64 the selection is the radix form whatever the option says) and the merge is
 // m2d_plan_merge into [nU, days, k]; with days == 1 and no plan caps L = k and every launch is the menu call's.
+// m2d_plan_groups (grp): a row is a group -- its M member rows are scored (fillers too: 4.12's known cost), reduced into the first of
+// them and listed from there; blocks hold whole groups, score scratch [Ub M, W].  With grp == null M is 1 and nothing here differs from
+// the per-user launches.  The order stays blocks outside, ranges inside (m2d_launch_groups has it the other way round): a block's lists
+// live in list scratch [S', Ub, L] until its merge, so ranges outside would need the lists of ALL rows at once, [S', nU, L], which no
+// option bounds.  The price: a range's dish vectors are rebuilt per block (m2d_slate_prepare, W K floats against the block's Ub M W K
+// products).
 int menu_walk(m2d_engine *h, const MenuIndex &ix, const int32_t *users, int64_t nU, int32_t days, int32_t k, const int32_t *caps,
-              const int32_t *plan_caps, const int64_t *excl_off, const int32_t *excl_ids, float *out_scores, int32_t *out_ids, hipStream_t st)
+              const int32_t *plan_caps, const int64_t *excl_off, const int32_t *excl_ids, float *out_scores, int32_t *out_ids, hipStream_t st,
+              const MenuGroups *grp = nullptr)
 {
     int rc;
     const int32_t L = days * k;
+    const int64_t M = grp ? grp->M : 1;
     const bool plan = days != 1 || plan_caps;
     const int64_t P = h->opt_deep_chunk_pairs;
     const auto range_of = [&](const int64_t n_s) {
@@ -485,9 +507,9 @@ int menu_walk(m2d_engine *h, const MenuIndex &ix, const int32_t *users, int64_t 
         ++S;
         if (range_of(n_s) > Wmax) Wmax = range_of(n_s);
     }
-    // user blocks: score scratch [Ub, W] and list scratch [S', Ub, L] both within P words
-    const int64_t Ub = m2d_block_rows(P, Wmax > S * L ? Wmax : S * L, nU);
-    if ((rc = h->slate_scores.grow(h, (size_t)Ub * Wmax)) != M2D_OK) return rc;
+    // user blocks: score scratch [Ub M, W] and list scratch [S', Ub, L] both within P words (a block holds one row at least)
+    const int64_t Ub = m2d_block_rows(P, M * Wmax > S * L ? M * Wmax : S * L, nU);
+    if ((rc = h->slate_scores.grow(h, (size_t)Ub * M * Wmax)) != M2D_OK) return rc;
     if ((rc = h->menu_list_scores.grow(h, (size_t)S * Ub * L)) != M2D_OK) return rc;
     if ((rc = h->menu_list_ids.grow(h, (size_t)S * Ub * L)) != M2D_OK) return rc;
     const bool deep = L > 64 || h->opt_menu_select != 0;
@@ -505,9 +527,13 @@ int menu_walk(m2d_engine *h, const MenuIndex &ix, const int32_t *users, int64_t 
                 SlateArgs a;
                 bool mfma;
                 if ((rc = m2d_slate_prepare(h, ids, 0, Wc, a, mfma, st)) != M2D_OK) return rc;
-                a.users = users + u0; a.nU = n; a.index_base = u0; a.out = h->slate_scores;
+                a.users = users + u0 * M; a.nU = n * M; a.index_base = u0 * M; a.out = h->slate_scores;
                 if ((rc = m2d_launch_slate_scores(h, a, mfma, st)) != M2D_OK) return rc;
+                if (grp && (rc = m2d_launch_group_reduce(h, grp->mode, h->slate_scores, grp->cnt + u0, n, (int)M, Wc, h->slate_scores,
+                                                         M * Wc, st)) != M2D_OK)
+                    return rc;
                 SelectJob job = SelectJob::row_major(h->slate_scores, n, Wc, ids, 0);
+                job.rs = M * Wc;                                                 // a group's list is read from its row 0
                 job.first = r0 == 0 ? 1 : 0;
                 job.k = L;
                 job.out_scores = h->menu_list_scores + (size_t)j * Ub * L;
@@ -542,10 +568,19 @@ int menu_walk(m2d_engine *h, const MenuIndex &ix, const int32_t *users, int64_t 
 // what every entry does in front of the loop: the table conditions, the catalogue's index, the callers' lists, the slate's index
 int menu_call(m2d_engine *h, const char *entry, const int32_t *users, int64_t nU, int32_t days, int32_t k, const int32_t *caps,
               const int32_t *plan_caps, const int64_t *excl_off, const int32_t *excl_ids, const int32_t *slate, int64_t nD, float *out_scores,
-              int32_t *out_ids, hipStream_t st)
+              int32_t *out_ids, hipStream_t st, const MenuGroups *groups = nullptr)
 {
     int rc;
     if ((rc = m2d_deep_conditions(h, entry, st)) != M2D_OK) return rc;
+    // groups: `users` is null and nU counts groups.  The member check is the call's first launch, the cap fold its second: their
+    // latches come before every other, and from here on users / caps / plan_caps are the dense members and one cap row per group
+    MenuGroups g;
+    if (groups) {
+        g = *groups;
+        if ((rc = m2d_launch_group_prepare(h, g.members, nU, g.M, g.caps_per_member ? caps : nullptr, g.caps_per_member ? plan_caps : nullptr,
+                                           &users, &g.cnt, &caps, &plan_caps, st)) != M2D_OK)
+            return rc;
+    }
     if ((rc = menu_ensure_index(h, st)) != M2D_OK) return rc;
     // the callers' lists are checked before any scoring launch in stream order: the positions the latch reports are the caller's
     if (excl_off && (rc = m2d_launch_check_exclusions(h, excl_off, excl_ids, nU, st)) != M2D_OK) return rc;
@@ -555,7 +590,7 @@ int menu_call(m2d_engine *h, const char *entry, const int32_t *users, int64_t nU
         if ((rc = menu_slate_index(h, slate, nD, seg, st)) != M2D_OK) return rc;
         ix = MenuIndex{h->menu_slate_perm, h->menu_slate_perm + nD, seg};
     }
-    return menu_walk(h, ix, users, nU, days, k, caps, plan_caps, excl_off, excl_ids, out_scores, out_ids, st);
+    return menu_walk(h, ix, users, nU, days, k, caps, plan_caps, excl_off, excl_ids, out_scores, out_ids, st, groups ? &g : nullptr);
 }
 
 }  // namespace
@@ -572,6 +607,14 @@ int m2d_launch_plan_menus(m2d_engine *h, const int32_t *users, int64_t nU, int32
                           float *out_scores, int32_t *out_ids, hipStream_t st)
 {
     return menu_call(h, "m2d_plan_menus", users, nU, days, k, caps, plan_caps, excl_off, excl_ids, slate, nD, out_scores, out_ids, st);
+}
+
+int m2d_launch_plan_groups(m2d_engine *h, const int32_t *members, int64_t nG, int32_t M, int32_t mode, int32_t days, int32_t k,
+                           const int32_t *caps, const int32_t *plan_caps, bool caps_per_member, const int64_t *excl_off,
+                           const int32_t *excl_ids, const int32_t *slate, int64_t nD, float *out_scores, int32_t *out_ids, hipStream_t st)
+{
+    const MenuGroups g{members, nullptr, M, mode, caps_per_member};
+    return menu_call(h, "m2d_plan_groups", nullptr, nG, days, k, caps, plan_caps, excl_off, excl_ids, slate, nD, out_scores, out_ids, st, &g);
 }
 
 int m2d_launch_topk_menu(m2d_engine *h, const int32_t *users, int64_t nU, int32_t k, const int32_t *caps, float *out_scores,

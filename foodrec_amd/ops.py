@@ -773,6 +773,64 @@ class ScoringEngine:
         self._group_keep = (members, None, None, slate)
         return out
 
+    def _plan_groups(self, members, days: int, k: int, caps: torch.Tensor, plan_caps=None, mode: str = "least", exclude=None, among=None,
+                     caps_per_member: bool = False):
+        """What ``torch.ops.m2d.plan_groups`` and ``Model.plan_group`` call (not a public method, for ``_topk_menu``'s reason; its
+        stream-order case is in tests/test_gpu_plan_groups.py).  EXTENSION, build-defined (``m2d_plan_groups``, include/m2d.h; DESIGN.md
+        section 4.16): ``_plan_menus`` for GROUPS of users -- the dishes are ordered by the group's word under ``mode``
+        (``score_groups``' word) -> (scores f32[nG, days, k], dish ids i32[nG, days, k]).  ``members`` / ``mode``: as ``topk_groups``.
+        ``caps`` / ``plan_caps``: int32 device tensors [nG, C] or [C], one row per group; with ``caps_per_member`` [nG, M, C], one row
+        per member slot -- the group's cap is the minimum over its real members (filler slots are never read).  ``exclude``: one list
+        per group; ``among`` and the synchronisation: as ``_plan_menus``.  1 <= k <= 64, days >= 1, days * k <= 1024."""
+        what = "plan_groups"
+        if mode not in GROUP_MODES:
+            raise ValueError("%s: mode must be one of %s, got %r" % (what, sorted(GROUP_MODES), mode))
+        if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or not 1 <= int(k) <= 64:
+            raise ValueError("%s: 1 <= k <= 64, got %r" % (what, k))
+        if isinstance(days, bool) or not isinstance(days, (int, np.integer)) or int(days) < 1 or int(days) * int(k) > 1024:
+            raise ValueError("%s: days >= 1 and days * k <= 1024, got days = %r, k = %r" % (what, days, k))
+        members = self._group_members(members, what)
+        nG, M = members.shape
+        k, days, per_member = int(k), int(days), bool(caps_per_member)
+
+        def table(t, name):
+            if not isinstance(t, torch.Tensor) or t.dtype != torch.int32 or t.device != self.device:
+                raise TypeError("%s: %s must be an int32 tensor on %s" % (what, name, self.device))
+            if per_member:
+                if tuple(t.shape) != (nG, M, self.C):
+                    raise ValueError("%s: with caps_per_member %s must be [%d, %d, %d], got %s" % (what, name, nG, M, self.C, tuple(t.shape)))
+                return t.contiguous()
+            if t.dim() == 1 and t.shape[0] == self.C:
+                t = t.reshape(1, self.C).expand(nG, self.C)
+            if t.dim() != 2 or tuple(t.shape) != (nG, self.C):
+                raise ValueError("%s: %s must be [%d, %d] or [%d], got %s" % (what, name, nG, self.C, self.C, tuple(t.shape)))
+            return t.contiguous()
+
+        caps = table(caps, "caps")
+        plan = table(plan_caps, "plan_caps") if plan_caps is not None else None
+        off = ids = None
+        if exclude is not None:
+            off, ids = exclusions_on_device(exclude, nG, self.device, what)
+        slate, nD = None, 0
+        if among is not None:
+            if not isinstance(among, torch.Tensor) or among.dtype != torch.int32 or among.device != self.device:
+                raise TypeError("%s: among must be an int32 tensor on %s" % (what, self.device))
+            slate = among.contiguous().reshape(-1)
+            nD = slate.numel()
+            if nD < 1:
+                raise ValueError("%s: among must hold at least one dish" % what)
+        out_s = torch.empty((nG, days, k), dtype=torch.float32, device=self.device)
+        out_i = torch.empty((nG, days, k), dtype=torch.int32, device=self.device)
+        xo, xi = (off.data_ptr(), ids.data_ptr()) if off is not None else (None, None)
+        with torch.cuda.device(self.device):
+            rc = _native.lib().m2d_plan_groups(self._h, members.data_ptr(), nG, M, GROUP_MODES[mode], days, k, caps.data_ptr(),
+                                               plan.data_ptr() if plan is not None else None, 1 if per_member else 0, xo, xi,
+                                               slate.data_ptr() if slate is not None else None, nD, out_s.data_ptr(), out_i.data_ptr(),
+                                               _stream_ptr())
+        _native.raise_for(rc, self._h)
+        self._plan_groups_keep = (members, caps, plan, off, ids, slate)   # stay alive until the queued kernels have read them
+        return out_s, out_i
+
     # -- market retrieval (include/m2d.h, "Market retrieval"; DESIGN.md section 4.8) -------------------------------------------
     def set_recipes(self, offsets, ids, num_ingredients: int):
         """EXTENSION (``m2d_set_recipes``): every dish's ingredient list, CSR -- offsets i32[I + 1], ids i32[nnz] in
@@ -1334,6 +1392,23 @@ def score_groups_op(engine: int, members: torch.Tensor, slate: torch.Tensor, mod
 @score_groups_op.register_fake
 def _(engine, members, slate, mode="least"):
     return members.new_empty((members.shape[0], slate.numel()), dtype=torch.float32)
+
+
+@torch.library.custom_op("m2d::plan_groups", mutates_args=(), device_types="cuda")
+def plan_groups_op(engine: int, members: torch.Tensor, caps: torch.Tensor, days: int, k: int, mode: str = "least",
+                   plan_caps: Optional[torch.Tensor] = None, caps_per_member: bool = False, excl_off: Optional[torch.Tensor] = None,
+                   excl_ids: Optional[torch.Tensor] = None, among: Optional[torch.Tensor] = None) -> tuple[torch.Tensor, torch.Tensor]:
+    """EXTENSION, build-defined (``m2d_plan_groups``, include/m2d.h): ``plan_menus`` for groups -- members
+    i32[nG, M] with -1 padding, `caps` / `plan_caps` [nG, C] or, with `caps_per_member`, [nG, M, C] -> (scores f32[nG, days, k], dish
+    ids i32[nG, days, k])."""
+    s, i = _engine(engine)._plan_groups(members, days, k, caps, plan_caps, mode, _excl_pair(excl_off, excl_ids), among, caps_per_member)
+    return s, i
+
+
+@plan_groups_op.register_fake
+def _(engine, members, caps, days, k, mode="least", plan_caps=None, caps_per_member=False, excl_off=None, excl_ids=None, among=None):
+    return (members.new_empty((members.shape[0], days, k), dtype=torch.float32),
+            members.new_empty((members.shape[0], days, k), dtype=torch.int32))
 
 
 @torch.library.custom_op("m2d::catalogue_rank", mutates_args=(), device_types="cuda")

@@ -576,24 +576,29 @@ class Model:
         self.engine.check()
         return s.cpu().numpy(), i.cpu().numpy()
 
+    def _cap_row(self, spec, k: int, what: str) -> list:
+        """one cap row as C ints: None is uncapped (k everywhere), a dict {category index: cap} caps what it names, a sequence is the row"""
+        C = self.engine.C
+        if spec is None:
+            return [k] * C
+        if isinstance(spec, dict):
+            r = [k] * C
+            for c, cap in spec.items():
+                if isinstance(c, bool) or not isinstance(c, (int, np.integer)) or not 0 <= int(c) < C:
+                    raise ValueError(what + ": category index %r outside [0, %d)" % (c, C))
+                r[int(c)] = int(cap)
+            return r
+        r = [int(cap) for cap in spec]
+        if len(r) != C:
+            raise ValueError(what + ": a cap row has %d entries for %d categories" % (len(r), C))
+        return r
+
     def _menu_caps(self, caps, k: int, n: int, what: str) -> torch.Tensor:
         """`caps` of `topk_menu` and `topk_menu_filtered` -> an int32 device tensor [n, C], or [C] (one row for every user)"""
         C = self.engine.C
 
         def row(spec):
-            if spec is None:
-                return [k] * C
-            if isinstance(spec, dict):
-                r = [k] * C
-                for c, cap in spec.items():
-                    if isinstance(c, bool) or not isinstance(c, (int, np.integer)) or not 0 <= int(c) < C:
-                        raise ValueError(what + ": category index %r outside [0, %d)" % (c, C))
-                    r[int(c)] = int(cap)
-                return r
-            r = [int(cap) for cap in spec]
-            if len(r) != C:
-                raise ValueError(what + ": a cap row has %d entries for %d categories" % (len(r), C))
-            return r
+            return self._cap_row(spec, k, what)
 
         per_user = (isinstance(caps, (list, tuple)) and len(caps) > 0
                     and all(c is None or isinstance(c, (dict, list, tuple, np.ndarray)) for c in caps))
@@ -749,6 +754,90 @@ class Model:
             self.engine.check()
             out_s[:, :kk], out_i[:, :kk] = s.cpu().numpy(), i.cpu().numpy()
         return out_s, out_i
+
+    def plan_group(self, groups, days: int = 7, k: int = 3, mode: str = "least", caps=None, plan_caps=None, member_caps=None,
+                   member_plan_caps=None, exclude=None, among=None, market=None, max_missing: int = 0):
+        """EXTENSION, build-defined (no reference counterpart): a MEAL PLAN per household -- `plan_menus` with
+        the dishes ordered by the household's word under `mode`, as in `topk_group`; a household menu is ``days=1``.  `groups` as in
+        `topk_group`.  Caps come per household or per member, not both: `caps` / `plan_caps` in the forms `plan_menus` accepts (a list
+        of rows is aligned with `groups`); `member_caps` / `member_plan_caps` are dicts {user id: caps} (str or int keys, compared as
+        ints; each value a dict {category index: cap} or a list of C ints) -- the household's cap for a category is the lowest any of
+        its members has, a member without an entry is uncapped: "one of us may have fish at most twice this week" is
+        ``member_plan_caps={her: {fish: 2}}``.  `exclude` in `topk_group`'s forms (a list aligned with `groups`, or a dict keyed by
+        user: a household leaves out the union of its members' lists); `among` / `market` / `max_missing` as there, but `exclude`
+        goes with either (an excluded dish outside the slate is ignored); `among` together with `market` raises.  1 <= k <= 64,
+        days >= 1, days * k <= 1024.  A day's row ends in id -1 / NaN where it cannot take k dishes -- all of them when the slate is
+        empty (the engine is not called).  Returns numpy (scores float32 [nG, days, k], dish ids int32 [nG, days, k]).
+        (``torch.ops.m2d.plan_groups``.)"""
+        what = "plan_group"
+        if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or not 1 <= int(k) <= 64:
+            raise ValueError("%s: 1 <= k <= 64, got %r" % (what, k))
+        if isinstance(days, bool) or not isinstance(days, (int, np.integer)) or int(days) < 1 or int(days) * int(k) > 1024:
+            raise ValueError("%s: days >= 1 and days * k <= 1024, got days = %r, k = %r" % (what, days, k))
+        k, days = int(k), int(days)
+        if mode not in ("least", "mean", "most"):
+            raise ValueError("%s: mode must be one of ['least', 'mean', 'most'], got %r" % (what, mode))
+        if (caps is not None or plan_caps is not None) and (member_caps is not None or member_plan_caps is not None):
+            raise ValueError("%s: caps / plan_caps (per household) together with member_caps / member_plan_caps (per member) is not "
+                             "supported" % what)
+        for name, table in (("member_caps", member_caps), ("member_plan_caps", member_plan_caps)):
+            if table is not None and not isinstance(table, dict):
+                raise ValueError("%s: %s must be a dict {user id: caps}" % (what, name))
+        if among is not None and market is not None:
+            raise ValueError("%s: among together with market is not supported" % what)
+        groups = [list(g) for g in groups]
+        nG = len(groups)
+        members = []
+        for g in groups:
+            m = _ids(g, "user")
+            members.append((m.cpu().numpy() if isinstance(m, torch.Tensor) else m).tolist())
+        if any(len(m) < 1 or len(m) > 64 for m in members):
+            raise ValueError("%s: a group has 1 to 64 members" % what)
+        M = max([len(m) for m in members] + [1])
+        per_member = member_caps is not None or member_plan_caps is not None
+        if per_member:
+            def expand(by_user, fill):
+                rows = {int(_ids([u], "user")[0]): self._cap_row(spec, fill, what) for u, spec in by_user.items()}
+                t = np.full((nG, M, self.engine.C), fill, dtype=np.int64)
+                for g, m in enumerate(members):
+                    for j, u in enumerate(m):
+                        if u in rows:
+                            t[g, j] = rows[u]
+                if t.size and (t.min() < 0 or t.max() > np.iinfo(np.int32).max):
+                    raise ValueError(what + ": caps must be >= 0")
+                return torch.from_numpy(t.astype(np.int32)).to(self.device)
+            table = expand(member_caps or {}, k)
+            plan = None if member_plan_caps is None else expand(member_plan_caps, days * k)
+        else:
+            table = self._menu_caps(caps, k, nG, what)
+            plan = None if plan_caps is None else self._menu_caps(plan_caps, days * k, nG, what)
+        off = ids = None
+        if exclude is not None:
+            from .ops import exclusions_on_device
+            if isinstance(exclude, dict):                    # keys and members are compared as ints: "7" and 7 are the same user
+                by_user = {int(u): x for u, x in exclude.items()}
+                had = [np.asarray(sorted({int(d) for u in m for d in by_user.get(u, ())}), dtype=np.int32) for m in members]
+            elif len(exclude) != nG:
+                raise ValueError("%s: %d exclusion lists for %d groups" % (what, len(exclude), nG))
+            else:
+                had = [(lambda x: x.cpu().numpy() if isinstance(x, torch.Tensor) else x)(_ids(x, "item")) for x in exclude]
+            off, ids = exclusions_on_device(had, nG, self.device, what)      # sorted and de-duplicated per group
+        slate = None
+        if market is not None:
+            slate = np.asarray(self.cookable(market, max_missing), dtype=np.int32)
+        elif among is not None:
+            d = _ids(among, "item")
+            slate = np.unique(np.asarray(d.cpu().numpy() if isinstance(d, torch.Tensor) else d, dtype=np.int32).reshape(-1))
+        if slate is not None and slate.size == 0:
+            return np.full((nG, days, k), np.nan, dtype=np.float32), np.full((nG, days, k), -1, dtype=np.int32)
+        padded = np.full((nG, M), -1, dtype=np.int32)
+        for g, m in enumerate(members):
+            padded[g, :len(m)] = m
+        st = None if slate is None else torch.from_numpy(slate).to(self.device)
+        s, i = torch.ops.m2d.plan_groups(self.engine.id, torch.from_numpy(padded).to(self.device), table, days, k, mode, plan, per_member,
+                                         off, ids, st)
+        self.engine.check()
+        return s.cpu().numpy(), i.cpu().numpy()
 
     def set_ingredients(self, ingredient_table, offsets, ids, weights=None):
         """EXTENSION: multi-hot ingredient lists per dish (CSR) replacing the category sum of the high-level path."""

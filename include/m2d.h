@@ -609,7 +609,7 @@ int m2d_topk_menu_filtered(m2d_engine *h, const int32_t *users /* device [nU] */
  * m2d_select_deep whatever "menu_select" says), and m2d_plan_merge -- one wave per user, lane s holding signature s's cursor and a
  * window of its next 8 entries in registers, refilled by independent loads -- runs the days: `full` is the categories at their day
  * cap (back the next morning) or at their plan cap (never back).  One scoring pass instead of `days`.
- * Not offered: per-day cap tables, minimum quotas, the MLP head, sharding, k above 64, C above 6, households. */
+ * Not offered: per-day cap tables, minimum quotas, the MLP head, sharding, k above 64, C above 6 (households: m2d_plan_groups below). */
 #define M2D_PLAN_MAX_LIST 1024
 int m2d_plan_menus(m2d_engine *h, const int32_t *users /* device [nU] */, int64_t nU, int32_t days, int32_t k,
                    const int32_t *caps /* device [nU, C]: per day */,
@@ -617,6 +617,58 @@ int m2d_plan_menus(m2d_engine *h, const int32_t *users /* device [nU] */, int64_
                    const int64_t *excl_off /* [nU + 1] or NULL */, const int32_t *excl_ids,
                    const int32_t *slate /* [nD] strictly ascending, or NULL: the whole catalogue */, int64_t nD,
                    float *out_scores /* [nU, days, k] */, int32_t *out_ids /* [nU, days, k] */, void *stream);
+
+/* ---- build-defined extension, NO reference counterpart ----
+ * Household meal plans: m2d_plan_menus for GROUPS of users -- `days` menus of k dishes per group, no dish twice, under caps per day and
+ * over the plan, the dishes ordered by the group's word under `mode`.  A household menu is days == 1.
+ *
+ * Definition.  Let w(g, d) be the word m2d_score_groups_slate gives group g for dish d under `mode`.  Row g of the result is
+ * m2d_plan_menus' row for a "user" whose score words are w(g, .): the same order (score descending, equal words and -0 / +0 to the lower
+ * id, NaN last), the same day caps, plan caps, exclusions (one segment per GROUP) and slate; a short day ends in id -1 / the fill NaN and
+ * every row of out_ids i32[nG, days, k] / out_scores f32[nG, days, k] is written.
+ *
+ * Caps.  caps_per_member == 0: caps and plan_caps are i32[nG, C], one row per group, passed on as they are; a cap below 0 is latched by
+ * the merge as in m2d_plan_menus with nG in place of nU (position g C + c, a plan cap nG C + g C + c) and counts as 0.
+ * caps_per_member == 1: both are i32[nG, M, C], one row per member SLOT; the group's cap for category c is the MINIMUM over the group's
+ * first cnt[g] members of max(cap, 0).  The rows of filler slots are never read: they may hold anything, bind nothing and latch
+ * nothing.  A cap below 0 of a real member: M2D_ERR_INVALID_ARG with the cap and position (g M + j) C + c; a plan cap below 0: position
+ * nG M C + (g M + j) C + c.  Either counts as 0.  plan_caps == NULL: none, in both forms.
+ *
+ * Arguments.  members i32[nG, M] / M / mode: as m2d_topk_groups, with its latched member errors by code, value and position (every
+ * member must lie in this engine's user_base range: sharding is out of scope).  1 <= k <= min(64, I), days >= 1,
+ * days * k <= M2D_PLAN_MAX_LIST, excl_off i64[nG + 1] / excl_ids, slate / nD, the list checks, the slate check, the refusals and the table
+ * conditions: as m2d_plan_menus, under this call's name.  caps_per_member other than 0 / 1, a null required pointer:
+ * M2D_ERR_INVALID_ARG.  nG == 0 returns M2D_OK and launches nothing.  The member check is the first launch in stream order and the cap
+ * fold the second, so their latches come before any other.  The rows of a call with a latched error are unspecified; no kernel reads
+ * or writes out of bounds and the engine stays usable.
+ *
+ * Invariants.  A row does not depend on options "deep_chunk_pairs" and "menu_select", on nG or the group's position, on M (the
+ * padding), or on member order -- except the first-member rule among equal words (LEAST / MOST return that member's word: -0 / +0 and
+ * NaN payloads can differ) and the sequential float32 sum of MEAN.
+ * Equalities.  A group of one member returns m2d_plan_menus' row for that user in every mode, ids and score words.  With every cap
+ * >= days * k and days == 1 the row is m2d_topk_groups' list of k (with a slate: m2d_topk_groups_slate's).  last_kernel is
+ * m2d_plan_merge, or m2d_menu_merge when days == 1 and plan_caps == NULL, as in m2d_plan_menus.
+ *
+ * How.  The prefix argument of m2d_plan_menus speaks of a row's score words only, so it holds for group words unchanged.
+ * m2d_group_members checks the slots and writes dense member ids and counts; m2d_group_caps (caps_per_member == 1; one thread per group
+ * and category walking the group's cnt rows, both tables) writes the folded, clamped tables into engine scratch, so the merge latches
+ * nothing on them.  Then m2d_plan_menus' loop with a group per row: per block of Gb whole groups, non-empty signature segment and range
+ * of W = min(segment size, P, 65536) dishes (P = option "deep_chunk_pairs") -- m2d_slate_prepare, the slate score kernel over the
+ * block's Gb M member rows into scratch [Gb M, W], m2d_group_reduce in place into each group's row 0, the selection over row 0 with row
+ * stride M W, k = L = days * k and the group's exclusion segment; then m2d_plan_merge (m2d_menu_merge when days == 1 without plan
+ * caps) over the block.  Blocks outside, ranges inside -- not m2d_topk_groups' order: a block's lists live in list scratch
+ * [segments, Gb, L] until its merge, so the other order would need every group's lists at once; a range's dish vectors are therefore
+ * rebuilt per block.  Gb = max(1, P / max(M W, segments * L)).  At one group per block the scratch is NOT bounded by the option: M W
+ * floats of scores (M = 64, W = 65 536: 16 MB) and segments * L list entries (64 * 1024 * 8 bytes) -- m2d_topk_groups has the same M W
+ * caveat.  KNOWN COST: filler rows are scored, as in m2d_topk_groups; no compaction.  Synchronises where m2d_plan_menus does -- the index
+ * build once per mask table, once per call with a slate -- and nowhere else; buffers grow only.
+ * Not offered: minimum quotas, per-day cap tables, the MLP head, sharding, k above 64, C above 6, member compaction. */
+int m2d_plan_groups(m2d_engine *h, const int32_t *members /* device [nG, M], -1 padded */, int64_t nG, int32_t M, int32_t mode,
+                    int32_t days, int32_t k,
+                    const int32_t *caps, const int32_t *plan_caps /* or NULL */, int32_t caps_per_member,
+                    const int64_t *excl_off /* [nG + 1] or NULL */, const int32_t *excl_ids,
+                    const int32_t *slate /* strictly ascending or NULL */, int64_t nD,
+                    float *out_scores /* [nG, days, k] */, int32_t *out_ids /* [nG, days, k] */, void *stream);
 
 /* Diagnostic (scripts/deep_time.py): one selection launch over a resident row-major score block f32[rows, W], ids 0 .. W - 1, no
  * exclusions, into out_scores / out_ids [rows, k] -- form 0: m2d_select_deep (k <= 1024), form 1: m2d_topk_mlp_select (k <= 64).
