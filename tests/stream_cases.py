@@ -53,9 +53,10 @@ def recipes():
     return off, ids
 
 
-def cookable(market, max_missing):
-    """market_cases.restate's cookable ids for recipes() (no empty list), vectorised; the CPU test holds it to that restatement."""
-    off, ids = recipes()
+def cookable(market, max_missing, lists=None):
+    """market_cases.restate's cookable ids for recipes() (no empty list), vectorised; the CPU test holds it to that restatement.
+    `lists`: another (offsets, ids) pair in place of recipes() (writer_cases.py: set_recipes again)."""
+    off, ids = recipes() if lists is None else lists
     present = np.zeros(R_INGREDIENTS, bool)
     present[np.asarray(market, np.int64)] = True
     missing = np.add.reduceat((~present[ids]).astype(np.int64), off[:-1])
@@ -65,12 +66,14 @@ def cookable(market, max_missing):
 class Model:
     """The float64 restatement of one engine configuration on one set of tables."""
 
-    def __init__(self, E, kind, tset=0, tabs=None):
-        assert kind in KINDS
+    def __init__(self, E, kind, tset=0, tabs=None, cats=None, head=None, recipes=None):
+        """cats / head / recipes: what a writer of writer_cases.py left in place of the kind's own (None: the kind's own)"""
+        assert kind in KINDS and (head is None or kind == "mlp") and (recipes is None or kind == "market")
         self.E, self.kind = E, kind
         self.PM, self.RE, self.CE = tables(E, tset) if tabs is None else tabs
-        self.cats = _masks(3)
-        self.head = _head(E, 1) if kind == "mlp" else None
+        self.cats = _masks(3) if cats is None else cats
+        self.head = (_head(E, 1) if head is None else head) if kind == "mlp" else None
+        self.recipes = recipes                              # None: recipes()
         self.ing = _ingredients(E, 2) if kind == "ing" else None
         self.coef = 0.5 if kind == "mlp" else 0.99          # (a head at 0.99 hides its low-level blocks: readers-after-writers' _cfg)
         self._rows = {}
@@ -378,7 +381,7 @@ def ans_profiles(what):
         if what == "score":
             return scores(m.pairs(d["rows"], d["items"], PM=PMc))
         S = m.rows(np.arange(n), PM=PMc)
-        allowed = [cookable(x, 1) for x in csr_lists(d["market_off"], d["market_ids"])] if what == "markets" else None
+        allowed = [cookable(x, 1, m.recipes) for x in csr_lists(d["market_off"], d["market_ids"])] if what == "markets" else None
         return lists_among(S, K, allowed=allowed, excluded=csr_lists(d["excl_off"], d["excl_ids"]) if "excl_off" in d else None)
     return ans
 
@@ -386,11 +389,11 @@ def ans_profiles(what):
 def ans_market(which):
     def ans(m, d):
         if which == "cookable":
-            return Answer(what="lists", value=cookable(d["market"], 1)[None, :], S=None, among=None)
+            return Answer(what="lists", value=cookable(d["market"], 1, m.recipes)[None, :], S=None, among=None)
         S = m.rows(d["users"])
         if which == "one":
-            return lists_among(S, K, allowed=[cookable(d["market"], 1)] * len(S))
-        return lists_among(S, K, allowed=[cookable(x, 1) for x in csr_lists(d["market_off"], d["market_ids"])],
+            return lists_among(S, K, allowed=[cookable(d["market"], 1, m.recipes)] * len(S))
+        return lists_among(S, K, allowed=[cookable(x, 1, m.recipes) for x in csr_lists(d["market_off"], d["market_ids"])],
                                     excluded=csr_lists(d["excl_off"], d["excl_ids"]) if "excl_off" in d else None)
     return ans
 

@@ -14,6 +14,12 @@ and asserts that the second snapshot equals the fresh engine's bit for bit (the 
 launch shapes, same bits), that it passes the oracle on the written tables, and that the writer CHANGED the answer -- more than
 a quarter of the lists, more than half of the scores -- so that a stale answer cannot pass.  Writers that must change nothing
 (a `general`-only Write_Memory, train_step(apply=False), an optimizer slot saved and restored) leave the snapshot bit-equal.
+
+This file holds the ten readers the engine had when it was written, each with the kernel it is there for.  THE FULL MATRIX -- every
+reader call the engine has since gained (rank_candidates, the deep, MLP, group, profile, slate, market and menu calls) against every
+writer -- lives in tests/writer_cases.py (the tables) and tests/test_gpu_readers_after_writers_all.py (the same pattern, one test per
+engine kind and writer).  A NEW READER MUST JOIN IT: tests/test_writer_cases_cpu.py fails until every public method of ScoringEngine
+is a reader row, a writer, or excused by name with a reason.
 """
 import functools
 import types

@@ -158,19 +158,19 @@ def _assert_list(s64, among, ids, scores, what):
         tm.compare_lists(scores[None, :n], ids[None, :n], s64[among][None, :], n, ids=[among], what=what)
 
 
-def _assert_right(r, real, out, what):
-    """The outputs of row r's call against the float64 restatement of the real request (stream_cases.answers)."""
+def _assert_right(r, real, out, what, m=None, ans=None):
+    """The outputs of row r's call against the float64 restatement of the real request (stream_cases.answers); m, ans: another
+    restatement (a stream_cases.Model of other tables) and its answer to `real` (test_gpu_readers_after_writers_all.py)."""
     import seen_dish_cases as sd
     what = "%s (%s)" % (r.name, what)
-    ans = st.answers(r.name)[0]
+    ans = st.answers(r.name)[0] if ans is None else ans
+    m = st.model(r.E, r.kind) if m is None else m
     if r.name.startswith("train_step"):
-        m = st.model(r.E, r.kind)
         assert_train_tables(out[1:], st.trained_tables(m, real), (m.PM, m.RE, m.CE), st.TRAIN[0], visible=(), what=what)
         assert np.isfinite(out[0]).all()
     elif r.options.get("pm_bf16"):                           # the graph on the rounded table (include/m2d.h, "Serving mirror")
         import torch
-        m = st.model(r.E, r.kind)
-        rounded = torch.from_numpy(m.PM).to(torch.bfloat16).to(torch.float32).numpy()
+        rounded = torch.from_numpy(np.ascontiguousarray(m.PM)).to(torch.bfloat16).to(torch.float32).numpy()
         assert_scores_close(out[0], m.pairs(real["users"], real["items"], real["cats"], PM=rounded), what=what)
     elif ans.what in ("scores", "rows"):
         assert_scores_close(out[0].reshape(-1), ans.value.reshape(-1), what=what)
